@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the substitution-mapping + pairwise-coevolution hot path on MI355X.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path over one batch of synthetic input (DESIGN.md section "Measurement"):
@@ -13,10 +13,13 @@ inputs resident in HBM when the timed region starts.
 Default workload = the configuration the metric is quoted on (BASELINE.json north_star): 10 000-column x 64-taxa
 protein alignment, JTT92+G4, correlation, 1 000 null replicates x 10 000 sites.  With N GPUs the SAME 1 000
 replicates are sharded over the ranks (strong scaling) and the observed all-pairs stage is split in row blocks.
-Next to the headline the JSON line carries: `roofline` (dominant kernel, HIP events on its stream), `cpu_baseline`
+A plain run sets up, warms up, times the steps and prints the headline.  With --full the JSON line also carries:
+`roofline` (dominant kernel, HIP events on its stream), `cpu_baseline`
 (oracle on the host cores, 1 thread as the reference runs + all cores), `host_to_host` (same step with the alignment
 coming from and the statistics / p-values going to host memory: BASELINE.md section 3's counting rule) and
-`mica_cfg5` (BASELINE configs[4], the Mica column-MI kernel with its own roofline and CPU figure).
+`mica_cfg5` (BASELINE configs[4], the Mica column-MI kernel with its own roofline and CPU figure); --no-cpu-baseline,
+--no-host and --no-mica leave one of them out.
+--dump-outputs DIR writes what the last timed step handed its caller to DIR/<name>.npy (float64; see dump_outputs).
 """
 import argparse
 import glob
@@ -214,6 +217,63 @@ def mica_leg(dev, steps, world=1, rank=0, gloo=False):
     return out
 
 
+DUMP_SAMPLE = 1 << 19        # entries kept of a larger output: 4 MB per array, the whole dump well under DUMP_MAX_BYTES
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _sample(n, k, seed):
+    """sorted positions of a fixed, seeded sample of k of n entries (all of them when n <= k)"""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, ana, last, pair_output, row_begin, row_end, n_null, suffix=""):
+    """--dump-outputs: what the last timed step handed its caller, as float64 <out_dir>/<name><suffix>.npy -- the
+    observed mapping (per-site vectors; `counts` on a sample of sites, `counts_sites`), this rank's null (`null_*`, at
+    positions `null_pos`) and this rank's pairs in the --pair-output form (`pair_*`, pair (pair_i, pair_j)).  An output of
+    more than DUMP_SAMPLE entries is a fixed, seeded sample, so two builds' dumps compare entry for entry."""
+    import torch
+    from comap_amd import engine as E
+    dev = ana.aln.device
+    n = ana.n
+
+    def take(t, pos):
+        return t.reshape(-1)[torch.from_numpy(pos).to(dev)]
+
+    arrays = dict(norm=ana.norm, post_rate=ana.post_rate, rate_class=ana.rate_class, logL=ana.logL)
+    sites = _sample(n, max(1, DUMP_SAMPLE // ana.counts.shape[0]), 1)
+    arrays["counts"] = ana.counts[:, torch.from_numpy(sites).to(dev)]
+    arrays["counts_sites"] = sites
+    if n_null:
+        b = ana.null_buffers(n_null)
+        pos = _sample(n_null, DUMP_SAMPLE, 2)
+        arrays.update(null_stat=take(b["stat"], pos), null_nmin=take(b["nmin"], pos), null_pos=pos)
+    if pair_output == "dense":
+        pos = _sample(n * n, DUMP_SAMPLE, 3)
+        arrays.update(pair_i=pos // n, pair_j=pos % n, pair_stat=take(ana.stat, pos), pair_pvalue=take(ana.pvalue, pos),
+                      pair_nsim=take(ana.nsim, pos))
+    else:
+        buf, count = last
+        dt = E.PAIR_COMPACT if pair_output == "compact" else E.PAIR_ROW
+        npairs = count if pair_output == "compact" else int(count.item())
+        pos = _sample(npairs, DUMP_SAMPLE, 3)
+        rec = buf[:npairs * dt.itemsize].view(npairs, dt.itemsize)[torch.from_numpy(pos).to(dev)]
+        rec = rec.cpu().numpy().view(dt).ravel()
+        if pair_output == "compact":   # records in (i, j) order over rows [row_begin, row_end): row i starts at off[i - row_begin]
+            r = np.arange(row_begin, row_end + 1, dtype=np.int64)
+            off = (r - row_begin) * (n - 1) - (r * (r - 1) - row_begin * (row_begin - 1)) // 2
+            i = row_begin + np.searchsorted(off, pos, side="right") - 1
+            arrays.update(pair_i=i, pair_j=i + 1 + pos - off[i - row_begin])
+        arrays.update({"pair_" + f: rec[f] for f in dt.names})
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: (v.cpu().numpy() if torch.is_tensor(v) else v).astype(np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -227,6 +287,10 @@ def main():
                     help="observed pair loop of this rank's row range: 16-byte records per pair (statistic, null count, class size; default -- "
                          "the job has no pair filters, cmx_expand_compact_rows rebuilds the 48-byte rows on the host), the 48-byte "
                          "statistics.txt rows compacted on the device, or dense N x N matrices")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the roofline, host-to-host, CPU baseline and Mica legs (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, a seeded sample of large outputs)")
     args = ap.parse_args()
 
     import torch
@@ -272,6 +336,8 @@ def main():
     rep_begin, rep_end = replicate_shard(rank, world, nrep_total)
     n_local = (rep_end - rep_begin) * ram
     row_begin, row_end = row_shard(rank, world, w["nsites"])   # this rank's share of the observed pair loop
+    # recorded in every timed step, --full or not: with them the null is simulated and mapped in two launches
+    # (IntraAnalysis.null_distribution), the timed path the headline has always measured
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
           for _ in range(args.steps)]
     ev_sim = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -318,7 +384,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i, True)
+        last = step(i, True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -334,63 +400,6 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = units_per_step * args.steps / elapsed
 
-    # roofline of the dominant kernel (map_kernel<S, null>): HIP events on the launch stream
-    null_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
-    alg, exe = flops_per_site(info, eng.B, eng.C, eng.S, eng.K, null=nrep_total > 0)
-    sites_per_launch = 2 * n_local if nrep_total else w["nsites"]
-    achieved = sites_per_launch * alg / (null_ms * 1e-3) / 1e12
-    ach_exe = sites_per_launch * exe / (null_ms * 1e-3) / 1e12
-    # `achieved` / `frac` follow SURVEY 8(d): ALGORITHMIC flops (7 B C S^2 per site, leaf edges counted as dense
-    # products) / time / peak.  `frac_executed` counts only the matrix products the kernel issues (leaf edges are row
-    # gathers, sibling messages are stored instead of recomputed): the matrix pipe's duty, always lower.
-    sim_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_sim])) if nrep_total else 0.0
-    kname = f"map_kernel<{eng.S},null>" if nrep_total else f"map_kernel<{eng.S},observed> (+ map_finalize_kernel when class-split)"
-    roofline = dict(bound="mfma", kernel=kname, achieved=achieved, peak=FP64_PEAK_TFLOPS,
-                    unit="TFLOP/s", frac=achieved / FP64_PEAK_TFLOPS, traffic=None,
-                    launch_ms=null_ms, simulate_ms=sim_ms, sites_per_launch=sites_per_launch, flops_per_site_algorithmic=alg,
-                    flops_per_site_executed=exe, achieved_executed=ach_exe, frac_executed=ach_exe / FP64_PEAK_TFLOPS)
-    # what is left of a step besides the simulator and the null's mapping launch: at N = 1 the observed stage (null sort +
-    # index, Gram, p-value lookup, filters, compacted rows; the observed alignment's mapping runs beside the null); at N > 1
-    # the all-gather too
-    roofline["rest_of_step_ms"] = ms_per_step - null_ms - sim_ms
-    if nrep_total:
-        # In the timed steps the observed alignment's mapping and the observed pairs' Gram run on the side stream beside this
-        # launch and share its CUs (they cost a protein null nothing measurable, the short nucleotide null of cfg4 up to a
-        # tenth).  Outside the timed region: the same launch with nothing beside it -- the kernel's own figure.
-        roofline["concurrent_in_timed_steps"] = "observed mapping + observed pairs' Gram (side stream)"
-        torch.cuda.synchronize()
-        ev_alone = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(2)]
-        for e2 in ev_alone:
-            ana.null_distribution(w["seed"] + 7, rep_begin, rep_end, ram, map_events=e2)
-        torch.cuda.synchronize()
-        alone_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_alone]))
-        roofline["launch_ms_alone"] = alone_ms
-        roofline["frac_alone"] = sites_per_launch * alg / (alone_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS
-    for tf in sorted(glob.glob(os.path.join(ROOT, "profiles", "traffic_r*.json")), reverse=True):
-        try:
-            t = json.load(open(tf))
-            if t.get("kernel_source_sha") == kernel_source_sha() and args.workload in t:
-                # per-launch bytes measured at N = 1; a sharded launch maps fewer sites (the traffic is per-site state)
-                ref_sites = t.get("sites_per_launch", {}).get(args.workload, sites_per_launch)
-                roofline["traffic"] = t[args.workload] * sites_per_launch / ref_sites
-                roofline["traffic_source"] = os.path.relpath(tf, ROOT)
-                break
-        except Exception:
-            pass
-    # next to the contract's algorithmic figure, say which roof the kernel really sits nearer to -- the fraction
-    # of the fp64 pipe it keeps busy (executed flops) against the fraction of the HBM rate its measured bytes take
-    if roofline["traffic"] is not None:
-        hbm_tbs = roofline["traffic"] / (null_ms * 1e-3) / 1e12
-        roofline["hbm_achieved_TBps"] = hbm_tbs
-        roofline["hbm_frac"] = hbm_tbs / HBM_PEAK_TBPS
-        roofline["nearest_roof"] = ("hbm" if roofline["hbm_frac"] > roofline["frac_executed"] else "fp64")
-        # VERDICT r3 / ADVICE r3: the label follows the measured nearer roof; achieved / peak / frac stay SURVEY 8(d)'s
-        # algorithmic fp64 figure (what the judge recomputes), the HBM side is hbm_achieved_TBps / hbm_frac
-        roofline["bound"] = "hbm" if roofline["nearest_roof"] == "hbm" else "mfma"
-        roofline["note"] = ("bound / achieved / frac price the ALGORITHMIC flops of SURVEY 8(d) (leaf edges as dense products); the kernel "
-                            "executes frac_executed of the fp64 peak in matrix products and moves `traffic` bytes = hbm_frac of the 8 TB/s "
-                            "HBM spec (its per-site intermediate state and the operator stream, DESIGN.md 4.1)")
-
     out = dict(metric="site-pair coevolution statistics/s (incl. null sims)", value=value,
                unit="site-pair statistics/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
                ms_per_step=ms_per_step, higher_is_better=True, scaling=w["scaling"], vs_baseline=None, dtype="f64",
@@ -404,13 +413,74 @@ def main():
                            walk_per_pass=dict(products=info["products_per_pass"], leaf_ops=info["leaf_ops_per_pass"],
                                               ws_loads=info["ws_loads_per_pass"], ws_stores=info["ws_stores_per_pass"],
                                               cherry_tables=info["cherry_tables"], products_null=info["products_per_pass_null"],
-                                              leaf_ops_null=info["leaf_ops_per_pass_null"])),
-               roofline=roofline)
+                                              leaf_ops_null=info["leaf_ops_per_pass_null"])))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ana, last, args.pair_output, row_begin, row_end, n_local,
+                     f".rank{rank}" if world > 1 else "")
+
+    if args.full:
+        # roofline of the dominant kernel (map_kernel<S, null>): HIP events on the launch stream
+        null_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+        alg, exe = flops_per_site(info, eng.B, eng.C, eng.S, eng.K, null=nrep_total > 0)
+        sites_per_launch = 2 * n_local if nrep_total else w["nsites"]
+        achieved = sites_per_launch * alg / (null_ms * 1e-3) / 1e12
+        ach_exe = sites_per_launch * exe / (null_ms * 1e-3) / 1e12
+        # `achieved` / `frac` follow SURVEY 8(d): ALGORITHMIC flops (7 B C S^2 per site, leaf edges counted as dense
+        # products) / time / peak.  `frac_executed` counts only the matrix products the kernel issues (leaf edges are row
+        # gathers, sibling messages are stored instead of recomputed): the matrix pipe's duty, always lower.
+        sim_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_sim])) if nrep_total else 0.0
+        kname = f"map_kernel<{eng.S},null>" if nrep_total else f"map_kernel<{eng.S},observed> (+ map_finalize_kernel when class-split)"
+        roofline = dict(bound="mfma", kernel=kname, achieved=achieved, peak=FP64_PEAK_TFLOPS,
+                        unit="TFLOP/s", frac=achieved / FP64_PEAK_TFLOPS, traffic=None,
+                        launch_ms=null_ms, simulate_ms=sim_ms, sites_per_launch=sites_per_launch, flops_per_site_algorithmic=alg,
+                        flops_per_site_executed=exe, achieved_executed=ach_exe, frac_executed=ach_exe / FP64_PEAK_TFLOPS)
+        # what is left of a step besides the simulator and the null's mapping launch: at N = 1 the observed stage (null sort +
+        # index, Gram, p-value lookup, filters, compacted rows; the observed alignment's mapping runs beside the null); at N > 1
+        # the all-gather too
+        roofline["rest_of_step_ms"] = ms_per_step - null_ms - sim_ms
+        if nrep_total:
+            # In the timed steps the observed alignment's mapping and the observed pairs' Gram run on the side stream beside this
+            # launch and share its CUs (they cost a protein null nothing measurable, the short nucleotide null of cfg4 up to a
+            # tenth).  Outside the timed region: the same launch with nothing beside it -- the kernel's own figure.
+            roofline["concurrent_in_timed_steps"] = "observed mapping + observed pairs' Gram (side stream)"
+            torch.cuda.synchronize()
+            ev_alone = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(2)]
+            for e2 in ev_alone:
+                ana.null_distribution(w["seed"] + 7, rep_begin, rep_end, ram, map_events=e2)
+            torch.cuda.synchronize()
+            alone_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_alone]))
+            roofline["launch_ms_alone"] = alone_ms
+            roofline["frac_alone"] = sites_per_launch * alg / (alone_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS
+        for tf in sorted(glob.glob(os.path.join(ROOT, "profiles", "traffic_r*.json")), reverse=True):
+            try:
+                t = json.load(open(tf))
+                if t.get("kernel_source_sha") == kernel_source_sha() and args.workload in t:
+                    # per-launch bytes measured at N = 1; a sharded launch maps fewer sites (the traffic is per-site state)
+                    ref_sites = t.get("sites_per_launch", {}).get(args.workload, sites_per_launch)
+                    roofline["traffic"] = t[args.workload] * sites_per_launch / ref_sites
+                    roofline["traffic_source"] = os.path.relpath(tf, ROOT)
+                    break
+            except Exception:
+                pass
+        # next to the contract's algorithmic figure, say which roof the kernel really sits nearer to -- the fraction
+        # of the fp64 pipe it keeps busy (executed flops) against the fraction of the HBM rate its measured bytes take
+        if roofline["traffic"] is not None:
+            hbm_tbs = roofline["traffic"] / (null_ms * 1e-3) / 1e12
+            roofline["hbm_achieved_TBps"] = hbm_tbs
+            roofline["hbm_frac"] = hbm_tbs / HBM_PEAK_TBPS
+            roofline["nearest_roof"] = ("hbm" if roofline["hbm_frac"] > roofline["frac_executed"] else "fp64")
+            # VERDICT r3 / ADVICE r3: the label follows the measured nearer roof; achieved / peak / frac stay SURVEY 8(d)'s
+            # algorithmic fp64 figure (the contract's figure), the HBM side is hbm_achieved_TBps / hbm_frac
+            roofline["bound"] = "hbm" if roofline["nearest_roof"] == "hbm" else "mfma"
+            roofline["note"] = ("bound / achieved / frac price the ALGORITHMIC flops of SURVEY 8(d) (leaf edges as dense products); the kernel "
+                                "executes frac_executed of the fp64 peak in matrix products and moves `traffic` bytes = hbm_frac of the 8 TB/s "
+                                "HBM spec (its per-site intermediate state and the operator stream, DESIGN.md 4.1)")
+        out["roofline"] = roofline
 
     # same step, host memory to host memory (SURVEY 8(d) / BASELINE.md section 3: the contract's clock; never `value`): the
     # alignment is uploaded inside the timed region and the statistic + p-value information of every pair ends in (pinned)
     # host memory.  Same --steps / --warmup as the headline.
-    if not args.no_host and world == 1:
+    if args.full and not args.no_host and world == 1:
         h_aln = torch.from_numpy(aln_h).pin_memory()
         d_in = torch.empty_like(d_aln)
         npairs_rank = sum_pairs(w["nsites"], row_begin, row_end)
@@ -470,12 +540,12 @@ def main():
             del rows_h, rec
         del hs, h_aln, d_in, h_site
 
-    if rank == 0:
+    if args.full and rank == 0:
         if args.no_cpu_baseline or world > 1:   # CPU baseline: rank 0 at N = 1 only
             out["cpu_baseline"] = None
         else:
             out["cpu_baseline"] = cpu_baseline(w, parent, blen, lot, mdl, Bk, clamp, nrep_total)
-    if not args.no_mica:
+    if args.full and not args.no_mica:
         del ana
         torch.cuda.empty_cache()
         out["mica_cfg5"] = mica_leg(dev, max(3, args.steps), world, rank, rehearsal)
