@@ -9,59 +9,9 @@ import pytest
 import oracle
 from comap_amd import engine, synthetic
 from conftest import rel_close
+from tree_shapes import _balanced, _caterpillar
 
 pytestmark = pytest.mark.gpu
-
-
-def _balanced(ntaxa):
-    """perfectly balanced rooted binary tree, leaves first (post-order with the root last): every leaf sits in a cherry"""
-    nodes, parent = list(range(ntaxa)), {}
-    nxt = ntaxa
-    level = nodes
-    while len(level) > 1:
-        up = []
-        for k in range(0, len(level) - 1, 2):
-            parent[level[k]] = parent[level[k + 1]] = nxt
-            up.append(nxt)
-            nxt += 1
-        if len(level) % 2:
-            up.append(level[-1])
-        level = up
-    nn = nxt
-    # renumber in post-order (children before parents, root last)
-    kids = {}
-    for c, p in parent.items():
-        kids.setdefault(p, []).append(c)
-    order = []
-
-    def visit(n):
-        for c in kids.get(n, []):
-            visit(c)
-        order.append(n)
-    visit(level[0])
-    new = {old: i for i, old in enumerate(order)}
-    par = np.full(nn, -1, dtype=np.int32)
-    for c, p in parent.items():
-        par[new[c]] = new[p]
-    lot = np.array([new[t] for t in range(ntaxa)], dtype=np.int32)
-    return par, lot
-
-
-def _caterpillar(ntaxa):
-    """((((t0, t1), t2), t3) ...): one cherry at the bottom, every other leaf pendant"""
-    nn = 2 * ntaxa - 1
-    par = np.full(nn, -1, dtype=np.int32)
-    lot = np.zeros(ntaxa, dtype=np.int32)
-    # post-order: t0, t1, i0, t2, i1, t3, i2, ...
-    lot[0], lot[1] = 0, 1
-    par[0] = par[1] = 2
-    cur = 2
-    for t in range(2, ntaxa):
-        leaf, inner = cur + 1, cur + 2
-        lot[t] = leaf
-        par[cur] = par[leaf] = inner
-        cur = inner
-    return par, lot
 
 
 @pytest.mark.parametrize("shape,ntaxa", [("balanced", 16), ("balanced", 13), ("caterpillar", 9), ("random", 40)])

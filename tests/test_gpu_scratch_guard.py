@@ -180,3 +180,52 @@ def test_guard_switched_on_after_buffers_exist():
         _clean(eng)
     finally:
         engine.scratch_guard(True)
+
+
+TINY = ["(x,x)", "((x,x),x)", "(x,x,x)", "((x,x),(x,x))", "(((x,x),x),x)", "unrooted6"]
+
+
+@pytest.mark.parametrize("nstates", [20, 4])
+@pytest.mark.parametrize("name", TINY)
+def test_tiny_trees_observed_pipeline_and_fused_null_under_the_guard(name, nstates):
+    """2..6 leaves (VERDICT's unexplained abort was a 3-6 taxon null): op streams of a handful of entries, empty load
+    schedules, zero to two cherries -- the fused null on simulated and on supplied alignments (the table walk for S = 4)"""
+    from tree_shapes import by_name, catalogue
+    shape = by_name(name, catalogue(2, 6))
+    blen = dict(shape.blen_variants())["sat5"]
+    mdl = synthetic.protein_model(0.5, 4) if nstates == 20 else synthetic.dna_model(0.7, 4)
+    case = dict(parent=shape.parent, blen=blen, lot=shape.lot, **mdl)
+    eng, om = _eng(case), _om(case)
+    aln, _ = oracle.simulate(om, 3, 0, 83)
+    m = eng.map_sites(aln)
+    rel_close(m["counts"], oracle.map_sites(om, aln)["counts"], 1e-6, 1e-12)
+    st = eng.pair_stats(0, m["counts"])
+    nl = eng.null_intra(0, 17, 2, 7, 37)                    # 5 replicates of 37 sites
+    o = oracle.null_intra(om, 0, 17, 2, 7, 37)
+    rel_close(nl["nmin"], o["nmin"], 1e-6)
+    assert np.array_equal(nl["rcmin"], o["rcmin"])
+    eng.intra_pvalues(st, m["norm"], 5, nl["stat"], nl["nmin"])
+    rows, total = eng.intra_rows(0, m["counts"], m["rate_class"], m["post_rate"], m["norm"], nl["stat"], nl["nmin"], 5)
+    assert total == 83 * 82 // 2 == len(rows)
+    few, total = eng.intra_rows(0, m["counts"], m["rate_class"], m["post_rate"], m["norm"], nl["stat"], nl["nmin"], 5, capacity=19)
+    assert len(few) == 19 and total == 83 * 82 // 2
+    sup = np.stack([np.stack([oracle.simulate(om, 5, (r * 2 + h) * 21, 21)[0] for h in range(2)]) for r in range(3)])
+    eng.null_intra(1, 0, 0, 3, 21, supplied=sup)
+    _clean(eng)
+
+
+def test_tiny_tree_unfused_nulls_under_the_guard():
+    """the unfused sequence (bounds statistic; nijt.average = no) on the 2- and 3-leaf rooted trees"""
+    from tree_shapes import by_name, catalogue
+    shapes = catalogue(2, 3)
+    mdl = synthetic.dna_model(0.7, 4)
+    for name in ("(x,x)", "((x,x),x)"):
+        shape = by_name(name, shapes)
+        case = dict(parent=shape.parent, blen=dict(shape.blen_variants())["sat5"], lot=shape.lot, **mdl)
+        eng = _eng(case)
+        bounds = np.array([-0.5, 0.02, 0.1, 0.3, 1.0, 1e4])
+        nl = eng.null_intra(engine.STAT_DISCRETE_MI_BOUNDS, 3, 1, 4, 45, threshold=bounds)     # 3 replicates of 45
+        assert nl["stat"].shape == (135,)
+        eng.set_mapping_options(False, True)
+        eng.null_intra(engine.STAT_CORRELATION, 3, 0, 3, 29)
+        _clean(eng)
