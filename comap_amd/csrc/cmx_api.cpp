@@ -94,6 +94,10 @@ struct cmx_ctx {
   bool leaf_rows_custom = false;   // the leaf operators' ambiguity rows were built from a caller's mask table
   bool map_average = true;         // nijt.average (cmx_set_mapping_options); false: the no-averaging mapping of cmx_variants.hip
   bool map_joint = true;           // nijt.joint; false: the ...Marginal variants of cmx_variants.hip
+  // Statistic::setWeights (cmx_set_statistic_weights): the normalised branch weights, host copy + device copy (B doubles,
+  // allocated at the first set); empty = unweighted
+  std::vector<double> stat_w;
+  double* d_stat_w = nullptr;
   // Mica's permutation test: host-side sources of its asynchronous table uploads (they must outlive the copies, also
   // when a later call fails), and which (L, taxa, shift) the fixed-point table F on the device was built for
   std::vector<long long> perm_dF_host, perm_F_host;
@@ -411,6 +415,7 @@ void cmx_ctx_destroy(cmx_ctx* ctx) {
   if (guard_on() && hipSetDevice(ctx->device) == hipSuccess && hipDeviceSynchronize() == hipSuccess)
     (void)guard_verify_all(ctx);   // destroy cannot fail: findings go to stderr and to cmx_debug_scratch_guard_failures
   for (void* p : ctx->model_allocs) (void)hipFree(p);
+  if (ctx->d_stat_w) (void)hipFree(ctx->d_stat_w);
   for (auto& kv : ctx->scratch) if (kv.second.p) (void)hipFree(kv.second.p);
   for (Workspace* ws : {&ctx->ws, &ctx->ws_obs}) {
     if (ws->D) (void)hipFree(ws->D);
@@ -700,6 +705,65 @@ cmx_status cmx_set_mapping_options(cmx_ctx* ctx, int average, int joint) {
   return CMX_OK;
 }
 
+// Statistic::setWeights / deleteWeights (CoMap/Statistics.h:83-104, 135-140): stored divided by their sum, in the
+// reference's summation order.  Validated before any device work; the device copy is written once here, after the
+// device has drained (a kernel of an earlier call on any stream may still read the previous weights).
+cmx_status cmx_set_statistic_weights(cmx_ctx* ctx, const double* w, size_t nbranches) {
+  cmx_status s = need_model(ctx);
+  if (s != CMX_OK) return s;
+  std::vector<double> wn;
+  if (w) {
+    if (nbranches != (size_t)ctx->hm.B)
+      return fail(ctx, CMX_ERR_INVALID, "cmx_set_statistic_weights: " + std::to_string(nbranches) + " weights for " +
+                                            std::to_string(ctx->hm.B) + " branches (DimensionException)");
+    double sum = 0.0;
+    for (size_t b = 0; b < nbranches; ++b) {
+      if (!std::isfinite(w[b]))
+        return fail(ctx, CMX_ERR_INVALID, "cmx_set_statistic_weights: weight " + std::to_string(b) + " is not finite");
+      if (w[b] < 0.0)
+        return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_set_statistic_weights: weight " + std::to_string(b) + " is negative");
+      sum += w[b];
+    }
+    if (!(sum > 0.0) || !std::isfinite(sum))
+      return fail(ctx, CMX_ERR_INVALID, "cmx_set_statistic_weights: the weights must have a positive, finite sum");
+    wn.resize(nbranches);
+    for (size_t b = 0; b < nbranches; ++b) wn[b] = w[b] / sum;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_stat_w) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_stat_w, sizeof(double) * ctx->hm.B));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(ctx->d_stat_w, wn.data(), sizeof(double) * nbranches, hipMemcpyHostToDevice));
+  }
+  ctx->stat_w.swap(wn);
+  ctx->gram_kept.valid = false;   // kept Gram blocks were scored with the previous weights
+  return CMX_OK;
+}
+
+cmx_status cmx_get_statistic_weights(const cmx_ctx* ctx, double* w_out, int32_t* has_weights) {
+  if (!ctx || !has_weights) return CMX_ERR_INVALID;
+  *has_weights = ctx->stat_w.empty() ? 0 : 1;
+  if (w_out) std::copy(ctx->stat_w.begin(), ctx->stat_w.end(), w_out);
+  return CMX_OK;
+}
+
+// the context's weights on the device when `kind` uses them (DESIGN A.7, weighted), else null.  Cosubstitution, the
+// discrete MI kinds and the scalar product ignore them as the reference does (Statistics.h:230-245, 307-327).
+static const double* stat_weights(const cmx_ctx* ctx, int kind) {
+  if (ctx->stat_w.empty()) return nullptr;
+  switch (kind) {
+    case CMX_STAT_CORRELATION: case CMX_STAT_CORRECTED_CORRELATION: case CMX_STAT_COVARIANCE: case CMX_STAT_COSINUS:
+    case CMX_STAT_COMPENSATION: case CMX_STAT_EUCLIDIAN_DISTANCE:
+      return ctx->d_stat_w;
+  }
+  return nullptr;
+}
+// the epilogue of pair_gram_kernel for `kind` (after CorrectedCorrelation -> Correlation): a weighted operand
+// (pair_prep_kernel with w) carries the weights already, so weighted correlation is g / sqrt(s_i s_j) -- the Cosinus
+// epilogue -- and weighted covariance is g -- the scalar product's: no (B-1) factors
+static int gram_kind(int gk, const double* d_w) {
+  if (!d_w) return gk;
+  return gk == CMX_STAT_CORRELATION ? CMX_STAT_COSINUS : gk == CMX_STAT_COVARIANCE ? CMX_STAT_SCALAR_PRODUCT : gk;
+}
+
 // the simulator's counter layout (cmx_kernels.hip philox_uniform): 47 bits of simulated-site index, 17 bits of draw index
 static cmx_status rng_range(cmx_ctx* ctx, uint64_t g_end, const char* who) {
   if (g_end > (1ull << 47) || (uint64_t)ctx->hm.nn + 2 > (1ull << 17))
@@ -871,21 +935,22 @@ cmx_status cmx_pair_stats_dev(cmx_ctx* ctx, int kind, const double* params, cons
   const double* d_mean = nullptr;
   if ((s = stat_mean_vectors(ctx, kind, params, &d_mean, stream)) != CMX_OK) return s;
   const int gk = kind == CMX_STAT_CORRECTED_CORRELATION ? CMX_STAT_CORRELATION : kind;   // same Gram + epilogue
+  const double* d_w = stat_weights(ctx, kind);
   const int Bp = (h.B + 3) / 4 * 4;
   const size_t ldx1 = (n1 + 15) / 16 * 16, ldx2 = (n2 + 15) / 16 * 16;
   double *X1, *s1, *r1, *X2, *s2, *r2;
   if ((s = scratch(ctx, "pair_X1", sizeof(double) * Bp * ldx1, (void**)&X1)) != CMX_OK) return s;
   if ((s = scratch(ctx, "pair_s1", sizeof(double) * n1, (void**)&s1)) != CMX_OK) return s;
   if ((s = scratch(ctx, "pair_r1", sizeof(double) * n1, (void**)&r1)) != CMX_OK) return s;
-  HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts1, n1, ld1, h.B, h.K, X1, ldx1, Bp, s1, r1, d_mean, st));
+  HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts1, n1, ld1, h.B, h.K, X1, ldx1, Bp, s1, r1, d_mean, st, 0, d_w));
   if (intra) { X2 = X1; s2 = s1; r2 = r1; }
   else {
     if ((s = scratch(ctx, "pair_X2", sizeof(double) * Bp * ldx2, (void**)&X2)) != CMX_OK) return s;
     if ((s = scratch(ctx, "pair_s2", sizeof(double) * n2, (void**)&s2)) != CMX_OK) return s;
     if ((s = scratch(ctx, "pair_r2", sizeof(double) * n2, (void**)&r2)) != CMX_OK) return s;
-    HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts2, n2, ld2, h.B, h.K, X2, ldx2, Bp, s2, r2, d_mean ? d_mean + h.B : nullptr, st));
+    HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts2, n2, ld2, h.B, h.K, X2, ldx2, Bp, s2, r2, d_mean ? d_mean + h.B : nullptr, st, 0, d_w));
   }
-  HIP_TRY(ctx, launch_pair_gram(gk, h.B, Bp, X1, s1, r1, n1, ldx1, X2, s2, r2, n2, intra ? ldx1 : ldx2, intra ? 1 : 0,
+  HIP_TRY(ctx, launch_pair_gram(gram_kind(gk, d_w), h.B, Bp, X1, s1, r1, n1, ldx1, X2, s2, r2, n2, intra ? ldx1 : ldx2, intra ? 1 : 0,
                                 d_out, ldo, st));
   return CMX_OK;
 }
@@ -1024,10 +1089,11 @@ cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint
   if ((s = check_kind(ctx, kind)) != CMX_OK) return s;
   if (rep_end <= rep_begin || rep_ram == 0 || !d_stat) return fail(ctx, CMX_ERR_INVALID, "cmx_null_intra: bad arguments");
   if ((s = rng_range(ctx, (uint64_t)rep_end * 2 * rep_ram, "cmx_null_intra")) != CMX_OK) return s;
-  if (!ctx->map_average || !ctx->map_joint || kind == CMX_STAT_DISCRETE_MI_BOUNDS || ctx->hm.plain) {
+  if (!ctx->map_average || !ctx->map_joint || kind == CMX_STAT_DISCRETE_MI_BOUNDS || ctx->hm.plain || stat_weights(ctx, kind)) {
     // nijt.average = no (AnalysisTools.cpp:598-610): the fused kernel only knows the averaged mapping; and a statistic that
     // needs a joint table per pair cannot be evaluated per lane inside the mapping wave.  The same simulate -> map ->
-    // score sequence then runs unfused, which is what the two-data-set null does with both sides equal.
+    // score sequence then runs unfused, which is what the two-data-set null does with both sides equal.  So does a
+    // statistic with branch weights (map_kernel's lanes score unweighted only).
     return null_unfused_dev(ctx, ctx, kind, params, seed, rep_begin, rep_end, rep_ram, d_supplied, d_stat, d_rcmin, d_prmin, d_nmin, stream);
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1225,8 +1291,9 @@ static cmx_status null_unfused_dev(cmx_ctx* ctx1, cmx_ctx* ctx2, int kind, const
   const double param = (kind == CMX_STAT_DISCRETE_MI) ? (params ? params[0] : 0.99) : 0.0;
   const double* d_mean = nullptr;
   if ((s = stat_mean_vectors(ctx1, kind, params, &d_mean, stream)) != CMX_OK) return s;
+  // branch weights: ctx1's (the reference scores both data sets with one Statistic object, AnalysisTools.cpp:728)
   HIP_TRY(ctx1, launch_pair_diag(kind, param, ctx1->hm.B, ctx1->hm.K, cnt[0], n, cnt[1], n, n, rc[0], rc[1], pr[0], pr[1],
-                                 nm[0], nm[1], d_stat, d_rcmin, d_prmin, d_nmin, d_mean, st));
+                                 nm[0], nm[1], d_stat, d_rcmin, d_prmin, d_nmin, d_mean, st, stat_weights(ctx1, kind)));
   return CMX_OK;
 }
 
@@ -1393,6 +1460,7 @@ cmx_status cmx_intra_rows_range_dev(cmx_ctx* ctx, int kind, const double* params
   const double* d_mean = nullptr;
   if ((s = stat_mean_vectors(ctx, kind, params, &d_mean, stream)) != CMX_OK) return s;
   const int gk = kind == CMX_STAT_CORRECTED_CORRELATION ? CMX_STAT_CORRELATION : kind;
+  const double* d_w = stat_weights(ctx, kind);
   const int Bp = (h.B + 3) / 4 * 4;
   const size_t ldx = (n + 15) / 16 * 16;
   double *X = nullptr, *sv = nullptr, *rv = nullptr;
@@ -1407,7 +1475,7 @@ cmx_status cmx_intra_rows_range_dev(cmx_ctx* ctx, int kind, const double* params
     if ((s = scratch(ctx, "pair_X1", sizeof(double) * Bp * ldx, (void**)&X)) != CMX_OK) return s;
     if ((s = scratch(ctx, "pair_s1", sizeof(double) * n, (void**)&sv)) != CMX_OK) return s;
     if ((s = scratch(ctx, "pair_r1", sizeof(double) * n, (void**)&rv)) != CMX_OK) return s;
-    HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts, n, ldc, h.B, h.K, X, ldx, Bp, sv, rv, d_mean, st));
+    HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts, n, ldc, h.B, h.K, X, ldx, Bp, sv, rv, d_mean, st, 0, d_w));
   }
   NullTable nt{};
   if (with_null && (s = prepare_null(ctx, d_norm, n, nclasses, d_null_stat, d_null_nmin, nnull, st, &nt)) != CMX_OK) return s;
@@ -1428,7 +1496,7 @@ cmx_status cmx_intra_rows_range_dev(cmx_ctx* ctx, int kind, const double* params
     const size_t rb = std::min(RB, row_end - i0);
     if (gk == CMX_STAT_EUCLIDIAN_DISTANCE) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_intra_rows_range: EuclidianDistance is a distance, not a statistic");
     if (mcls) HIP_TRY(ctx, launch_mi_pairs_block(h.B, mcls + i0, mbad + i0, rb, mldx, mcls, mbad, n, mldx, 2, blk_stat, n, i0, st));
-    else HIP_TRY(ctx, launch_pair_gram(gk, h.B, Bp, X + i0, sv + i0, rv + i0, rb, ldx, X, sv, rv, n, ldx, 2, blk_stat, n, st, 1, 0, 0, 0, i0));
+    else HIP_TRY(ctx, launch_pair_gram(gram_kind(gk, d_w), h.B, Bp, X + i0, sv + i0, rv + i0, rb, ldx, X, sv, rv, n, ldx, 2, blk_stat, n, st, 1, 0, 0, 0, i0));
     HIP_TRY(ctx, launch_pair_rows(blk_stat, n, nullptr, nullptr, n, d_rate_class, d_post_rate, d_norm, f, rowcount, tmp, tmp_bytes,
                                   d_rows, capacity, reinterpret_cast<unsigned long long*>(d_count), st, i0, rb,
                                   reinterpret_cast<unsigned long long*>(d_count), with_null ? &nt : nullptr));
@@ -1468,10 +1536,11 @@ cmx_status cmx_intra_gram_prefetch_dev(cmx_ctx* ctx, int kind, const double* d_c
   if ((s = scratch(ctx, "gram_s1", sizeof(double) * n, (void**)&sv)) != CMX_OK) return s;
   if ((s = scratch(ctx, "gram_r1", sizeof(double) * n, (void**)&rv)) != CMX_OK) return s;
   if ((s = scratch(ctx, "gram_kept", sizeof(double) * nblk * RB * n, (void**)&kept)) != CMX_OK) return s;
-  HIP_TRY(ctx, launch_pair_prep(kind, 0.0, d_counts, n, ldc, h.B, h.K, X, ldx, Bp, sv, rv, nullptr, st));
+  const double* d_w = stat_weights(ctx, kind);
+  HIP_TRY(ctx, launch_pair_prep(kind, 0.0, d_counts, n, ldc, h.B, h.K, X, ldx, Bp, sv, rv, nullptr, st, 0, d_w));
   for (size_t i0 = row_begin; i0 < row_end; i0 += RB) {
     const size_t rb = std::min(RB, row_end - i0);
-    HIP_TRY(ctx, launch_pair_gram(kind, h.B, Bp, X + i0, sv + i0, rv + i0, rb, ldx, X, sv, rv, n, ldx, 2, kept + (i0 - row_begin) * n, n, st, 1, 0, 0, 0, i0));
+    HIP_TRY(ctx, launch_pair_gram(gram_kind(kind, d_w), h.B, Bp, X + i0, sv + i0, rv + i0, rb, ldx, X, sv, rv, n, ldx, 2, kept + (i0 - row_begin) * n, n, st, 1, 0, 0, 0, i0));
   }
   ctx->gram_kept = {true, kind, d_counts, n, ldc, row_begin, row_end, kept};
   return CMX_OK;
@@ -1492,6 +1561,7 @@ cmx_status cmx_intra_compact_range_dev(cmx_ctx* ctx, int kind, const double* par
   if (h.B < 2) return fail(ctx, CMX_ERR_INVALID, "cmx_intra_compact_range: need at least two branches");
   const int gk = kind == CMX_STAT_CORRECTED_CORRELATION ? CMX_STAT_CORRELATION : kind;
   if (gk == CMX_STAT_EUCLIDIAN_DISTANCE) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_intra_compact_range: EuclidianDistance is a distance, not a statistic");
+  const double* d_w = stat_weights(ctx, kind);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   if (row_begin == row_end) return CMX_OK;
@@ -1520,7 +1590,7 @@ cmx_status cmx_intra_compact_range_dev(cmx_ctx* ctx, int kind, const double* par
     if ((s = scratch(ctx, "pair_X1", sizeof(double) * Bp * ldx, (void**)&X)) != CMX_OK) return s;
     if ((s = scratch(ctx, "pair_s1", sizeof(double) * n, (void**)&sv)) != CMX_OK) return s;
     if ((s = scratch(ctx, "pair_r1", sizeof(double) * n, (void**)&rv)) != CMX_OK) return s;
-    HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts, n, ldc, h.B, h.K, X, ldx, Bp, sv, rv, d_mean, st));
+    HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts, n, ldc, h.B, h.K, X, ldx, Bp, sv, rv, d_mean, st, 0, d_w));
   }
   NullTable nt{};
   if (with_null && (s = prepare_null(ctx, d_norm, n, nclasses, d_null_stat, d_null_nmin, nnull, st, &nt)) != CMX_OK) return s;
@@ -1532,7 +1602,7 @@ cmx_status cmx_intra_compact_range_dev(cmx_ctx* ctx, int kind, const double* par
     const double* blk = kept ? kept + (i0 - row_begin) * n : blk_stat;
     if (kept) {
     } else if (mcls) HIP_TRY(ctx, launch_mi_pairs_block(h.B, mcls + i0, mbad + i0, rb, mldx, mcls, mbad, n, mldx, 2, blk_stat, n, i0, st));
-    else HIP_TRY(ctx, launch_pair_gram(gk, h.B, Bp, X + i0, sv + i0, rv + i0, rb, ldx, X, sv, rv, n, ldx, 2, blk_stat, n, st, 1, 0, 0, 0, i0));
+    else HIP_TRY(ctx, launch_pair_gram(gram_kind(gk, d_w), h.B, Bp, X + i0, sv + i0, rv + i0, rb, ldx, X, sv, rv, n, ldx, 2, blk_stat, n, st, 1, 0, 0, 0, i0));
     HIP_TRY(ctx, launch_pair_compact(blk, n, n, d_norm, with_null ? &nt : nullptr, d_out, capacity, st, i0, rb, row_begin));
   }
   return CMX_OK;
@@ -1670,7 +1740,7 @@ cmx_status cmx_inter_rows_dev(cmx_ctx* ctx, int kind, const double* params, cons
       const double* d_mean = nullptr;
       if ((s = stat_mean_vectors(ctx, kind, params, &d_mean, stream)) != CMX_OK) return s;
       HIP_TRY(ctx, launch_pair_diag(kind, param, h.B, h.K, d_counts1, ld1, d_counts2, ld2, n1, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                    nullptr, dstat, nullptr, nullptr, nullptr, d_mean, st));
+                                    nullptr, dstat, nullptr, nullptr, nullptr, d_mean, st, stat_weights(ctx, kind)));
     }
     if ((s = scratch(ctx, "rows_count", sizeof(unsigned long long) * (n1 + 1), (void**)&rowcount)) != CMX_OK) return s;
     HIP_TRY(ctx, launch_inter_rows(dstat, 1, n2, d_rc1, d_pr1, d_nm1, d_rc2, d_pr2, d_nm2, f, rowcount, nullptr, tmp_bytes, d_rows, capacity,
@@ -1685,6 +1755,7 @@ cmx_status cmx_inter_rows_dev(cmx_ctx* ctx, int kind, const double* params, cons
   const double param = (kind == CMX_STAT_DISCRETE_MI) ? (params ? params[0] : 0.99) : 0.0;
   const double* d_mean = nullptr;
   const int gk = kind == CMX_STAT_CORRECTED_CORRELATION ? CMX_STAT_CORRELATION : kind;
+  const double* d_w = stat_weights(ctx, kind);
   const int Bp = (h.B + 3) / 4 * 4;
   const size_t ldx1 = (n1 + 15) / 16 * 16, ldx2 = (n2 + 15) / 16 * 16;
   double *X1 = nullptr, *s1 = nullptr, *r1 = nullptr, *X2 = nullptr, *s2 = nullptr, *r2 = nullptr;
@@ -1704,8 +1775,8 @@ cmx_status cmx_inter_rows_dev(cmx_ctx* ctx, int kind, const double* params, cons
     if ((s = scratch(ctx, "pair_X2", sizeof(double) * Bp * ldx2, (void**)&X2)) != CMX_OK) return s;
     if ((s = scratch(ctx, "pair_s2", sizeof(double) * n2, (void**)&s2)) != CMX_OK) return s;
     if ((s = scratch(ctx, "pair_r2", sizeof(double) * n2, (void**)&r2)) != CMX_OK) return s;
-    HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts1, n1, ld1, h.B, h.K, X1, ldx1, Bp, s1, r1, d_mean, st));
-    HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts2, n2, ld2, h.B, h.K, X2, ldx2, Bp, s2, r2, d_mean ? d_mean + h.B : nullptr, st));
+    HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts1, n1, ld1, h.B, h.K, X1, ldx1, Bp, s1, r1, d_mean, st, 0, d_w));
+    HIP_TRY(ctx, launch_pair_prep(gk, param, d_counts2, n2, ld2, h.B, h.K, X2, ldx2, Bp, s2, r2, d_mean ? d_mean + h.B : nullptr, st, 0, d_w));
   }
   size_t RB = ((size_t)256 << 20) / (8 * n2) / 64 * 64;
   RB = std::max<size_t>(64, std::min<size_t>(RB, (n1 + 63) / 64 * 64));
@@ -1718,7 +1789,7 @@ cmx_status cmx_inter_rows_dev(cmx_ctx* ctx, int kind, const double* params, cons
   for (size_t i0 = 0; i0 < n1; i0 += RB) {
     const size_t rb = std::min(RB, n1 - i0);
     if (mi) HIP_TRY(ctx, launch_mi_pairs_block(h.B, c1 + i0, b1 + i0, rb, lx1, c2, b2, n2, lx2, 0, blk, n2, i0, st));
-    else HIP_TRY(ctx, launch_pair_gram(gk, h.B, Bp, X1 + i0, s1 + i0, r1 + i0, rb, ldx1, X2, s2, r2, n2, ldx2, 0, blk, n2, st));
+    else HIP_TRY(ctx, launch_pair_gram(gram_kind(gk, d_w), h.B, Bp, X1 + i0, s1 + i0, r1 + i0, rb, ldx1, X2, s2, r2, n2, ldx2, 0, blk, n2, st));
     HIP_TRY(ctx, launch_inter_rows(blk, n2, n2, d_rc1, d_pr1, d_nm1, d_rc2, d_pr2, d_nm2, f, rowcount, tmp, tmp_bytes, d_rows, capacity,
                                    reinterpret_cast<unsigned long long*>(d_count), st, i0, rb, reinterpret_cast<unsigned long long*>(d_count)));
   }
@@ -2035,7 +2106,7 @@ cmx_status cmx_group_stats_dev(cmx_ctx* ctx, int kind, const double* params, con
   const double* d_mean = nullptr;
   if ((s = stat_mean_vectors(ctx, kind, params, &d_mean, stream)) != CMX_OK) return s;
   HIP_TRY(ctx, launch_group_stats(kind, param, ctx->hm.B, ctx->hm.K, d_counts, ldc, d_offsets, d_sites, ngroups, d_out, d_mean,
-                                  (hipStream_t)stream));
+                                  (hipStream_t)stream, stat_weights(ctx, kind)));
   return CMX_OK;
 }
 
@@ -2567,8 +2638,9 @@ static cmx_status cluster_batch_dev(cmx_ctx* ctx, int dist_kind, int linkage, co
     if ((s = scratch(ctx, "pair_X1", sizeof(double) * Bp * ldx * batch, (void**)&X)) != CMX_OK) return s;
     if ((s = scratch(ctx, "pair_s1", sizeof(double) * N, (void**)&sv)) != CMX_OK) return s;
     if ((s = scratch(ctx, "pair_r1", sizeof(double) * N, (void**)&rv)) != CMX_OK) return s;
-    HIP_TRY(ctx, launch_pair_prep(stat_kind, 0.0, d_counts, N, ldc, h.B, h.K, X, ldx, Bp, sv, rv, nullptr, st, n));
-    HIP_TRY(ctx, launch_pair_gram(stat_kind, h.B, Bp, X, sv, rv, n, ldx, X, sv, rv, n, ldx, 2 /* upper triangle only */, D, n, st,
+    const double* d_w = stat_weights(ctx, stat_kind);   // (the tree's "Stat" property below stays unweighted, Distance.h:403-421)
+    HIP_TRY(ctx, launch_pair_prep(stat_kind, 0.0, d_counts, N, ldc, h.B, h.K, X, ldx, Bp, sv, rv, nullptr, st, n, d_w));
+    HIP_TRY(ctx, launch_pair_gram(gram_kind(stat_kind, d_w), h.B, Bp, X, sv, rv, n, ldx, X, sv, rv, n, ldx, 2 /* upper triangle only */, D, n, st,
                                   batch, n, n * n, (size_t)Bp * ldx));
   }
   HIP_TRY(ctx, launch_dist_finish(dist_kind, D, n, n, n * n, batch, st));

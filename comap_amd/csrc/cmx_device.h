@@ -130,9 +130,10 @@ hipError_t launch_extend_leaf_rows(const DevModel& m, const uint32_t* d_masks, h
 hipError_t launch_pair_diag(int kind, double param, int B, int K, const double* c1, size_t ld1, const double* c2, size_t ld2,
                             size_t n, const int32_t* rc1, const int32_t* rc2, const double* pr1, const double* pr2,
                             const double* nm1, const double* nm2, double* stat, int32_t* rcmin, double* prmin, double* nmin,
-                            const double* d_mean, hipStream_t stream);
+                            const double* d_mean, hipStream_t stream, const double* d_w = nullptr);
 hipError_t launch_group_stats(int kind, double param, int B, int K, const double* d_counts, size_t ld, const int64_t* d_offsets,
-                              const int32_t* d_sites, size_t ngroups, double* d_out, const double* d_mean, hipStream_t stream);
+                              const int32_t* d_sites, size_t ngroups, double* d_out, const double* d_mean, hipStream_t stream,
+                              const double* d_w = nullptr);
 // DiscreteMI with a bounds vector (cmx_stat_mi.hip): class words [B][ldx] (class | marginal count << 16) + per-site
 // out-of-range flags; all-pairs block, diagonal pairs, groups
 hipError_t launch_mi_classify(const double* d_counts, size_t n, size_t ldc, int B, int K, const double* d_bounds, int nb,
@@ -206,7 +207,7 @@ hipError_t launch_simulate_continuous(const DevModel& m, uint64_t seed, uint64_t
                                       uint8_t* d_aln, size_t ld, double* d_rates, uint8_t* d_states, hipStream_t stream);
 hipError_t launch_pair_prep(int kind, double param, const double* d_counts, size_t n, size_t ldc, int B, int K,
                             double* d_X, size_t ldx, int Bp, double* d_s, double* d_r, const double* d_mvec,
-                            hipStream_t stream, size_t blk = 0);
+                            hipStream_t stream, size_t blk = 0, const double* d_w = nullptr);
 hipError_t launch_pair_gram(int kind, int B, int Bp, const double* d_X1, const double* d_s1, const double* d_r1,
                             size_t n1, size_t ldx1, const double* d_X2, const double* d_s2, const double* d_r2,
                             size_t n2, size_t ldx2, int intra, double* d_out, size_t ldo, hipStream_t stream,

@@ -1105,10 +1105,12 @@ __global__ void pair_diag_kernel(int kind, double param, int B, int K, const dou
                                  const int32_t* __restrict__ rc2, const double* __restrict__ pr1,
                                  const double* __restrict__ pr2, const double* __restrict__ nm1,
                                  const double* __restrict__ nm2, double* __restrict__ stat, int32_t* __restrict__ rcmin,
-                                 double* __restrict__ prmin, double* __restrict__ nmin, const double* __restrict__ mv) {
+                                 double* __restrict__ prmin, double* __restrict__ nmin, const double* __restrict__ mv,
+                                 const double* __restrict__ w) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  if (stat) stat[j] = pair_stat_strided(kind, param, B, K, c1 + j, ld1, c2 + j, ld2, mv);
+  if (stat) stat[j] = w ? pair_stat_weighted(kind, param, B, K, c1 + j, ld1, c2 + j, ld2, mv, w)
+                        : pair_stat_strided(kind, param, B, K, c1 + j, ld1, c2 + j, ld2, mv);
   if (rcmin) rcmin[j] = rc1[j] < rc2[j] ? rc1[j] : rc2[j];
   if (prmin) prmin[j] = pr1[j] < pr2[j] ? pr1[j] : pr2[j];
   if (nmin) nmin[j] = nm1[j] < nm2[j] ? nm1[j] : nm2[j];
@@ -1117,19 +1119,21 @@ __global__ void pair_diag_kernel(int kind, double param, int B, int K, const dou
 hipError_t launch_pair_diag(int kind, double param, int B, int K, const double* c1, size_t ld1, const double* c2, size_t ld2,
                             size_t n, const int32_t* rc1, const int32_t* rc2, const double* pr1, const double* pr2,
                             const double* nm1, const double* nm2, double* stat, int32_t* rcmin, double* prmin, double* nmin,
-                            const double* d_mean, hipStream_t stream) {
+                            const double* d_mean, hipStream_t stream, const double* d_w) {
   hipLaunchKernelGGL(pair_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, kind, param, B, K, c1, ld1,
-                     c2, ld2, n, rc1, rc2, pr1, pr2, nm1, nm2, stat, rcmin, prmin, nmin, d_mean);
+                     c2, ld2, n, rc1, rc2, pr1, pr2, nm1, nm2, stat, rcmin, prmin, nmin, d_mean, d_w);
   return hipGetLastError();
 }
 
 // Statistic of a group of sites, Statistic::getValueForGroup: the smallest pairwise value over the group
 // (AbstractMinimumStatistic, CoMap/Statistics.h:121-133) or, for Compensation, the closed form of Statistics.h:267-294.
 // One wave per group; group g owns sites[offsets[g] .. offsets[g+1]) (columns of the branch-major counts).
+// w (or null): normalised branch weights; the Compensation closed form then sums w t^2 (Statistics.h:275-285) as
+// (weight_factor * t)^2, the pairs use pair_stat_weighted.
 __global__ __launch_bounds__(kWave) void group_stat_kernel(int kind, double param, int B, int K, const double* __restrict__ counts,
                                                           size_t ld, const int64_t* __restrict__ offsets,
                                                           const int32_t* __restrict__ sites, double* __restrict__ out,
-                                                          const double* __restrict__ mv) {
+                                                          const double* __restrict__ mv, const double* __restrict__ w) {
   const size_t g = blockIdx.x;
   const int lane = threadIdx.x;
   const int32_t* mem = sites + offsets[g];
@@ -1141,6 +1145,7 @@ __global__ __launch_bounds__(kWave) void group_stat_kernel(int kind, double para
       for (int b = lane; b < B; b += kWave) {
         double t = 0.0;
         for (int k = 0; k < K; ++k) t += counts[((size_t)b * K + k) * ld + mem[j]];
+        if (w) t *= weight_factor(kind, w[b]);
         q += t * t;
       }
       for (int off = 32; off; off >>= 1) q += __shfl_xor(q, off);
@@ -1150,6 +1155,7 @@ __global__ __launch_bounds__(kWave) void group_stat_kernel(int kind, double para
       double t = 0.0;
       for (int j = 0; j < m; ++j)
         for (int k = 0; k < K; ++k) t += counts[((size_t)b * K + k) * ld + mem[j]];
+      if (w) t *= weight_factor(kind, w[b]);
       sq2 += t * t;
     }
     for (int off = 32; off; off >>= 1) sq2 += __shfl_xor(sq2, off);
@@ -1164,7 +1170,8 @@ __global__ __launch_bounds__(kWave) void group_stat_kernel(int kind, double para
     while (i * (i - 1) / 2 > p) --i;
     while ((i + 1) * i / 2 <= p) ++i;
     const int j = p - i * (i - 1) / 2;
-    const double v = pair_stat_strided(kind, param, B, K, counts + mem[i], ld, counts + mem[j], ld, mv);
+    const double v = w ? pair_stat_weighted(kind, param, B, K, counts + mem[i], ld, counts + mem[j], ld, mv, w)
+                       : pair_stat_strided(kind, param, B, K, counts + mem[i], ld, counts + mem[j], ld, mv);
     if (v < best) best = v;
   }
   for (int off = 32; off; off >>= 1) {
@@ -1175,10 +1182,11 @@ __global__ __launch_bounds__(kWave) void group_stat_kernel(int kind, double para
 }
 
 hipError_t launch_group_stats(int kind, double param, int B, int K, const double* d_counts, size_t ld, const int64_t* d_offsets,
-                              const int32_t* d_sites, size_t ngroups, double* d_out, const double* d_mean, hipStream_t stream) {
+                              const int32_t* d_sites, size_t ngroups, double* d_out, const double* d_mean, hipStream_t stream,
+                              const double* d_w) {
   if (ngroups == 0) return hipSuccess;
   hipLaunchKernelGGL(group_stat_kernel, dim3((unsigned)ngroups), dim3(kWave), 0, stream, kind, param, B, K, d_counts, ld,
-                     d_offsets, d_sites, d_out, d_mean);
+                     d_offsets, d_sites, d_out, d_mean, d_w);
   return hipGetLastError();
 }
 
@@ -1581,15 +1589,43 @@ hipError_t launch_simulate_continuous(const DevModel& m, uint64_t seed, uint64_t
 // prep: X[b][i] (Bp rows, zero padded) and per-site scalars s (sum of squares) and r (row sum of indicators)
 //   kind 0/4: X = type-0 count - mean;  3: X = type-0 count;  1: X = per-branch total;
 //   2: X = [total >= 1];  5: X = [total >= threshold], r = sum X, s = NaN flag when a total leaves [0, 10000)
+// w (normalised branch weights, or null; kinds 0, 1, 3, 4, 7 only): X_b = weight_factor(kind, w_b) * (the value above),
+// the mean of kind 0/4 is sum w x; the caller then scores kind 0 with the Cosinus epilogue and kind 4 with the scalar
+// product's (no (B-1) factors: DESIGN A.7, weighted)
 __global__ void pair_prep_kernel(int kind, double param, const double* __restrict__ counts, size_t n, size_t ldc, int B,
                                  int K, double* __restrict__ X, size_t ldx, int Bp, double* __restrict__ sv,
-                                 double* __restrict__ rv, const double* __restrict__ mvec /* [B] or null */, size_t blk) {
+                                 double* __restrict__ rv, const double* __restrict__ mvec /* [B] or null */, size_t blk,
+                                 const double* __restrict__ w) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   // blk > 0: the sites are `blk`-site blocks side by side (replicates of the clustering null); every block gets its own
   // [Bp][ldx] operand so that a block's rows stay ldx * 8 bytes apart (not the whole batch's row length: 128 rows
   // 4 MB apart thrash the TLB and land on one L2 channel)
   if (blk) X += (i / blk) * ((size_t)Bp * ldx) - (i / blk) * blk;
+  if (w) {
+    const bool centred = kind == 0 || kind == 4;
+    double mean = 0.0;
+    if (centred)
+      for (int b = 0; b < B; ++b) mean += w[b] * (counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0));
+    double s = 0.0, r = 0.0;
+    for (int b = 0; b < B; ++b) {
+      double v;
+      if (centred) v = counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0) - mean;
+      else if (kind == 3) v = counts[(size_t)b * K * ldc + i];
+      else {
+        v = 0.0;
+        for (int k = 0; k < K; ++k) v += counts[((size_t)b * K + k) * ldc + i];
+      }
+      v *= weight_factor(kind, w[b]);
+      X[(size_t)b * ldx + i] = v;
+      s += v * v;
+      r += v;
+    }
+    for (int b = B; b < Bp; ++b) X[(size_t)b * ldx + i] = 0.0;
+    sv[i] = s;
+    rv[i] = r;
+    return;
+  }
   double mean = 0.0;
   if (kind == 0 || kind == 4) {   // (CorrectedCorrelation arrives as kind 0 with its mean vector in mvec)
     for (int b = 0; b < B; ++b) mean += counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0);
@@ -1622,10 +1658,10 @@ __global__ void pair_prep_kernel(int kind, double param, const double* __restric
 
 hipError_t launch_pair_prep(int kind, double param, const double* d_counts, size_t n, size_t ldc, int B, int K,
                             double* d_X, size_t ldx, int Bp, double* d_s, double* d_r, const double* d_mvec,
-                            hipStream_t stream, size_t blk) {
+                            hipStream_t stream, size_t blk, const double* d_w) {
   const int block = 256;
   hipLaunchKernelGGL(pair_prep_kernel, dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, stream, kind, param,
-                     d_counts, n, ldc, B, K, d_X, ldx, Bp, d_s, d_r, d_mvec, blk);
+                     d_counts, n, ldc, B, K, d_X, ldx, Bp, d_s, d_r, d_mvec, blk, d_w);
   return hipGetLastError();
 }
 

@@ -83,6 +83,67 @@ __device__ __forceinline__ double pair_stat_strided(int kind, double param, int 
   return __builtin_nan("");
 }
 
+// ---- per-branch weights (Statistic::setWeights, CoMap/Statistics.h:83-104; DESIGN A.7, weighted).  w is normalised
+// (sum 1).  Every weighted kind is a plain sum of products of scaled operands X_b = weight_factor(kind, w_b) * value_b,
+// on the lanes here and in the Gram operand of pair_prep_kernel alike, so a corrected reading of bpp-core's
+// VectorTools changes this one line: Cosinus squares the weights (scalar(x, y, w) = sum w^2 x y and norm(x, w)),
+// Correlation / Covariance / Compensation / EuclidianDistance take them once.
+__device__ __forceinline__ double weight_factor(int kind, double w) { return kind == 3 ? w : sqrt(w); }
+
+// weighted per-lane statistic (kinds 0, 1, 3, 4, 6, 7; the others ignore weights as the reference does).  A function of
+// its own: pair_stat_strided is inlined into map_kernel's null mode and stays as it is.
+//   0 / 6: VectorTools::cor(x, y, w, false) = sum w dx dy / sqrt(sum w dx^2 sum w dy^2), m = sum w x (no (B-1) factors)
+//   4:     VectorTools::cov(x, y, w, false, false) = sum w dx dy
+//   3:     sum w^2 x y / (sqrt(sum w^2 x^2) sqrt(sum w^2 y^2))
+//   1:     1 - sqrt(sum w (t1 + t2)^2) / (sqrt(sum w t1^2) + sqrt(sum w t2^2))   (Statistics.h:255-264)
+//   7:     sqrt(sum w (t2 - t1)^2)                                                   (Distance.h:160-168)
+__device__ inline double pair_stat_weighted(int kind, double param, int B, int K, const double* __restrict__ c1,
+                                                  size_t ld1, const double* __restrict__ c2, size_t ld2,
+                                                  const double* __restrict__ mv, const double* __restrict__ w) {
+  switch (kind) {
+    case 0: case 4: case 6: {
+      const double* u1 = kind == 6 ? mv : nullptr;
+      const double* u2 = kind == 6 ? mv + B : nullptr;
+      double m1 = 0, m2 = 0;
+      for (int b = 0; b < B; ++b) {
+        m1 += w[b] * (c1[(size_t)b * K * ld1] - (u1 ? u1[b] : 0.0));
+        m2 += w[b] * (c2[(size_t)b * K * ld2] - (u2 ? u2[b] : 0.0));
+      }
+      double sxy = 0, sxx = 0, syy = 0;
+      for (int b = 0; b < B; ++b) {
+        const double f = weight_factor(kind, w[b]);
+        const double dx = f * (c1[(size_t)b * K * ld1] - (u1 ? u1[b] : 0.0) - m1), dy = f * (c2[(size_t)b * K * ld2] - (u2 ? u2[b] : 0.0) - m2);
+        sxy += dx * dy; sxx += dx * dx; syy += dy * dy;
+      }
+      if (kind == 4) return sxy;
+      return sxy / (sqrt(sxx) * sqrt(syy));
+    }
+    case 3: {
+      double sxy = 0, sxx = 0, syy = 0;
+      for (int b = 0; b < B; ++b) {
+        const double f = weight_factor(kind, w[b]);
+        const double x = f * c1[(size_t)b * K * ld1], y = f * c2[(size_t)b * K * ld2];
+        sxy += x * y; sxx += x * x; syy += y * y;
+      }
+      return sxy / (sqrt(sxx) * sqrt(syy));
+    }
+    case 1: case 7: {
+      double s1 = 0, s2 = 0, s3 = 0, d = 0;
+      for (int b = 0; b < B; ++b) {
+        double t1 = 0, t2 = 0;
+        for (int k = 0; k < K; ++k) { t1 += c1[((size_t)b * K + k) * ld1]; t2 += c2[((size_t)b * K + k) * ld2]; }
+        const double f = weight_factor(kind, w[b]);
+        t1 *= f; t2 *= f;
+        s1 += t1 * t1; s2 += t2 * t2; s3 += (t1 + t2) * (t1 + t2);
+        d = __builtin_fma(t2 - t1, t2 - t1, d);
+      }
+      if (kind == 7) return sqrt(d);
+      return 1.0 - sqrt(s3) / (sqrt(s1) + sqrt(s2));
+    }
+  }
+  return pair_stat_strided(kind, param, B, K, c1, ld1, c2, ld2, mv);
+}
+
 __device__ __forceinline__ double pair_stat_lane(int kind, double param, int B, int K, const double* __restrict__ c1,
                                                  const double* __restrict__ c2) {
   return pair_stat_strided(kind, param, B, K, c1, (size_t)kWave, c2, (size_t)kWave);

@@ -49,7 +49,7 @@ COUNT_EXPECTED, COUNT_NAIVE = 0, 1
 
 EXPORTS = [
     "cmx_version", "cmx_ctx_create", "cmx_ctx_destroy", "cmx_last_error", "cmx_get_info",
-    "cmx_get_transition_matrices", "cmx_synchronize", "cmx_debug_walk", "cmx_map_sites", "cmx_set_mapping_options", "cmx_map_sites_dev", "cmx_simulate", "cmx_simulate_dev", "cmx_simulate_continuous",
+    "cmx_get_transition_matrices", "cmx_synchronize", "cmx_debug_walk", "cmx_map_sites", "cmx_set_mapping_options", "cmx_set_statistic_weights", "cmx_get_statistic_weights", "cmx_map_sites_dev", "cmx_simulate", "cmx_simulate_dev", "cmx_simulate_continuous",
     "cmx_simulate_continuous_dev", "cmx_null_intra_continuous", "cmx_null_intra_continuous_dev", "cmx_mi_pairs_dev",
     "cmx_pair_stats", "cmx_pair_stats_dev", "cmx_null_intra", "cmx_null_simulate_dev", "cmx_null_intra_dev", "cmx_null_inter",
     "cmx_null_inter_dev", "cmx_intra_pvalues", "cmx_intra_rows", "cmx_intra_rows_dev", "cmx_intra_rows_range_dev",
@@ -377,6 +377,24 @@ class Engine:
         """nijt.average / nijt.joint (CoETools.cpp:393-406): which of computeSubstitutionVectors{, NoAveraging, Marginal,
         NoAveragingMarginal} every later mapping of this engine (observed data and nulls) uses; default (True, True)."""
         self._check(self._lib.cmx_set_mapping_options(self._ctx, int(bool(average)), int(bool(joint))))
+
+    def set_statistic_weights(self, w=None):
+        """Statistic::setWeights / deleteWeights (CoMap/Statistics.h:83-104): per-branch weights [B] in the counts'
+        branch order, stored divided by their sum; None removes them.  Used by Correlation, CorrectedCorrelation,
+        Covariance, Cosinus, Compensation and EuclidianDistance (and the clustering distances) in every later call of
+        this engine; ignored by Cosubstitution, the discrete MI kinds and the scalar product (weighted)."""
+        if w is None:
+            self._check(self._lib.cmx_set_statistic_weights(self._ctx, _vp(None), _sz(0)))
+            return
+        a = _f64(w).ravel()
+        self._check(self._lib.cmx_set_statistic_weights(self._ctx, _vp(a), _sz(a.size)))
+
+    def statistic_weights(self):
+        """the stored (normalised) weights as an ndarray [B], or None"""
+        w = np.zeros(max(self.B, 1))
+        has = ctypes.c_int32(0)
+        self._check(self._lib.cmx_get_statistic_weights(self._ctx, _vp(w), ctypes.byref(has)))
+        return w[:self.B].copy() if has.value else None
 
     def simulate(self, seed, g0, n):
         aln = np.zeros((self.T, n), dtype=np.uint8)

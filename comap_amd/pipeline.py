@@ -13,10 +13,14 @@ import torch
 
 
 class IntraAnalysis:
-    def __init__(self, engine, d_aln, statistic="Correlation", nclasses=10, threshold=0.99):
+    def __init__(self, engine, d_aln, statistic="Correlation", nclasses=10, threshold=0.99, weights=None):
+        """weights: per-branch weights of the statistic (Statistic::setWeights), set on the engine for every later
+        call; None leaves the engine's weights as they are"""
         from .engine import STAT_BY_NAME
         assert d_aln.is_cuda and d_aln.dtype == torch.uint8 and d_aln.dim() == 2
         self.eng = engine
+        if weights is not None:
+            engine.set_statistic_weights(weights)
         self.aln = d_aln
         self.kind = STAT_BY_NAME[statistic] if isinstance(statistic, str) else int(statistic)
         self.nclasses = int(nclasses)        # statistic.null.nb_rate_classes (CoETools.cpp:638)

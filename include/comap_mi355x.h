@@ -173,6 +173,23 @@ cmx_status cmx_map_sites_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, 
  * class do not depend on the variant.  Parity unpinned: bpp-phyl is not in the reference tree. */
 cmx_status cmx_set_mapping_options(cmx_ctx* ctx, int average, int joint);
 
+/* ---- per-branch weights of the statistic (Statistic::setWeights / deleteWeights / hasWeights / getWeights,
+ * CoMap/Statistics.h:83-104, 135-140; Distance::setWeights, Distance.h:96-102), context state like the mapping options.
+ * w[b] is the weight of branch b in the counts' branch order; nbranches must equal cmx_info.nbranches (else
+ * CMX_ERR_INVALID, the reference's DimensionException).  Every w[b] is finite and >= 0 and the sum is > 0 (NaN / inf
+ * / a zero sum: CMX_ERR_INVALID; a negative weight: CMX_ERR_UNSUPPORTED; named in cmx_last_error; the context keeps its
+ * previous weights).  The weights are stored divided by their sum.  w == NULL removes them.  Setting or removing them
+ * waits for the device and discards the Gram blocks kept by cmx_intra_gram_prefetch_dev.
+ * Used by Correlation, CorrectedCorrelation, Covariance, Cosinus, Compensation (pair and group) and EuclidianDistance,
+ * hence by the three clustering distances, in every entry point that scores substitution vectors (pair statistics,
+ * rows, compact records, kept Gram blocks, nulls, groups, candidate groups, clustering).  Ignored, as in the reference,
+ * by Cosubstitution, the discrete MI kinds, the scalar product and cmx_vector_matrix; the site norms, the p-values'
+ * norm classes and the clustering tree's "Stat" property stay unweighted.  A weighted null runs unfused (simulate ->
+ * map -> score); cmx_null_inter scores with ctx1's weights.  Definitions: DESIGN.md A.7, weighted. */
+cmx_status cmx_set_statistic_weights(cmx_ctx* ctx, const double* w, size_t nbranches);
+/* has_weights = 0 / 1; w_out [nbranches] (may be NULL) receives the stored, normalised weights */
+cmx_status cmx_get_statistic_weights(const cmx_ctx* ctx, double* w_out, int32_t* has_weights);
+
 /* ---- sequence simulator (NonHomogeneousSequenceSimulator::simulate, AnalysisTools.cpp:591): counter-based RNG,
  * global site indices g0 .. g0+n-1 (see DESIGN.md "RNG").  aln_out: [T][n]. */
 cmx_status cmx_simulate(cmx_ctx* ctx, uint64_t seed, uint64_t g0, size_t n, uint8_t* aln_out, int32_t* classes_out);

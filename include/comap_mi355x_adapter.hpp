@@ -216,7 +216,45 @@ class ProbabilisticSubstitutionMapping {
 };
 
 // ------------------------------------------------------------------------------------------------ statistics
-class Statistic {
+// Statistic::setWeights / deleteWeights / hasWeights / getWeights (CoMap/Statistics.h:83-104, 135-140): a copy divided
+// by its sum.  Distance::setWeights (Distance.h:96-102) keeps the same copy.
+class BranchWeights {
+ public:
+  void setWeights(const Vdouble& w) {
+    double sum = 0.;
+    for (double x : w) sum += x;
+    w_ = w;
+    for (double& x : w_) x /= sum;
+    has_ = true;
+  }
+  void deleteWeights() { w_.clear(); has_ = false; }
+  bool hasWeights() const { return has_; }
+  const Vdouble* getWeights() const { return has_ ? &w_ : nullptr; }
+
+ private:
+  Vdouble w_;
+  bool has_ = false;
+};
+
+// The context's weights for one adapter call: set from the statistic (or distance) handed in, or cleared, and cleared
+// again when the call returns, so that the adapter keeps no weights state in the context.  A size other than the
+// number of branches throws DimensionException, as EuclidianDistance::getDistanceForPair does (Distance.h:160-162).
+class ScopedWeights {
+ public:
+  ScopedWeights(const Engine& eng, const Vdouble* w, const char* where) : eng_(eng) {
+    if (w && w->size() != eng.getNumberOfBranches()) throw DimensionException(where, w->size(), eng.getNumberOfBranches());
+    if (w) eng.check(cmx_set_statistic_weights(eng.ctx(), w->data(), w->size()));
+    else (void)cmx_set_statistic_weights(eng.ctx(), nullptr, 0);   // (a model-free context has none to clear)
+  }
+  ~ScopedWeights() { (void)cmx_set_statistic_weights(eng_.ctx(), nullptr, 0); }
+  ScopedWeights(const ScopedWeights&) = delete;
+  ScopedWeights& operator=(const ScopedWeights&) = delete;
+
+ private:
+  const Engine& eng_;
+};
+
+class Statistic : public BranchWeights {
  public:
   virtual ~Statistic() {}
   virtual int kind() const = 0;                       // cmx_stat_kind
@@ -225,6 +263,7 @@ class Statistic {
   Vdouble getValuesForAllPairs(const Engine& eng, const ProbabilisticSubstitutionMapping& mapping) const {
     const size_t n = mapping.getNumberOfSites();
     Vdouble out(n * n);
+    ScopedWeights sw(eng, getWeights(), "Statistic::getValuesForAllPairs.");
     eng.check(cmx_pair_stats(eng.ctx(), kind(), params(), mapping.data(), n, nullptr, 0, out.data()));
     return out;
   }
@@ -234,6 +273,7 @@ class Statistic {
     if (m1.getNumberOfBranches() != m2.getNumberOfBranches())
       throw DimensionException("Statistic::getValuesForAllPairs.", m2.getNumberOfBranches(), m1.getNumberOfBranches());
     Vdouble out(m1.getNumberOfSites() * m2.getNumberOfSites());
+    ScopedWeights sw(eng, getWeights(), "Statistic::getValuesForAllPairs.");
     eng.check(cmx_pair_stats(eng.ctx(), kind(), params(), m1.data(), m1.getNumberOfSites(), m2.data(),
                              m2.getNumberOfSites(), out.data()));
     return out;
@@ -323,18 +363,24 @@ class StatisticBasedDistance {
     for (double& v : d) v = comp_ - v;
     return d;
   }
+  // Distance.h:342-345, 397-400: the weights are the statistic's
+  void setWeights(const Vdouble& w) { stat_->setWeights(w); }
+  void deleteWeights() { stat_->deleteWeights(); }
+  bool hasWeights() const { return stat_->hasWeights(); }
+  const Vdouble* getWeights() const { return stat_->getWeights(); }
 
  private:
   std::shared_ptr<Statistic> stat_;
   double comp_;
 };
 // CoMap/Distance.h:150-173
-class EuclidianDistance {
+class EuclidianDistance : public BranchWeights {   // its own weights (Distance.h:96-102)
  public:
   int distanceKind() const { return CMX_DIST_EUCLIDIAN; }
   Vdouble getDistancesForAllPairs(const Engine& eng, const ProbabilisticSubstitutionMapping& mapping) const {
     const size_t n = mapping.getNumberOfSites();
     Vdouble out(n * n);
+    ScopedWeights sw(eng, getWeights(), "EuclidianDistance::getDistanceForPair.");
     eng.check(cmx_pair_stats(eng.ctx(), CMX_STAT_EUCLIDIAN_DISTANCE, nullptr, mapping.data(), n, nullptr, 0, out.data()));
     return out;
   }
@@ -424,6 +470,7 @@ class AnalysisTools {
     const size_t n = repCPU * repRAM;
     Vdouble stat(n), pr(n), nm(n);
     std::vector<int32_t> rc(n);
+    ScopedWeights sw(eng, statistic.getWeights(), "AnalysisTools::getNullDistributionIntraDR.");
     if (continuous)   // simulator and mapping both on the device, the alignments never leave it
       eng.check(cmx_null_intra_continuous(eng.ctx(), statistic.kind(), statistic.params(), seed, repBegin, repBegin + repCPU, repRAM,
                                           continuous->gammaAlpha, continuous->pInvariant, stat.data(), rc.data(), pr.data(), nm.data()));
@@ -452,6 +499,7 @@ class AnalysisTools {
     const size_t n = repCPU * repRAM;
     Vdouble stat(n), pr(n), nm(n);
     std::vector<int32_t> rc(n);
+    ScopedWeights sw(eng1, statistic.getWeights(), "AnalysisTools::getNullDistributionInterDR.");   // eng1's are the ones used
     eng1.check(cmx_null_inter(eng1.ctx(), eng2.ctx(), statistic.kind(), statistic.params(), seed, repBegin,
                               repBegin + repCPU, repRAM, stat.data(), rc.data(), pr.data(), nm.data()));
     if (rows)
@@ -497,6 +545,7 @@ class CoETools {
                                                      const ContinuousRates* continuous = nullptr) {
     const size_t n = mapping.getNumberOfSites();
     const Vdouble norms = AnalysisTools::computeNorms(mapping);
+    ScopedWeights sw(eng, statistic.getWeights(), "CoETools::computeIntraStats.");
     Vdouble ns, nm;
     if (computeNull) {
       const size_t nn = nbRepCPU * nbRepRAM;
@@ -557,6 +606,7 @@ class CoETools {
     const size_t cap = independentComparisons ? n1 : n1 * n2;
     std::vector<cmx_pair_row> raw(cap ? cap : 1);
     uint64_t count = 0;
+    ScopedWeights sw(eng, statistic.getWeights(), "CoETools::computeInterStats.");
     eng.check(cmx_inter_rows(eng.ctx(), statistic.kind(), statistic.params(), mapping1.data(), n1, mapping1.rateClasses.data(),
                              mapping1.posteriorRates.data(), norms1.data(), mapping2.data(), n2, mapping2.rateClasses.data(),
                              mapping2.posteriorRates.data(), norms2.data(), &f, raw.data(), cap, &count));
@@ -607,6 +657,7 @@ class CandidateGroup {
     std::vector<int32_t> idx(sites_.size());
     for (size_t i = 0; i < sites_.size(); ++i) idx[i] = static_cast<int32_t>(sites_[i].getIndex());
     const int64_t off[2] = {0, static_cast<int64_t>(idx.size())};
+    ScopedWeights sw(eng, stat.getWeights(), "CandidateGroup::computeStatisticValue.");
     eng.check(cmx_group_stats(eng.ctx(), stat.kind(), stat.params(), mapping.data(), mapping.getNumberOfSites(), off, idx.data(), 1,
                               &statistic_));
   }
@@ -668,6 +719,7 @@ inline void CoETools::computePValuesForCandidateGroups(CandidateGroupSet& candid
     ok[g] = c.isAnalysable() ? 1 : 0;
   }
   uint32_t trials = 0;
+  ScopedWeights sw(eng, candidates.statistic_->getWeights(), "CoETools::computePValuesForCandidateGroups.");
   eng.check(cmx_candidate_groups(eng.ctx(), candidates.statistic_->kind(), candidates.statistic_->params(), G, off.data(),
                                  lo.data(), hi.data(), ok.data(), observed.data(), candidates.minSim_, repRAM, maxTrials, 0, seed,
                                  candidates.n1_.data(), candidates.n2_.data(), &trials, &candidates.nbBatches_));
@@ -720,6 +772,7 @@ class ClusterTools {
     t.merge.resize(2 * (t.n - 1)); t.size.resize(t.n - 1);
     t.dmax.resize(t.n - 1); t.stat.resize(t.n - 1); t.nmin.resize(t.n - 1);
     if (wantMatrix) t.distances.resize(t.n * t.n);
+    ScopedWeights sw(eng, distance.getWeights(), "ClusterTools::cluster.");
     eng.check(cmx_cluster_sites(eng.ctx(), distance.distanceKind(), method, mapping.data(), t.n,
                                 wantMatrix ? t.distances.data() : nullptr, t.merge.data(), t.dmax.data(), t.size.data(),
                                 t.stat.data(), t.nmin.data()));
@@ -773,6 +826,7 @@ class ClusterTools {
     const size_t nm = sizeOfDataSet - 1;
     std::vector<int32_t> merge(2 * nm * nrep), size(nm * nrep);
     Vdouble dmax(nm * nrep), stat(nm * nrep), nmin(nm * nrep);
+    ScopedWeights sw(eng, distance.getWeights(), "ClusterTools::computeGlobalDistanceDistribution.");
     eng.check(cmx_cluster_null(eng.ctx(), distance.distanceKind(), method, seed, 0, nrep, sizeOfDataSet, merge.data(),
                                dmax.data(), size.data(), stat.data(), nmin.data()));
     if (!out) return;

@@ -212,6 +212,12 @@ class BasicMultiGpu {
       hip(hipStreamSynchronize(streams_[r]));
       hip(hipStreamSynchronize(side_[r]));
     }
+    // the statistic's branch weights (or none) on every rank's context, for all the work enqueued below
+    const Vdouble* w = statistic.getWeights();
+    if (w && w->size() != engines_[0]->getNumberOfBranches())
+      throw DimensionException("MultiGpu::computeIntraStats.", w->size(), engines_[0]->getNumberOfBranches());
+    for (size_t r = 0; r < N; ++r)
+      engines_[r]->check(cmx_set_statistic_weights(engines_[r]->ctx(), w ? w->data() : nullptr, w ? w->size() : 0));
     std::memcpy(hostAln_.p, aln, T * n);
     if (masks) {
       if (!hostMasks_) hip(hipHostMalloc((void**)&hostMasks_, 256 * sizeof(uint32_t), hipHostMallocDefault));
