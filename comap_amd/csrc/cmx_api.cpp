@@ -109,6 +109,8 @@ struct cmx_ctx {
   const double *va_P = nullptr, *va_N1 = nullptr, *va_NC = nullptr;   // their operators, uploaded at first use
   const double *va_PN = nullptr, *va_pi = nullptr;                     // plain path: joint counts and frequencies, padded
   const int *va_first = nullptr, *va_next = nullptr;
+  const int* asr_inner = nullptr;   // cmx_ancestral_states*: the internal nodes, ascending (uploaded at first use)
+  int asr_n_inner = 0;
   mutable std::string err;
 };
 
@@ -531,16 +533,11 @@ static std::vector<double> pad_mats(const std::vector<double>& m, int S, int SP)
   return o;
 }
 
-// plain: the caller is map_plain (alphabets other than 4 / 20 states): every mapping option, the default one included, and
-// the site scalars come from these kernels
-static cmx_status map_variant(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks,
-                              double* d_counts, size_t ldc, double* d_norm, void* stream, bool full_grid,
-                              double* d_logL = nullptr, double* d_post_rate = nullptr, int32_t* d_rate_class = nullptr) {
+// the operators of the plain kernels (cmx_variants.hip), uploaded at the first use by the mapping variants or by the
+// ancestral states (padded with zeros to kPlainStates on the plain path)
+static cmx_status upload_variant_operators(cmx_ctx* ctx) {
   const HostModel& h = ctx->hm;
-  const bool scalars = h.plain && (d_logL || d_post_rate || d_rate_class);
-  if (!h.plain && ((ctx->map_average && ctx->map_joint) || (!d_counts && !d_norm))) return CMX_OK;
-  if (h.plain && !d_counts && !d_norm && !scalars) return CMX_OK;
-  const int SD = h.plain ? kPlainStates : h.S;   // device states
+  const int SD = h.plain ? kPlainStates : h.S;
   cmx_status s;
   if (!ctx->va_P) {
     if ((s = upload(ctx, pad_mats(h.P, h.S, SD), &ctx->va_P)) != CMX_OK) return s;
@@ -555,18 +552,42 @@ static cmx_status map_variant(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites,
       if ((s = upload(ctx, pi, &ctx->va_pi)) != CMX_OK) return s;
     }
   }
+  return CMX_OK;
+}
+
+// the model and alignment fields of the plain kernels' arguments (operators uploaded); the caller sets the mode, the
+// outputs and the sites per pass
+static NoAvgArgs variant_args(cmx_ctx* ctx, const uint8_t* d_aln, size_t ld, const uint32_t* d_masks) {
+  const HostModel& h = ctx->hm;
+  NoAvgArgs a{};
+  a.S = h.plain ? kPlainStates : h.S; a.Sreal = h.S; a.C = h.C; a.K = h.K; a.nn = h.nn; a.B = h.B; a.root = h.root;
+  a.first_child = ctx->va_first; a.next_sib = ctx->va_next; a.taxon_of = ctx->dm.taxon_of; a.parent = ctx->dm.parent;
+  a.P = ctx->va_P; a.N1 = ctx->va_N1; a.NC = ctx->va_NC; a.PN = ctx->va_PN; a.pi = h.plain ? ctx->va_pi : ctx->dm.pi; a.probs = ctx->dm.probs;
+  a.rates = ctx->dm.rates;
+  a.masks = d_masks; a.aln = d_aln; a.ld = ld;
+  return a;
+}
+
+// plain: the caller is map_plain (alphabets other than 4 / 20 states): every mapping option, the default one included, and
+// the site scalars come from these kernels
+static cmx_status map_variant(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks,
+                              double* d_counts, size_t ldc, double* d_norm, void* stream, bool full_grid,
+                              double* d_logL = nullptr, double* d_post_rate = nullptr, int32_t* d_rate_class = nullptr) {
+  const HostModel& h = ctx->hm;
+  const bool scalars = h.plain && (d_logL || d_post_rate || d_rate_class);
+  if (!h.plain && ((ctx->map_average && ctx->map_joint) || (!d_counts && !d_norm))) return CMX_OK;
+  if (h.plain && !d_counts && !d_norm && !scalars) return CMX_OK;
+  const int SD = h.plain ? kPlainStates : h.S;   // device states
+  cmx_status s;
+  if ((s = upload_variant_operators(ctx)) != CMX_OK) return s;
   const bool want_counts = d_counts || d_norm;
   if (!d_counts && want_counts) {   // only the norms were asked for: they still need the counts
     if ((s = scratch(ctx, full_grid ? "va_counts_null" : "va_counts_obs", sizeof(double) * (size_t)h.B * h.K * nsites, (void**)&d_counts)) != CMX_OK) return s;
     ldc = nsites;
   }
-  NoAvgArgs a{};
-  a.S = SD; a.Sreal = h.S; a.C = h.C; a.K = h.K; a.nn = h.nn; a.B = h.B; a.root = h.root;
+  NoAvgArgs a = variant_args(ctx, d_aln, ld, d_masks);
   a.mode = ctx->map_joint ? (ctx->map_average ? kVariantJoint : kVariantNoAvg) : (ctx->map_average ? kVariantMarginal : kVariantNoAvgMarginal);
-  a.first_child = ctx->va_first; a.next_sib = ctx->va_next; a.taxon_of = ctx->dm.taxon_of; a.parent = ctx->dm.parent;
-  a.P = ctx->va_P; a.N1 = ctx->va_N1; a.NC = ctx->va_NC; a.PN = ctx->va_PN; a.pi = h.plain ? ctx->va_pi : ctx->dm.pi; a.probs = ctx->dm.probs;
-  a.rates = ctx->dm.rates; a.logL = d_logL; a.post_rate = d_post_rate; a.rate_class = d_rate_class;
-  a.masks = d_masks; a.aln = d_aln; a.ld = ld;
+  a.logL = d_logL; a.post_rate = d_post_rate; a.rate_class = d_rate_class;
   // sites per pass: per-node vectors of a pass stay under 1 GiB
   const size_t per_site = sizeof(double) * noavg_scratch_doubles(SD, h.C, h.nn, 1);
   a.chunk = std::max<size_t>(256, std::min<size_t>(nsites, ((size_t)1 << 30) / per_site / 256 * 256));
@@ -642,24 +663,50 @@ cmx_status cmx_map_sites_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, 
   return map_sites_impl(ctx, d_aln, nsites, ld, d_masks, d_counts, ldc, d_logL, d_post_rate, d_rate_class, d_norm, stream, false);
 }
 
-cmx_status cmx_map_sites(cmx_ctx* ctx, const uint8_t* aln, size_t nsites, size_t ld, const uint32_t* masks,
-                         size_t nmasks, double* counts, double* logL, double* post_rate, int32_t* rate_class,
-                         double* norm) {
+// the host-pointer entry points' alignment rules (who names the entry point in the message): [T][ld] codes, every code a
+// state or one of the nmasks masks; a mask table only for 4 / 20 states, at most max_ambig(S) ambiguity ids
+static cmx_status check_host_alignment(cmx_ctx* ctx, const char* who, const uint8_t* aln, size_t nsites, size_t ld,
+                                       const uint32_t* masks, size_t nmasks) {
   cmx_status s = need_model(ctx);
   if (s != CMX_OK) return s;
-  if (!aln || nsites == 0 || ld < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_map_sites: bad alignment arguments");
+  const std::string w(who);
+  if (!aln || nsites == 0 || ld < nsites) return fail(ctx, CMX_ERR_INVALID, w + ": bad alignment arguments");
   const HostModel& h = ctx->hm;
   if (masks && h.plain)
-    return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_map_sites: no ambiguity table for alphabets other than 4 / 20 states (codes >= nstates are unknowns)");
+    return fail(ctx, CMX_ERR_UNSUPPORTED, w + ": no ambiguity table for alphabets other than 4 / 20 states (codes >= nstates are unknowns)");
   if (masks && nmasks > (size_t)(h.S + max_ambig(h.S)))
-    return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_map_sites: at most " + std::to_string(max_ambig(h.S)) +
+    return fail(ctx, CMX_ERR_UNSUPPORTED, w + ": at most " + std::to_string(max_ambig(h.S)) +
                                               " ambiguity ids (codes >= nstates) are supported for this alphabet");
   // every code must be a state or a known mask (the reference throws BadCharException at alignment parsing)
   for (int t = 0; t < h.T; ++t)
     for (size_t i = 0; i < nsites; ++i) {
       const unsigned c = aln[(size_t)t * ld + i];
-      if (c >= (unsigned)h.S && masks && c >= nmasks) return fail(ctx, CMX_ERR_INVALID, "cmx_map_sites: alignment code without a mask");
+      if (c >= (unsigned)h.S && masks && c >= nmasks) return fail(ctx, CMX_ERR_INVALID, w + ": alignment code without a mask");
     }
+  return CMX_OK;
+}
+
+// the checked alignment as [T][nsites] device temporaries, the mask table (if any) padded to 256 entries of "every state"
+static cmx_status upload_host_alignment(cmx_ctx* ctx, TmpDev& tmp, const uint8_t* aln, size_t nsites, size_t ld, const uint32_t* masks,
+                                        size_t nmasks, uint8_t** d_aln, uint32_t** d_masks) {
+  const HostModel& h = ctx->hm;
+  HIP_TRY(ctx, tmp.alloc((void**)d_aln, (size_t)h.T * nsites));
+  HIP_TRY(ctx, hipMemcpy2D(*d_aln, nsites, aln, ld, nsites, h.T, hipMemcpyHostToDevice));
+  if (masks) {
+    std::vector<uint32_t> mk(256, h.S >= 32 ? 0xffffffffu : ((1u << h.S) - 1u));
+    for (size_t i = 0; i < nmasks && i < 256; ++i) mk[i] = masks[i];
+    HIP_TRY(ctx, tmp.alloc((void**)d_masks, 256 * sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMemcpy(*d_masks, mk.data(), 256 * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
+  return CMX_OK;
+}
+
+cmx_status cmx_map_sites(cmx_ctx* ctx, const uint8_t* aln, size_t nsites, size_t ld, const uint32_t* masks,
+                         size_t nmasks, double* counts, double* logL, double* post_rate, int32_t* rate_class,
+                         double* norm) {
+  cmx_status s = check_host_alignment(ctx, "cmx_map_sites", aln, nsites, ld, masks, nmasks);
+  if (s != CMX_OK) return s;
+  const HostModel& h = ctx->hm;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   TmpDev tmp;
   uint8_t* d_aln = nullptr;
@@ -667,14 +714,7 @@ cmx_status cmx_map_sites(cmx_ctx* ctx, const uint8_t* aln, size_t nsites, size_t
   double *d_counts = nullptr, *d_logL = nullptr, *d_pr = nullptr, *d_norm = nullptr;
   int32_t* d_rc = nullptr;
   const size_t BK = (size_t)h.B * h.K;
-  HIP_TRY(ctx, tmp.alloc((void**)&d_aln, (size_t)h.T * nsites));
-  HIP_TRY(ctx, hipMemcpy2D(d_aln, nsites, aln, ld, nsites, h.T, hipMemcpyHostToDevice));
-  if (masks) {
-    std::vector<uint32_t> mk(256, h.S >= 32 ? 0xffffffffu : ((1u << h.S) - 1u));
-    for (size_t i = 0; i < nmasks && i < 256; ++i) mk[i] = masks[i];
-    HIP_TRY(ctx, tmp.alloc((void**)&d_masks, 256 * sizeof(uint32_t)));
-    HIP_TRY(ctx, hipMemcpy(d_masks, mk.data(), 256 * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
+  if ((s = upload_host_alignment(ctx, tmp, aln, nsites, ld, masks, nmasks, &d_aln, &d_masks)) != CMX_OK) return s;
   if (counts) HIP_TRY(ctx, tmp.alloc((void**)&d_counts, BK * nsites * sizeof(double)));
   HIP_TRY(ctx, tmp.alloc((void**)&d_logL, nsites * sizeof(double)));
   HIP_TRY(ctx, tmp.alloc((void**)&d_pr, nsites * sizeof(double)));
@@ -702,6 +742,74 @@ cmx_status cmx_set_mapping_options(cmx_ctx* ctx, int average, int joint) {
   if (s != CMX_OK) return s;
   ctx->map_average = average != 0;
   ctx->map_joint = joint != 0;
+  return CMX_OK;
+}
+
+// asr.method = marginal (CoMap/CoMap.cpp:169-197): the inside / outside kernels of the mapping variants, then
+// ancestral_kernel (cmx_variants.hip).  Scratch of its own ("asr_nodes", not the mapping's "va_nodes_*"), so it may run on
+// a stream beside a mapping or a null; it reads the caller's mask table directly and leaves the leaf operators' ambiguity
+// rows and the kept Gram blocks alone.  Sites per pass: the four per-node vectors of a pass stay under kAsrScratchBytes,
+// the passes balanced and rounded up to whole workgroups.
+constexpr size_t kAsrScratchBytes = (size_t)2 << 30;
+
+cmx_status cmx_ancestral_states_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks,
+                                    uint8_t* d_states, size_t lds, double* d_post, size_t ldp, void* stream) {
+  cmx_status s = need_model(ctx);
+  if (s != CMX_OK) return s;
+  const HostModel& h = ctx->hm;
+  if (!d_aln || nsites == 0 || ld < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_ancestral_states: bad alignment arguments");
+  if (d_masks && h.plain)
+    return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_ancestral_states: no ambiguity table for alphabets other than 4 / 20 states (codes >= nstates are unknowns)");
+  if (!d_states) return fail(ctx, CMX_ERR_INVALID, "cmx_ancestral_states: states is NULL");
+  if (lds < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_ancestral_states: lds < nsites");
+  if (d_post && ldp < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_ancestral_states: ldp < nsites");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if ((s = upload_variant_operators(ctx)) != CMX_OK) return s;
+  if (!ctx->asr_inner) {
+    std::vector<int> inner;
+    for (int n = 0; n < h.nn; ++n)
+      if (h.first_child[n] >= 0) inner.push_back(n);
+    if ((s = upload(ctx, inner, &ctx->asr_inner)) != CMX_OK) return s;
+    ctx->asr_n_inner = (int)inner.size();
+  }
+  NoAvgArgs a = variant_args(ctx, d_aln, ld, d_masks);
+  const size_t per_site = sizeof(double) * noavg_scratch_doubles(a.S, h.C, h.nn, 1);
+  const size_t max_chunk = std::max<size_t>(256, kAsrScratchBytes / per_site / 256 * 256);
+  const size_t passes = (nsites + max_chunk - 1) / max_chunk;
+  a.chunk = std::min(nsites, ((nsites + passes - 1) / passes + 255) / 256 * 256);
+  double* buf;
+  if ((s = scratch(ctx, "asr_nodes", sizeof(double) * noavg_scratch_doubles(a.S, h.C, h.nn, a.chunk), (void**)&buf)) != CMX_OK) return s;
+  HIP_TRY(ctx, launch_ancestral(a, nsites, buf, ctx->asr_inner, ctx->asr_n_inner, d_states, lds, d_post, ldp, (hipStream_t)stream));
+  return CMX_OK;
+}
+
+cmx_status cmx_ancestral_states(cmx_ctx* ctx, const uint8_t* aln, size_t nsites, size_t ld, const uint32_t* masks, size_t nmasks,
+                                uint8_t* states, double* post) {
+  cmx_status s = check_host_alignment(ctx, "cmx_ancestral_states", aln, nsites, ld, masks, nmasks);
+  if (s != CMX_OK) return s;
+  if (!states) return fail(ctx, CMX_ERR_INVALID, "cmx_ancestral_states: states is NULL");
+  const HostModel& h = ctx->hm;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  TmpDev tmp;
+  uint8_t* d_aln = nullptr;
+  uint32_t* d_masks = nullptr;
+  uint8_t* d_states = nullptr;
+  double* d_post = nullptr;
+  if ((s = upload_host_alignment(ctx, tmp, aln, nsites, ld, masks, nmasks, &d_aln, &d_masks)) != CMX_OK) return s;
+  int n_inner = 0;
+  for (int n = 0; n < h.nn; ++n) n_inner += h.first_child[n] >= 0;
+  HIP_TRY(ctx, tmp.alloc((void**)&d_states, (size_t)n_inner * nsites));
+  if (post) HIP_TRY(ctx, tmp.alloc((void**)&d_post, sizeof(double) * n_inner * h.S * nsites));
+  if ((s = cmx_ancestral_states_dev(ctx, d_aln, nsites, nsites, d_masks, d_states, nsites, d_post, nsites, nullptr)) != CMX_OK) return s;
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(states, d_states, (size_t)n_inner * nsites, hipMemcpyDeviceToHost));
+  if (post) {   // [n_inner][S][N] -> [n_inner][N][S]
+    std::vector<double> pm((size_t)n_inner * h.S * nsites);
+    HIP_TRY(ctx, hipMemcpy(pm.data(), d_post, sizeof(double) * pm.size(), hipMemcpyDeviceToHost));
+    for (int q = 0; q < n_inner; ++q)
+      for (int x = 0; x < h.S; ++x)
+        for (size_t i = 0; i < nsites; ++i) post[((size_t)q * nsites + i) * h.S + x] = pm[((size_t)q * h.S + x) * nsites + i];
+  }
   return CMX_OK;
 }
 

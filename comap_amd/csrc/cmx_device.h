@@ -172,6 +172,9 @@ struct NoAvgArgs {
 };
 size_t noavg_scratch_doubles(int S, int C, int nn, size_t chunk);
 hipError_t launch_map_noavg(NoAvgArgs a, size_t nsites_total, double* scratch, double* d_norm, hipStream_t stream);
+// asr.method = marginal (cmx_ancestral_states*): states [n_inner][lds], optional posterior [n_inner][Sreal][ldp]
+hipError_t launch_ancestral(NoAvgArgs a, size_t nsites_total, double* scratch, const int* d_inner, int n_inner, uint8_t* d_states,
+                            size_t lds, double* d_post, size_t ldp, hipStream_t stream);
 // Mica post-processing (cmx_mica_post.hip)
 hipError_t launch_mica_average(const double* d_mi, size_t n, size_t ld, double* d_avg, double* d_full, hipStream_t stream);
 hipError_t launch_mica_zscore(int which, const double* d_mi, size_t n, size_t ld, const double* d_avg, const double* d_full,

@@ -249,6 +249,44 @@ __global__ __launch_bounds__(256) void site_scalars_kernel(const NoAvgArgs a) {
   if (a.rate_class) a.rate_class[a.site0 + j] = bc;
 }
 
+// ---- marginal ancestral state reconstruction (asr.method = marginal, CoMap/CoMap.cpp:169-197:
+// LegacyMarginalAncestralStateReconstruction::getAncestralStatesForNode), on the per-node vectors of the two kernels above:
+//   post_n(i, x) = sum_c p_c Up_n(i, c, x) D_n(i, c, x) / L_i   (Up_root = root frequencies)
+//   state_n(i)   = first x that maximises post_n(i, x)            (VectorTools::whichMax: strict ">" scan)
+// the posterior of marginal_kernel, summed in its order.  One thread per (site, internal node); states [n_inner][lds] and
+// the optional posterior of the real states [n_inner][Sreal][ldp] are coalesced over sites.  L_i = 0: NaN, state 0.
+struct AncOut {
+  const int* inner;   // [n_inner] the internal nodes, ascending
+  uint8_t* states;
+  size_t lds;
+  double* post;       // NULL: states only
+  size_t ldp;
+};
+
+template <int S>
+__global__ __launch_bounds__(256) void ancestral_kernel(const NoAvgArgs a, const AncOut o) {
+  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= a.nsites) return;
+  const int q = blockIdx.y, n = o.inner[q], nn = a.nn, C = a.C;
+  const size_t ch = a.chunk;
+  double L = 0.0;
+  for (int c = 0; c < C; ++c) {
+    double s = 0.0;
+    for (int x = 0; x < S; ++x) s += a.pi[x] * a.D[(((size_t)c * nn + a.root) * S + x) * ch + j];
+    L += a.probs[c] * s;
+  }
+  int best = 0;
+  double bv = -__builtin_inf();
+  for (int x = 0; x < a.Sreal; ++x) {
+    double s = 0.0;
+    for (int c = 0; c < C; ++c)
+      s += a.Up[(((size_t)c * nn + n) * S + x) * ch + j] * a.D[(((size_t)c * nn + n) * S + x) * ch + j] * a.probs[c] / L;
+    if (o.post) o.post[((size_t)q * a.Sreal + x) * o.ldp + a.site0 + j] = s;
+    if (s > bv) { bv = s; best = x; }
+  }
+  o.states[(size_t)q * o.lds + a.site0 + j] = (uint8_t)best;
+}
+
 // computeNormForSite over the (branch-major) counts: sqrt(sum_b (sum_k count)^2), branches in order
 __global__ __launch_bounds__(256) void counts_norm_kernel(const double* __restrict__ counts, size_t ldc, int B, int K, size_t n,
                                                           double* __restrict__ norm) {
@@ -300,6 +338,37 @@ hipError_t launch_map_noavg(NoAvgArgs a, size_t nsites_total, double* scratch, d
   if (d_norm && a.counts)
     hipLaunchKernelGGL(counts_norm_kernel, dim3((unsigned)((nsites_total + 255) / 256)), dim3(256), 0, stream, a.counts, a.ldc, a.B,
                        a.K, nsites_total, d_norm);
+  return hipGetLastError();
+}
+
+// asr.method = marginal: the inside and outside kernels of the mapping variants, unchanged, then ancestral_kernel, a.chunk
+// sites per pass (a's operator fields as map_variant fills them; a.D .. a.Up carved from scratch here)
+hipError_t launch_ancestral(NoAvgArgs a, size_t nsites_total, double* scratch, const int* d_inner, int n_inner, uint8_t* d_states,
+                            size_t lds, double* d_post, size_t ldp, hipStream_t stream) {
+  const size_t per = (size_t)a.C * a.nn * a.S * a.chunk;
+  a.D = scratch; a.M = scratch + per; a.U = scratch + 2 * per; a.Up = scratch + 3 * per;
+  a.counts = nullptr; a.logL = a.post_rate = nullptr; a.rate_class = nullptr;
+  const AncOut o{d_inner, d_states, lds, d_post, ldp};
+  for (size_t s0 = 0; s0 < nsites_total; s0 += a.chunk) {
+    a.site0 = s0;
+    a.nsites = std::min(a.chunk, nsites_total - s0);
+    const unsigned gx = (unsigned)((a.nsites + 255) / 256);
+    if (a.S == 20) {
+      hipLaunchKernelGGL(noavg_inside_kernel<20>, dim3(gx, a.C), dim3(256), 0, stream, a);
+      hipLaunchKernelGGL(noavg_outside_kernel<20>, dim3(gx, a.C), dim3(256), 0, stream, a);
+      hipLaunchKernelGGL(ancestral_kernel<20>, dim3(gx, n_inner), dim3(256), 0, stream, a, o);
+    } else if (a.S == 4) {
+      hipLaunchKernelGGL(noavg_inside_kernel<4>, dim3(gx, a.C), dim3(256), 0, stream, a);
+      hipLaunchKernelGGL(noavg_outside_kernel<4>, dim3(gx, a.C), dim3(256), 0, stream, a);
+      hipLaunchKernelGGL(ancestral_kernel<4>, dim3(gx, n_inner), dim3(256), 0, stream, a, o);
+    } else if (a.S == kPlainStatesDev) {
+      hipLaunchKernelGGL(noavg_inside_kernel<kPlainStatesDev>, dim3(gx, a.C), dim3(256), 0, stream, a);
+      hipLaunchKernelGGL(noavg_outside_kernel<kPlainStatesDev>, dim3(gx, a.C), dim3(256), 0, stream, a);
+      hipLaunchKernelGGL(ancestral_kernel<kPlainStatesDev>, dim3(gx, n_inner), dim3(256), 0, stream, a, o);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  }
   return hipGetLastError();
 }
 

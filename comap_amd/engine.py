@@ -49,7 +49,7 @@ COUNT_EXPECTED, COUNT_NAIVE = 0, 1
 
 EXPORTS = [
     "cmx_version", "cmx_ctx_create", "cmx_ctx_destroy", "cmx_last_error", "cmx_get_info",
-    "cmx_get_transition_matrices", "cmx_synchronize", "cmx_debug_walk", "cmx_map_sites", "cmx_set_mapping_options", "cmx_set_statistic_weights", "cmx_get_statistic_weights", "cmx_map_sites_dev", "cmx_simulate", "cmx_simulate_dev", "cmx_simulate_continuous",
+    "cmx_get_transition_matrices", "cmx_synchronize", "cmx_debug_walk", "cmx_map_sites", "cmx_set_mapping_options", "cmx_set_statistic_weights", "cmx_get_statistic_weights", "cmx_map_sites_dev", "cmx_ancestral_states", "cmx_ancestral_states_dev", "cmx_simulate", "cmx_simulate_dev", "cmx_simulate_continuous",
     "cmx_simulate_continuous_dev", "cmx_null_intra_continuous", "cmx_null_intra_continuous_dev", "cmx_mi_pairs_dev",
     "cmx_pair_stats", "cmx_pair_stats_dev", "cmx_null_intra", "cmx_null_simulate_dev", "cmx_null_intra_dev", "cmx_null_inter",
     "cmx_null_inter_dev", "cmx_intra_pvalues", "cmx_intra_rows", "cmx_intra_rows_dev", "cmx_intra_rows_range_dev",
@@ -373,6 +373,27 @@ class Engine:
                                             _vp(rc), _vp(norm)))
         return dict(counts=counts, logL=logL, post_rate=pr, rate_class=rc, norm=norm)
 
+    def inner_nodes(self):
+        """the internal nodes in ascending node index (post-order, root last): the rows of ancestral_states"""
+        p = self._keep[0]
+        return [n for n in range(len(p)) if (p == n).any()]
+
+    def ancestral_states(self, aln, masks=None, want_posterior=False):
+        """asr.method = marginal (CoMap/CoMap.cpp:169-197): the marginal ancestral state of every internal node and site.
+        aln: uint8 [T, N].  Returns dict(nodes=[inner node ids, ascending], states=uint8 [n_inner, N] (model state indices),
+        post=[n_inner, N, S] posterior summed over the rate classes, or None)."""
+        aln = np.ascontiguousarray(aln, dtype=np.uint8)
+        T, N = aln.shape
+        if T != self.T:
+            raise CmxError(-1, f"alignment has {T} rows, tree has {self.T} taxa")
+        nodes = self.inner_nodes()
+        states = np.zeros((len(nodes), N), dtype=np.uint8)
+        post = np.zeros((len(nodes), N, self.S)) if want_posterior else None
+        mk = None if masks is None else np.ascontiguousarray(masks, dtype=np.uint32)
+        self._check(self._lib.cmx_ancestral_states(self._ctx, _vp(aln), _sz(N), _sz(N), _vp(mk), _sz(0 if mk is None else len(mk)),
+                                                   _vp(states), _vp(post)))
+        return dict(nodes=nodes, states=states, post=post)
+
     def set_mapping_options(self, average=True, joint=True):
         """nijt.average / nijt.joint (CoETools.cpp:393-406): which of computeSubstitutionVectors{, NoAveraging, Marginal,
         NoAveragingMarginal} every later mapping of this engine (observed data and nulls) uses; default (True, True)."""
@@ -682,6 +703,16 @@ class Engine:
         self._check(self._lib.cmx_map_sites_dev(self._ctx, _vp(d_aln), _sz(n), _sz(d_aln.stride(0)), _vp(masks),
                                                 _vp(counts), _sz(0 if counts is None else counts.stride(0)), _vp(logL),
                                                 _vp(post_rate), _vp(rate_class), _vp(norm), self._stream()))
+
+    def ancestral_states_dev(self, d_aln, states, post=None, masks=None):
+        """d_aln: uint8 [T, ld] CUDA tensor; states: uint8 [n_inner, lds]; post: float64 [n_inner, S, ldp] or None (the
+        rows are inner_nodes(); asynchronous on the current stream)"""
+        n = d_aln.shape[1]
+        if post is not None and post.stride(0) != self.S * post.stride(1):
+            raise CmxError(-1, "ancestral_states_dev: post must be [n_inner, S, ldp] with the rows ldp apart")
+        self._check(self._lib.cmx_ancestral_states_dev(self._ctx, _vp(d_aln), _sz(n), _sz(d_aln.stride(0)), _vp(masks), _vp(states),
+                                                       _sz(states.stride(0)), _vp(post), _sz(0 if post is None else post.stride(1)),
+                                                       self._stream()))
 
     def simulate_dev(self, seed, g0, n, aln, classes=None):
         """aln: uint8 [T, ld] CUDA tensor (ld >= n)"""

@@ -236,3 +236,37 @@ def to_text(writer, *args, **kw):
     buf = io.StringIO()
     writer(buf, *args, **kw)
     return buf.getvalue()
+
+
+# ------------------------------------------------------------------------------------------- output.sequence.file
+def write_ancestral_fasta(out, nodes, states, names, aln, nstates=None, symbols=None, unknown=None, node_names=None,
+                          chars_per_line=100):
+    """asr.method = marginal, output.sequence.file (CoMap/CoMap.cpp:169-197): the ancestral sequences (one per internal
+    node, named by node id; engine.ancestral_states()), then the extant ones (SequenceContainerTools::append), in Fasta
+    with `chars_per_line` characters per line.  symbols[code] is the text of a state and codes >= len(symbols) print as
+    `unknown`; without symbols, nstates 4 gives "ACGT" / "N" and 20 gives protein_models.AA_ORDER / "X".  node_names: the
+    names of `nodes` (default: the node ids).  Byte parity with Bio++'s Fasta writer is unpinned (the reference ships no
+    ancestors file)."""
+    if symbols is None:
+        from . import protein_models
+        if nstates not in (4, 20):
+            raise ValueError("write_ancestral_fasta: give the symbol table for an alphabet other than 4 / 20 states")
+        symbols = "ACGT" if nstates == 4 else protein_models.AA_ORDER
+    symbols = list(symbols)
+    if unknown is None:
+        if len(symbols) not in (4, 20):
+            raise ValueError("write_ancestral_fasta: give the unknown character for an alphabet other than 4 / 20 states")
+        unknown = "N" if len(symbols) == 4 else "X"
+    table = symbols + [unknown] * max(0, 256 - len(symbols))
+    if node_names is None:
+        node_names = [str(int(n)) for n in nodes]
+    f, own = _open(out, "w")
+    try:
+        for name, row in list(zip(node_names, np.asarray(states))) + list(zip(names, np.asarray(aln))):
+            text = "".join(table[int(c)] for c in row)
+            f.write(">" + str(name) + "\n")
+            for k in range(0, len(text), chars_per_line):
+                f.write(text[k:k + chars_per_line] + "\n")
+    finally:
+        if own:
+            f.close()

@@ -173,6 +173,25 @@ cmx_status cmx_map_sites_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, 
  * class do not depend on the variant.  Parity unpinned: bpp-phyl is not in the reference tree. */
 cmx_status cmx_set_mapping_options(cmx_ctx* ctx, int average, int joint);
 
+/* ---- marginal ancestral state reconstruction (asr.method = marginal, CoMap/CoMap.cpp:169-197:
+ * LegacyMarginalAncestralStateReconstruction::getAncestralSequences / getAncestralStatesForNode).  For every internal node
+ * n (ascending node index: post-order, root last -- the order of cmx_tree and of the .vec rows) and site i:
+ *   post_n(i, x) = sum_c p_c Up_n(i, c, x) D_n(i, c, x) / L_i   (Up_root = the root frequencies)
+ *   state_n(i)   = the first x that maximises post_n(i, x)       (VectorTools::whichMax)
+ * States are model state indices 0 .. S-1 (codon models: the caller maps them to codons).  Leaves are not included
+ * (CoMap appends the extant sequences itself).  Independent of cmx_set_mapping_options and of the statistic weights.
+ * A site whose likelihood underflows to 0 gets post = NaN and state 0.  Parity: the likelihood re-rooted at the node for
+ * stationary reversible models; for non-homogeneous model sets unpinned.
+ * Alignment and mask rules as cmx_map_sites (a mask table with an alphabet other than 4 / 20 states: CMX_ERR_UNSUPPORTED);
+ * states == NULL: CMX_ERR_INVALID.  states [n_inner][N]; post (NULL: not computed) [n_inner][N][S]. */
+cmx_status cmx_ancestral_states(cmx_ctx* ctx, const uint8_t* aln, size_t nsites, size_t ld, const uint32_t* masks, size_t nmasks,
+                                uint8_t* states /*[n_inner][N]*/, double* post /*[n_inner][N][S] or NULL*/);
+/* CoMap/CoMap.cpp:169-197 on device memory, asynchronous on `stream`: d_states [n_inner][lds], d_post [n_inner][S][ldp] or
+ * NULL (both coalesced over sites); lds / ldp < nsites or d_states == NULL: CMX_ERR_INVALID.  Its own scratch: it may
+ * run on a second stream beside cmx_map_sites_dev or cmx_null_intra_dev. */
+cmx_status cmx_ancestral_states_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks,
+                                    uint8_t* d_states, size_t lds, double* d_post, size_t ldp, void* stream);
+
 /* ---- per-branch weights of the statistic (Statistic::setWeights / deleteWeights / hasWeights / getWeights,
  * CoMap/Statistics.h:83-104, 135-140; Distance::setWeights, Distance.h:96-102), context state like the mapping options.
  * w[b] is the weight of branch b in the counts' branch order; nbranches must equal cmx_info.nbranches (else

@@ -26,6 +26,7 @@
 #include <cmath>
 #include <cstdint>
 #include <limits>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -147,6 +148,11 @@ class Engine {
     nbBranches_ = static_cast<size_t>(ct.nnodes) - 1;
     nbTypes_ = static_cast<size_t>(cm.ntypes);
     nbTaxa_ = static_cast<size_t>(ct.ntaxa);
+    std::vector<char> isFather(t.parent.size(), 0);
+    for (int32_t f : t.parent)
+      if (f >= 0) isFather[static_cast<size_t>(f)] = 1;
+    for (size_t n = 0; n < isFather.size(); ++n)
+      if (isFather[n]) innerNodes_.push_back(static_cast<int>(n));
   }
   // model-free context: pair statistics / distances / Mica column MI only (cmx_ctx_create(NULL, NULL, ...))
   explicit Engine(int device = 0) : S_(0) {
@@ -175,6 +181,8 @@ class Engine {
   size_t getNumberOfSubstitutionTypes() const { return nbTypes_; }
   size_t getNumberOfTaxa() const { return nbTaxa_; }
   int getNumberOfStates() const { return S_; }
+  // the internal nodes (positions in TreeArrays), ascending: post-order with the root last
+  const std::vector<int>& getInnerNodes() const { return innerNodes_; }
   void check(cmx_status s) const {
     if (s != CMX_OK) throw Exception(cmx_last_error(ctx_));
   }
@@ -183,6 +191,7 @@ class Engine {
   cmx_ctx* ctx_ = nullptr;
   int S_;
   size_t nbBranches_ = 0, nbTypes_ = 0, nbTaxa_ = 0;
+  std::vector<int> innerNodes_;
 };
 
 // ------------------------------------------------------------------------------------------------ mapping
@@ -213,6 +222,59 @@ class ProbabilisticSubstitutionMapping {
  private:
   size_t n_, b_, k_;
   Vdouble counts_;
+};
+
+// ------------------------------------------------------------------------------------------------ ancestral states
+// LegacyMarginalAncestralStateReconstruction stand-in (asr.method = marginal, CoMap/CoMap.cpp:169-197): one device call
+// (cmx_ancestral_states) at construction.  Nodes are TreeArrays positions; only the internal ones have states (CoMap
+// appends the extant sequences itself).  States are model state indices; probabilities are the posterior summed over
+// the rate classes.  aln: [taxon][site] codes as for getVectors; masks: the ambiguity table, or empty.
+class MarginalAncestralStateReconstruction {
+ public:
+  MarginalAncestralStateReconstruction(const Engine& eng, const std::vector<uint8_t>& aln, size_t nbSites,
+                                       const std::vector<uint32_t>& masks = {}, bool withProbabilities = true)
+      : nodes_(eng.getInnerNodes()), n_(nbSites), S_(static_cast<size_t>(eng.getNumberOfStates())) {
+    if (aln.size() != eng.getNumberOfTaxa() * nbSites)
+      throw DimensionException("MarginalAncestralStateReconstruction: alignment", aln.size(), eng.getNumberOfTaxa() * nbSites);
+    states_.resize(nodes_.size() * n_);
+    if (withProbabilities) post_.resize(nodes_.size() * n_ * S_);
+    eng.check(cmx_ancestral_states(eng.ctx(), aln.data(), n_, n_, masks.empty() ? nullptr : masks.data(), masks.size(),
+                                   states_.data(), withProbabilities ? post_.data() : nullptr));
+    for (size_t q = 0; q < nodes_.size(); ++q) row_[nodes_[q]] = q;
+  }
+  const std::vector<int>& getInnerNodes() const { return nodes_; }
+  size_t getNumberOfSites() const { return n_; }
+  std::vector<size_t> getAncestralStatesForNode(int node) const {
+    const size_t q = row(node);
+    return std::vector<size_t>(states_.begin() + q * n_, states_.begin() + (q + 1) * n_);
+  }
+  // probs[site][state] (LegacyMarginalAncestralStateReconstruction: the posterior per state at the node)
+  std::vector<size_t> getAncestralStatesForNode(int node, VVdouble& probs) const {
+    if (post_.empty()) throw Exception("MarginalAncestralStateReconstruction: built without probabilities");
+    const size_t q = row(node);
+    probs.assign(n_, Vdouble(S_));
+    for (size_t i = 0; i < n_; ++i)
+      std::copy(post_.begin() + (q * n_ + i) * S_, post_.begin() + (q * n_ + i + 1) * S_, probs[i].begin());
+    return getAncestralStatesForNode(node);
+  }
+  // every internal node's states, by node (ascending = getInnerNodes order)
+  std::map<int, std::vector<size_t>> getAncestralSequences() const {
+    std::map<int, std::vector<size_t>> out;
+    for (int node : nodes_) out[node] = getAncestralStatesForNode(node);
+    return out;
+  }
+
+ private:
+  size_t row(int node) const {
+    auto it = row_.find(node);
+    if (it == row_.end()) throw Exception("MarginalAncestralStateReconstruction: node " + std::to_string(node) + " is not an internal node");
+    return it->second;
+  }
+  std::vector<int> nodes_;
+  size_t n_, S_;
+  std::vector<uint8_t> states_;
+  Vdouble post_;   // [n_inner][N][S]
+  std::map<int, size_t> row_;
 };
 
 // ------------------------------------------------------------------------------------------------ statistics
