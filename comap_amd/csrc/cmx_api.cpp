@@ -42,6 +42,18 @@ std::mutex g_guard_mu;
 std::vector<std::string> g_guard_failures;   // buffers found trampled, in the order found (process-wide)
 std::map<std::string, size_t> g_guard_shrink;   // test hook: logical size override per buffer name
 
+// cmx_debug_null_hash_bits: the fused null's column hash keeps only its low bits (tests force collisions with it)
+std::atomic<int> g_pat_hash_bits{64};
+
+// CMX_NULL_PASS_BYTES: tests exercise the null's multi-pass paths with small nulls (0 = not set)
+size_t null_pass_bytes_env() {
+  static const size_t v = [] {
+    const char* e = getenv("CMX_NULL_PASS_BYTES");
+    return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)0;
+  }();
+  return v;
+}
+
 bool guard_on() {
   int g = g_guard.load();
   if (g < 0) {
@@ -111,6 +123,11 @@ struct cmx_ctx {
   const int *va_first = nullptr, *va_next = nullptr;
   const int* asr_inner = nullptr;   // cmx_ancestral_states*: the internal nodes, ascending (uploaded at first use)
   int asr_n_inner = 0;
+  // the fused null's distinct columns (cmx_set_null_patterns): -1 automatic, 0 off, 1 on; what the last null mapped
+  int null_patterns = -1;
+  int null_depth = 0;                         // > 0 inside the simulating null's own pass loop (one null, several calls)
+  unsigned long long null_mapped_host = 0;    // sites the last null mapped site by site
+  bool null_mapped_dev = false;               // ... plus the patterns counted on the device (scratch "pat_total")
   mutable std::string err;
 };
 
@@ -262,6 +279,7 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
   *out = nullptr;
   cmx_ctx* ctx = new cmx_ctx();
   ctx->device = device;
+  if (const char* e = getenv("CMX_NULL_PATTERNS")) ctx->null_patterns = e[0] == '0' ? 0 : (e[0] == '1' ? 1 : -1);   // A/B runs
   auto bail = [&](cmx_status s) {
     g_create_error = ctx->err;
     cmx_ctx_destroy(ctx);
@@ -736,6 +754,37 @@ cmx_status cmx_map_sites(cmx_ctx* ctx, const uint8_t* aln, size_t nsites, size_t
   return CMX_OK;
 }
 
+cmx_status cmx_set_null_patterns(cmx_ctx* ctx, int on) {
+  cmx_status s = need_model(ctx);
+  if (s != CMX_OK) return s;
+  ctx->null_patterns = on < 0 ? -1 : (on ? 1 : 0);
+  return CMX_OK;
+}
+
+cmx_status cmx_null_pattern_count(cmx_ctx* ctx, unsigned long long* count) {
+  cmx_status s = need_model(ctx);
+  if (s != CMX_OK) return s;
+  if (!count) return fail(ctx, CMX_ERR_INVALID, "cmx_null_pattern_count: count is NULL");
+  unsigned long long n = ctx->null_mapped_host;
+  if (ctx->null_mapped_dev) {
+    void* p = nullptr;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if ((s = scratch(ctx, "pat_total", sizeof(unsigned long long), &p)) != CMX_OK) return s;
+    unsigned long long d = 0;
+    HIP_TRY(ctx, hipMemcpy(&d, p, sizeof d, hipMemcpyDeviceToHost));
+    n += d;
+  }
+  *count = n;
+  return CMX_OK;
+}
+
+int cmx_debug_null_hash_bits(int bits) {
+  const int was = g_pat_hash_bits.load();
+  if (bits > 0) g_pat_hash_bits.store(bits > 64 ? 64 : bits);
+  return was;
+}
+
 // nijt.average / nijt.joint of CoETools.cpp:393-394 ("really for benchmarking only" there)
 cmx_status cmx_set_mapping_options(cmx_ctx* ctx, int average, int joint) {
   cmx_status s = need_model(ctx);
@@ -1189,6 +1238,80 @@ static cmx_status null_unfused_dev(cmx_ctx* ctx1, cmx_ctx* ctx2, int kind, const
                                    size_t rep_begin, size_t rep_end, size_t rep_ram, const uint8_t* d_supplied, double* d_stat,
                                    int32_t* d_rcmin, double* d_prmin, double* d_nmin, void* stream);
 
+// The fused null's distinct columns (cmx_null_patterns.hip).  Per site of a pass the pattern path holds, at
+// worst (every site its own pattern), B*K doubles of counts, the packed column and 68 bytes of keys, indices and per-pattern
+// scalars; a pass is as many whole replicates as fit kNullPatternPassBytes (CMX_NULL_PASS_BYTES in tests).  One pass at the
+// target (2 * 10^7 sites x 1 132 bytes): the deduplication is done over the whole launch, with a single mapping tail.
+constexpr size_t kNullPatternPassBytes = (size_t)24 << 30;
+
+static size_t null_pattern_site_bytes(const cmx_ctx* ctx) {
+  return (size_t)ctx->hm.B * ctx->hm.K * sizeof(double) + null_pattern_row_bytes(ctx->hm.T) + 68;
+}
+
+// replicates per pattern pass, or 0: map every site of every pair (patterns off, or one replicate exceeds the budget)
+static size_t null_pattern_reps(const cmx_ctx* ctx, size_t rep_ram) {
+  const bool on = ctx->null_patterns < 0 ? (ctx->hm.S == 20 && ctx->hm.fuse == 1) : ctx->null_patterns == 1;
+  if (!on) return 0;
+  const size_t budget = null_pass_bytes_env() ? null_pass_bytes_env() : kNullPatternPassBytes;
+  const size_t per_rep = 2 * rep_ram * null_pattern_site_bytes(ctx);
+  if (per_rep > budget || 2 * rep_ram > ((size_t)1 << 31)) return 0;
+  return std::min(budget / per_rep, ((size_t)1 << 31) / (2 * rep_ram));   // (32-bit site indices)
+}
+
+// a.supplied / a.rep_ram / a.stat_* / a.null_* describe the whole null; passes of whole replicates, sized evenly
+static cmx_status null_patterns_dev(cmx_ctx* ctx, MapArgs a, size_t nrep, size_t reps_max, void* stream) {
+  const HostModel& h = ctx->hm;
+  const size_t rep_ram = a.rep_ram, T = (size_t)h.T, BK = (size_t)h.B * h.K, rowb = null_pattern_row_bytes(h.T);
+  const size_t npass = (nrep + reps_max - 1) / reps_max, reps = (nrep + npass - 1) / npass;
+  const size_t cap = reps * 2 * rep_ram;   // sites of the largest pass
+  NullPatternBufs b{};
+  double *cnt, *pr, *nm;
+  int32_t* rc;
+  cmx_status s;
+  if ((s = scratch(ctx, "pat_key", sizeof(uint64_t) * cap, (void**)&b.key)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_key_s", sizeof(uint64_t) * cap, (void**)&b.key_s)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_g", sizeof(uint32_t) * cap, (void**)&b.g)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_g_s", sizeof(uint32_t) * cap, (void**)&b.g_s)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_col", rowb * cap, (void**)&b.col)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_head", sizeof(uint32_t) * cap, (void**)&b.head)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_incl", sizeof(uint32_t) * cap, (void**)&b.incl)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_of", sizeof(uint32_t) * cap, (void**)&b.pat_of)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_site", sizeof(uint32_t) * cap, (void**)&b.rep_site)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_cnt", sizeof(double) * BK * cap, (void**)&cnt)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_pr", sizeof(double) * cap, (void**)&pr)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_nm", sizeof(double) * cap, (void**)&nm)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_rc", sizeof(int32_t) * cap, (void**)&rc)) != CMX_OK) return s;
+  if ((s = scratch(ctx, "pat_total", sizeof(unsigned long long), (void**)&b.total)) != CMX_OK) return s;
+  const int hash_bits = g_pat_hash_bits.load();
+  HIP_TRY(ctx, null_pattern_tmp_bytes(cap, hash_bits, &b.tmp_bytes));
+  if ((s = scratch(ctx, "pat_tmp", b.tmp_bytes ? b.tmp_bytes : 16, &b.tmp)) != CMX_OK) return s;
+  if (!ctx->null_mapped_dev) {
+    HIP_TRY(ctx, hipMemsetAsync(b.total, 0, sizeof(unsigned long long), (hipStream_t)stream));
+    ctx->null_mapped_dev = true;
+  }
+  const uint8_t* sup = a.supplied;
+  double* stat = a.null_stat;
+  int32_t* rcmin = a.null_rcmin;
+  double *prmin = a.null_prmin, *nmin = a.null_nmin;
+  a.counts = cnt; a.ldc = cap; a.post_rate = pr; a.rate_class = rc; a.norm = nm;
+  a.rep_site = b.rep_site;
+  const size_t ks = (size_t)map_sites_per_wave(h.dS);
+  for (size_t r0 = 0; r0 < nrep; r0 += reps) {
+    const size_t r1 = std::min(nrep, r0 + reps), n = (r1 - r0) * 2 * rep_ram, o = r0 * rep_ram;
+    a.supplied = sup + r0 * 2 * T * rep_ram;
+    HIP_TRY(ctx, launch_null_patterns(a.supplied, h.T, rep_ram, n, hash_bits, b, (hipStream_t)stream));
+    // the pattern count stays on the device: the grid is sized for every site its own pattern, the waves read the count
+    a.nsites = n;
+    a.npat = b.incl + (n - 1);
+    const size_t blocks_needed = ((n + ks - 1) / ks + kWavesPerBlock - 1) / kWavesPerBlock;
+    HIP_TRY(ctx, launch_map(a, kModeNullPatterns, (int)std::min<size_t>(blocks_needed, (size_t)ctx->grid_blocks), (hipStream_t)stream));
+    HIP_TRY(ctx, launch_null_pattern_pairs(a.stat_kind, a.stat_param, h.B, h.K, cnt, cap, pr, rc, nm, b.pat_of, rep_ram, n / 2,
+                                           a.stat_mean, stat + o, rcmin ? rcmin + o : nullptr, prmin ? prmin + o : nullptr,
+                                           nmin ? nmin + o : nullptr, (hipStream_t)stream));
+  }
+  return CMX_OK;
+}
+
 cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint64_t seed, size_t rep_begin,
                               size_t rep_end, size_t rep_ram, const uint8_t* d_supplied, double* d_stat,
                               int32_t* d_rcmin, double* d_prmin, double* d_nmin, void* stream) {
@@ -1202,27 +1325,27 @@ cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint
     // needs a joint table per pair cannot be evaluated per lane inside the mapping wave.  The same simulate -> map ->
     // score sequence then runs unfused, which is what the two-data-set null does with both sides equal.  So does a
     // statistic with branch weights (map_kernel's lanes score unweighted only).
+    if (ctx->null_depth == 0) { ctx->null_mapped_host = 2 * (rep_end - rep_begin) * rep_ram; ctx->null_mapped_dev = false; }
     return null_unfused_dev(ctx, ctx, kind, params, seed, rep_begin, rep_end, rep_ram, d_supplied, d_stat, d_rcmin, d_prmin, d_nmin, stream);
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (ctx->null_depth == 0) { ctx->null_mapped_host = 0; ctx->null_mapped_dev = false; }
   if (!d_supplied) {
     // simulate first, at full occupancy, then map the alignments as "supplied" ones: the same draws, the same results
     // as a simulator inside the mapping waves (round 1; 7.8 % of the launch there, latency nobody could hide).  The
     // alignments of a pass stay under 4 GiB: a larger null runs as several passes over replicate ranges.
     const size_t per_rep = 2 * (size_t)ctx->hm.T * rep_ram;
-    static const size_t pass_bytes = [] {   // CMX_NULL_PASS_BYTES: tests exercise the multi-pass path with small nulls
-      const char* e = getenv("CMX_NULL_PASS_BYTES");
-      return e ? (size_t)strtoull(e, nullptr, 10) : ((size_t)4 << 30);
-    }();
+    const size_t pass_bytes = null_pass_bytes_env() ? null_pass_bytes_env() : ((size_t)4 << 30);
     const size_t reps_per_pass = std::max<size_t>(1, pass_bytes / per_rep);
     if (rep_end - rep_begin > reps_per_pass) {
-      for (size_t r0 = rep_begin; r0 < rep_end; r0 += reps_per_pass) {
+      ++ctx->null_depth;
+      for (size_t r0 = rep_begin; r0 < rep_end && s == CMX_OK; r0 += reps_per_pass) {
         const size_t r1 = std::min(rep_end, r0 + reps_per_pass), o = (r0 - rep_begin) * rep_ram;
-        if ((s = cmx_null_intra_dev(ctx, kind, params, seed, r0, r1, rep_ram, nullptr, d_stat + o, d_rcmin ? d_rcmin + o : nullptr,
-                                    d_prmin ? d_prmin + o : nullptr, d_nmin ? d_nmin + o : nullptr, stream)) != CMX_OK)
-          return s;
+        s = cmx_null_intra_dev(ctx, kind, params, seed, r0, r1, rep_ram, nullptr, d_stat + o, d_rcmin ? d_rcmin + o : nullptr,
+                               d_prmin ? d_prmin + o : nullptr, d_nmin ? d_nmin + o : nullptr, stream);
       }
-      return CMX_OK;
+      --ctx->null_depth;
+      return s;
     }
     uint8_t* d_aln;
     if ((s = scratch(ctx, "null_aln", (rep_end - rep_begin) * per_rep, (void**)&d_aln)) != CMX_OK) return s;
@@ -1237,10 +1360,13 @@ cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint
   if ((s = stat_mean_vectors(ctx, kind, params, &a.stat_mean, stream)) != CMX_OK) return s;
   a.seed = seed; a.rep_begin = rep_begin; a.rep_ram = rep_ram; a.supplied = d_supplied;
   a.null_stat = d_stat; a.null_rcmin = d_rcmin; a.null_prmin = d_prmin; a.null_nmin = d_nmin;
+  const size_t reps_per_pass = null_pattern_reps(ctx, rep_ram);
+  if (reps_per_pass) return null_patterns_dev(ctx, a, rep_end - rep_begin, reps_per_pass, stream);
   const size_t ks = (size_t)map_sites_per_wave(ctx->hm.dS);
   const size_t blocks_needed = ((a.nsites + ks - 1) / ks + kWavesPerBlock - 1) / kWavesPerBlock;
   const int grid = (int)std::min<size_t>(blocks_needed, (size_t)ctx->grid_blocks);
   HIP_TRY(ctx, launch_map(a, kModeNull, grid, (hipStream_t)stream));
+  ctx->null_mapped_host += 2 * a.nsites;
   return CMX_OK;
 }
 

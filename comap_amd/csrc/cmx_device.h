@@ -86,7 +86,9 @@ struct Workspace {
 
 // kModeObservedSplit: one (site block, rate class) per wave-task for small alignments (an alignment of 2 000 sites is
 // 32 site blocks: one task per wave would be four class passes of pure latency), classes summed by map_finalize_kernel
-enum MapMode { kModeObserved = 0, kModeNull = 1, kModeObservedSplit = 2 };
+// kModeNullPatterns: the fused null's distinct columns: lane = pattern, walked as kModeNull walks a site, with
+// counts / post rate / norm / rate class written per pattern as in observed mode; the pairs are scored afterwards
+enum MapMode { kModeObserved = 0, kModeNull = 1, kModeObservedSplit = 2, kModeNullPatterns = 3 };
 
 struct MapArgs {
   DevModel m;
@@ -117,6 +119,10 @@ struct MapArgs {
   int32_t* null_rcmin;
   double* null_prmin;
   double* null_nmin;
+  // pattern mode (appended: the fields above keep their kernel-argument offsets): the pass's site of the first occurrence
+  // of every pattern, and the number of patterns (device; the grid is sized for every site its own pattern)
+  const uint32_t* rep_site;
+  const uint32_t* npat;
 };
 
 // launchers (cmx_kernels.hip)
@@ -215,6 +221,30 @@ hipError_t launch_pair_gram(int kind, int B, int Bp, const double* d_X1, const d
                             size_t n1, size_t ldx1, const double* d_X2, const double* d_s2, const double* d_r2,
                             size_t n2, size_t ldx2, int intra, double* d_out, size_t ldo, hipStream_t stream,
                             size_t nblk = 1, size_t zsite = 0, size_t zout = 0, size_t zx = 0, size_t irow0 = 0);
+// the fused null's patterns (cmx_null_patterns.hip).  Sites g of a pass: [replicate][batch][taxon][rep_ram] alignments,
+// g = (rep * 2 + batch) * rep_ram + j.  Columns are copied site-major, null_pattern_row_bytes(T) bytes each.
+size_t null_pattern_row_bytes(int T);
+hipError_t null_pattern_tmp_bytes(size_t n, int hash_bits, size_t* bytes);   // rocPRIM temporary of a pass of n sites
+struct NullPatternBufs {
+  uint64_t *key, *key_s;   // [n] column hashes (low hash_bits bits), sorted
+  uint32_t *g, *g_s;       // [n] site index, in hash order
+  uint8_t* col;            // [n][row bytes] packed columns
+  uint32_t* head;          // [n] sorted position of the first element of each sorted element's run
+  uint32_t* incl;          // [n] inclusive sum over g of "g is the first site of its run": pattern of a first site + 1
+  uint32_t* pat_of;        // [n] pattern of site g
+  uint32_t* rep_site;      // [n] first site of pattern p (the first incl[n - 1] entries)
+  unsigned long long* total;   // patterns of every pass so far are added here
+  void* tmp;
+  size_t tmp_bytes;
+};
+// key + packed copy, stable radix sort of (hash, g), run flags, the two scans, pattern numbers in first-occurrence order
+hipError_t launch_null_patterns(const uint8_t* d_sup, int T, size_t rep_ram, size_t n, int hash_bits, const NullPatternBufs& b,
+                                hipStream_t stream);
+// statistic and minima of pair q = (rep, j) from the patterns of sites (rep, 0, j) and (rep, 1, j); counts [B*K][ldc]
+hipError_t launch_null_pattern_pairs(int kind, double param, int B, int K, const double* counts, size_t ldc, const double* post_rate,
+                                     const int32_t* rate_class, const double* norm, const uint32_t* pat_of, size_t rep_ram,
+                                     size_t npairs, const double* d_mean, double* stat, int32_t* rcmin, double* prmin, double* nmin,
+                                     hipStream_t stream);
 hipError_t launch_max_reduce(const double* d_x, size_t n, double* d_out, hipStream_t stream);
 hipError_t launch_null_classify(const double* d_stat, const double* d_nmin, size_t nnull, const double* d_maxnorm,
                                 int nclasses, uint32_t* d_cls, uint32_t* d_hist, hipStream_t stream);

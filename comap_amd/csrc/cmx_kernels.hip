@@ -17,6 +17,8 @@
 //   MODE == kModeNull: map (x2 batches) -> per-pair statistic of AnalysisTools::getNullDistributionIntraDR
 //   (CoMap/AnalysisTools.cpp:587-653) per wave, on alignments simulated beforehand by simulate_lds_kernel /
 //   simulate_blocked_kernel at full occupancy (round 1 simulated inside the mapping wave).
+//   MODE == kModeNullPatterns: the same walk over the null's distinct columns, one lane per pattern; the pairs are scored
+//   by null_pattern_pairs_kernel (cmx_null_patterns.hip).
 // pair_gram_kernel: all-pairs statistic as X.X^T on v_mfma_f64_16x16x4_f64 with per-statistic epilogues
 //   (CoMap/Statistics.h:164-329; loops CoMap/CoETools.cpp:672-692, 786-810).
 // mica_mfma_kernel: column mutual information as a one-hot Gram on v_mfma_i32_32x32x32_i8 (CoMap/Mica.cpp:349-361).
@@ -870,7 +872,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
   constexpr int kRow = NG == 3 ? 64 : kSites;
   const DevModel& m = a.m;
   // the null's alignments are fully resolved: class-fused nucleotide models walk them with the cherry tables' stream
-  constexpr bool kTables = MODE == kModeNull && DevWalk<S, FUSE, NG, true>::kCherryTables;
+  constexpr bool kTables = (MODE == kModeNull || MODE == kModeNullPatterns) && DevWalk<S, FUSE, NG, true>::kCherryTables;
   const ConstModel cm(m, kTables);
   const int lane = threadIdx.x & (kWave - 1);
   const int sidx = NG >= 3 ? lane : (NG == 2 ? (((lane >> 5) << 4) | (lane & 15)) : (lane & 15));   // site of this lane in the wave's block
@@ -913,6 +915,30 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
       a.split_lc[(ntasks + task) * kSites + sidx] = pr;
       a.split_lc[(2 * ntasks + task) * kSites + sidx] = nrm;          // weight of the pass's best class
       a.split_lc[(3 * ntasks + task) * kSites + sidx] = (double)rc;   // ... and its index
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    return;
+  }
+  if constexpr (MODE == kModeNullPatterns) {
+    // lane = pattern p (numbered in first-occurrence order): the column of its first site g, walked exactly as
+    // the null mode walks a site of a pair; per pattern what observed mode writes per site
+    const size_t npat = *a.npat;
+    const size_t nb = (npat + kSites - 1) / kSites;
+    for (size_t sb = wave; sb < nb; sb += nwaves) {
+      const size_t p = sb * kSites + sidx;
+      const bool active = p < npat && sidx < kSites;
+      const size_t g = a.rep_site[active ? p : npat - 1];
+      const size_t rh = g / a.rep_ram, j = g - rh * a.rep_ram;   // rh = rep_local * 2 + h
+      double L, pr, nrm;
+      int rc;
+      map_sites_wave<S, FUSE, NG, true>(a, wsD, wsU, part, cnt0, lds_off, a.supplied + rh * (size_t)m.T * a.rep_ram + j, a.rep_ram,
+                                        lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
+      if (active) {
+        a.post_rate[p] = pr;
+        a.rate_class[p] = rc;
+        a.norm[p] = nrm;
+        for (int r = 0; r < m.B * m.K; ++r) a.counts[(size_t)r * a.ldc + p] = cnt0[(size_t)r * kRow + sidx];
+      }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     return;
@@ -990,11 +1016,13 @@ hipError_t launch_map(const MapArgs& a_in, int mode, int grid_blocks, hipStream_
     hipLaunchKernelGGL((map_kernel<S_, MODE_, F_>), grid, block, lds, stream, a);                             \
   } while (0)
   // (the null instantiations of the class-fused layouts read the cherry-table walk's stream)
-  if (mode == kModeNull && a.m.fuse > 1 && a.m.msched_r == nullptr) return hipErrorInvalidValue;
+  if ((mode == kModeNull || mode == kModeNullPatterns) && a.m.fuse > 1 && a.m.msched_r == nullptr) return hipErrorInvalidValue;
+  if (mode == kModeNullPatterns && (!a.rep_site || !a.npat || !a.counts || !a.post_rate || !a.rate_class || !a.norm)) return hipErrorInvalidValue;
 #define CMX_LAUNCH_MODES(S_, F_)                                            \
   do {                                                                      \
     if (mode == kModeObserved) CMX_LAUNCH(S_, kModeObserved, F_);           \
     else if (mode == kModeObservedSplit) CMX_LAUNCH(S_, kModeObservedSplit, F_); \
+    else if (mode == kModeNullPatterns) CMX_LAUNCH(S_, kModeNullPatterns, F_); \
     else CMX_LAUNCH(S_, kModeNull, F_);                                     \
   } while (0)
   if (a.m.S == 20 && a.m.fuse == 1 && mode == kModeObservedSplit && a.split_sites == 16) {

@@ -1,0 +1,182 @@
+// The fused null's distinct columns.  A third of the sites the target's null maps repeat a column mapped
+// earlier in the same launch (Gamma with alpha = 0.5: the slowest class's columns are mostly constant), and a column's
+// counts, norm, posterior rate and rate class depend on the column alone.  So a pass of the null:
+//   null_pattern_key_kernel   one thread per simulated site g: 64-bit hash of its column + a site-major byte copy
+//   radix sort of (hash, g)   stable: in a run of equal hashes the smallest g comes first
+//   null_pattern_flag_kernel  a sorted element starts a run when its hash or its column bytes differ from its predecessor's
+//                             (a hash collision costs deduplication, never correctness)
+//   two scans                 run head of every sorted element (max); number of run heads up to g (sum, over g)
+//   null_pattern_assign_kernel  pattern of every site, first site of every pattern: patterns numbered in first-occurrence
+//                             order, so a mapping wave's 64 patterns stay on nearby columns (the symbol reads coalesce)
+// then map_kernel<S, kModeNullPatterns> maps each pattern once, and null_pattern_pairs_kernel scores the pairs from the
+// pattern table with the null mode's own pair_stat_strided and minima.
+#include <algorithm>
+#include <cstring>
+
+#include <rocprim/rocprim.hpp>
+
+#include "cmx_device.h"
+#include "cmx_pairstat.h"
+
+namespace cmx {
+
+namespace {
+
+constexpr int kPatThreads = 256;
+
+__device__ __forceinline__ uint64_t pat_mix(uint64_t h, uint64_t x) {
+  h ^= x * 0x9E3779B97F4A7C15ull;
+  h ^= h >> 29;
+  return h * 0xBF58476D1CE4E5B9ull;
+}
+
+__device__ __forceinline__ uint64_t pat_final(uint64_t h) {   // MurmurHash3's fmix64
+  h ^= h >> 33;
+  h *= 0xff51afd7ed558ccdull;
+  h ^= h >> 33;
+  h *= 0xc4ceb9fe1a85ec53ull;
+  h ^= h >> 33;
+  return h;
+}
+
+__global__ __launch_bounds__(kPatThreads) void null_pattern_key_kernel(const uint8_t* __restrict__ sup, int T, size_t rep_ram, size_t n,
+                                                                       int rowb, int hash_bits, uint64_t* __restrict__ key,
+                                                                       uint32_t* __restrict__ gidx, uint8_t* __restrict__ col) {
+  const size_t g = (size_t)blockIdx.x * kPatThreads + threadIdx.x;
+  if (g >= n) return;
+  const size_t rh = g / rep_ram, j = g - rh * rep_ram;
+  const uint8_t* src = sup + rh * (size_t)T * rep_ram + j;   // taxon t at src[t * rep_ram]: a wave reads 64 neighbouring bytes
+  uint4* dst = reinterpret_cast<uint4*>(col + g * (size_t)rowb);
+  uint64_t h = 0x243F6A8885A308D3ull ^ (uint64_t)T;
+  for (int t0 = 0; t0 < rowb; t0 += 16) {
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int t = t0 + u;
+      const uint32_t b = t < T ? (uint32_t)src[(size_t)t * rep_ram] : 0u;
+      w[u >> 2] |= b << (8 * (u & 3));
+    }
+    dst[t0 >> 4] = make_uint4(w[0], w[1], w[2], w[3]);
+    h = pat_mix(h, (uint64_t)w[0] | ((uint64_t)w[1] << 32));
+    h = pat_mix(h, (uint64_t)w[2] | ((uint64_t)w[3] << 32));
+  }
+  h = pat_final(h);
+  if (hash_bits < 64) h &= (1ull << hash_bits) - 1;
+  key[g] = h;
+  gidx[g] = (uint32_t)g;
+}
+
+__global__ __launch_bounds__(kPatThreads) void null_pattern_flag_kernel(size_t n, const uint64_t* __restrict__ key_s,
+                                                                        const uint32_t* __restrict__ g_s, const uint8_t* __restrict__ col,
+                                                                        int rowb, uint32_t* __restrict__ head, uint32_t* __restrict__ first) {
+  const size_t i = (size_t)blockIdx.x * kPatThreads + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t g = g_s[i];
+  bool starts = i == 0;
+  if (!starts) {
+    starts = key_s[i] != key_s[i - 1];
+    if (!starts) {   // equal hashes: the columns themselves decide, byte for byte
+      const uint4* x = reinterpret_cast<const uint4*>(col + (size_t)g * rowb);
+      const uint4* y = reinterpret_cast<const uint4*>(col + (size_t)g_s[i - 1] * rowb);
+      for (int c = 0; c < rowb / 16; ++c) {
+        const uint4 a = x[c], b = y[c];
+        if (a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w) { starts = true; break; }
+      }
+    }
+  }
+  head[i] = starts ? (uint32_t)i : 0u;
+  first[g] = starts ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(kPatThreads) void null_pattern_assign_kernel(size_t n, const uint32_t* __restrict__ g_s,
+                                                                          const uint32_t* __restrict__ head, const uint32_t* __restrict__ incl,
+                                                                          uint32_t* __restrict__ pat_of, uint32_t* __restrict__ rep_site,
+                                                                          unsigned long long* __restrict__ total) {
+  const size_t i = (size_t)blockIdx.x * kPatThreads + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t g = g_s[i], hi = head[i];
+  const uint32_t p = incl[g_s[hi]] - 1u;
+  pat_of[g] = p;
+  if (hi == (uint32_t)i) rep_site[p] = g;
+  if (i == n - 1) *total += incl[n - 1];   // (stream order: the previous pass's add is done)
+}
+
+// pair q = (rep, j): sites g0 = 2 rep rep_ram + j (batch 0) and g1 = g0 + rep_ram (batch 1); the minima take batch 0 first,
+// then "<", as map_kernel's null mode does (AnalysisTools.cpp:643-652)
+__global__ __launch_bounds__(kPatThreads) void null_pattern_pairs_kernel(int kind, double param, int B, int K, const double* __restrict__ counts,
+                                                                         size_t ldc, const double* __restrict__ post_rate,
+                                                                         const int32_t* __restrict__ rate_class, const double* __restrict__ norm,
+                                                                         const uint32_t* __restrict__ pat_of, size_t rep_ram, size_t npairs,
+                                                                         const double* __restrict__ mean, double* __restrict__ stat,
+                                                                         int32_t* __restrict__ rcmin, double* __restrict__ prmin,
+                                                                         double* __restrict__ nmin) {
+  const size_t q = (size_t)blockIdx.x * kPatThreads + threadIdx.x;
+  if (q >= npairs) return;
+  const size_t r = q / rep_ram, j = q - r * rep_ram, g0 = 2 * r * rep_ram + j;
+  const uint32_t pa = pat_of[g0], pb = pat_of[g0 + rep_ram];
+  stat[q] = pair_stat_strided(kind, param, B, K, counts + pa, ldc, counts + pb, ldc, mean);
+  if (rcmin) {
+    const int32_t a = rate_class[pa], b = rate_class[pb];
+    rcmin[q] = b < a ? b : a;
+  }
+  if (prmin) {
+    const double a = post_rate[pa], b = post_rate[pb];
+    prmin[q] = b < a ? b : a;
+  }
+  if (nmin) {
+    const double a = norm[pa], b = norm[pb];
+    nmin[q] = b < a ? b : a;
+  }
+}
+
+inline unsigned pat_grid(size_t n) { return (unsigned)((n + kPatThreads - 1) / kPatThreads); }
+
+}  // namespace
+
+size_t null_pattern_row_bytes(int T) { return ((size_t)T + 15) / 16 * 16; }
+
+hipError_t null_pattern_tmp_bytes(size_t n, int hash_bits, size_t* bytes) {
+  size_t a = 0, b = 0, c = 0;
+  const int bits = hash_bits < 1 || hash_bits > 64 ? 64 : hash_bits;
+  hipError_t e = rocprim::radix_sort_pairs(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                           n, 0, bits, (hipStream_t)0);
+  if (e != hipSuccess) return e;
+  e = rocprim::inclusive_scan(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::maximum<uint32_t>(), (hipStream_t)0);
+  if (e != hipSuccess) return e;
+  e = rocprim::inclusive_scan(nullptr, c, (uint32_t*)nullptr, (uint32_t*)nullptr, n, rocprim::plus<uint32_t>(), (hipStream_t)0);
+  *bytes = std::max(a, std::max(b, c));
+  return e;
+}
+
+hipError_t launch_null_patterns(const uint8_t* d_sup, int T, size_t rep_ram, size_t n, int hash_bits, const NullPatternBufs& b,
+                                hipStream_t stream) {
+  const int rowb = (int)null_pattern_row_bytes(T);
+  const int bits = hash_bits < 1 || hash_bits > 64 ? 64 : hash_bits;
+  hipLaunchKernelGGL(null_pattern_key_kernel, dim3(pat_grid(n)), dim3(kPatThreads), 0, stream, d_sup, T, rep_ram, n, rowb, bits, b.key,
+                     b.g, b.col);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  size_t tb = b.tmp_bytes;
+  if ((e = rocprim::radix_sort_pairs(b.tmp, tb, b.key, b.key_s, b.g, b.g_s, n, 0, bits, stream)) != hipSuccess) return e;
+  hipLaunchKernelGGL(null_pattern_flag_kernel, dim3(pat_grid(n)), dim3(kPatThreads), 0, stream, n, b.key_s, b.g_s, b.col, rowb, b.head,
+                     b.incl);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  tb = b.tmp_bytes;
+  if ((e = rocprim::inclusive_scan(b.tmp, tb, b.head, b.head, n, rocprim::maximum<uint32_t>(), stream)) != hipSuccess) return e;
+  tb = b.tmp_bytes;
+  if ((e = rocprim::inclusive_scan(b.tmp, tb, b.incl, b.incl, n, rocprim::plus<uint32_t>(), stream)) != hipSuccess) return e;
+  hipLaunchKernelGGL(null_pattern_assign_kernel, dim3(pat_grid(n)), dim3(kPatThreads), 0, stream, n, b.g_s, b.head, b.incl, b.pat_of,
+                     b.rep_site, b.total);
+  return hipGetLastError();
+}
+
+hipError_t launch_null_pattern_pairs(int kind, double param, int B, int K, const double* counts, size_t ldc, const double* post_rate,
+                                     const int32_t* rate_class, const double* norm, const uint32_t* pat_of, size_t rep_ram,
+                                     size_t npairs, const double* d_mean, double* stat, int32_t* rcmin, double* prmin, double* nmin,
+                                     hipStream_t stream) {
+  hipLaunchKernelGGL(null_pattern_pairs_kernel, dim3(pat_grid(npairs)), dim3(kPatThreads), 0, stream, kind, param, B, K, counts, ldc,
+                     post_rate, rate_class, norm, pat_of, rep_ram, npairs, d_mean, stat, rcmin, prmin, nmin);
+  return hipGetLastError();
+}
+
+}  // namespace cmx

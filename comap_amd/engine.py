@@ -59,6 +59,7 @@ EXPORTS = [
     "cmx_hclust", "cmx_hclust_dev", "cmx_cluster_sites", "cmx_cluster_sites_dev", "cmx_cluster_null",
     "cmx_intra_compact_range_dev", "cmx_intra_gram_prefetch_dev", "cmx_expand_compact_rows", "cmx_vector_matrix",
     "cmx_scratch_check", "cmx_debug_scratch_guard", "cmx_debug_scratch_guard_failures", "cmx_debug_scratch_shrink",
+    "cmx_set_null_patterns", "cmx_null_pattern_count", "cmx_debug_null_hash_bits",
 ]
 # clustering.distance / clustering.method options of the reference (CoMap/CoMap.cpp:402-428, :460-472)
 DIST_CORRELATION, DIST_COMPENSATION, DIST_EUCLIDIAN = range(3)
@@ -91,6 +92,13 @@ def scratch_shrink(name, nbytes):
     lib = load_library()
     lib.cmx_debug_scratch_shrink.restype = None
     lib.cmx_debug_scratch_shrink(None if name is None else name.encode(), ctypes.c_size_t(nbytes))
+
+
+def null_hash_bits(bits=None):
+    """cmx_debug_null_hash_bits: keep only the low `bits` bits of the fused null's column hash (process-wide; forces
+    collisions in tests); None queries.  Returns the previous value."""
+    lib = load_library()
+    return int(lib.cmx_debug_null_hash_bits(ctypes.c_int(0 if bits is None else int(bits))))
 
 
 def mica_bootstrap_indices(seed, nsites, nrep_cpu, nrep_ram):
@@ -398,6 +406,17 @@ class Engine:
         """nijt.average / nijt.joint (CoETools.cpp:393-406): which of computeSubstitutionVectors{, NoAveraging, Marginal,
         NoAveragingMarginal} every later mapping of this engine (observed data and nulls) uses; default (True, True)."""
         self._check(self._lib.cmx_set_mapping_options(self._ctx, int(bool(average)), int(bool(joint))))
+
+    def set_null_patterns(self, on=None):
+        """cmx_set_null_patterns: the fused null maps each distinct simulated column once (True), every site of every pair
+        (False), or decides by model (None, the default: 20-state models).  The same results either way."""
+        self._check(self._lib.cmx_set_null_patterns(self._ctx, -1 if on is None else int(bool(on))))
+
+    def null_pattern_count(self):
+        """columns the last null of this engine mapped (its distinct patterns when it deduplicated); synchronises"""
+        n = ctypes.c_ulonglong(0)
+        self._check(self._lib.cmx_null_pattern_count(self._ctx, ctypes.byref(n)))
+        return int(n.value)
 
     def set_statistic_weights(self, w=None):
         """Statistic::setWeights / deleteWeights (CoMap/Statistics.h:83-104): per-branch weights [B] in the counts'

@@ -258,6 +258,19 @@ cmx_status cmx_null_intra(cmx_ctx* ctx, int kind, const double* params, uint64_t
 cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint64_t seed, size_t rep_begin,
                               size_t rep_end, size_t rep_ram, const uint8_t* d_supplied, double* d_stat,
                               int32_t* d_rcmin, double* d_prmin, double* d_nmin, void* stream);
+/* The fused null (the averaged joint mapping, unweighted statistics other than the bounds MI) maps each distinct column
+ * of its simulated alignments once and scores the pairs from the distinct columns' results; a column's counts, norm,
+ * posterior rate and rate class depend on the column alone, so the results are the same bytes as mapping every site of
+ * every pair.  on: 1 deduplicate, 0 map every site (the path before), -1 automatic (the default: 20-state models).
+ * CMX_NULL_PATTERNS=0 / 1 in the environment sets the default of contexts created afterwards. */
+cmx_status cmx_set_null_patterns(cmx_ctx* ctx, int on);
+/* columns the last intra null of this context mapped (cmx_null_intra, cmx_null_intra_dev; of a continuous-rate null, its
+ * last 4 GiB pass): its distinct patterns summed over its passes (a pass deduplicates inside itself), plus every site of
+ * a pass or null that did not deduplicate.  Synchronises the device. */
+cmx_status cmx_null_pattern_count(cmx_ctx* ctx, unsigned long long* count);
+/* test hook: the fused null's column hash keeps only its low `bits` bits (1 .. 64, process-wide), to force collisions
+ * (they cost deduplication, never correctness); bits <= 0 queries.  Returns the previous value. */
+int cmx_debug_null_hash_bits(int bits);
 
 /* the same null under simulations.continuous = yes (CoMap.cpp:146, 213): the two batches of every replicate are drawn by
  * the continuous-rate simulator on the device and mapped there (cmx_simulate_continuous_dev + cmx_null_intra_dev with
