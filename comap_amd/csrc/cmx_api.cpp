@@ -1239,13 +1239,15 @@ static cmx_status null_unfused_dev(cmx_ctx* ctx1, cmx_ctx* ctx2, int kind, const
                                    int32_t* d_rcmin, double* d_prmin, double* d_nmin, void* stream);
 
 // The fused null's distinct columns (cmx_null_patterns.hip).  Per site of a pass the pattern path holds, at
-// worst (every site its own pattern), B*K doubles of counts, the packed column and 68 bytes of keys, indices and per-pattern
-// scalars; a pass is as many whole replicates as fit kNullPatternPassBytes (CMX_NULL_PASS_BYTES in tests).  One pass at the
-// target (2 * 10^7 sites x 1 132 bytes): the deduplication is done over the whole launch, with a single mapping tail.
+// worst (every site its own pattern), B*K doubles of counts, the packed column and 84 bytes of keys, indices and per-pattern
+// scalars (mean and squared deviations among them); a pass is as many whole replicates as fit kNullPatternPassBytes
+// (CMX_NULL_PASS_BYTES in tests).  One pass at the target (2 * 10^7 sites x 1 148 bytes): the deduplication is done over
+// the whole launch, with a single mapping tail.  The count table is rounded up to whole tiles of one mapping wave's
+// patterns (under 64 KB a pass): that rounding is no part of the replicates-per-pass arithmetic.
 constexpr size_t kNullPatternPassBytes = (size_t)24 << 30;
 
 static size_t null_pattern_site_bytes(const cmx_ctx* ctx) {
-  return (size_t)ctx->hm.B * ctx->hm.K * sizeof(double) + null_pattern_row_bytes(ctx->hm.T) + 68;
+  return (size_t)ctx->hm.B * ctx->hm.K * sizeof(double) + null_pattern_row_bytes(ctx->hm.T) + 84;
 }
 
 // replicates per pattern pass, or 0: map every site of every pair (patterns off, or one replicate exceeds the budget)
@@ -1277,7 +1279,16 @@ static cmx_status null_patterns_dev(cmx_ctx* ctx, MapArgs a, size_t nrep, size_t
   if ((s = scratch(ctx, "pat_incl", sizeof(uint32_t) * cap, (void**)&b.incl)) != CMX_OK) return s;
   if ((s = scratch(ctx, "pat_of", sizeof(uint32_t) * cap, (void**)&b.pat_of)) != CMX_OK) return s;
   if ((s = scratch(ctx, "pat_site", sizeof(uint32_t) * cap, (void**)&b.rep_site)) != CMX_OK) return s;
-  if ((s = scratch(ctx, "pat_cnt", sizeof(double) * BK * cap, (void**)&cnt)) != CMX_OK) return s;
+  // tile-major: a mapping wave's ks patterns are one [B*K][kr] block, the last tile whole (its spare columns are written)
+  const size_t ks = (size_t)map_sites_per_wave(h.dS), kr = map_ng(h.dS) == 3 ? 64 : ks, ntiles = (cap + ks - 1) / ks;
+  if ((s = scratch(ctx, "pat_cnt", sizeof(double) * BK * kr * ntiles, (void**)&cnt)) != CMX_OK) return s;
+  // Correlation / Covariance: the pairs are scored in one pass from per-pattern moments (pair_stat_moments)
+  const bool moments = a.stat_kind == CMX_STAT_CORRELATION || a.stat_kind == CMX_STAT_COVARIANCE;
+  double *pmean = nullptr, *pss = nullptr;
+  if (moments) {
+    if ((s = scratch(ctx, "pat_mean", sizeof(double) * cap, (void**)&pmean)) != CMX_OK) return s;
+    if ((s = scratch(ctx, "pat_ss", sizeof(double) * cap, (void**)&pss)) != CMX_OK) return s;
+  }
   if ((s = scratch(ctx, "pat_pr", sizeof(double) * cap, (void**)&pr)) != CMX_OK) return s;
   if ((s = scratch(ctx, "pat_nm", sizeof(double) * cap, (void**)&nm)) != CMX_OK) return s;
   if ((s = scratch(ctx, "pat_rc", sizeof(int32_t) * cap, (void**)&rc)) != CMX_OK) return s;
@@ -1293,9 +1304,8 @@ static cmx_status null_patterns_dev(cmx_ctx* ctx, MapArgs a, size_t nrep, size_t
   double* stat = a.null_stat;
   int32_t* rcmin = a.null_rcmin;
   double *prmin = a.null_prmin, *nmin = a.null_nmin;
-  a.counts = cnt; a.ldc = cap; a.post_rate = pr; a.rate_class = rc; a.norm = nm;
+  a.counts = cnt; a.ldc = 0; a.post_rate = pr; a.rate_class = rc; a.norm = nm;
   a.rep_site = b.rep_site;
-  const size_t ks = (size_t)map_sites_per_wave(h.dS);
   for (size_t r0 = 0; r0 < nrep; r0 += reps) {
     const size_t r1 = std::min(nrep, r0 + reps), n = (r1 - r0) * 2 * rep_ram, o = r0 * rep_ram;
     a.supplied = sup + r0 * 2 * T * rep_ram;
@@ -1305,7 +1315,9 @@ static cmx_status null_patterns_dev(cmx_ctx* ctx, MapArgs a, size_t nrep, size_t
     a.npat = b.incl + (n - 1);
     const size_t blocks_needed = ((n + ks - 1) / ks + kWavesPerBlock - 1) / kWavesPerBlock;
     HIP_TRY(ctx, launch_map(a, kModeNullPatterns, (int)std::min<size_t>(blocks_needed, (size_t)ctx->grid_blocks), (hipStream_t)stream));
-    HIP_TRY(ctx, launch_null_pattern_pairs(a.stat_kind, a.stat_param, h.B, h.K, cnt, cap, pr, rc, nm, b.pat_of, rep_ram, n / 2,
+    if (moments)
+      HIP_TRY(ctx, launch_null_pattern_moments(h.B, h.K, cnt, (int)ks, (int)kr, a.npat, n, pmean, pss, (hipStream_t)stream));
+    HIP_TRY(ctx, launch_null_pattern_pairs(a.stat_kind, a.stat_param, h.B, h.K, cnt, (int)ks, (int)kr, pmean, pss, pr, rc, nm, b.pat_of, rep_ram, n / 2,
                                            a.stat_mean, stat + o, rcmin ? rcmin + o : nullptr, prmin ? prmin + o : nullptr,
                                            nmin ? nmin + o : nullptr, (hipStream_t)stream));
   }

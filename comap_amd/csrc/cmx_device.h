@@ -123,6 +123,8 @@ struct MapArgs {
   // of every pattern, and the number of patterns (device; the grid is sized for every site its own pattern)
   const uint32_t* rep_site;
   const uint32_t* npat;
+  // ... counts is then the tile-major pattern table: tile p / kSites is [B*K][kRow] doubles, pattern p its column p % kSites
+  // (kSites patterns per wave, kRow the wave's row stride: the block map_sites_wave's epilogue writes)
 };
 
 // launchers (cmx_kernels.hip)
@@ -240,8 +242,14 @@ struct NullPatternBufs {
 // key + packed copy, stable radix sort of (hash, g), run flags, the two scans, pattern numbers in first-occurrence order
 hipError_t launch_null_patterns(const uint8_t* d_sup, int T, size_t rep_ram, size_t n, int hash_bits, const NullPatternBufs& b,
                                 hipStream_t stream);
-// statistic and minima of pair q = (rep, j) from the patterns of sites (rep, 0, j) and (rep, 1, j); counts [B*K][ldc]
-hipError_t launch_null_pattern_pairs(int kind, double param, int B, int K, const double* counts, size_t ldc, const double* post_rate,
+// Correlation / Covariance: mean over branches and sum of squared deviations of every pattern of the pass (pattern_moments),
+// one thread per pattern, after the mapping; npat on the device, the grid sized for cap patterns
+hipError_t launch_null_pattern_moments(int B, int K, const double* counts, int tile_sites, int tile_row, const uint32_t* npat,
+                                       size_t cap, double* pat_mean, double* pat_ss, hipStream_t stream);
+// statistic and minima of pair q = (rep, j) from the patterns of sites (rep, 0, j) and (rep, 1, j); counts in tiles of
+// [B*K][tile_row] doubles, tile_sites patterns each (MapArgs); pat_mean / pat_ss for kinds 0 and 4
+hipError_t launch_null_pattern_pairs(int kind, double param, int B, int K, const double* counts, int tile_sites, int tile_row,
+                                     const double* pat_mean, const double* pat_ss, const double* post_rate,
                                      const int32_t* rate_class, const double* norm, const uint32_t* pat_of, size_t rep_ram,
                                      size_t npairs, const double* d_mean, double* stat, int32_t* rcmin, double* prmin, double* nmin,
                                      hipStream_t stream);

@@ -931,13 +931,15 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
       const size_t rh = g / a.rep_ram, j = g - rh * a.rep_ram;   // rh = rep_local * 2 + h
       double L, pr, nrm;
       int rc;
-      map_sites_wave<S, FUSE, NG, true>(a, wsD, wsU, part, cnt0, lds_off, a.supplied + rh * (size_t)m.T * a.rep_ram + j, a.rep_ram,
+      // tile sb of the pattern table is this wave's count block: the class-sum epilogue writes the final counts there,
+      // once, with its own row stride (lanes past npat write their clamped copy into the last tile's spare columns)
+      double* tile = a.counts + sb * ((size_t)m.B * m.K * kRow);
+      map_sites_wave<S, FUSE, NG, true>(a, wsD, wsU, part, tile, lds_off, a.supplied + rh * (size_t)m.T * a.rep_ram + j, a.rep_ram,
                                         lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
       if (active) {
         a.post_rate[p] = pr;
         a.rate_class[p] = rc;
         a.norm[p] = nrm;
-        for (int r = 0; r < m.B * m.K; ++r) a.counts[(size_t)r * a.ldc + p] = cnt0[(size_t)r * kRow + sidx];
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

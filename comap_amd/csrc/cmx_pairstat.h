@@ -83,6 +83,41 @@ __device__ __forceinline__ double pair_stat_strided(int kind, double param, int 
   return __builtin_nan("");
 }
 
+// ---- Correlation / Covariance (kinds 0 and 4) in one pass over the pair (the fused null's pattern table).
+// pair_stat_strided's first pass and two of its three second-pass sums depend on one operand alone, so they are taken once
+// per pattern (null_pattern_moments_kernel) -- in its order, with its expressions, the squares contracted into v_fma_f64 as the compiler contracts them
+// there -- and a pair adds the cross products.  The statistic is the same bytes as pair_stat_strided's.  That rests on the
+// build's -ffp-contract=fast (hipcc's default for device code), under which "sxx += dx * dx" in pair_stat_strided becomes one
+// v_fma_f64; the explicit fma here pins this side only.  A build that stops contracting splits the two paths, and
+// tests/test_gpu_null_patterns.py / test_gpu_null_pattern_tiles.py (bytes against the per-site path) say so.
+__device__ __forceinline__ void pattern_moments(int B, int K, const double* __restrict__ c, size_t ld, double& mean, double& ss) {
+  double m = 0;
+#pragma unroll 8
+  for (int b = 0; b < B; ++b) m += c[(size_t)b * K * ld];
+  m /= B;
+  double sxx = 0;
+#pragma unroll 8
+  for (int b = 0; b < B; ++b) {
+    const double dx = c[(size_t)b * K * ld] - m;
+    sxx = __builtin_fma(dx, dx, sxx);
+  }
+  mean = m;
+  ss = sxx;
+}
+
+__device__ __forceinline__ double pair_stat_moments(int kind, int B, int K, const double* __restrict__ c1, size_t ld1, double m1,
+                                                    double sxx, const double* __restrict__ c2, size_t ld2, double m2, double syy) {
+  double sxy = 0;
+#pragma unroll 8
+  for (int b = 0; b < B; ++b) {
+    const double dx = c1[(size_t)b * K * ld1] - m1, dy = c2[(size_t)b * K * ld2] - m2;
+    sxy = __builtin_fma(dx, dy, sxy);
+  }
+  const double cov = sxy / (B - 1);
+  if (kind == 4) return cov;
+  return cov / (sqrt(sxx / (B - 1)) * sqrt(syy / (B - 1)));
+}
+
 // ---- per-branch weights (Statistic::setWeights, CoMap/Statistics.h:83-104; DESIGN A.7, weighted).  w is normalised
 // (sum 1).  Every weighted kind is a plain sum of products of scaled operands X_b = weight_factor(kind, w_b) * value_b,
 // on the lanes here and in the Gram operand of pair_prep_kernel alike, so a corrected reading of bpp-core's
