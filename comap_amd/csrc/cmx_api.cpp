@@ -640,8 +640,12 @@ static cmx_status map_sites_impl(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsit
   MapArgs a{};
   a.m = ctx->dm; a.ws = full_grid ? ctx->ws : ctx->ws_obs;
   a.aln = d_aln; a.ld = ld; a.nsites = nsites;
-  // ambiguity ids S .. S+max_ambig(S)-1: rebuild the extra rows of the leaf operators when the table changes
-  if (d_masks || ctx->leaf_rows_custom) {
+  // ambiguity ids S .. S+max_ambig(S)-1: rebuild the extra rows of the leaf operators when the table changes.
+  // Not for the engine's own pipelines (full_grid): their simulated alignments are fully resolved and never read those
+  // rows, and rebuilding them on the null's stream would race with an observed mapping of ambiguous codes that a caller
+  // has in flight on a second stream.  leaf_rows_custom stays as it is, so the next public call without a table still
+  // restores the default rows.
+  if (!full_grid && (d_masks || ctx->leaf_rows_custom)) {
     HIP_TRY(ctx, launch_extend_leaf_rows(ctx->dm, d_masks, (hipStream_t)stream));
     ctx->leaf_rows_custom = d_masks != nullptr;
   }
@@ -963,6 +967,8 @@ cmx_status cmx_simulate(cmx_ctx* ctx, uint64_t seed, uint64_t g0, size_t n, uint
   if (classes_out) HIP_TRY(ctx, hipMemcpy(classes_out, d_cls, n * sizeof(int32_t), hipMemcpyDeviceToHost));
   return CMX_OK;
 }
+
+static_assert(kPlainStates <= kSimContinuousMaxStates, "simulate_continuous_kernel's per-thread row must hold the largest alphabet");
 
 cmx_status cmx_simulate_continuous_dev(cmx_ctx* ctx, uint64_t seed, uint64_t g0, size_t n, double gamma_alpha, double p_invariant,
                                        uint8_t* d_aln, size_t ld, double* d_rates, void* stream) {

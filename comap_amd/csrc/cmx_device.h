@@ -14,6 +14,9 @@ constexpr int kWavesPerBlock = 4;   // mapping kernels: 4 independent waves per 
 // operator: row S+a = sum of the rows of the states compatible with ambiguity id a (filled per call from the caller's
 // mask table, default "every state").  A = 12 for nucleotides (IUPAC + gap), 4 for proteins (B, Z, J, X/gap).
 constexpr int max_ambig(int S) { return S == 4 ? 12 : 4; }
+// simulate_continuous_kernel keeps one row of the transition matrix per thread: the largest alphabet a context takes
+// (== kPlainStates of cmx_host_model.h; cmx_api.cpp asserts it)
+constexpr int kSimContinuousMaxStates = 64;
 // A transposed leaf operator is read row by row, the row named by a site's symbol: sixteen sites of a lane group read
 // sixteen rows at once.  With rows of S doubles (40 dwords for S = 20, 32 for the class-fused 16) rows 8 (2) apart fall
 // on the same LDS banks -- 61 % of the mapping kernel's LDS cycles were bank conflicts.  One double of padding per row

@@ -768,6 +768,15 @@ class Engine:
                                                  _sz(rep_begin), _sz(rep_end), _sz(rep_ram), _vp(supplied), _vp(stat),
                                                  _vp(rcmin), _vp(prmin), _vp(nmin), self._stream()))
 
+    def null_intra_continuous_dev(self, kind, seed, rep_begin, rep_end, rep_ram, gamma_alpha, stat, rcmin=None, prmin=None,
+                                  nmin=None, p_invariant=0.0, threshold=0.99, mean_vectors=None):
+        """null_intra_continuous with the outputs in CUDA tensors ([nrep * rep_ram]; asynchronous on the current stream)"""
+        params = _stat_params(kind, threshold, mean_vectors)
+        self._check(self._lib.cmx_null_intra_continuous_dev(self._ctx, int(kind), _vp(params), ctypes.c_uint64(seed),
+                                                            _sz(rep_begin), _sz(rep_end), _sz(rep_ram),
+                                                            ctypes.c_double(gamma_alpha), ctypes.c_double(p_invariant),
+                                                            _vp(stat), _vp(rcmin), _vp(prmin), _vp(nmin), self._stream()))
+
     def null_inter_dev(self, other, kind, seed, rep_begin, rep_end, rep_ram, stat, rcmin=None, prmin=None, nmin=None,
                        threshold=0.99, mean_vectors=None):
         params = _stat_params(kind, threshold, mean_vectors)

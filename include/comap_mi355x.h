@@ -250,7 +250,10 @@ cmx_status cmx_null_simulate_dev(cmx_ctx* ctx, uint64_t seed, size_t rep_begin, 
  * instead of simulating (deterministic cross-implementation checks).  Supplied alignments must be FULLY RESOLVED (every
  * code a state, as a simulator's output is): the null's kernel stages only the state rows of a leaf operator and, for
  * class-fused nucleotide models, takes cherries from tables indexed by their two symbols.  The host-pointer entry checks
- * it (CMX_ERR_INVALID); with the device-pointer entry it is the caller's contract.  Sharding replicates over GPUs gives
+ * it (CMX_ERR_INVALID); with the device-pointer entry it is the caller's contract, for the fused and for the unfused null
+ * (weights, bounds MI, nijt.average / joint = no) alike: the unfused null's own mapping leaves the leaf operators'
+ * ambiguity rows as the last public mapping built them, so a code >= nstates in d_supplied would be read through that
+ * caller's mask table.  Sharding replicates over GPUs gives
  * results independent of the number of shards. */
 cmx_status cmx_null_intra(cmx_ctx* ctx, int kind, const double* params, uint64_t seed, size_t rep_begin,
                           size_t rep_end, size_t rep_ram, const uint8_t* supplied, double* stat, int32_t* rcmin,

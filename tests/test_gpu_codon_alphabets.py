@@ -96,3 +96,15 @@ def test_plain_alphabet_refuses_a_mask_table():
     with pytest.raises(engine.CmxError) as e:
         eng.map_sites(case["aln"], masks=np.full(64, 0xFFFFFFFF, dtype=np.uint32))
     assert "ambiguity table" in str(e.value)
+
+
+def test_plain_alphabet_continuous_rate_simulator_matches_oracle():
+    """simulations.continuous = yes on 61 states: the per-thread row V[x][k] exp(lambda_k r t) has S entries (it was sized
+    for 20, so every state past the 20th trampled the thread's private memory); same rates and alignments as the oracle,
+    at the bounds of test_continuous_rate_simulator_matches_oracle"""
+    case = _case(61, ntaxa=8, nsites=10)
+    eng, om = _pair(case)
+    a, r = eng.simulate_continuous(77, 1000, 100, 0.7, 0.1)
+    ao, ro = oracle.simulate_continuous(om, 77, 1000, 100, 0.7, 0.1)
+    rel_close(r, ro, 1e-12, 1e-300)
+    assert (a != ao).mean() < 1e-4 and a.max() < 61
