@@ -1,0 +1,479 @@
+// C-ABI of the engine (include/comap_mi355x.h).  Host-side orchestration only: uploads the prepared model,
+// owns the per-wave workspace, launches the HIP kernels.  There is no CPU compute path: without a HIP device every
+// compute entry point fails with CMX_ERR_DEVICE.
+// This file: the context, the scratch buffers and their guard, settings and debug hooks.  The stages are in
+// cmx_api_map.cpp, cmx_api_null.cpp, cmx_api_pairs.cpp, cmx_api_mica.cpp and cmx_api_cluster.cpp.
+#include "cmx_ctx.h"
+
+thread_local std::string g_create_error;
+
+// CMX_SCRATCH_GUARD=1 (or cmx_debug_scratch_guard(1)): every scratch buffer, per-wave workspace and temporary is
+// allocated kGuardBytes longer, the bytes after what the caller asked for hold a canary, and scratch() (before it hands a
+// buffer out again), cmx_synchronize, cmx_scratch_check and cmx_ctx_destroy verify it and name the buffer that was
+// written past its end.  Round 3: a scratch buffer sized [nn][rep_ram] for a kernel that writes [nn][nrep * rep_ram] lived
+// through a round of green tests on allocator slack.  Debug mode: every check synchronises the device.
+constexpr int kGuardByte = 0xC5;
+std::atomic<int> g_guard{-1};
+std::mutex g_guard_mu;
+std::vector<std::string> g_guard_failures;
+std::map<std::string, size_t> g_guard_shrink;
+
+std::atomic<int> g_pat_hash_bits{64};   // (tests force collisions with it)
+
+bool guard_on() {
+  int g = g_guard.load();
+  if (g < 0) {
+    const char* e = getenv("CMX_SCRATCH_GUARD");
+    g = (e && e[0] == '1') ? 1 : 0;
+    g_guard.store(g);
+  }
+  return g == 1;
+}
+
+void guard_record(const std::string& what) {
+  std::lock_guard<std::mutex> lk(g_guard_mu);
+  g_guard_failures.push_back(what);
+  std::fprintf(stderr, "CMX_SCRATCH_GUARD: %s\n", what.c_str());
+}
+
+hipError_t guard_arm(void* base, size_t logical) {
+  return hipMemset(static_cast<char*>(base) + logical, kGuardByte, kGuardBytes);
+}
+
+// true when the canary after `logical` bytes is intact; the device must be idle
+bool guard_intact(const void* base, size_t logical, size_t* first_bad) {
+  static thread_local std::vector<unsigned char> h(kGuardBytes);
+  if (hipMemcpy(h.data(), static_cast<const char*>(base) + logical, kGuardBytes, hipMemcpyDeviceToHost) != hipSuccess) return false;
+  for (size_t i = 0; i < kGuardBytes; ++i)
+    if (h[i] != (unsigned char)kGuardByte) { if (first_bad) *first_bad = i; return false; }
+  return true;
+}
+
+// grow-only named scratch buffers (allocated on first use, released with the context)
+cmx_status scratch(cmx_ctx* ctx, const char* name, size_t bytes, void** out) {
+  DevBuf& b = ctx->scratch[name];
+  if (guard_on()) {
+    // the previous user's canary is checked before the buffer is handed out again (it may move with the size asked for)
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (b.p && !b.guarded) {   // allocated before the guard was switched on: no room for a canary, start over
+      HIP_TRY(ctx, hipFree(b.p));
+      b.p = nullptr;
+      b.bytes = 0;
+    }
+    size_t off = 0;
+    if (b.p && !guard_intact(b.p, b.logical, &off)) {
+      const std::string msg = std::string("buffer 'scratch:") + name + "' was written past its end (" + std::to_string(b.logical) +
+                              " bytes asked for, first bad byte at +" + std::to_string(off) + ")";
+      guard_record(msg);
+      (void)guard_arm(b.p, b.logical);
+      return fail(ctx, CMX_ERR_INTERNAL, "CMX_SCRATCH_GUARD: " + msg);
+    }
+    size_t logical = bytes ? bytes : 16;
+    {
+      std::lock_guard<std::mutex> lk(g_guard_mu);
+      auto it = g_guard_shrink.find(name);
+      if (it != g_guard_shrink.end() && it->second < logical) logical = it->second;   // test hook: pretend the caller asked for less
+    }
+    if (b.bytes < bytes || !b.p) {
+      if (b.p) HIP_TRY(ctx, hipFree(b.p));
+      b.p = nullptr;
+      b.bytes = 0;
+      HIP_TRY(ctx, hipMalloc(&b.p, (bytes ? bytes : 16) + kGuardBytes));
+      b.bytes = bytes;
+      b.guarded = true;
+    }
+    b.logical = logical;
+    HIP_TRY(ctx, guard_arm(b.p, b.logical));
+    *out = b.p;
+    return CMX_OK;
+  }
+  if (b.bytes < bytes) {
+    if (b.p) HIP_TRY(ctx, hipFree(b.p));
+    b.p = nullptr;
+    b.bytes = 0;
+    HIP_TRY(ctx, hipMalloc(&b.p, bytes ? bytes : 16));
+    b.bytes = bytes;
+    b.guarded = false;
+  }
+  *out = b.p;
+  return CMX_OK;
+}
+
+TmpDev::~TmpDev() {
+  if (!sizes.empty()) {
+    (void)hipDeviceSynchronize();
+    for (size_t i = 0; i < ptrs.size(); ++i) {
+      size_t off = 0;
+      if (!guard_intact(ptrs[i], sizes[i], &off))
+        guard_record("temporary #" + std::to_string(i) + " of a host-pointer entry point was written past its end (" +
+                     std::to_string(sizes[i]) + " bytes asked for, first bad byte at +" + std::to_string(off) + ")");
+    }
+  }
+  for (void* p : ptrs) (void)hipFree(p);
+}
+
+hipError_t TmpDev::alloc_bytes(void** p, size_t bytes) {
+  if (!bytes) bytes = 16;
+  const bool g = guard_on();
+  hipError_t e = hipMalloc(p, bytes + (g ? kGuardBytes : 0));
+  if (e != hipSuccess) return e;
+  ptrs.push_back(*p);
+  if (g) {
+    sizes.push_back(bytes);
+    e = guard_arm(*p, bytes);
+  }
+  return e;
+}
+
+cmx_status TmpDev::upload_branch_major(cmx_ctx* ctx, double** p, const double* sm, size_t n, size_t BK) {
+  std::vector<double> bm(BK * n);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t r = 0; r < BK; ++r) bm[r * n + i] = sm[i * BK + r];
+  return upload(ctx, p, bm.data(), bm.size());
+}
+
+// verify every guarded buffer of a context (device idle); the first trampled one is named in ctx->err
+static cmx_status guard_verify_all(cmx_ctx* ctx) {
+  if (!guard_on()) return CMX_OK;
+  cmx_status rc = CMX_OK;
+  auto bad = [&](const std::string& name, size_t logical, size_t off) {
+    const std::string msg = "buffer '" + name + "' was written past its end (" + std::to_string(logical) + " bytes asked for, first bad byte at +" + std::to_string(off) + ")";
+    guard_record(msg);
+    if (rc == CMX_OK) { ctx->err = "CMX_SCRATCH_GUARD: " + msg; rc = CMX_ERR_INTERNAL; }
+  };
+  size_t off = 0;
+  for (auto& kv : ctx->scratch)
+    if (kv.second.p && kv.second.guarded && !guard_intact(kv.second.p, kv.second.logical, &off)) {
+      bad("scratch:" + kv.first, kv.second.logical, off);
+      (void)guard_arm(kv.second.p, kv.second.logical);   // report an overflow once, not at every later check
+    }
+  for (auto& f : ctx->guarded_fixed)
+    if (!guard_intact(f.p, f.bytes, &off)) {
+      bad(f.name, f.bytes, off);
+      (void)guard_arm(f.p, f.bytes);
+    }
+  return rc;
+}
+
+
+const char* cmx_version(void) { return "comap_mi355x 0.1 (gfx950)"; }
+
+const char* cmx_last_error(const cmx_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
+
+cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int device, cmx_ctx** out) {
+  if (!out) return CMX_ERR_INVALID;
+  *out = nullptr;
+  cmx_ctx* ctx = new cmx_ctx();
+  ctx->device = device;
+  if (const char* e = getenv("CMX_NULL_PATTERNS")) ctx->null_patterns = e[0] == '0' ? 0 : (e[0] == '1' ? 1 : -1);   // A/B runs
+  auto bail = [&](cmx_status s) {
+    g_create_error = ctx->err;
+    cmx_ctx_destroy(ctx);
+    return s;
+  };
+  if ((model == nullptr) != (tree == nullptr)) {
+    ctx->err = "model and tree must be given together (both NULL creates a context for cmx_mi_columns only)";
+    return bail(CMX_ERR_INVALID);
+  }
+  if (model) {
+    int code = CMX_OK;
+    std::string msg = build_host_model(model, tree, &ctx->hm, &code);
+    if (!msg.empty()) {
+      ctx->err = msg;
+      return bail((cmx_status)code);
+    }
+    ctx->has_model = true;
+  }
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev <= 0) {
+    ctx->err = std::string("no HIP device available (") + (e != hipSuccess ? hipGetErrorString(e) : "count = 0") +
+               "); this engine has no CPU path";
+    return bail(CMX_ERR_DEVICE);
+  }
+  if (device < 0 || device >= ndev) {
+    ctx->err = "device index out of range";
+    return bail(CMX_ERR_INVALID);
+  }
+  auto dev_init = [&]() -> cmx_status {
+    HIP_TRY(ctx, hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIP_TRY(ctx, hipGetDeviceProperties(&prop, device));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+      return fail(ctx, CMX_ERR_UNSUPPORTED, std::string("built for gfx950 only, device is ") + prop.gcnArchName);
+    ctx->cu_count = prop.multiProcessorCount;
+    std::vector<uint32_t> dm(256);
+    for (int i = 0; i < 256; ++i) dm[i] = i < 32 ? (1u << i) : 0xffffffffu;
+    const uint32_t* p = nullptr;
+    CMX_TRY(upload(ctx, dm, &p));
+    ctx->d_default_masks = const_cast<uint32_t*>(p);
+    if (!ctx->has_model) return CMX_OK;
+    const HostModel& h = ctx->hm;
+    DevModel& d = ctx->dm;
+    d.S = h.dS; d.C = h.dC; d.S0 = h.S; d.C0 = h.C; d.fuse = h.fuse; d.K = h.K; d.nn = h.nn; d.B = h.B; d.T = h.T; d.NI = h.NI; d.NIW = h.NIW; d.NV = h.NV; d.root = h.root;
+#define UP(field) CMX_TRY(upload(ctx, h.field, &d.field))
+    UP(taxon_of); UP(parent);
+    if (h.plain) {
+      // alphabets other than 4 / 20 states: simulator tables and tree only; the sites are mapped by the plain kernels of
+      // cmx_variants.hip on scratch buffers (map_plain below), no operator stream, no per-wave workspaces
+      UP(simg); UP(simord);
+      d.nsimg = (int)(h.simg.size() / 16);
+      UP(eigV); UP(eigVi); UP(eigLam); UP(model_of); UP(blen);
+      UP(CP); UP(CPG); UP(pi); UP(rates); UP(probs); UP(cum_pi); UP(cum_probs);
+      return CMX_OK;
+    }
+    {
+      const double* mat = nullptr;
+      CMX_TRY(upload(ctx, h.MAT, &mat));
+      d.MAT = const_cast<double*>(mat);
+    }
+    d.MC = h.MC;
+    {  // device copy of the operator stream: operator indices premultiplied to element offsets, and the first two entries
+       // repeated after the last one so that "the entry two ops ahead" never needs a wrap test
+      std::vector<int> ms(h.msched);
+      const int unit = mat_unit(h.dS);
+      for (size_t i = 0; i < ms.size(); i += 2) ms[i] *= unit;
+      const size_t n2 = ms.size();
+      for (size_t i = 0; i < 4; ++i) ms.push_back(ms[i % n2]);
+      const int* dms = nullptr;
+      CMX_TRY(upload(ctx, ms, &dms));
+      d.msched = dms;
+      d.nmv = (int)(h.msched.size() / 2);
+      d.msched_r = nullptr;
+      d.nmv_r = 0;
+      if (!h.msched_r.empty()) {   // the cherry-table walk's stream, prepared the same way
+        std::vector<int> mr(h.msched_r);
+        for (size_t i = 0; i < mr.size(); i += 2) mr[i] *= unit;
+        const size_t nr = mr.size();
+        for (size_t i = 0; i < 4; ++i) mr.push_back(mr[i % nr]);
+        const int* dmr = nullptr;
+        CMX_TRY(upload(ctx, mr, &dmr));
+        d.msched_r = dmr;
+        d.nmv_r = (int)(h.msched_r.size() / 2);
+      }
+    }
+    UP(nrec); UP(simg); UP(simord);
+    d.nsimg = (int)(h.simg.size() / 16);
+    {  // two zero entries (not prefetchable) after the last load: the kernel reads one entry ahead without a bounds test
+      std::vector<int> ld(h.ldsched);
+      ld.push_back(0);
+      ld.push_back(0);
+      const int* dld = nullptr;
+      CMX_TRY(upload(ctx, ld, &dld));
+      d.ldsched = dld;
+    }
+    UP(eigV); UP(eigVi); UP(eigLam); UP(model_of); UP(blen);
+    UP(CP); UP(CPG); UP(pi); UP(rates); UP(probs); UP(cum_pi); UP(cum_probs);
+#undef UP
+    // ambiguity rows of the leaf operators: default "every state compatible" until a call brings a mask table
+    HIP_TRY(ctx, launch_extend_leaf_rows(d, nullptr, nullptr));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    ctx->leaf_rows_custom = false;
+    // ambiguity masks default: code c >= S compatible with every state; fix the table for this S
+    for (int i = 0; i < 256; ++i) dm[i] = i < h.S ? (1u << i) : ((h.S >= 32) ? 0xffffffffu : ((1u << h.S) - 1u));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_default_masks, dm.data(), sizeof(uint32_t) * 256, hipMemcpyHostToDevice));
+    // per-wave workspaces: 1 wave per SIMD on every CU for the null; a quarter of that for observed alignments
+    ctx->grid_blocks = ctx->cu_count * map_waves_per_simd(h.dS);   // 4-wave workgroups, that many per CU
+    ctx->waves = ctx->grid_blocks * kWavesPerBlock;
+    ctx->obs_blocks = std::max(1, ctx->grid_blocks / 4);
+    auto alloc_ws = [&](Workspace* ws, size_t w, size_t* bytes) -> cmx_status {
+      const size_t ks = (size_t)map_sites_per_wave(h.dS);   // sites per mapping wave
+      const size_t bD = w * h.NIW * h.dS * ks * sizeof(double);
+      // (rows of the per-site scratch arrays: the sites of a wave, or 64 lanes for the 48-site experiment layout)
+      const size_t kr = map_ng(h.dS) == 3 ? 64 : ks;
+      const size_t bC = w * 2 * h.B * h.K * kr * sizeof(double);
+      const size_t bP = w * h.dC * h.B * h.K * kr * sizeof(double);
+      const size_t bS = w * h.nn * ks, bA = w * h.T * ks;
+      const bool g = guard_on();
+      auto one = [&](const char* nm, void** p, size_t bytes) -> cmx_status {
+        HIP_TRY(ctx, hipMalloc(p, bytes + (g ? kGuardBytes : 0)));
+        if (g) {
+          HIP_TRY(ctx, guard_arm(*p, bytes));
+          ctx->guarded_fixed.push_back({std::string(ws == &ctx->ws ? "workspace:" : "workspace_obs:") + nm, *p, bytes});
+        }
+        return CMX_OK;
+      };
+      CMX_TRY(one("D", (void**)&ws->D, bD));
+      CMX_TRY(one("U", (void**)&ws->U, bD));
+      CMX_TRY(one("cnt", (void**)&ws->cnt, bC));
+      CMX_TRY(one("part", (void**)&ws->part, bP));
+      CMX_TRY(one("st", (void**)&ws->st, bS));
+      CMX_TRY(one("aln", (void**)&ws->aln, bA));
+      ws->waves = (int)w;
+      *bytes += 2 * bD + bC + bP + bS + bA;
+      return CMX_OK;
+    };
+    ctx->ws_bytes = 0;
+    CMX_TRY(alloc_ws(&ctx->ws, (size_t)ctx->waves, &ctx->ws_bytes));
+    CMX_TRY(alloc_ws(&ctx->ws_obs, (size_t)ctx->obs_blocks * kWavesPerBlock, &ctx->ws_bytes));
+    return CMX_OK;
+  };
+  cmx_status s = dev_init();
+  if (s != CMX_OK) return bail(s);
+  *out = ctx;
+  return CMX_OK;
+}
+
+void cmx_ctx_destroy(cmx_ctx* ctx) {
+  if (!ctx) return;
+  if (guard_on() && hipSetDevice(ctx->device) == hipSuccess && hipDeviceSynchronize() == hipSuccess)
+    (void)guard_verify_all(ctx);   // destroy cannot fail: findings go to stderr and to cmx_debug_scratch_guard_failures
+  for (void* p : ctx->model_allocs) (void)hipFree(p);
+  if (ctx->d_stat_w) (void)hipFree(ctx->d_stat_w);
+  for (auto& kv : ctx->scratch) if (kv.second.p) (void)hipFree(kv.second.p);
+  for (Workspace* ws : {&ctx->ws, &ctx->ws_obs}) {
+    if (ws->D) (void)hipFree(ws->D);
+    if (ws->U) (void)hipFree(ws->U);
+    if (ws->cnt) (void)hipFree(ws->cnt);
+    if (ws->part) (void)hipFree(ws->part);
+    if (ws->st) (void)hipFree(ws->st);
+    if (ws->aln) (void)hipFree(ws->aln);
+  }
+  delete ctx;
+}
+
+cmx_status cmx_get_info(const cmx_ctx* ctx, cmx_info* info) {
+  if (!ctx || !info) return CMX_ERR_INVALID;
+  std::memset(info, 0, sizeof(*info));
+  info->nstates = ctx->hm.S; info->nclasses = ctx->hm.C; info->ntypes = ctx->hm.K; info->nnodes = ctx->hm.nn;
+  info->nbranches = ctx->hm.B; info->ntaxa = ctx->hm.T; info->ninternal = ctx->hm.NI;
+  info->device = ctx->device; info->cu_count = ctx->cu_count; info->waves = ctx->waves;
+  info->workspace_bytes = ctx->ws_bytes;
+  info->device_states = ctx->hm.dS; info->device_classes = ctx->hm.dC;
+  info->products_per_pass = (int32_t)ctx->hm.n_products; info->leaf_ops_per_pass = (int32_t)ctx->hm.n_leaf_ops;
+  info->ws_loads_per_pass = (int32_t)ctx->hm.n_loads; info->ws_stores_per_pass = (int32_t)ctx->hm.n_stores;
+  info->products_per_pass_null = (int32_t)ctx->hm.n_products_r; info->leaf_ops_per_pass_null = (int32_t)ctx->hm.n_leaf_ops_r;
+  info->cherry_tables = ctx->hm.msched_r.empty() ? 0 : ctx->hm.ncherry;
+  return CMX_OK;
+}
+
+cmx_status cmx_get_transition_matrices(const cmx_ctx* ctx, double* P) {
+  if (!ctx || !P || !ctx->has_model) return CMX_ERR_INVALID;
+  std::memcpy(P, ctx->hm.P.data(), sizeof(double) * ctx->hm.P.size());
+  return CMX_OK;
+}
+
+cmx_status cmx_debug_walk(const cmx_model* model, const cmx_tree* tree, int32_t* nrec, size_t nrec_cap, size_t* nrec_n,
+                          int32_t* ldsched, size_t ld_cap, size_t* ld_n, int32_t* msched, size_t m_cap, size_t* m_n,
+                          int32_t* slot_of_node, uint64_t* stats /*[7]: loads, stores, products, leaf ops per pass; products, leaf ops of the cherry-table walk, cherries with tables*/) {
+  HostModel hm;
+  int code = CMX_OK;
+  const std::string msg = build_host_model(model, tree, &hm, &code);
+  if (!msg.empty()) {
+    g_create_error = msg;
+    return (cmx_status)code;
+  }
+  if (hm.nrec.size() > nrec_cap || hm.ldsched.size() > ld_cap || hm.msched.size() > m_cap) {
+    g_create_error = "cmx_debug_walk: buffers too small";
+    return CMX_ERR_INVALID;
+  }
+  std::memcpy(nrec, hm.nrec.data(), hm.nrec.size() * sizeof(int32_t));
+  std::memcpy(ldsched, hm.ldsched.data(), hm.ldsched.size() * sizeof(int32_t));
+  std::memcpy(msched, hm.msched.data(), hm.msched.size() * sizeof(int32_t));
+  *nrec_n = hm.nrec.size(); *ld_n = hm.ldsched.size(); *m_n = hm.msched.size();
+  if (slot_of_node) std::memcpy(slot_of_node, hm.slot.data(), hm.slot.size() * sizeof(int32_t));
+  if (stats) {
+    stats[0] = hm.n_loads; stats[1] = hm.n_stores; stats[2] = hm.n_products; stats[3] = hm.n_leaf_ops;
+    stats[4] = hm.n_products_r; stats[5] = hm.n_leaf_ops_r; stats[6] = hm.msched_r.empty() ? 0 : (uint64_t)hm.ncherry;
+  }
+  return CMX_OK;
+}
+
+cmx_status cmx_synchronize(cmx_ctx* ctx) {
+  if (!ctx) return CMX_ERR_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  return guard_verify_all(ctx);
+}
+
+cmx_status cmx_scratch_check(cmx_ctx* ctx) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (!guard_on()) return fail(ctx, CMX_ERR_UNSUPPORTED, "the scratch guard is off (CMX_SCRATCH_GUARD=1 or cmx_debug_scratch_guard(1) before the context is created)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  return guard_verify_all(ctx);
+}
+
+int cmx_debug_scratch_guard(int on) {
+  const int was = guard_on() ? 1 : 0;
+  if (on >= 0) g_guard.store(on ? 1 : 0);
+  return was;
+}
+
+size_t cmx_debug_scratch_guard_failures(char* buf, size_t cap, int clear) {
+  std::lock_guard<std::mutex> lk(g_guard_mu);
+  const size_t n = g_guard_failures.size();
+  if (buf && cap) {
+    std::string all;
+    for (const std::string& f : g_guard_failures) { all += f; all += '\n'; }
+    std::snprintf(buf, cap, "%s", all.c_str());
+  }
+  if (clear) g_guard_failures.clear();
+  return n;
+}
+
+void cmx_debug_scratch_shrink(const char* name, size_t bytes) {
+  std::lock_guard<std::mutex> lk(g_guard_mu);
+  if (!name) { g_guard_shrink.clear(); return; }
+  if (bytes == 0) g_guard_shrink.erase(name);
+  else g_guard_shrink[name] = bytes;
+}
+
+cmx_status cmx_set_null_patterns(cmx_ctx* ctx, int on) {
+  CMX_TRY(need_model(ctx));
+  ctx->null_patterns = on < 0 ? -1 : (on ? 1 : 0);
+  return CMX_OK;
+}
+
+int cmx_debug_null_hash_bits(int bits) {
+  const int was = g_pat_hash_bits.load();
+  if (bits > 0) g_pat_hash_bits.store(bits > 64 ? 64 : bits);
+  return was;
+}
+
+// nijt.average / nijt.joint of CoETools.cpp:393-394 ("really for benchmarking only" there)
+cmx_status cmx_set_mapping_options(cmx_ctx* ctx, int average, int joint) {
+  CMX_TRY(need_model(ctx));
+  ctx->map_average = average != 0;
+  ctx->map_joint = joint != 0;
+  return CMX_OK;
+}
+
+// Statistic::setWeights / deleteWeights (CoMap/Statistics.h:83-104, 135-140): stored divided by their sum, in the
+// reference's summation order.  Validated before any device work; the device copy is written once here, after the
+// device has drained (a kernel of an earlier call on any stream may still read the previous weights).
+cmx_status cmx_set_statistic_weights(cmx_ctx* ctx, const double* w, size_t nbranches) {
+  CMX_TRY(need_model(ctx));
+  std::vector<double> wn;
+  if (w) {
+    if (nbranches != (size_t)ctx->hm.B)
+      return fail(ctx, CMX_ERR_INVALID, "cmx_set_statistic_weights: " + std::to_string(nbranches) + " weights for " +
+                                            std::to_string(ctx->hm.B) + " branches (DimensionException)");
+    double sum = 0.0;
+    for (size_t b = 0; b < nbranches; ++b) {
+      if (!std::isfinite(w[b]))
+        return fail(ctx, CMX_ERR_INVALID, "cmx_set_statistic_weights: weight " + std::to_string(b) + " is not finite");
+      if (w[b] < 0.0)
+        return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_set_statistic_weights: weight " + std::to_string(b) + " is negative");
+      sum += w[b];
+    }
+    if (!(sum > 0.0) || !std::isfinite(sum))
+      return fail(ctx, CMX_ERR_INVALID, "cmx_set_statistic_weights: the weights must have a positive, finite sum");
+    wn.resize(nbranches);
+    for (size_t b = 0; b < nbranches; ++b) wn[b] = w[b] / sum;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_stat_w) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_stat_w, sizeof(double) * ctx->hm.B));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(ctx->d_stat_w, wn.data(), sizeof(double) * nbranches, hipMemcpyHostToDevice));
+  }
+  ctx->stat_w.swap(wn);
+  ctx->gram_kept.valid = false;   // kept Gram blocks were scored with the previous weights
+  return CMX_OK;
+}
+
+cmx_status cmx_get_statistic_weights(const cmx_ctx* ctx, double* w_out, int32_t* has_weights) {
+  if (!ctx || !has_weights) return CMX_ERR_INVALID;
+  *has_weights = ctx->stat_w.empty() ? 0 : 1;
+  if (w_out) std::copy(ctx->stat_w.begin(), ctx->stat_w.end(), w_out);
+  return CMX_OK;
+}

@@ -1,0 +1,349 @@
+// C-ABI, mapping stage: substitution mapping of observed alignments and its variants, ancestral states, the simulators.
+#include "cmx_ctx.h"
+
+// nijt.average = no (cmx_set_mapping_options): counts and norms of the sites just mapped are replaced by those of
+// computeSubstitutionVectorsNoAveraging (cmx_variants.hip); likelihood, posterior rate and rate class stay.
+// full_grid names the caller as in map_sites_impl: the engine's own null / clustering / candidate pipelines (true) and the
+// public observed-alignment mapping (false) may run on two streams at once, so each has its own scratch -- the averaged
+// path keeps ws and ws_obs apart for the same reason.
+// S x S matrices padded with zeros to SP x SP (the plain path's kernels run at kPlainStates states)
+static std::vector<double> pad_mats(const std::vector<double>& m, int S, int SP) {
+  if (S == SP) return m;
+  const size_t nm = m.size() / ((size_t)S * S);
+  std::vector<double> o(nm * (size_t)SP * SP, 0.0);
+  for (size_t q = 0; q < nm; ++q)
+    for (int x = 0; x < S; ++x)
+      for (int y = 0; y < S; ++y) o[(q * SP + x) * SP + y] = m[(q * S + x) * S + y];
+  return o;
+}
+
+// the operators of the plain kernels (cmx_variants.hip), uploaded at the first use by the mapping variants or by the
+// ancestral states (padded with zeros to kPlainStates on the plain path)
+static cmx_status upload_variant_operators(cmx_ctx* ctx) {
+  const HostModel& h = ctx->hm;
+  const int SD = h.plain ? kPlainStates : h.S;
+  if (!ctx->va_P) {
+    CMX_TRY(upload(ctx, pad_mats(h.P, h.S, SD), &ctx->va_P));
+    CMX_TRY(upload(ctx, pad_mats(h.N1, h.S, SD), &ctx->va_N1));
+    CMX_TRY(upload(ctx, pad_mats(h.NC, h.S, SD), &ctx->va_NC));
+    CMX_TRY(upload(ctx, h.first_child, &ctx->va_first));
+    CMX_TRY(upload(ctx, h.next_sib, &ctx->va_next));
+    if (h.plain) {
+      std::vector<double> pi(SD, 0.0);
+      std::copy(h.pi.begin(), h.pi.end(), pi.begin());
+      CMX_TRY(upload(ctx, pad_mats(h.PN, h.S, SD), &ctx->va_PN));
+      CMX_TRY(upload(ctx, pi, &ctx->va_pi));
+    }
+  }
+  return CMX_OK;
+}
+
+// the model and alignment fields of the plain kernels' arguments (operators uploaded); the caller sets the mode, the
+// outputs and the sites per pass
+static NoAvgArgs variant_args(cmx_ctx* ctx, const uint8_t* d_aln, size_t ld, const uint32_t* d_masks) {
+  const HostModel& h = ctx->hm;
+  NoAvgArgs a{};
+  a.S = h.plain ? kPlainStates : h.S; a.Sreal = h.S; a.C = h.C; a.K = h.K; a.nn = h.nn; a.B = h.B; a.root = h.root;
+  a.first_child = ctx->va_first; a.next_sib = ctx->va_next; a.taxon_of = ctx->dm.taxon_of; a.parent = ctx->dm.parent;
+  a.P = ctx->va_P; a.N1 = ctx->va_N1; a.NC = ctx->va_NC; a.PN = ctx->va_PN; a.pi = h.plain ? ctx->va_pi : ctx->dm.pi; a.probs = ctx->dm.probs;
+  a.rates = ctx->dm.rates;
+  a.masks = d_masks; a.aln = d_aln; a.ld = ld;
+  return a;
+}
+
+// plain: the caller is map_plain (alphabets other than 4 / 20 states): every mapping option, the default one included, and
+// the site scalars come from these kernels
+static cmx_status map_variant(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks,
+                              double* d_counts, size_t ldc, double* d_norm, void* stream, bool full_grid,
+                              double* d_logL = nullptr, double* d_post_rate = nullptr, int32_t* d_rate_class = nullptr) {
+  const HostModel& h = ctx->hm;
+  const bool scalars = h.plain && (d_logL || d_post_rate || d_rate_class);
+  if (!h.plain && ((ctx->map_average && ctx->map_joint) || (!d_counts && !d_norm))) return CMX_OK;
+  if (h.plain && !d_counts && !d_norm && !scalars) return CMX_OK;
+  const int SD = h.plain ? kPlainStates : h.S;   // device states
+  CMX_TRY(upload_variant_operators(ctx));
+  const bool want_counts = d_counts || d_norm;
+  if (!d_counts && want_counts) {   // only the norms were asked for: they still need the counts
+    CMX_TRY(scratch(ctx, full_grid ? "va_counts_null" : "va_counts_obs", (size_t)h.B * h.K * nsites, &d_counts));
+    ldc = nsites;
+  }
+  NoAvgArgs a = variant_args(ctx, d_aln, ld, d_masks);
+  a.mode = ctx->map_joint ? (ctx->map_average ? kVariantJoint : kVariantNoAvg) : (ctx->map_average ? kVariantMarginal : kVariantNoAvgMarginal);
+  a.logL = d_logL; a.post_rate = d_post_rate; a.rate_class = d_rate_class;
+  // sites per pass: per-node vectors of a pass stay under 1 GiB
+  const size_t per_site = sizeof(double) * noavg_scratch_doubles(SD, h.C, h.nn, 1);
+  a.chunk = std::max<size_t>(256, std::min<size_t>(nsites, ((size_t)1 << 30) / per_site / 256 * 256));
+  a.counts = d_counts; a.ldc = ldc;
+  double* buf;
+  CMX_TRY(scratch(ctx, full_grid ? "va_nodes_null" : "va_nodes_obs", noavg_scratch_doubles(SD, h.C, h.nn, a.chunk), &buf));
+  HIP_TRY(ctx, launch_map_noavg(a, nsites, buf, d_norm, (hipStream_t)stream));
+  return CMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ mapping
+// full_grid: use the whole-chip workspace of the null launches instead of the quarter-chip slice reserved for
+// observed alignments (which exists so that a caller can overlap the observed mapping with cmx_null_intra_dev on a
+// second stream).  Only the engine's own simulate -> map pipelines (inter null, clustering null, candidate groups)
+// ask for it: they are blocking calls on the null stream and map hundreds of thousands of simulated sites.
+cmx_status map_sites_impl(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks, double* d_counts,
+                          size_t ldc, double* d_logL, double* d_post_rate, int32_t* d_rate_class, double* d_norm, void* stream,
+                          bool full_grid) {
+  CMX_TRY(need_model(ctx));
+  if (!d_aln || nsites == 0 || ld < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_map_sites: bad alignment arguments");
+  if (d_counts && ldc < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_map_sites: ldc < nsites");
+  if (d_counts && d_counts == ctx->gram_kept.counts) ctx->gram_kept.valid = false;   // the vectors the kept Gram blocks were made from are rewritten
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (ctx->hm.plain) {
+    // alphabets other than 4 / 20 states (codon models): likelihood, rates and every mapping option from the plain kernels.
+    // No mask table: every code >= nstates is an unknown.
+    if (d_masks) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_map_sites: no ambiguity table for alphabets other than 4 / 20 states (codes >= nstates are unknowns)");
+    return map_variant(ctx, d_aln, nsites, ld, d_masks, d_counts, ldc, d_norm, stream, full_grid, d_logL, d_post_rate, d_rate_class);
+  }
+  const int max_blocks = full_grid ? ctx->grid_blocks : ctx->obs_blocks;
+  MapArgs a{};
+  a.m = ctx->dm; a.ws = full_grid ? ctx->ws : ctx->ws_obs;
+  a.aln = d_aln; a.ld = ld; a.nsites = nsites;
+  // ambiguity ids S .. S+max_ambig(S)-1: rebuild the extra rows of the leaf operators when the table changes.
+  // Not for the engine's own pipelines (full_grid): their simulated alignments are fully resolved and never read those
+  // rows, and rebuilding them on the null's stream would race with an observed mapping of ambiguous codes that a caller
+  // has in flight on a second stream.  leaf_rows_custom stays as it is, so the next public call without a table still
+  // restores the default rows.
+  if (!full_grid && (d_masks || ctx->leaf_rows_custom)) {
+    HIP_TRY(ctx, launch_extend_leaf_rows(ctx->dm, d_masks, (hipStream_t)stream));
+    ctx->leaf_rows_custom = d_masks != nullptr;
+  }
+  a.counts = d_counts; a.ldc = ldc; a.logL = d_logL; a.post_rate = d_post_rate; a.rate_class = d_rate_class;
+  a.norm = d_norm;
+  size_t ks = (size_t)map_sites_per_wave(ctx->hm.dS);
+  size_t nblocks = (nsites + ks - 1) / ks;
+  const size_t obs_waves = (size_t)max_blocks * kWavesPerBlock;
+  if (nblocks * (size_t)ctx->hm.dC <= obs_waves && ctx->hm.dC > 1 && map_ng(ctx->hm.dS) != 3) {   // (48-site experiment builds: no class split)
+    // small alignment: one (site block, class) per wave, classes summed by a second kernel (same arithmetic order)
+    // Proteins, when even that leaves most of the chip idle: 16-site blocks (one site group per wave) -- four times the
+    // tasks, a quarter of the matrix work per operator op, and a wave's slices of the workspaces are a quarter as large,
+    // so 4 * obs_waves of them fit the same allocation
+    if (ctx->hm.dS == 20 && ctx->hm.fuse == 1 && ks == 64 && ((nsites + 15) / 16) * (size_t)ctx->hm.dC <= 4 * obs_waves) {
+      ks = 16;
+      nblocks = (nsites + ks - 1) / ks;
+    }
+    a.split_sites = (int)ks;
+    const size_t ntasks = nblocks * (size_t)ctx->hm.dC, BK = (size_t)ctx->hm.B * ctx->hm.K;
+    // (per caller, like the workspaces: the public observed mapping and the engine's own pipelines may overlap on two streams)
+    CMX_TRY(scratch(ctx, full_grid ? "split_part_null" : "split_part_obs", ntasks * BK * ks, &a.split_part));
+    CMX_TRY(scratch(ctx, full_grid ? "split_lc_null" : "split_lc_obs", 4 * ntasks * ks, &a.split_lc));
+    const int grid = (int)((ntasks + kWavesPerBlock - 1) / kWavesPerBlock);
+    HIP_TRY(ctx, launch_map(a, kModeObservedSplit, grid, (hipStream_t)stream));
+    HIP_TRY(ctx, launch_map_finalize(a, (hipStream_t)stream));
+    return map_variant(ctx, d_aln, nsites, ld, d_masks, d_counts, ldc, d_norm, stream, full_grid);
+  }
+  const size_t blocks_needed = (nblocks + kWavesPerBlock - 1) / kWavesPerBlock;
+  const int grid = (int)std::min<size_t>(blocks_needed, (size_t)max_blocks);
+  HIP_TRY(ctx, launch_map(a, kModeObserved, grid, (hipStream_t)stream));
+  return map_variant(ctx, d_aln, nsites, ld, d_masks, d_counts, ldc, d_norm, stream, full_grid);
+}
+
+cmx_status cmx_map_sites_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks,
+                             double* d_counts, size_t ldc, double* d_logL, double* d_post_rate, int32_t* d_rate_class,
+                             double* d_norm, void* stream) {
+  return map_sites_impl(ctx, d_aln, nsites, ld, d_masks, d_counts, ldc, d_logL, d_post_rate, d_rate_class, d_norm, stream, false);
+}
+
+// the host-pointer entry points' alignment rules (who names the entry point in the message): [T][ld] codes, every code a
+// state or one of the nmasks masks; a mask table only for 4 / 20 states, at most max_ambig(S) ambiguity ids
+static cmx_status check_host_alignment(cmx_ctx* ctx, const char* who, const uint8_t* aln, size_t nsites, size_t ld,
+                                       const uint32_t* masks, size_t nmasks) {
+  CMX_TRY(need_model(ctx));
+  const std::string w(who);
+  if (!aln || nsites == 0 || ld < nsites) return fail(ctx, CMX_ERR_INVALID, w + ": bad alignment arguments");
+  const HostModel& h = ctx->hm;
+  if (masks && h.plain)
+    return fail(ctx, CMX_ERR_UNSUPPORTED, w + ": no ambiguity table for alphabets other than 4 / 20 states (codes >= nstates are unknowns)");
+  if (masks && nmasks > (size_t)(h.S + max_ambig(h.S)))
+    return fail(ctx, CMX_ERR_UNSUPPORTED, w + ": at most " + std::to_string(max_ambig(h.S)) +
+                                              " ambiguity ids (codes >= nstates) are supported for this alphabet");
+  // every code must be a state or a known mask (the reference throws BadCharException at alignment parsing)
+  for (int t = 0; t < h.T; ++t)
+    for (size_t i = 0; i < nsites; ++i) {
+      const unsigned c = aln[(size_t)t * ld + i];
+      if (c >= (unsigned)h.S && masks && c >= nmasks) return fail(ctx, CMX_ERR_INVALID, w + ": alignment code without a mask");
+    }
+  return CMX_OK;
+}
+
+// the checked alignment as [T][nsites] device temporaries, the mask table (if any) padded to 256 entries of "every state"
+static cmx_status upload_host_alignment(cmx_ctx* ctx, TmpDev& tmp, const uint8_t* aln, size_t nsites, size_t ld, const uint32_t* masks,
+                                        size_t nmasks, uint8_t** d_aln, uint32_t** d_masks) {
+  const HostModel& h = ctx->hm;
+  CMX_TRY(tmp.alloc(ctx, d_aln, (size_t)h.T * nsites));
+  HIP_TRY(ctx, hipMemcpy2D(*d_aln, nsites, aln, ld, nsites, h.T, hipMemcpyHostToDevice));
+  if (masks) {
+    std::vector<uint32_t> mk(256, h.S >= 32 ? 0xffffffffu : ((1u << h.S) - 1u));
+    for (size_t i = 0; i < nmasks && i < 256; ++i) mk[i] = masks[i];
+    CMX_TRY(tmp.upload(ctx, d_masks, mk.data(), 256));
+  }
+  return CMX_OK;
+}
+
+cmx_status cmx_map_sites(cmx_ctx* ctx, const uint8_t* aln, size_t nsites, size_t ld, const uint32_t* masks,
+                         size_t nmasks, double* counts, double* logL, double* post_rate, int32_t* rate_class,
+                         double* norm) {
+  CMX_TRY(check_host_alignment(ctx, "cmx_map_sites", aln, nsites, ld, masks, nmasks));
+  const HostModel& h = ctx->hm;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  TmpDev tmp;
+  uint8_t* d_aln = nullptr;
+  uint32_t* d_masks = nullptr;
+  double *d_counts = nullptr, *d_logL = nullptr, *d_pr = nullptr, *d_norm = nullptr;
+  int32_t* d_rc = nullptr;
+  const size_t BK = (size_t)h.B * h.K;
+  CMX_TRY(upload_host_alignment(ctx, tmp, aln, nsites, ld, masks, nmasks, &d_aln, &d_masks));
+  if (counts) CMX_TRY(tmp.alloc(ctx, &d_counts, BK * nsites));
+  CMX_TRY(tmp.alloc(ctx, &d_logL, nsites));
+  CMX_TRY(tmp.alloc(ctx, &d_pr, nsites));
+  CMX_TRY(tmp.alloc(ctx, &d_norm, nsites));
+  CMX_TRY(tmp.alloc(ctx, &d_rc, nsites));
+  CMX_TRY(cmx_map_sites_dev(ctx, d_aln, nsites, nsites, d_masks, d_counts, nsites, d_logL, d_pr, d_rc, d_norm, nullptr));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  if (counts) {  // branch-major [B*K][N] -> site-major [N][B][K] (reference layout mapping[i][b][k])
+    std::vector<double> bm(BK * nsites);
+    CMX_TRY(download(ctx, bm.data(), d_counts, bm.size()));
+    for (size_t r = 0; r < BK; ++r)
+      for (size_t i = 0; i < nsites; ++i) counts[i * BK + r] = bm[r * nsites + i];
+  }
+  CMX_TRY(download(ctx, logL, d_logL, nsites));
+  CMX_TRY(download(ctx, post_rate, d_pr, nsites));
+  CMX_TRY(download(ctx, norm, d_norm, nsites));
+  return download(ctx, rate_class, d_rc, nsites);
+}
+
+// asr.method = marginal (CoMap/CoMap.cpp:169-197): the inside / outside kernels of the mapping variants, then
+// ancestral_kernel (cmx_variants.hip).  Scratch of its own ("asr_nodes", not the mapping's "va_nodes_*"), so it may run on
+// a stream beside a mapping or a null; it reads the caller's mask table directly and leaves the leaf operators' ambiguity
+// rows and the kept Gram blocks alone.  Sites per pass: the four per-node vectors of a pass stay under kAsrScratchBytes,
+// the passes balanced and rounded up to whole workgroups.
+constexpr size_t kAsrScratchBytes = (size_t)2 << 30;
+
+cmx_status cmx_ancestral_states_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks,
+                                    uint8_t* d_states, size_t lds, double* d_post, size_t ldp, void* stream) {
+  CMX_TRY(need_model(ctx));
+  const HostModel& h = ctx->hm;
+  if (!d_aln || nsites == 0 || ld < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_ancestral_states: bad alignment arguments");
+  if (d_masks && h.plain)
+    return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_ancestral_states: no ambiguity table for alphabets other than 4 / 20 states (codes >= nstates are unknowns)");
+  if (!d_states) return fail(ctx, CMX_ERR_INVALID, "cmx_ancestral_states: states is NULL");
+  if (lds < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_ancestral_states: lds < nsites");
+  if (d_post && ldp < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_ancestral_states: ldp < nsites");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  CMX_TRY(upload_variant_operators(ctx));
+  if (!ctx->asr_inner) {
+    std::vector<int> inner;
+    for (int n = 0; n < h.nn; ++n)
+      if (h.first_child[n] >= 0) inner.push_back(n);
+    CMX_TRY(upload(ctx, inner, &ctx->asr_inner));
+    ctx->asr_n_inner = (int)inner.size();
+  }
+  NoAvgArgs a = variant_args(ctx, d_aln, ld, d_masks);
+  const size_t per_site = sizeof(double) * noavg_scratch_doubles(a.S, h.C, h.nn, 1);
+  const size_t max_chunk = std::max<size_t>(256, kAsrScratchBytes / per_site / 256 * 256);
+  const size_t passes = (nsites + max_chunk - 1) / max_chunk;
+  a.chunk = std::min(nsites, ((nsites + passes - 1) / passes + 255) / 256 * 256);
+  double* buf;
+  CMX_TRY(scratch(ctx, "asr_nodes", noavg_scratch_doubles(a.S, h.C, h.nn, a.chunk), &buf));
+  HIP_TRY(ctx, launch_ancestral(a, nsites, buf, ctx->asr_inner, ctx->asr_n_inner, d_states, lds, d_post, ldp, (hipStream_t)stream));
+  return CMX_OK;
+}
+
+cmx_status cmx_ancestral_states(cmx_ctx* ctx, const uint8_t* aln, size_t nsites, size_t ld, const uint32_t* masks, size_t nmasks,
+                                uint8_t* states, double* post) {
+  CMX_TRY(check_host_alignment(ctx, "cmx_ancestral_states", aln, nsites, ld, masks, nmasks));
+  if (!states) return fail(ctx, CMX_ERR_INVALID, "cmx_ancestral_states: states is NULL");
+  const HostModel& h = ctx->hm;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  TmpDev tmp;
+  uint8_t* d_aln = nullptr;
+  uint32_t* d_masks = nullptr;
+  uint8_t* d_states = nullptr;
+  double* d_post = nullptr;
+  CMX_TRY(upload_host_alignment(ctx, tmp, aln, nsites, ld, masks, nmasks, &d_aln, &d_masks));
+  int n_inner = 0;
+  for (int n = 0; n < h.nn; ++n) n_inner += h.first_child[n] >= 0;
+  CMX_TRY(tmp.alloc(ctx, &d_states, (size_t)n_inner * nsites));
+  if (post) CMX_TRY(tmp.alloc(ctx, &d_post, (size_t)n_inner * h.S * nsites));
+  CMX_TRY(cmx_ancestral_states_dev(ctx, d_aln, nsites, nsites, d_masks, d_states, nsites, d_post, nsites, nullptr));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  CMX_TRY(download(ctx, states, d_states, (size_t)n_inner * nsites));
+  if (post) {   // [n_inner][S][N] -> [n_inner][N][S]
+    std::vector<double> pm((size_t)n_inner * h.S * nsites);
+    CMX_TRY(download(ctx, pm.data(), d_post, pm.size()));
+    for (int q = 0; q < n_inner; ++q)
+      for (int x = 0; x < h.S; ++x)
+        for (size_t i = 0; i < nsites; ++i) post[((size_t)q * nsites + i) * h.S + x] = pm[((size_t)q * h.S + x) * nsites + i];
+  }
+  return CMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ simulator
+cmx_status cmx_simulate_dev(cmx_ctx* ctx, uint64_t seed, uint64_t g0, size_t n, uint8_t* d_aln, size_t ld, int32_t* d_classes,
+                            void* stream) {
+  CMX_TRY(need_model(ctx));
+  if (!d_aln || n == 0 || ld < n) return fail(ctx, CMX_ERR_INVALID, "cmx_simulate: bad arguments");
+  CMX_TRY(rng_range(ctx, g0 + n, "cmx_simulate"));
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // node states of the n sites: a scratch of their own per stream would be needed to overlap two simulations of one
+  // context; calls on one context are serialised by the caller (header)
+  uint8_t* d_st;
+  int32_t* d_cls = d_classes;
+  CMX_TRY(scratch(ctx, "sim_states", (size_t)ctx->hm.nn * ld, &d_st));
+  if (!d_cls) CMX_TRY(scratch(ctx, "sim_classes", n, &d_cls));
+  HIP_TRY(ctx, launch_simulate(ctx->dm, seed, g0, n, d_aln, ld, d_cls, d_st, (hipStream_t)stream));
+  return CMX_OK;
+}
+
+cmx_status cmx_simulate(cmx_ctx* ctx, uint64_t seed, uint64_t g0, size_t n, uint8_t* aln_out, int32_t* classes_out) {
+  CMX_TRY(need_model(ctx));
+  if (!aln_out || n == 0) return fail(ctx, CMX_ERR_INVALID, "cmx_simulate: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const HostModel& h = ctx->hm;
+  TmpDev tmp;
+  uint8_t* d_aln = nullptr;
+  int32_t* d_cls = nullptr;
+  CMX_TRY(tmp.alloc(ctx, &d_aln, (size_t)h.T * n));
+  CMX_TRY(tmp.alloc(ctx, &d_cls, n));
+  CMX_TRY(cmx_simulate_dev(ctx, seed, g0, n, d_aln, n, d_cls, nullptr));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  CMX_TRY(download(ctx, aln_out, d_aln, (size_t)h.T * n));
+  return download(ctx, classes_out, d_cls, n);
+}
+
+static_assert(kPlainStates <= kSimContinuousMaxStates, "simulate_continuous_kernel's per-thread row must hold the largest alphabet");
+
+cmx_status cmx_simulate_continuous_dev(cmx_ctx* ctx, uint64_t seed, uint64_t g0, size_t n, double gamma_alpha, double p_invariant,
+                                       uint8_t* d_aln, size_t ld, double* d_rates, void* stream) {
+  CMX_TRY(need_model(ctx));
+  if (!d_aln || n == 0 || ld < n || !(gamma_alpha > 0.0) || !(p_invariant >= 0.0 && p_invariant < 1.0))
+    return fail(ctx, CMX_ERR_INVALID, "cmx_simulate_continuous: bad arguments (alpha > 0, 0 <= p_invariant < 1)");
+  CMX_TRY(rng_range(ctx, g0 + n, "cmx_simulate_continuous"));
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint8_t* d_st;
+  CMX_TRY(scratch(ctx, "sim_states", (size_t)ctx->hm.nn * ld, &d_st));
+  HIP_TRY(ctx, launch_simulate_continuous(ctx->dm, seed, g0, n, gamma_alpha, p_invariant, d_aln, ld, d_rates, d_st, (hipStream_t)stream));
+  return CMX_OK;
+}
+
+cmx_status cmx_simulate_continuous(cmx_ctx* ctx, uint64_t seed, uint64_t g0, size_t n, double gamma_alpha, double p_invariant,
+                                   uint8_t* aln_out, double* rates_out) {
+  CMX_TRY(need_model(ctx));
+  if (!aln_out || n == 0) return fail(ctx, CMX_ERR_INVALID, "cmx_simulate_continuous: bad arguments (alpha > 0, 0 <= p_invariant < 1)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const HostModel& h = ctx->hm;
+  TmpDev tmp;
+  uint8_t* d_aln = nullptr;
+  double* d_r = nullptr;
+  CMX_TRY(tmp.alloc(ctx, &d_aln, (size_t)h.T * n));
+  CMX_TRY(tmp.alloc(ctx, &d_r, n));
+  CMX_TRY(cmx_simulate_continuous_dev(ctx, seed, g0, n, gamma_alpha, p_invariant, d_aln, n, d_r, nullptr));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  CMX_TRY(download(ctx, aln_out, d_aln, (size_t)h.T * n));
+  return download(ctx, rates_out, d_r, n);
+}
+

@@ -1,0 +1,443 @@
+// C-ABI, Mica stage: mutual information of alignment columns, the bootstrap nulls, averages / z-scores, the permutation test.
+#include "cmx_ctx.h"
+
+// the 256 compatibility masks of an alphabet: a state is itself, every other code "unknown" (compatible with all states)
+// unless the caller's table says otherwise (an empty mask there is an unknown too)
+static std::vector<uint32_t> mi_mask_table(int nalpha, const uint32_t* masks = nullptr, size_t nmasks = 0) {
+  std::vector<uint32_t> mk(256, (1u << nalpha) - 1u);
+  for (int i = 0; i < nalpha; ++i) mk[i] = 1u << i;
+  if (masks) for (size_t i = 0; i < nmasks && i < 256; ++i) mk[i] = masks[i];
+  for (size_t i = 0; i < 256; ++i) if (mk[i] == 0) mk[i] = (1u << nalpha) - 1u;
+  return mk;
+}
+// a _dev call without a table: the default one, in scratch
+static cmx_status default_mi_masks(cmx_ctx* ctx, int nalpha, const uint32_t** d_masks) {
+  if (*d_masks) return CMX_OK;
+  uint32_t* p = nullptr;
+  CMX_TRY(scratch(ctx, "mi_masks", 256, &p));
+  HIP_TRY(ctx, hipMemcpy(p, mi_mask_table(nalpha).data(), 256 * sizeof(uint32_t), hipMemcpyHostToDevice));
+  *d_masks = p;
+  return CMX_OK;
+}
+
+cmx_status cmx_mi_columns_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* d_masks, const uint8_t* d_aln1,
+                              size_t n1, size_t ld1, const uint8_t* d_aln2, size_t n2, size_t ld2, double* d_mi,
+                              double* d_hjoint, size_t ldo, double* d_h1, double* d_h2, void* stream) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (nalpha != 4 && nalpha != 20) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mi_columns: alphabet size must be 4 or 20");
+  const bool intra = d_aln2 == nullptr;
+  if (intra) { d_aln2 = d_aln1; n2 = n1; ld2 = ld1; }
+  CMX_TRY(default_mi_masks(ctx, nalpha, &d_masks));
+  if (!d_aln1 || !d_mi || !d_hjoint || ntaxa < 1 || n1 == 0 || n2 == 0 || ld1 < n1 || ld2 < n2 || ldo < n2)
+    return fail(ctx, CMX_ERR_INVALID, "cmx_mi_columns: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // MFMA path (one-hot Gram) whenever the c ln c table fits the kernel's LDS; columns with ambiguous symbols are
+  // left to the LDS-table kernel pair by pair
+  MicaWork w{};
+  const bool mfma = ntaxa <= 2047;   // table + operand buffers within 64 KiB of LDS
+  if (mfma) {
+    w.Tp = (ntaxa + 31) / 32 * 32;
+    const size_t hb = 32 * (size_t)w.Tp;
+    const bool needH = mica_needs_onehot(nalpha, w.Tp);   // 32 Tp bytes per column: only where a kernel reads them
+    CMX_TRY(scratch(ctx, "mica_H1", needH ? hb * n1 : 16, &w.H1));
+    CMX_TRY(scratch(ctx, "mica_C1", (size_t)w.Tp * (n1 + kMicaCodePad), &w.C1));
+    CMX_TRY(scratch(ctx, "mica_f1", n1, &w.flag1));
+    CMX_TRY(scratch(ctx, "mica_g1", n1, &w.gap1));
+    CMX_TRY(scratch(ctx, "mica_S1", n1, &w.S1));
+    if (!intra) {
+      CMX_TRY(scratch(ctx, "mica_H2", needH ? hb * n2 : 16, &w.H2));
+      CMX_TRY(scratch(ctx, "mica_C2", (size_t)w.Tp * (n2 + kMicaCodePad), &w.C2));
+      CMX_TRY(scratch(ctx, "mica_f2", n2, &w.flag2));
+      CMX_TRY(scratch(ctx, "mica_g2", n2, &w.gap2));
+      CMX_TRY(scratch(ctx, "mica_S2", n2, &w.S2));
+    }
+    CMX_TRY(scratch(ctx, "mica_ftab", ((size_t)(ntaxa + 1) + 2 * ((size_t)nalpha * nalpha * ntaxa + 1) + 2), &w.ftab));
+    CMX_TRY(scratch(ctx, "mica_any", 1, &w.anyflag));
+    if (nalpha == 20) {   // block info of the four-wave kernel, padded to whole tiles of 12 columns
+      CMX_TRY(scratch(ctx, "mica_info1", ((n1 + 11) / 12 * 4 + 4), &w.info1));
+      CMX_TRY(scratch(ctx, "mica_order1", n1, &w.order1));
+      CMX_TRY(scratch(ctx, "mica_Cs1", (size_t)w.Tp * (n1 + kMicaCodePad), &w.Cs1));
+      CMX_TRY(scratch(ctx, "mica_Ss1", n1, &w.Ss1));
+      if (mica4_serves(nalpha, w.Tp, n1, intra ? n1 : n2)) CMX_TRY(scratch(ctx, "mica_img2", mica4_image_bytes(w.Tp, intra ? n1 : n2), &w.img2));
+      if (!intra) {
+        CMX_TRY(scratch(ctx, "mica_info2", ((n2 + 11) / 12 * 4 + 4), &w.info2));
+        CMX_TRY(scratch(ctx, "mica_order2", n2, &w.order2));
+        CMX_TRY(scratch(ctx, "mica_Cs2", (size_t)w.Tp * (n2 + kMicaCodePad), &w.Cs2));
+        CMX_TRY(scratch(ctx, "mica_Ss2", n2, &w.Ss2));
+      }
+    }
+  }
+  HIP_TRY(ctx, launch_mi_columns(nalpha, ntaxa, d_masks, d_aln1, n1, ld1, d_aln2, n2, ld2, intra ? 1 : 0, d_mi, d_hjoint,
+                                 ldo, d_h1, intra ? nullptr : d_h2, mfma ? &w : nullptr, (hipStream_t)stream));
+  return CMX_OK;
+}
+
+cmx_status cmx_mi_columns(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* masks, size_t nmasks, const uint8_t* aln1,
+                          size_t n1, const uint8_t* aln2, size_t n2, double* mi, double* hjoint, double* h1, double* h2) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (!aln1 || !mi || !hjoint || n1 == 0 || ntaxa < 1 || nalpha < 2 || nalpha > 31) return fail(ctx, CMX_ERR_INVALID, "cmx_mi_columns: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!aln2) n2 = n1;
+  TmpDev tmp;
+  uint32_t* d_masks;
+  uint8_t *d1, *d2 = nullptr;
+  double *d_mi, *d_hj, *d_h1, *d_h2 = nullptr;
+  CMX_TRY(tmp.upload(ctx, &d_masks, mi_mask_table(nalpha, masks, nmasks).data(), 256));
+  CMX_TRY(tmp.upload(ctx, &d1, aln1, (size_t)ntaxa * n1));
+  if (aln2) {
+    CMX_TRY(tmp.upload(ctx, &d2, aln2, (size_t)ntaxa * n2));
+    CMX_TRY(tmp.alloc(ctx, &d_h2, n2));
+  }
+  CMX_TRY(tmp.alloc(ctx, &d_mi, n1 * n2));
+  CMX_TRY(tmp.alloc(ctx, &d_hj, n1 * n2));
+  CMX_TRY(tmp.alloc(ctx, &d_h1, n1));
+  CMX_TRY(cmx_mi_columns_dev(ctx, nalpha, ntaxa, d_masks, d1, n1, n1, d2, n2, n2, d_mi, d_hj, n2, d_h1, d_h2, nullptr));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  CMX_TRY(download(ctx, mi, d_mi, n1 * n2));
+  CMX_TRY(download(ctx, hjoint, d_hj, n1 * n2));
+  CMX_TRY(download(ctx, h1, d_h1, n1));
+  return download(ctx, h2, aln2 ? d_h2 : d_h1, n2);
+}
+
+// d_masks: device table of 256 compatibility masks (NULL: codes >= nalpha are unknowns); column indices are validated by
+// the caller (the host entry point checks them)
+cmx_status cmx_mi_pairs_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* d_masks, const uint8_t* d_aln1, size_t n1, size_t ld1,
+                            const uint8_t* d_aln2, size_t n2, size_t ld2, const int64_t* d_idx1, const int64_t* d_idx2, size_t npairs,
+                            double* d_mi, double* d_hjoint, void* stream) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (nalpha != 4 && nalpha != 20) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mi_pairs: alphabet size must be 4 or 20");
+  if (!d_aln2) { d_aln2 = d_aln1; n2 = n1; ld2 = ld1; }
+  if (!d_aln1 || !d_idx1 || !d_idx2 || !d_mi || !d_hjoint || n1 == 0 || n2 == 0 || ld1 < n1 || ld2 < n2 || ntaxa < 1 || npairs == 0)
+    return fail(ctx, CMX_ERR_INVALID, "cmx_mi_pairs: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  CMX_TRY(default_mi_masks(ctx, nalpha, &d_masks));
+  HIP_TRY(ctx, launch_mi_pairs(nalpha, ntaxa, d_masks, d_aln1, ld1, d_aln2, ld2, d_idx1, d_idx2, npairs, d_mi, d_hjoint, (hipStream_t)stream));
+  return CMX_OK;
+}
+
+cmx_status cmx_mi_pairs(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* masks, size_t nmasks, const uint8_t* aln1,
+                        size_t n1, const uint8_t* aln2, size_t n2, const int64_t* idx1, const int64_t* idx2, size_t npairs,
+                        double* mi, double* hjoint) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (nalpha != 4 && nalpha != 20) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mi_pairs: alphabet size must be 4 or 20");
+  if (!aln1 || !idx1 || !idx2 || !mi || !hjoint || n1 == 0 || ntaxa < 1 || npairs == 0)
+    return fail(ctx, CMX_ERR_INVALID, "cmx_mi_pairs: bad arguments");
+  if (!aln2) n2 = n1;
+  for (size_t p = 0; p < npairs; ++p)
+    if (idx1[p] < 0 || (size_t)idx1[p] >= n1 || idx2[p] < 0 || (size_t)idx2[p] >= n2)
+      return fail(ctx, CMX_ERR_INVALID, "cmx_mi_pairs: column index out of range");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  TmpDev tmp;
+  uint32_t* d_masks;
+  uint8_t *d1, *d2 = nullptr;
+  int64_t *di1, *di2;
+  double *d_mi, *d_hj;
+  CMX_TRY(tmp.upload(ctx, &d_masks, mi_mask_table(nalpha, masks, nmasks).data(), 256));
+  CMX_TRY(tmp.upload(ctx, &d1, aln1, (size_t)ntaxa * n1));
+  if (aln2) CMX_TRY(tmp.upload(ctx, &d2, aln2, (size_t)ntaxa * n2));
+  CMX_TRY(tmp.upload(ctx, &di1, idx1, npairs));
+  CMX_TRY(tmp.upload(ctx, &di2, idx2, npairs));
+  CMX_TRY(tmp.alloc(ctx, &d_mi, npairs));
+  CMX_TRY(tmp.alloc(ctx, &d_hj, npairs));
+  CMX_TRY(cmx_mi_pairs_dev(ctx, nalpha, ntaxa, d_masks, d1, n1, n1, d2, n2, n2, di1, di2, npairs, d_mi, d_hj, nullptr));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  CMX_TRY(download(ctx, mi, d_mi, npairs));
+  return download(ctx, hjoint, d_hj, npairs);
+}
+
+// ---- Mica's bootstrap nulls.  Site indices of the non-parametric bootstrap (SiteContainerTools::sampleSites,
+// CoMap/Mica.cpp:426-430) come from the engine's counter RNG (cmx_kernels.hip philox_uniform: Philox2x32-10, key from the
+// seed, counter = (g, draw)), so that every binding -- this library's C++ adapter, the Python mirror, a Mica.cpp linked
+// against the C-ABI -- draws the same pairs: idx_h[r * rep_ram + j] = floor(u(seed, g = (r * 2 + h) * rep_ram + j, draw 0) * nsites).
+static double host_philox_uniform(uint64_t seed, uint64_t g, uint32_t draw) {
+  uint32_t c0 = (uint32_t)g, c1 = ((uint32_t)(g >> 32) & 0x7fffu) | (draw << 15);
+  uint32_t k = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x9E3779B9u) ^ 0x434d5832u;
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p = (uint64_t)0xD256D193u * (uint64_t)c0;
+    c0 = (uint32_t)(p >> 32) ^ k ^ c1;
+    c1 = (uint32_t)p;
+    k += 0x9E3779B9u;
+  }
+  const uint64_t bits = (((uint64_t)c0 << 32) | c1) >> 11;
+  return (double)bits * (1.0 / 9007199254740992.0);
+}
+
+cmx_status cmx_mica_bootstrap_indices(uint64_t seed, size_t nsites, size_t nrep_cpu, size_t nrep_ram, int64_t* idx1, int64_t* idx2) {
+  if (nsites == 0 || !idx1 || !idx2 || (uint64_t)nrep_cpu * 2 * nrep_ram > (1ull << 47)) return CMX_ERR_INVALID;
+  for (size_t r = 0; r < nrep_cpu; ++r)
+    for (size_t j = 0; j < nrep_ram; ++j)
+      for (int h = 0; h < 2; ++h) {
+        size_t v = (size_t)(host_philox_uniform(seed, ((uint64_t)r * 2 + h) * nrep_ram + j, 0) * (double)nsites);
+        if (v >= nsites) v = nsites - 1;
+        (h ? idx2 : idx1)[r * nrep_ram + j] = (int64_t)v;
+      }
+  return CMX_OK;
+}
+
+// null.method = parametric-bootstrap (CoMap/Mica.cpp:469-548): per replicate two alignments of nrep_ram sites are simulated
+// under the context's model, column j of the one is scored against column j of the other (MI, joint entropy), and -- Mica's
+// `use_model` case -- both are mapped for their norms.  One simulation, one MI launch and one mapping over all replicates,
+// none of it leaving the device; only the null's columns come back.
+cmx_status cmx_mica_parametric_null(cmx_ctx* ctx, int nalpha, uint64_t seed, size_t nrep_cpu, size_t nrep_ram, double gamma_alpha,
+                                    double p_invariant, double* mi, double* hjoint, double* nmin) {
+  CMX_TRY(need_model(ctx));
+  if (nrep_cpu == 0 || nrep_ram == 0 || !mi || !hjoint) return fail(ctx, CMX_ERR_INVALID, "cmx_mica_parametric_null: bad arguments");
+  if (nalpha != ctx->hm.S) return fail(ctx, CMX_ERR_INVALID, "cmx_mica_parametric_null: the alphabet is the model's");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t n = nrep_cpu * nrep_ram, T = (size_t)ctx->hm.T;
+  TmpDev tmp;
+  uint8_t* d_aln;
+  int64_t *d_i1, *d_i2;
+  double *d_mi, *d_hj, *d_norm = nullptr;
+  CMX_TRY(tmp.alloc(ctx, &d_aln, T * 2 * n));
+  CMX_TRY(tmp.alloc(ctx, &d_i1, n));
+  CMX_TRY(tmp.alloc(ctx, &d_i2, n));
+  CMX_TRY(tmp.alloc(ctx, &d_mi, n));
+  CMX_TRY(tmp.alloc(ctx, &d_hj, n));
+  // simulated-site index g = (rep * 2 + batch) * nrep_ram + j = its column in the [T][2 n] alignment
+  if (gamma_alpha > 0.0) CMX_TRY(cmx_simulate_continuous_dev(ctx, seed, 0, 2 * n, gamma_alpha, p_invariant, d_aln, 2 * n, nullptr, nullptr));
+  else CMX_TRY(cmx_simulate_dev(ctx, seed, 0, 2 * n, d_aln, 2 * n, nullptr, nullptr));
+  std::vector<int64_t> i1(n), i2(n);
+  for (size_t q = 0; q < n; ++q) {
+    const size_t rep = q / nrep_ram, j = q % nrep_ram;
+    i1[q] = (int64_t)((rep * 2) * nrep_ram + j);
+    i2[q] = (int64_t)((rep * 2 + 1) * nrep_ram + j);
+  }
+  HIP_TRY(ctx, hipMemcpy(d_i1, i1.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(d_i2, i2.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
+  CMX_TRY(cmx_mi_pairs_dev(ctx, nalpha, (int)T, nullptr, d_aln, 2 * n, 2 * n, nullptr, 0, 0, d_i1, d_i2, n, d_mi, d_hj, nullptr));
+  if (nmin) {
+    CMX_TRY(tmp.alloc(ctx, &d_norm, 2 * n));
+    CMX_TRY(map_sites_impl(ctx, d_aln, 2 * n, 2 * n, nullptr, nullptr, 0, nullptr, nullptr, nullptr, d_norm, nullptr, true));
+  }
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  CMX_TRY(download(ctx, mi, d_mi, n));
+  CMX_TRY(download(ctx, hjoint, d_hj, n));
+  if (nmin) {
+    std::vector<double> norm(2 * n);
+    CMX_TRY(download(ctx, norm.data(), d_norm, 2 * n));
+    for (size_t q = 0; q < n; ++q) nmin[q] = std::min(norm[(size_t)i1[q]], norm[(size_t)i2[q]]);
+  }
+  return CMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ Mica post-processing
+cmx_status cmx_mica_average_mi_dev(cmx_ctx* ctx, const double* d_mi, size_t n, size_t ldo, double* d_average,
+                                   double* d_full_average, void* stream) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (!d_mi || n < 2 || ldo < n || !d_average || !d_full_average) return fail(ctx, CMX_ERR_INVALID, "cmx_mica_average_mi: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, launch_mica_average(d_mi, n, ldo, d_average, d_full_average, (hipStream_t)stream));
+  return CMX_OK;
+}
+
+cmx_status cmx_mica_average_mi(cmx_ctx* ctx, const double* mi, size_t n, double* average, double* full_average) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (!mi || n < 2 || !average || !full_average) return fail(ctx, CMX_ERR_INVALID, "cmx_mica_average_mi: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  TmpDev tmp;
+  double *d_mi, *d_avg, *d_full;
+  CMX_TRY(tmp.upload(ctx, &d_mi, mi, n * n));
+  CMX_TRY(tmp.alloc(ctx, &d_avg, n));
+  CMX_TRY(tmp.alloc(ctx, &d_full, 1));
+  CMX_TRY(cmx_mica_average_mi_dev(ctx, d_mi, n, n, d_avg, d_full, nullptr));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  CMX_TRY(download(ctx, average, d_avg, n));
+  return download(ctx, full_average, d_full, 1);
+}
+
+cmx_status cmx_mica_zscore_null_dev(cmx_ctx* ctx, int which, const double* d_mi, size_t n, size_t ldo, const double* d_average,
+                                    const double* d_full_average, const double* d_key, double* d_null_stat,
+                                    double* d_null_key, void* stream) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (which < CMX_MICA_MI || which > CMX_MICA_MIC) return fail(ctx, CMX_ERR_INVALID, "cmx_mica_zscore_null: unknown statistic");
+  if (!d_mi || n < 2 || ldo < n || !d_key || !d_null_stat || !d_null_key || (which != CMX_MICA_MI && (!d_average || !d_full_average)))
+    return fail(ctx, CMX_ERR_INVALID, "cmx_mica_zscore_null: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, launch_mica_zscore(which, d_mi, n, ldo, d_average, d_full_average, d_key, d_null_stat, d_null_key,
+                                  (hipStream_t)stream));
+  return CMX_OK;
+}
+
+cmx_status cmx_mica_zscore_null(cmx_ctx* ctx, int which, const double* mi, size_t n, const double* key, double* null_stat,
+                                double* null_key) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (!mi || n < 2 || !key || !null_stat || !null_key) return fail(ctx, CMX_ERR_INVALID, "cmx_mica_zscore_null: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t np = n * (n - 1) / 2;
+  TmpDev tmp;
+  double *d_mi, *d_avg, *d_full, *d_key, *d_ns, *d_nk;
+  CMX_TRY(tmp.upload(ctx, &d_mi, mi, n * n));
+  CMX_TRY(tmp.alloc(ctx, &d_avg, n));
+  CMX_TRY(tmp.alloc(ctx, &d_full, 1));
+  CMX_TRY(tmp.upload(ctx, &d_key, key, n));
+  CMX_TRY(tmp.alloc(ctx, &d_ns, np));
+  CMX_TRY(tmp.alloc(ctx, &d_nk, np));
+  CMX_TRY(cmx_mica_average_mi_dev(ctx, d_mi, n, n, d_avg, d_full, nullptr));
+  CMX_TRY(cmx_mica_zscore_null_dev(ctx, which, d_mi, n, n, d_avg, d_full, d_key, d_ns, d_nk, nullptr));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  CMX_TRY(download(ctx, null_stat, d_ns, np));
+  return download(ctx, null_key, d_nk, np);
+}
+
+// extended codes of the permutation test: states 0..A-1; a code in [A, min(nmasks, 31)) with a partial mask keeps its
+// number; everything else (codes without an entry, gap, X, N: all states) is 31 = unknown.  L = lcm of the state counts.
+namespace {
+struct PermCodes {
+  uint8_t emap[256];
+  uint32_t emask[32], ewgt[32];
+  uint32_t L;
+  int sh;
+};
+cmx_status perm_codes(cmx_ctx* ctx, int A, const uint32_t* masks, size_t nmasks, int T, PermCodes* pc) {
+  const uint32_t all = (1u << A) - 1u;
+  unsigned long long L = (unsigned long long)A;
+  auto lcm = [](unsigned long long a, unsigned long long b) {
+    unsigned long long x = a, y = b;
+    while (y) { const unsigned long long r = x % y; x = y; y = r; }
+    return a / x * b;
+  };
+  int k[32];
+  for (int e = 0; e < 32; ++e) { pc->emask[e] = e < A ? (1u << e) : all; k[e] = e < A ? 1 : A; }
+  for (int c = 0; c < 256; ++c) {
+    if (c < A) { pc->emap[c] = (uint8_t)c; continue; }
+    if (!masks || (size_t)c >= nmasks) { pc->emap[c] = 31; continue; }
+    const uint32_t m = masks[c] & all;
+    if (m == 0) return fail(ctx, CMX_ERR_INVALID, "cmx_mica_permutation_test: mask of code " + std::to_string(c) + " has no state");
+    if (m == all) { pc->emap[c] = 31; continue; }
+    if (c >= 31) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: partial ambiguity codes must be < 31");
+    pc->emap[c] = (uint8_t)c;
+    pc->emask[c] = m;
+    k[c] = __builtin_popcount(m);
+    L = lcm(L, (unsigned long long)k[c]);
+  }
+  const double M = (double)L * (double)L * (double)T;
+  if (M > 67108864.0)
+    return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: lcm of the ambiguity codes' state counts too large for the fixed-point table");
+  pc->L = (uint32_t)L;
+  for (int e = 0; e < 32; ++e) pc->ewgt[e] = (uint32_t)(L / (unsigned long long)k[e]);
+  pc->sh = std::min(40, 62 - (int)std::ceil(std::log2(M * std::log(M))));
+  return CMX_OK;
+}
+}  // namespace
+
+cmx_status cmx_mica_permutation_test_masks_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* masks, size_t nmasks,
+                                               const uint8_t* d_aln, size_t n, size_t ld, uint32_t max_perm, uint64_t seed,
+                                               size_t pair_begin, size_t pair_end, double* d_pvalue, int32_t* d_nperm, void* stream) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (nalpha != 4 && nalpha != 20) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: alphabet size must be 4 or 20");
+  if (ntaxa < 2 || ntaxa > mica_perm_max_taxa())
+    return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: 2 <= ntaxa <= " + std::to_string(mica_perm_max_taxa()));
+  if (!d_aln || n < 2 || ld < n || max_perm == 0 || pair_end <= pair_begin || pair_end > n * (n - 1) / 2 || !d_pvalue || !d_nperm)
+    return fail(ctx, CMX_ERR_INVALID, "cmx_mica_permutation_test: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  PermCodes pc;
+  CMX_TRY(perm_codes(ctx, nalpha, masks, nmasks, ntaxa, &pc));
+  uint16_t *d_cnt, *d_ext;
+  uint8_t *d_emap, *d_hasamb;
+  uint32_t* d_tab;   // emask[32] | ewgt[32]
+  int* d_bad;
+  long long* d_dF;
+  CMX_TRY(scratch(ctx, "perm_cnt", n * nalpha, &d_cnt));
+  CMX_TRY(scratch(ctx, "perm_ext", n * 32, &d_ext));
+  CMX_TRY(scratch(ctx, "perm_emap", 256, &d_emap));
+  CMX_TRY(scratch(ctx, "perm_hasamb", n, &d_hasamb));
+  CMX_TRY(scratch(ctx, "perm_tab", 64, &d_tab));
+  CMX_TRY(scratch(ctx, "perm_bad", 2, &d_bad));
+  CMX_TRY(scratch(ctx, "perm_dF", ntaxa, &d_dF));
+  // resolved pairs: F[c] = round(c ln c * 2^40); the kernel accumulates F[c+1] - F[c] per increment of a joint count
+  // (sources owned by the context: a failing call further down must not free memory an upload still reads)
+  std::vector<long long>& dF = ctx->perm_dF_host;
+  dF.assign(ntaxa, 0);
+  long long prev = 0;
+  for (int c = 1; c <= ntaxa; ++c) {
+    const long long f = std::llround((double)c * std::log((double)c) * 1099511627776.0);
+    dF[c - 1] = f - prev;
+    prev = f;
+  }
+  ctx->perm_tab_host.assign(256 + 64 * sizeof(uint32_t), 0);
+  std::memcpy(ctx->perm_tab_host.data(), pc.emap, 256);
+  std::memcpy(ctx->perm_tab_host.data() + 256, pc.emask, 32 * sizeof(uint32_t));
+  std::memcpy(ctx->perm_tab_host.data() + 256 + 32 * sizeof(uint32_t), pc.ewgt, 32 * sizeof(uint32_t));
+  HIP_TRY(ctx, hipMemcpyAsync(d_dF, dF.data(), sizeof(long long) * ntaxa, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_emap, ctx->perm_tab_host.data(), 256, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_tab, ctx->perm_tab_host.data() + 256, sizeof(uint32_t) * 64, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemsetAsync(d_bad, 0, 2 * sizeof(int), st));
+  HIP_TRY(ctx, launch_mica_colcount(d_aln, ntaxa, n, ld, nalpha, d_emap, d_cnt, d_ext, d_hasamb, d_bad, st));
+  int bad[2] = {0, 0};
+  HIP_TRY(ctx, hipMemcpyAsync(bad, d_bad, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));   // the one host decision of this call: are there pairs with unknowns at all
+  int cus = 0;
+  HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  const size_t npairs = pair_end - pair_begin;
+  bool preset = false;
+  if (bad[0]) {
+    // pairs with gaps / unknowns / ambiguity codes (SiteTools::*(.., resolveUnknowns = true)): their own kernel, first
+    if (mica_perm_general_lds(ntaxa, nalpha, bad[1]) == 0)
+      return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: " + std::to_string(ntaxa) + " taxa with " + std::to_string(bad[1]) +
+                                            " distinct ambiguity codes in one column do not fit the LDS");
+    const size_t M = (size_t)pc.L * pc.L * (size_t)ntaxa;
+    long long* d_F;
+    uint16_t* d_order;
+    CMX_TRY(scratch(ctx, "perm_F", (M + 1), &d_F));
+    CMX_TRY(scratch(ctx, "perm_order", n * (size_t)ntaxa, &d_order));
+    // F[m] = round(m ln m 2^sh), up to 2^26 entries with a logarithm each: built once per (L, taxa, shift) and kept on the
+    // device -- a caller that shards the pairs over several calls pays for it once.  (Built on the host with the oracle's
+    // logarithm so that the fixed-point sums, and with them every tie, are the oracle's.)
+    if (ctx->perm_F_L != pc.L || ctx->perm_F_T != ntaxa || ctx->perm_F_sh != pc.sh || ctx->perm_F_host.size() != M + 1) {
+      ctx->perm_F_sh = -1;
+      std::vector<long long>& F = ctx->perm_F_host;
+      F.assign(M + 1, 0);
+      const double scale = std::ldexp(1.0, pc.sh);
+      for (size_t m = 1; m <= M; ++m) F[m] = std::llround((double)m * std::log((double)m) * scale);
+      HIP_TRY(ctx, hipMemcpyAsync(d_F, F.data(), sizeof(long long) * (M + 1), hipMemcpyHostToDevice, st));
+      ctx->perm_F_L = pc.L; ctx->perm_F_T = ntaxa; ctx->perm_F_sh = pc.sh;
+    }
+    HIP_TRY(ctx, launch_mica_colorder(d_aln, ntaxa, n, ld, nalpha, d_emap, d_ext, d_order, st));
+    if (!mica_perm_opening_fits(ntaxa, nalpha)) {
+      HIP_TRY(ctx, hipMemsetAsync(d_nperm, 0xFF, sizeof(int32_t) * npairs, st));   // -1: undecided, no hits (resolved pairs)
+      preset = true;
+    }
+    HIP_TRY(ctx, launch_mica_perm_general(d_aln, ntaxa, n, ld, nalpha, d_emap, d_ext, d_order, d_hasamb, d_tab, d_tab + 32, d_F, pc.L,
+                                          bad[1], max_perm, seed, pair_begin, pair_end, d_pvalue, d_nperm, cus, st));
+  }
+  HIP_TRY(ctx, launch_mica_perm(d_aln, ntaxa, n, ld, nalpha, d_cnt, d_hasamb, d_dF, preset, max_perm, seed, pair_begin, pair_end,
+                                d_pvalue, d_nperm, cus, st));
+  return CMX_OK;
+}
+
+cmx_status cmx_mica_permutation_test_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint8_t* d_aln, size_t n, size_t ld,
+                                         uint32_t max_perm, uint64_t seed, size_t pair_begin, size_t pair_end,
+                                         double* d_pvalue, int32_t* d_nperm, void* stream) {
+  return cmx_mica_permutation_test_masks_dev(ctx, nalpha, ntaxa, nullptr, 0, d_aln, n, ld, max_perm, seed, pair_begin, pair_end,
+                                             d_pvalue, d_nperm, stream);
+}
+
+cmx_status cmx_mica_permutation_test_masks(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* masks, size_t nmasks,
+                                           const uint8_t* aln, size_t n, uint32_t max_perm, uint64_t seed, double* pvalue,
+                                           int32_t* nperm) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (!aln || n < 2 || ntaxa < 2 || !pvalue || !nperm) return fail(ctx, CMX_ERR_INVALID, "cmx_mica_permutation_test: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t np = n * (n - 1) / 2;
+  TmpDev tmp;
+  uint8_t* d_aln;
+  double* d_pv;
+  int32_t* d_np;
+  CMX_TRY(tmp.upload(ctx, &d_aln, aln, (size_t)ntaxa * n));
+  CMX_TRY(tmp.alloc(ctx, &d_pv, np));
+  CMX_TRY(tmp.alloc(ctx, &d_np, np));
+  cmx_status s = cmx_mica_permutation_test_masks_dev(ctx, nalpha, ntaxa, masks, nmasks, d_aln, n, n, max_perm, seed, 0, np, d_pv, d_np,
+                                                     nullptr);
+  if (s != CMX_OK) return s;
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  CMX_TRY(download(ctx, pvalue, d_pv, np));
+  return download(ctx, nperm, d_np, np);
+}
+
+cmx_status cmx_mica_permutation_test(cmx_ctx* ctx, int nalpha, int ntaxa, const uint8_t* aln, size_t n, uint32_t max_perm,
+                                     uint64_t seed, double* pvalue, int32_t* nperm) {
+  return cmx_mica_permutation_test_masks(ctx, nalpha, ntaxa, nullptr, 0, aln, n, max_perm, seed, pvalue, nperm);
+}
+

@@ -23,7 +23,7 @@ ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--warmup", type=int, default=2)
 a = ap.parse_args()
 dev = torch.device("cuda:0")
-BUDGET = 2 << 30      # kAsrScratchBytes (cmx_api.cpp)
+BUDGET = 2 << 30      # kAsrScratchBytes (cmx_api_map.cpp)
 
 
 def timed(fn):

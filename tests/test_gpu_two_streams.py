@@ -23,7 +23,7 @@ README.md reports 3.9 ms for the observed stage of 10 000 x 64 protein sites; 4 
 or two of mapping, against some tens of microseconds between the two enqueues.
 
 This module must not run under the scratch guard: with CMX_SCRATCH_GUARD on, every scratch() request calls
-hipDeviceSynchronize() (comap_amd/csrc/cmx_api.cpp, scratch()) and the two streams never overlap.  The module fixture
+hipDeviceSynchronize() (comap_amd/csrc/cmx_api_ctx.cpp, scratch()) and the two streams never overlap.  The module fixture
 switches the guard off for contexts it creates and puts the previous state back."""
 import numpy as np
 import pytest
