@@ -146,7 +146,7 @@ cmx_status cmx_mi_pairs(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* mas
 }
 
 // ---- Mica's bootstrap nulls.  Site indices of the non-parametric bootstrap (SiteContainerTools::sampleSites,
-// CoMap/Mica.cpp:426-430) come from the engine's counter RNG (cmx_kernels.hip philox_uniform: Philox2x32-10, key from the
+// CoMap/Mica.cpp:426-430) come from the engine's counter RNG (cmx_simulate.hip philox_uniform: Philox2x32-10, key from the
 // seed, counter = (g, draw)), so that every binding -- this library's C++ adapter, the Python mirror, a Mica.cpp linked
 // against the C-ABI -- draws the same pairs: idx_h[r * rep_ram + j] = floor(u(seed, g = (r * 2 + h) * rep_ram + j, draw 0) * nsites).
 static double host_philox_uniform(uint64_t seed, uint64_t g, uint32_t draw) {

@@ -210,7 +210,7 @@ inline int gram_kind(int gk, const double* d_w) {
   return gk == CMX_STAT_CORRELATION ? CMX_STAT_COSINUS : gk == CMX_STAT_COVARIANCE ? CMX_STAT_SCALAR_PRODUCT : gk;
 }
 
-// the simulator's counter layout (cmx_kernels.hip philox_uniform): 47 bits of simulated-site index, 17 bits of draw index
+// the simulator's counter layout (cmx_simulate.hip philox_uniform): 47 bits of simulated-site index, 17 bits of draw index
 inline cmx_status rng_range(cmx_ctx* ctx, uint64_t g_end, const char* who) {
   if (g_end > (1ull << 47) || (uint64_t)ctx->hm.nn + 2 > (1ull << 17))
     return fail(ctx, CMX_ERR_UNSUPPORTED, std::string(who) + ": simulated-site index beyond 2^47 or more than 2^17 - 2 nodes");

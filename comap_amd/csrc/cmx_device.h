@@ -76,6 +76,12 @@ struct DevModel {
   const double* cum_probs; // [C]
 };
 
+// Read-only, wave-uniform metadata (tree program, schedules, pi, class rates) is read through the CONSTANT address
+// space so that hipcc emits s_load (scalar cache, lgkmcnt) instead of global_load + v_readfirstlane: the latter would
+// queue every dependent tree-walk step behind the HBM prefetches outstanding on vmcnt.
+typedef const int __attribute__((address_space(4)))* cmx_cint;
+typedef const double __attribute__((address_space(4)))* cmx_cdbl;
+
 // Per-wave workspace strides (in elements); every wave owns one slice of each array.
 struct Workspace {
   double* D;        // [waves][NIW][S][64]  messages M_n = P_n D_n of internal nodes (inside pass)
@@ -130,12 +136,10 @@ struct MapArgs {
   // (kSites patterns per wave, kRow the wave's row stride: the block map_sites_wave's epilogue writes)
 };
 
-// launchers (cmx_kernels.hip)
+// launchers by source file (cmx_map.hip; pair_diag and group_stats are there for map_kernel's sake)
 int map_lds_per_wave(int S, int nn, int mode);
 hipError_t launch_map(const MapArgs& a, int mode, int grid_blocks, hipStream_t stream);
 hipError_t launch_map_finalize(const MapArgs& a, hipStream_t stream);
-hipError_t launch_simulate_blocked(const DevModel& m, uint64_t seed, uint64_t g0, size_t nsites, size_t blk, uint8_t* d_aln,
-                                   uint8_t* d_states, size_t chunk, hipStream_t stream);
 // fills rows S.. of every leaf operator from d_masks[S .. S+max_ambig(S)) (null: every state compatible)
 hipError_t launch_extend_leaf_rows(const DevModel& m, const uint32_t* d_masks, hipStream_t stream);
 hipError_t launch_pair_diag(int kind, double param, int B, int K, const double* c1, size_t ld1, const double* c2, size_t ld2,
@@ -145,7 +149,22 @@ hipError_t launch_pair_diag(int kind, double param, int B, int K, const double* 
 hipError_t launch_group_stats(int kind, double param, int B, int K, const double* d_counts, size_t ld, const int64_t* d_offsets,
                               const int32_t* d_sites, size_t ngroups, double* d_out, const double* d_mean, hipStream_t stream,
                               const double* d_w = nullptr);
-// DiscreteMI with a bounds vector (cmx_stat_mi.hip): class words [B][ldx] (class | marginal count << 16) + per-site
+// (cmx_simulate.hip)
+hipError_t launch_simulate(const DevModel& m, uint64_t seed, uint64_t g0, size_t n, uint8_t* d_aln, size_t ld,
+                           int32_t* d_classes, uint8_t* d_states, hipStream_t stream, size_t rep_ram = 0, uint64_t gstep = 0);
+hipError_t launch_simulate_continuous(const DevModel& m, uint64_t seed, uint64_t g0, size_t n, double alpha, double p_inv,
+                                      uint8_t* d_aln, size_t ld, double* d_rates, uint8_t* d_states, hipStream_t stream);
+hipError_t launch_simulate_blocked(const DevModel& m, uint64_t seed, uint64_t g0, size_t nsites, size_t blk, uint8_t* d_aln,
+                                   uint8_t* d_states, size_t chunk, hipStream_t stream);
+// (cmx_pairs.hip)
+hipError_t launch_pair_prep(int kind, double param, const double* d_counts, size_t n, size_t ldc, int B, int K,
+                            double* d_X, size_t ldx, int Bp, double* d_s, double* d_r, const double* d_mvec,
+                            hipStream_t stream, size_t blk = 0, const double* d_w = nullptr);
+hipError_t launch_pair_gram(int kind, int B, int Bp, const double* d_X1, const double* d_s1, const double* d_r1,
+                            size_t n1, size_t ldx1, const double* d_X2, const double* d_s2, const double* d_r2,
+                            size_t n2, size_t ldx2, int intra, double* d_out, size_t ldo, hipStream_t stream,
+                            size_t nblk = 1, size_t zsite = 0, size_t zout = 0, size_t zx = 0, size_t irow0 = 0);
+// (cmx_stat_mi.hip) DiscreteMI with a bounds vector: class words [B][ldx] (class | marginal count << 16) + per-site
 // out-of-range flags; all-pairs block, diagonal pairs, groups
 hipError_t launch_mi_classify(const double* d_counts, size_t n, size_t ldc, int B, int K, const double* d_bounds, int nb,
                               uint32_t* d_cls, size_t ldx, uint8_t* d_bad, hipStream_t stream);
@@ -156,7 +175,7 @@ hipError_t launch_mi_pairs_diag(int B, const uint32_t* d_cls1, const uint8_t* d_
                                 const uint8_t* d_bad2, size_t ld2, size_t n, double* d_out, hipStream_t stream);
 hipError_t launch_mi_group(int B, const uint32_t* d_cls, const uint8_t* d_bad, size_t ld, const int64_t* d_offsets,
                            const int32_t* d_sites, size_t ngroups, double* d_out, hipStream_t stream);
-// nijt.average = no (cmx_variants.hip): the no-averaging mapping as plain kernels over a global scratch
+// (cmx_variants.hip) nijt.average = no: the no-averaging mapping as plain kernels over a global scratch
 // mode: which LegacySubstitutionMappingTools function (CoETools.cpp:395-405)
 // kVariantJoint: the default mapping (computeSubstitutionVectors: averaged, joint) for the alphabets the matrix-core walk
 // does not serve
@@ -186,7 +205,7 @@ hipError_t launch_map_noavg(NoAvgArgs a, size_t nsites_total, double* scratch, d
 // asr.method = marginal (cmx_ancestral_states*): states [n_inner][lds], optional posterior [n_inner][Sreal][ldp]
 hipError_t launch_ancestral(NoAvgArgs a, size_t nsites_total, double* scratch, const int* d_inner, int n_inner, uint8_t* d_states,
                             size_t lds, double* d_post, size_t ldp, hipStream_t stream);
-// Mica post-processing (cmx_mica_post.hip)
+// (cmx_mica_post.hip) Mica post-processing
 hipError_t launch_mica_average(const double* d_mi, size_t n, size_t ld, double* d_avg, double* d_full, hipStream_t stream);
 hipError_t launch_mica_zscore(int which, const double* d_mi, size_t n, size_t ld, const double* d_avg, const double* d_full,
                               const double* d_key, double* d_stat, double* d_outkey, hipStream_t stream);
@@ -205,7 +224,7 @@ hipError_t launch_mica_perm_general(const uint8_t* d_aln, int T, size_t n, size_
 hipError_t launch_mica_perm(const uint8_t* d_aln, int T, size_t n, size_t ld, int A, const uint16_t* d_colcnt,
                             const uint8_t* d_hasamb, const long long* d_dF, bool nperm_preset, uint32_t max_perm, uint64_t seed,
                             size_t pair_begin, size_t pair_end, double* d_pvalue, int32_t* d_nperm, int cu_count, hipStream_t stream);
-// clustering (cmx_cluster.hip)
+// (cmx_cluster.hip)
 size_t hclust_lds_bytes(int n);
 size_t cluster_props_lds_bytes(int n);
 hipError_t launch_dist_finish(int dist_kind, double* d_D, size_t n, size_t ld, size_t mat_stride, size_t batch,
@@ -215,18 +234,7 @@ hipError_t launch_hclust(int linkage, double* d_D, size_t n, size_t ld, size_t m
 hipError_t launch_cluster_props(int dist_kind, int n, int B, int K, size_t batch, const int32_t* d_merge, const double* d_dmax,
                                 const double* d_norm, const double* d_counts, size_t ldc, size_t site_stride, double* d_sigma,
                                 double* d_stat, double* d_nmin, hipStream_t stream);
-hipError_t launch_simulate(const DevModel& m, uint64_t seed, uint64_t g0, size_t n, uint8_t* d_aln, size_t ld,
-                           int32_t* d_classes, uint8_t* d_states, hipStream_t stream, size_t rep_ram = 0, uint64_t gstep = 0);
-hipError_t launch_simulate_continuous(const DevModel& m, uint64_t seed, uint64_t g0, size_t n, double alpha, double p_inv,
-                                      uint8_t* d_aln, size_t ld, double* d_rates, uint8_t* d_states, hipStream_t stream);
-hipError_t launch_pair_prep(int kind, double param, const double* d_counts, size_t n, size_t ldc, int B, int K,
-                            double* d_X, size_t ldx, int Bp, double* d_s, double* d_r, const double* d_mvec,
-                            hipStream_t stream, size_t blk = 0, const double* d_w = nullptr);
-hipError_t launch_pair_gram(int kind, int B, int Bp, const double* d_X1, const double* d_s1, const double* d_r1,
-                            size_t n1, size_t ldx1, const double* d_X2, const double* d_s2, const double* d_r2,
-                            size_t n2, size_t ldx2, int intra, double* d_out, size_t ldo, hipStream_t stream,
-                            size_t nblk = 1, size_t zsite = 0, size_t zout = 0, size_t zx = 0, size_t irow0 = 0);
-// the fused null's patterns (cmx_null_patterns.hip).  Sites g of a pass: [replicate][batch][taxon][rep_ram] alignments,
+// (cmx_null_patterns.hip) the fused null's patterns.  Sites g of a pass: [replicate][batch][taxon][rep_ram] alignments,
 // g = (rep * 2 + batch) * rep_ram + j.  Columns are copied site-major, null_pattern_row_bytes(T) bytes each.
 size_t null_pattern_row_bytes(int T);
 hipError_t null_pattern_tmp_bytes(size_t n, int hash_bits, size_t* bytes);   // rocPRIM temporary of a pass of n sites
@@ -256,6 +264,7 @@ hipError_t launch_null_pattern_pairs(int kind, double param, int B, int K, const
                                      const int32_t* rate_class, const double* norm, const uint32_t* pat_of, size_t rep_ram,
                                      size_t npairs, const double* d_mean, double* stat, int32_t* rcmin, double* prmin, double* nmin,
                                      hipStream_t stream);
+// (cmx_rows.hip)
 hipError_t launch_max_reduce(const double* d_x, size_t n, double* d_out, hipStream_t stream);
 hipError_t launch_null_classify(const double* d_stat, const double* d_nmin, size_t nnull, const double* d_maxnorm,
                                 int nclasses, uint32_t* d_cls, uint32_t* d_hist, hipStream_t stream);
@@ -294,14 +303,15 @@ hipError_t launch_inter_rows(const double* d_stat, size_t ldo, size_t n2, const 
                              unsigned long long* d_rowcount, void* d_tmp, size_t& tmp_bytes, cmx_pair_row* d_rows, size_t capacity,
                              unsigned long long* d_count, hipStream_t stream, size_t irow0, size_t nrows,
                              const unsigned long long* d_base);
+// (cmx_mica.hip)
 hipError_t launch_mi_pairs(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t ld1, const uint8_t* d_aln2,
                            size_t ld2, const int64_t* d_idx1, const int64_t* d_idx2, size_t npairs, double* d_mi,
                            double* d_hj, hipStream_t stream);
-// scratch of the MFMA Mica path (all device pointers; H1 null = LDS-table kernel only)
+// scratch of the MFMA Mica path (all device pointers; a null H1 = LDS-table kernel only)
 constexpr int kMicaLdsF2 = 4096;   // entries of f2 the weighted four-wave kernel keeps in LDS (m < 4096: cells of up to ten taxa)
 constexpr int kMicaCodePad = 64;   // columns of "no row" symbols behind the last column of C1 / C2 (the four-wave kernels read whole tiles: 12 / 64 columns)
 struct MicaWork {
-  int8_t *H1, *H2;         // one-hot [n][32][Tp] int8 (one-column-per-tile kernel)
+  int8_t *H1, *H2;         // one-hot [n][32][Tp] int8 where mica_needs_onehot (the one-column-per-tile kernel), else a 16-byte stand-in
   uint8_t *C1, *C2;        // [n + kMicaCodePad][Tp] one-hot row of each taxon (state, A = unknown, 255 = none): the packed protein kernel's operands
   uint8_t *flag1, *flag2;  // [n] column has ambiguous symbols other than "unknown" (-> LDS-table kernel)
   uint8_t *gap1, *gap2;    // [n] column has unknowns (gap / X / N: compatible with every state; handled on the matrix cores)
@@ -316,7 +326,10 @@ struct MicaWork {
   int Tp;                  // T rounded up to a multiple of 32 (taxa per MFMA step)
 };
 bool mica_needs_onehot(int A, int Tp);   // whether launch_mi_columns reads MicaWork::H1 / H2 for this alphabet
-// cmx_mica4.hip: the four-wave protein kernel (unknowns included; partial ambiguity codes are not served)
+hipError_t launch_mi_columns(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t n1, size_t ld1,
+                             const uint8_t* d_aln2, size_t n2, size_t ld2, int intra, double* d_mi, double* d_hj,
+                             size_t ldo, double* d_h1, double* d_h2, const MicaWork* work, hipStream_t stream);
+// (cmx_mica4.hip) the four-wave protein kernel (unknowns included; partial ambiguity codes are not served)
 bool mica4_serves(int A, int Tp, size_t n1, size_t n2);
 size_t mica4_image_bytes(int Tp, size_t n2);
 hipError_t launch_mica4(int T, const MicaWork* wk, size_t n1, size_t n2, int intra, double* d_mi, double* d_hj, size_t ldo,
@@ -325,8 +338,4 @@ hipError_t launch_mica4(int T, const MicaWork* wk, size_t n1, size_t n2, int int
 bool mica_dna4_serves(int A, int Tp, size_t n1, size_t n2);
 hipError_t launch_mica_dna4(int T, const MicaWork* wk, size_t n1, size_t n2, int intra, double* d_mi, double* d_hj, size_t ldo,
                             hipStream_t stream);
-hipError_t launch_mi_columns(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t n1, size_t ld1,
-                             const uint8_t* d_aln2, size_t n2, size_t ld2, int intra, double* d_mi, double* d_hj,
-                             size_t ldo, double* d_h1, double* d_h2, const MicaWork* work, hipStream_t stream);
-
 }  // namespace cmx

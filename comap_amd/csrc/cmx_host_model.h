@@ -35,7 +35,7 @@ struct HostModel {
   std::vector<double> eigV, eigVi, eigLam;   // [NM][S*S], [NM][S*S], [NM][S]: right / left eigenvectors and eigenvalues of the generators
   std::vector<int> model_of;                  // [B] generator of each branch (all 0 for a homogeneous model)
   std::vector<double> CP;   // [C][nn][S][S]    running row sums of P
-  std::vector<uint8_t> CPG; // [C][nn][S][32]   guide table of the simulator's inverse-CDF search (cmx_kernels.hip: draw_guided)
+  std::vector<uint8_t> CPG; // [C][nn][S][32]   guide table of the simulator's inverse-CDF search (cmx_simulate.hip: draw_guided)
   std::vector<int> simg;    // [nsimg][16] simulator: groups of four nodes of equal depth (DevModel::simg)
   std::vector<int> simord;  // [nn - 1] the non-root nodes by depth (DevModel::simord)
   int NV = 0;               // visited nodes of the binary device tree (internal, not inlined; pseudo nodes included)

@@ -1,0 +1,1152 @@
+// The mapping walk: hand-written gfx950 (CDNA4) kernels.  fp64 throughout (the reference computes in double and its
+// DR likelihood has no per-node rescaling, CoMap/CoETools.cpp:244).
+//
+// map_kernel<S, MODE>
+//   one wavefront = 64 sites (lane == site) x all rate classes in turn; four independent waves per workgroup.
+//   Replaces, per site: DRHomogeneousTreeLikelihood::initialize (post-order "inside" pass), the pre-order
+//   "outside" pass, LegacySubstitutionMappingTools::computeSubstitutionVectors and computeNormForSite
+//   (call sites CoMap/CoETools.cpp:397, CoMap/AnalysisTools.cpp:592-612; algorithm SURVEY.md A.2/A.3/A.6).
+//   The SxS operator of an edge is the same for all 64 lanes: every operator use of a class pass (products on
+//   internal edges, row gathers by observed symbol on leaf edges) is listed by the host in one op stream and staged
+//   in LDS by LDS-DMA one op ahead; products run on the matrix cores (v_mfma_f64_4x4x4_4b, 100 per 20x20 product) in
+//   a layout where lane = (state inside a 4-state tile, site of a group of 16).
+//   Matrices are packed host-side in 4x4 blocks so that one copy serves both P.d (inside) and P^T.u (outside).
+//   Inside vectors / outside messages that must survive go to a per-wave HBM workspace as [S/2][lane][2]: every
+//   access is one fully coalesced 1 KiB row; loads are prefetched into LDS by DMA under a host-built schedule.
+//   DESIGN.md 4.1 has the full description and the measurements.
+//   MODE == kModeNull: map (x2 batches) -> per-pair statistic of AnalysisTools::getNullDistributionIntraDR
+//   (CoMap/AnalysisTools.cpp:587-653) per wave, on alignments simulated beforehand by simulate_lds_kernel /
+//   simulate_blocked_kernel at full occupancy (round 1 simulated inside the mapping wave).
+//   MODE == kModeNullPatterns: the same walk over the null's distinct columns, one lane per pattern; the pairs are scored
+//   by null_pattern_pairs_kernel (cmx_null_patterns.hip).
+#include "cmx_device.h"
+#include "cmx_lanes.h"
+#include "cmx_pairstat.h"
+#include "cmx_walk.h"
+
+namespace cmx {
+
+// ------------------------------------------------------------------------------------------------ ring matvec
+typedef double d2 __attribute__((ext_vector_type(2)));
+
+// Every edge of the tree applies one SxS operator that is the same for all 64 lanes: a matrix-vector product on
+// internal edges, a row gather by observed symbol on leaf edges.  The sequence of operators of a class pass is known
+// (host-built op stream, m.msched), so each operator is DMAed into LDS one op ahead: two S*S*8-byte stage buffers per
+// wave, op i reads buffer i&1 while the DMA of op i+1 fills the other (global_load_lds_dwordx4, 1 KiB per
+// instruction, no VGPRs).  A product reads the A operand of each 4x4 tile with one ds_read_b64 and runs on
+// v_mfma_f64_4x4x4_4b (see "Matrix-core layout" below); a leaf op reads the values its lane holds of row `symbol` of
+// the transposed matrix.  The symbols of the next leaf op are DMAed the same way (global_load_lds_ubyte into a
+// 256-byte slot).
+// History: an s_load-fed v_fma_f64 version ran at 39 TFLOP/s; tiles in a VGPR ring applied with
+// v_fmac_f64_dpp row_newbcast (53 TFLOP/s in isolation) needed either fixed registers -- amdgpu_num_vgpr turned out not
+// to be a hard limit, the compiler reused them under pressure -- or 50 more loop-carried registers than two waves per
+// SIMD can afford; the LDS-staged DPP version (lane = site) reached 16.7 ms per launch, the matrix-core layout 15.5 ms;
+// gathering leaf rows straight from L2 (lane-divergent 160-byte rows, latency exposed at every leaf) cost 5 of 21 ms.
+
+typedef __attribute__((address_space(1))) const void* cmx_gptr;
+typedef __attribute__((address_space(3))) void* cmx_lptr;
+
+template <int S>
+struct MatStage {
+  static constexpr int NROW = S + max_ambig(S);              // rows of a transposed leaf operator (states + ambiguity ids)
+  static constexpr int UNIT = mat_unit(S);                   // doubles per device matrix
+  static constexpr int BYTES = UNIT * 8;                     // one operator
+  static constexpr int FULL = BYTES / 1024;                  // full 1 KiB DMA rows
+  static constexpr int TAIL = (BYTES % 1024) / 16;           // lanes of the last, partial row
+  static constexpr int ROWS = FULL + (TAIL ? 1 : 0);         // VMEM instructions per operator
+  static_assert(BYTES % 16 == 0, "operator size must be a multiple of 16 bytes");
+};
+constexpr int kCodeSlotBytes = 4 * kWave;  // one dword per lane
+
+// LDS-DMA is issued through inline asm on purpose.  hipcc models __builtin_amdgcn_global_load_lds as a write to
+// LDS that any later ds_read may alias, and puts s_waitcnt vmcnt(0) in front of the next LDS read: with one dynamic LDS
+// array every operator, workspace vector and symbol would then be waited for right after the NEXT one was requested,
+// i.e. the whole L2/HBM latency exposed once per op.  An asm DMA is invisible to that bookkeeping; the ordering
+// between a DMA and the LDS reads of its data is kept by the counted waits below (wait_vm), and compiler-issued
+// vmcnt waits for its own loads only become stricter (it undercounts what is in flight).
+// One instruction moves 64 lanes x 16 B = 1 KiB; the instruction offset advances the global and the LDS address alike,
+// so consecutive 1 KiB rows need one M0 value and one address register.
+__device__ __forceinline__ uint32_t lds_addr(const uint8_t* p) {
+  // wave-uniform by construction; readfirstlane tells the compiler so (M0 is written from an SGPR)
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)(uintptr_t)(__attribute__((address_space(3))) const uint8_t*)p);
+}
+template <int NROWS>
+__device__ __forceinline__ void dma_rows16(const void* g /* per lane: row 0 address of this lane */, uint32_t lds) {
+  static_assert(NROWS >= 1 && NROWS <= 4, "instruction offset range");
+  if constexpr (NROWS == 1)
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(g) : "memory");
+  else if constexpr (NROWS == 2)
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+                 "global_load_lds_dwordx4 %1, off offset:1024" ::"s"(lds), "v"(g) : "memory");
+  else if constexpr (NROWS == 3)
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+                 "global_load_lds_dwordx4 %1, off offset:1024\n\tglobal_load_lds_dwordx4 %1, off offset:2048" ::"s"(lds), "v"(g) : "memory");
+  else
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+                 "global_load_lds_dwordx4 %1, off offset:1024\n\tglobal_load_lds_dwordx4 %1, off offset:2048\n\t"
+                 "global_load_lds_dwordx4 %1, off offset:3072" ::"s"(lds), "v"(g) : "memory");
+}
+
+// DMA the operator at `src` (global, wave-uniform) into the stage buffer `buf` (LDS, wave-uniform)
+template <int S>
+__device__ __forceinline__ void mat_dma_l(const double* src, uint32_t l, int lane);
+template <int S>
+__device__ __forceinline__ void mat_dma(const double* src, uint8_t* buf, int lane) { mat_dma_l<S>(src, lds_addr(buf), lane); }
+template <int S>
+__device__ __forceinline__ void mat_dma_l(const double* src, uint32_t l /* LDS byte address, wave-uniform */, int lane) {
+  const double* g = src + 2 * lane;
+  if constexpr (MatStage<S>::FULL > 0) dma_rows16<MatStage<S>::FULL>(g, l);
+  if constexpr (MatStage<S>::TAIL > 0) {
+    if (lane < MatStage<S>::TAIL) dma_rows16<1>(g + MatStage<S>::FULL * 128, l + MatStage<S>::FULL * 1024);
+  }
+}
+// the first BYTES bytes of an operator only (compile-time): products of a class-fused model need their NB diagonal tiles,
+// leaf ops on fully resolved alignments (the null's simulated ones) the S0 state rows of the transposed operator
+template <int BYTES>
+struct MatPart {
+  static constexpr int FULL = BYTES / 1024, TAIL = (BYTES % 1024 + 15) / 16, ROWS = FULL + (TAIL ? 1 : 0);
+};
+template <int BYTES>
+__device__ __forceinline__ void mat_dma_part(const double* src, uint32_t l, int lane) {
+  const double* g = src + 2 * lane;
+  if constexpr (MatPart<BYTES>::FULL > 0) dma_rows16<MatPart<BYTES>::FULL>(g, l);
+  if constexpr (MatPart<BYTES>::TAIL > 0) {
+    if (lane < MatPart<BYTES>::TAIL) dma_rows16<1>(g + MatPart<BYTES>::FULL * 128, l + MatPart<BYTES>::FULL * 1024);
+  }
+}
+// DMA one symbol per lane (address p is per lane) into dword `lane` of the code slot.  The symbols of the null are
+// written by this very wave (simulation) through the same address, hence the L1-bypassing cache policy (sc0 sc1).
+__device__ __forceinline__ void code_dma_l(const uint8_t* p, uint32_t l) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_ubyte %1, off sc0 sc1" ::"s"(l), "v"(p) : "memory");
+}
+__device__ __forceinline__ void code_dma(const uint8_t* p, uint8_t* slot) { code_dma_l(p, lds_addr(slot)); }
+
+// s_waitcnt vmcnt(n) needs an immediate: pick the largest supported threshold <= allowed (waiting for more is safe)
+template <int N>
+__device__ __forceinline__ void waitcnt_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
+template <int S, int VL>
+__device__ __forceinline__ void wait_vm(int allowed) {
+  // what can have been issued after X: the next operator (1 .. R DMA rows, +1 with symbols) and up to three workspace
+  // vectors (stores or loads, H instructions each).  The operator part varies per op since round 4 (products of a fused
+  // model and leaf ops of resolved alignments stage a part of the unit), so every count up to R + 1 + H is exact and the
+  // steps above are the multiples of H the vectors add; a smaller immediate than `allowed` only waits for more.
+  constexpr int R = MatStage<S>::ROWS, H = (VL + 1) / 2;
+  static_assert(R + 1 + 2 * H < 64, "vmcnt is a 6-bit counter");
+  static_assert(R + 1 <= 6, "operator rows + symbols");
+  const int v = allowed % H < 7 ? allowed % H : 6, q = allowed / H;   // (H >= 7 for every instantiation but S = 4: there v < H anyway)
+  if (q == 0) {
+    if (v <= 3) { if (v <= 1) { if (v == 0) waitcnt_vm<0>(); else waitcnt_vm<1>(); } else { if (v == 2) waitcnt_vm<2>(); else waitcnt_vm<3>(); } }
+    else { if (v == 4) waitcnt_vm<4>(); else if (v == 5) waitcnt_vm<5>(); else waitcnt_vm<6>(); }
+  } else if (q == 1) {
+    if (v <= 3) { if (v <= 1) { if (v == 0) waitcnt_vm<H>(); else waitcnt_vm<H + 1>(); } else { if (v == 2) waitcnt_vm<H + 2>(); else waitcnt_vm<H + 3>(); } }
+    else { if (v == 4) waitcnt_vm<H + 4>(); else if (v == 5) waitcnt_vm<H + 5>(); else waitcnt_vm<H + 6>(); }
+  } else if (q == 2 && 2 * H + 6 < 64) {
+    if (v <= 3) { if (v <= 1) { if (v == 0) waitcnt_vm<2 * H>(); else waitcnt_vm<2 * H + 1>(); } else { if (v == 2) waitcnt_vm<2 * H + 2>(); else waitcnt_vm<2 * H + 3>(); } }
+    else { if (v == 4) waitcnt_vm<2 * H + 4>(); else if (v == 5) waitcnt_vm<2 * H + 5>(); else waitcnt_vm<2 * H + 6>(); }
+  } else {
+    // three vectors or more in flight: whatever the counter can still tell apart (it saturates at 63)
+    constexpr int TOP = (3 * H + 4 < 64) ? 3 * H : (2 * H + 6 < 64 ? 2 * H + 6 : 2 * H);
+    waitcnt_vm<TOP>();
+  }
+}
+
+// ---- Matrix-core layout of an S-vector of the wave's 64 sites.  v_mfma_f64_4x4x4_4b computes four independent
+// D[4x4] += A[4x4] . B[4x4]; measured on gfx950 (scripts/probe_mfma_f64_4x4x4.hip): A lane = 16 k + 4 blk + i,
+// B lane = 16 k + 4 blk + n, D lane = 16 i + 4 blk + n.  With i / k = state inside a 4-state tile and (blk, n) = site inside
+// a group of 16, B and D share one layout:
+//     register v[sb * 4 + g] of lane l holds state 4 sb + (l >> 4) of site 16 g + (l & 15)
+// (sb = state tile, g = site group).  A product is one MFMA per (output tile, input tile, site group): 100 matrix
+// instructions instead of 400 DPP-broadcast FMAs, the accumulators of the four site groups are independent chains, and
+// the other wave's vector work issues while they run.  The operator tile is read from the same packed 4x4 blocks as
+// before, each lane taking the one element its A slot needs.  Elementwise work is layout-blind; sums over states
+// become a reduce-scatter over the lane bits 4 and 5 that leaves lane l with the total of site l.
+
+// reduce-scatter of per-site-group partial sums over the four state-in-tile lanes: lane l returns the total of site l.
+// v_permlane32_swap exchanges the upper half of its first operand with the lower half of its second one,
+// v_permlane16_swap does the same for the odd / even rows of 16 lanes: after swap(a, b) the sum a + b holds, in the
+// lanes that keep a's site group, own + partner's a, and in the others own + partner's b -- no LDS round trip.
+template <int NG>
+__device__ __forceinline__ double reduce_sites(const double (&p)[NG]) {
+  if constexpr (NG == 4) {
+    double p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3];
+    swap32(p0, p2);            // lanes < 32: own p0, partner's p0   | lanes >= 32: partner's p2, own p2
+    swap32(p1, p3);
+    double k0 = p0 + p2, k1 = p1 + p3;   // site groups 0 / 1 in the lower half of the wave, 2 / 3 in the upper
+    swap16(k0, k1);            // even rows: own k0, partner's k0    | odd rows: partner's k1, own k1
+    return k0 + k1;            // site group lane >> 4: lane l holds site l
+  } else if constexpr (NG == 3) {
+    // three site groups (48 sites per wave, three waves per SIMD): the four-group exchange with an empty fourth group;
+    // lanes 48 .. 63 end with nothing of interest
+    double p0 = p[0], p1 = p[1], p2 = p[2], p3 = 0.0;
+    swap32(p0, p2);
+    swap32(p1, p3);
+    double k0 = p0 + p2, k1 = p1 + p3;
+    swap16(k0, k1);
+    return k0 + k1;
+  } else if constexpr (NG == 2) {
+    // two site groups (32 sites per wave): lanes l and l ^ 16 both end with the total of site 16 (l >> 5) + (l & 15)
+    double p0 = p[0], p1 = p[1];
+    swap32(p0, p1);            // lanes < 32: own p0, partner's p0   | lanes >= 32: partner's p1, own p1
+    double k = p0 + p1, q = k;
+    swap16(k, q);              // even rows: k own, q = partner's (odd row) k   | odd rows: k = partner's, q own
+    return k + q;
+  } else {
+    // one site group (16 sites per wave, small alignments): all four lanes l, l ^ 16, l ^ 32, l ^ 48 end with the total of site l & 15
+    static_assert(NG == 1, "site groups per wave");
+    double p0 = p[0], p1 = p0;
+    swap32(p0, p1);            // p0 = the lower half's value everywhere, p1 = the upper half's
+    double k = p0 + p1, q = k;
+    swap16(k, q);
+    return k + q;
+  }
+}
+
+// step q of a product: output tile o = q / NB, input tile i = q % NB; the stored tile is (o, i), or (i, o) for the
+// transposed product.  Tiles are read three steps ahead of their use (an LDS read takes ~100+ cycles and longer under
+// load, the four MFMAs of a step 64); the empty asm pins the read in front of the MFMAs it overlaps.
+// DIAG (class-fused nucleotide model: one 4-state tile per class, the operator is block diagonal): only the NB diagonal
+// tiles are applied, step q = tile (q, q) -- the same bits as the dense product, whose other tiles are exact zeros.
+template <int S, bool TR, bool DIAG>
+__device__ __forceinline__ constexpr int mfma_tile(int q) {
+  return DIAG ? q : (TR ? (q % (S / 4)) * (S / 4) + q / (S / 4) : q);   // (DIAG: the host stores tile (q, q) at position q)
+}
+template <int S, bool TR, int NG, bool DIAG, int Q>
+__device__ __forceinline__ void mfma_steps(const uint8_t* tile0, double m0, double m1, double m2, const double (&x)[S / 4 * NG],
+                                           double (&y)[S / 4 * NG]) {
+  constexpr int NB = S / 4, NT = DIAG ? NB : NB * NB;
+  if constexpr (Q < NT) {
+    constexpr int o = DIAG ? Q : Q / NB, i = DIAG ? Q : Q % NB;
+    double m3 = 0.0;
+    if constexpr (Q + 3 < NT) {
+      m3 = *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, DIAG>(Q + 3) * 128);
+      asm volatile("" ::: "memory");
+    }
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+      y[o * NG + g] = __builtin_amdgcn_mfma_f64_4x4x4f64(m0, x[i * NG + g], (DIAG || i == 0) ? 0.0 : y[o * NG + g], 0, 0, 0);
+    mfma_steps<S, TR, NG, DIAG, Q + 1>(tile0, m1, m2, m3, x, y);
+  }
+}
+
+// y = M x (TR = false) or y = M^T x (TR = true) with M = the packed matrix staged in buf (already landed)
+template <int S, bool TR, int NG, bool DIAG>
+__device__ __forceinline__ void matvec_stage(const uint8_t* buf, int lane, const double (&x)[S / 4 * NG],
+                                             double (&y)[S / 4 * NG]) {
+  static_assert(S % 4 == 0, "state count must be a multiple of 4");
+  constexpr int NT = DIAG ? S / 4 : (S / 4) * (S / 4);
+  // element (row r, column c) of a packed tile sits at (4 r + c) * 8; the A slot of lane l is row l & 3, column l >> 4
+  // (transposed product: the transposed tile, i.e. row l >> 4, column l & 3)
+  const uint8_t* tile0 = buf + (TR ? (4 * (lane >> 4) + (lane & 3)) : (4 * (lane & 3) + (lane >> 4))) * 8;
+  mfma_steps<S, TR, NG, DIAG, 0>(tile0, *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, DIAG>(0) * 128),
+                       NT > 1 ? *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, DIAG>(1) * 128) : 0.0,
+                       NT > 2 ? *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, DIAG>(2) * 128) : 0.0, x, y);
+}
+
+// Message of a leaf edge from the transposed operator staged in buf ([z][x] = M[x][z], rows >= S: ambiguity ids):
+// lane l needs, for each site group g, element 4 sb + (l >> 4) of the row named by the symbol of site 16 g + (l & 15).
+// SET out = row, MUL out = row o in (in may be out), DOT returns sum_x in[x] * row[x] of site l (reduce_sites).
+enum { LEAF_SET = 0, LEAF_MUL = 1, LEAF_DOT = 2 };
+template <int S, int MODE, int NG>
+__device__ __forceinline__ double leaf_apply(const uint8_t* buf, const uint8_t* codes /* slot + 4 * (lane & 15) */, int lane,
+                                             const double (&in)[S / 4 * NG], double (&out)[S / 4 * NG]) {
+  constexpr int NB = S / 4;
+  double part[NG];
+  // all symbols first (one LDS round trip), then per site group the row values and their use: the reads of the next
+  // group do not depend on anything computed for the previous one
+  unsigned code[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) code[g] = codes[g * (NG == 3 ? 64 : 256 / NG)];   // one dword per LANE in the slot, group g at 64 / NG * g (three groups: as four)
+  const double* r[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const unsigned row = code[g] < (unsigned)MatStage<S>::NROW ? code[g] : (unsigned)(MatStage<S>::NROW - 1);
+    // rows are stored state-in-tile major: state 4 sb + s4 at position s4 * NB + sb (cmx_host_model.cpp)
+    r[g] = reinterpret_cast<const double*>(buf + row * (leaf_row_stride(S) * 8)) + (lane >> 4) * NB;
+  }
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    part[g] = 0.0;
+    double v[NB];
+#pragma unroll
+    for (int sb = 0; sb < NB; ++sb) v[sb] = r[g][sb];
+#pragma unroll
+    for (int sb = 0; sb < NB; ++sb) {
+      if (MODE == LEAF_SET) out[sb * NG + g] = v[sb];
+      else if (MODE == LEAF_MUL) out[sb * NG + g] = v[sb] * in[sb * NG + g];
+      else part[g] = __builtin_fma(in[sb * NG + g], v[sb], part[g]);
+    }
+  }
+  if (MODE != LEAF_DOT) return 0.0;
+  return reduce_sites<NG>(part);
+}
+
+// Row of a cherry table (cmx_walk.h): the row is named by the symbols of the cherry's two leaves, 4 * symbol(l1) + symbol(l2)
+// (fully resolved alignments only: both symbols are states of the 4-letter alphabet), the columns are a leaf row's.
+template <int S, int MODE, int NG>
+__device__ __forceinline__ double cherry_apply(const uint8_t* buf, const uint8_t* codes1, const uint8_t* codes2, int lane,
+                                               const double (&in)[S / 4 * NG], double (&out)[S / 4 * NG]) {
+  constexpr int NB = S / 4;
+  double part[NG];
+  unsigned c1[NG], c2[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) { c1[g] = codes1[g * (NG == 3 ? 64 : 256 / NG)]; c2[g] = codes2[g * (NG == 3 ? 64 : 256 / NG)]; }
+  const double* r[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const unsigned row = ((c1[g] & 3u) << 2) | (c2[g] & 3u);
+    r[g] = reinterpret_cast<const double*>(buf + row * (leaf_row_stride(S) * 8)) + (lane >> 4) * NB;
+  }
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    part[g] = 0.0;
+    double v[NB];
+#pragma unroll
+    for (int sb = 0; sb < NB; ++sb) v[sb] = r[g][sb];
+#pragma unroll
+    for (int sb = 0; sb < NB; ++sb) {
+      if (MODE == LEAF_SET) out[sb * NG + g] = v[sb];
+      else part[g] = __builtin_fma(in[sb * NG + g], v[sb], part[g]);
+    }
+  }
+  if (MODE != LEAF_DOT) return 0.0;
+  return reduce_sites<NG>(part);
+}
+
+// ------------------------------------------------------------------------------------------------ small helpers
+// Workspace vectors are stored as [S/2][64 lanes][2 doubles]: one 16-byte access per lane and row, 1 KiB per
+// wave-instruction, the same image in HBM and (for prefetched vectors) in LDS.  An odd length (16-site tasks: S = 5) ends
+// with a row of single doubles.
+// (Round 4 tried [S][64] with 64-bit accesses: hipcc puts v_mov copies and the s_waitcnt for them right behind the 128-bit
+// loads at 3 of the 5 load sites of map_kernel<20, null> -- the loaded quads do not match the registers the vector's phi
+// with the other arms of the child switch got -- and 64-bit loads remove copies and early waits alike.  Twice the VMEM
+// instructions cost what that saved: target launch 445 -> 450 ms, same box, profiles/r04_ab_workspace_64bit.log.)
+template <int S>
+__device__ __forceinline__ void load_vec(const double* p /* slice base */, double (&v)[S], int lane) {
+  p += 2 * lane;
+#pragma unroll
+  for (int i = 0; i < S / 2; ++i) {
+    const d2 t = *reinterpret_cast<const d2*>(p + (size_t)i * 2 * kWave);
+    v[2 * i] = t[0];
+    v[2 * i + 1] = t[1];
+  }
+  if constexpr (S % 2) v[S - 1] = p[(size_t)(S / 2) * 2 * kWave - lane];
+}
+template <int S>
+__device__ __forceinline__ void store_vec(double* p, const double (&v)[S], int lane) {
+  p += 2 * lane;
+#pragma unroll
+  for (int i = 0; i < S / 2; ++i) {
+    d2 t;
+    t[0] = v[2 * i];
+    t[1] = v[2 * i + 1];
+    *reinterpret_cast<d2*>(p + (size_t)i * 2 * kWave) = t;
+  }
+  if constexpr (S % 2) p[(size_t)(S / 2) * 2 * kWave - lane] = v[S - 1];
+}
+
+// asynchronous HBM -> LDS copy of one workspace vector (S/2 LDS-DMA instructions, no VGPR destination)
+template <int S>
+__device__ __forceinline__ void prefetch_vec_lds(const double* p /* slice base + 2*lane */, uint8_t* lds /* wave-uniform */) {
+  constexpr int R = S / 2;
+  const uint32_t l = lds_addr(lds);
+#pragma unroll
+  for (int i = 0; i + 4 <= R; i += 4) dma_rows16<4>(p + (size_t)i * 2 * kWave, l + i * 1024);
+  if constexpr (R % 4 != 0) dma_rows16<R % 4>(p + (size_t)(R / 4) * 4 * 2 * kWave, l + (R / 4) * 4 * 1024);
+}
+template <int S>
+__device__ __forceinline__ void read_vec_lds(const uint8_t* lds /* wave-uniform */, int lane, double (&v)[S]) {
+#pragma unroll
+  for (int i = 0; i < S / 2; ++i) {
+    const d2 t = *reinterpret_cast<const d2*>(lds + (size_t)(i * kWave + lane) * 16);
+    v[2 * i] = t[0];
+    v[2 * i + 1] = t[1];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ mapping core
+extern __shared__ __attribute__((aligned(16))) uint8_t cmx_smem[];
+
+// per-visited-node record of the tree walk (cmx_walk.h): 16 ints, one scalar load
+typedef int cmx_i16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ void sload_rec(cmx_cint p, cmx_i16& r) {
+  asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r) : "s"(p) : "memory");
+}
+
+struct ConstModel {
+  cmx_cint taxon_of, parent, nrec, msched, ldsched;
+  cmx_cdbl pi, rates, probs, cum_pi, cum_probs;
+  // tables: the cherry-table walk's operator stream (class-fused nucleotide models on resolved alignments)
+  __device__ __forceinline__ explicit ConstModel(const DevModel& m, bool tables = false)
+      : taxon_of((cmx_cint)m.taxon_of), parent((cmx_cint)m.parent), nrec((cmx_cint)m.nrec),
+        msched((cmx_cint)(tables ? m.msched_r : m.msched)), ldsched((cmx_cint)m.ldsched), pi((cmx_cdbl)m.pi), rates((cmx_cdbl)m.rates),
+        probs((cmx_cdbl)m.probs), cum_pi((cmx_cdbl)m.cum_pi), cum_probs((cmx_cdbl)m.cum_probs) {}
+};
+// Operator-stream bookkeeping of a wave (wave-uniform, lives across site blocks).  vs counts the VMEM instructions this
+// code issued and knows about (DMA rows, vector stores); an asynchronous transfer remembers vs right after its issue,
+// and "wait for X" is s_waitcnt vmcnt(vs - X_seq): VMEM completes in order, so the instructions issued after X may stay
+// in flight.  Instructions that are not counted only make the wait stricter.
+// (The phase timers, the ablation switches and the round-1 fused-simulator arrangement that produced the figures quoted in
+// DESIGN.md were stripped from this file in round 3: scripts/experiments/ablations/README.md names the tagged source.)
+struct OpState {
+  int pre_mat, pre_tx;  // op-stream entry of the NEXT op, loaded one op early (its latency hides behind the current op)
+  unsigned par;      // stage buffer / code slot of the current operator op
+  unsigned vs;       // counted VMEM instructions issued so far
+  unsigned cur_seq;  // vs right after the current operator op's operator (and symbols) were requested
+};
+
+// Device backend of the tree walk (cmx_walk.h): registers R0..R3 are S-vectors of the wave's sites in the matrix-core
+// layout.  The walk names what it wants; the operator stream (m.msched) and the load schedule (m.ldsched) -- recorded
+// from the same walk on the host and checked numerically there -- say where it is.
+// RESOLVED: every symbol of the alignment is a state (the null's simulated or supplied alignments): leaf ops then stage the
+// S0 state rows of the transposed operator only, not its ambiguity rows
+template <int S, int FUSE, int NG, bool RESOLVED>
+struct DevWalk {
+  static constexpr int VL = S / 4 * NG, kSites = 16 * NG;
+  static constexpr int kRow = NG == 3 ? 64 : kSites;   // lanes per row of the wave's per-site scratch arrays (three groups: lanes 48 .. 63 own unused columns)
+  static constexpr bool DIAG = FUSE > 1 && S / FUSE == 4;
+  static constexpr int kProductBytes = DIAG ? (S / 4) * 128 : MatStage<S>::BYTES;                      // diagonal tiles come first
+  static constexpr int kLeafBytes = RESOLVED ? (S / FUSE) * leaf_row_stride(S) * 8 : MatStage<S>::BYTES;
+#ifndef CMX_NO_CHERRY_TABLES
+#define CMX_NO_CHERRY_TABLES 0     // 1: A/B builds without the cherry tables (scripts/ab_libs.sh)
+#endif
+  static constexpr int kVecInstrs = (VL + 1) / 2;   // VMEM instructions of one workspace vector
+  static constexpr bool kCherryTables = RESOLVED && DIAG && !CMX_NO_CHERRY_TABLES;   // cmx_walk.h: cset / cdot instead of a cherry's operator ops
+  static constexpr int kCherryBytes = 16 * leaf_row_stride(S) * 8;   // a table's 16 rows (one per symbol pair)
+  static constexpr int kCherryFlag = 0x40000000;                     // stream entry: taxon of l1 | taxon of l2 << 15 | flag
+  static_assert(kCherryBytes <= MatStage<S>::BYTES, "a cherry table fits a stage buffer");
+  double R0[VL], R1[VL], R2[VL], R3[VL];
+  OpState& os;
+  const ConstModel& cm;
+  const double* pi;            // root frequencies (vector loads: lane-dependent index)
+  int nmv;
+  const double *mat_c, *mat_after;
+  double *wsM, *wsU, *pcnt;
+  const uint8_t* gcodes;
+  size_t gstride;
+  uint8_t *stage, *cslot, *cslot2;
+  uint32_t lds_stage, lds_codes, lds_codes2;
+  int lane, c, c_end;
+  double pc;
+  double Lg[FUSE];
+  int mi;
+
+  __device__ __forceinline__ DevWalk(OpState& os_, const ConstModel& cm_) : os(os_), cm(cm_) {}
+
+  // The lane index as an opaque value: address arithmetic built on it is redone at every use (a few VALU instructions)
+  // instead of being hoisted out of the walk as a dozen loop-invariant 64-bit per-lane addresses, which the register
+  // allocator then spills -- and every reload of a spilled address is a scratch load whose vmcnt(0) wait drains the
+  // DMAs in flight.
+  __device__ __forceinline__ int vlane() const {
+    int l = lane;
+    asm volatile("" : "+v"(l));
+    return l;
+  }
+  // site of the lane inside the wave's block (see map_sites_wave)
+  __device__ __forceinline__ int vsidx() const {
+    const int l = vlane();
+    return NG >= 3 ? l : (NG == 2 ? (((l >> 5) << 4) | (l & 15)) : (l & 15));
+  }
+  template <int I>
+  __device__ __forceinline__ double (&reg())[VL] {
+    if constexpr (I == 0) return R0;
+    else if constexpr (I == 1) return R1;
+    else if constexpr (I == 2) return R2;
+    else return R3;
+  }
+  __device__ __forceinline__ void begin_pass() {
+    mi = 0;
+#pragma unroll
+    for (int g = 0; g < FUSE; ++g) Lg[g] = 0.0;
+  }
+  __device__ __forceinline__ void rec(int v, int (&r)[16]) const {
+    cmx_i16 q;
+    sload_rec(cm.nrec + v * 16, q);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) r[i] = q[i];
+  }
+  // tells the compiler a register's old value is dead here (defines it without an instruction)
+  // (ONE asm statement: hipcc puts an `s_nop 0` behind every inline asm, and a wave issues one instruction per four
+  // cycles -- sixty one-element kills per visited node were sixty issue slots of the walk's chain: target launch -0.6 %, same box)
+  template <int R>
+  __device__ __forceinline__ void kill() {
+    double(&r)[VL] = reg<R>();
+    static_assert(VL == 4 || VL == 5 || VL == 8 || VL == 12 || VL == 15 || VL == 16 || VL == 20, "kill() names every element in one statement");
+    if constexpr (VL == 12)
+      asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]), "=v"(r[5]), "=v"(r[6]), "=v"(r[7]), "=v"(r[8]), "=v"(r[9]), "=v"(r[10]), "=v"(r[11]));
+    else if constexpr (VL == 15)
+      asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]), "=v"(r[5]), "=v"(r[6]), "=v"(r[7]), "=v"(r[8]), "=v"(r[9]), "=v"(r[10]), "=v"(r[11]), "=v"(r[12]), "=v"(r[13]), "=v"(r[14]));
+    else
+    if constexpr (VL == 5)
+      asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]));
+    else if constexpr (VL == 4)
+      asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]));
+    else if constexpr (VL == 8)
+      asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]), "=v"(r[5]), "=v"(r[6]), "=v"(r[7]));
+    else if constexpr (VL == 16)
+      asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]), "=v"(r[5]), "=v"(r[6]), "=v"(r[7]), "=v"(r[8]),
+                        "=v"(r[9]), "=v"(r[10]), "=v"(r[11]), "=v"(r[12]), "=v"(r[13]), "=v"(r[14]), "=v"(r[15]));
+    else
+      asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]), "=v"(r[5]), "=v"(r[6]), "=v"(r[7]), "=v"(r[8]),
+                        "=v"(r[9]), "=v"(r[10]), "=v"(r[11]), "=v"(r[12]), "=v"(r[13]), "=v"(r[14]), "=v"(r[15]), "=v"(r[16]),
+                        "=v"(r[17]), "=v"(r[18]), "=v"(r[19]));
+  }
+  // One operator op: request the operator (and symbols) of the NEXT op of the stream -- entry mi + 1, or entry 0 of the
+  // next class / next site block -- into the other buffer, then wait for this op's operator.  Returns its buffer.
+  __device__ __forceinline__ const uint8_t* op_begin(unsigned& nseq) {
+    const bool more = (mi + 1 < nmv);
+    const int emat = os.pre_mat, etx = os.pre_tx;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS reads of the other buffer are done
+    unsigned issued;
+    {
+      const double* src = (more ? mat_c : mat_after) + emat;   // element offset, premultiplied on the host
+      const uint32_t dst = lds_stage + (os.par ^ 1u) * MatStage<S>::BYTES;
+      if constexpr (kProductBytes == MatStage<S>::BYTES && kLeafBytes == MatStage<S>::BYTES) {
+        mat_dma_l<S>(src, dst, vlane());
+        issued = MatStage<S>::ROWS;
+      } else if (etx >= 0) {   // (wave-uniform: the next op is a leaf op -- or a cherry-table op)
+        if (kCherryTables && (etx & kCherryFlag)) {
+          mat_dma_part<kCherryBytes>(src, dst, vlane());
+          issued = MatPart<kCherryBytes>::ROWS;
+        } else {
+          mat_dma_part<kLeafBytes>(src, dst, vlane());
+          issued = MatPart<kLeafBytes>::ROWS;
+        }
+      } else {
+        mat_dma_part<kProductBytes>(src, dst, vlane());
+        issued = MatPart<kProductBytes>::ROWS;
+      }
+    }
+    if (etx >= 0 && (more || c + 1 < c_end)) {
+      if (kCherryTables && (etx & kCherryFlag)) {
+        code_dma_l(gcodes + (size_t)(etx & 0x7fff) * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
+        code_dma_l(gcodes + (size_t)((etx >> 15) & 0x7fff) * gstride, lds_codes2 + (os.par ^ 1u) * kCodeSlotBytes);
+        issued += 2;
+      } else {
+        code_dma_l(gcodes + (size_t)etx * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
+        issued += 1;
+      }
+    }
+    {  // entry two ops ahead; the stream carries its first two entries again after the last (no wrap test)
+      const int i2 = more ? mi + 2 : 1;
+      os.pre_mat = cm.msched[2 * i2];
+      os.pre_tx = cm.msched[2 * i2 + 1];
+    }
+    wait_vm<S, VL>((int)(os.vs - os.cur_seq + issued));
+    os.vs += issued;
+    nseq = os.vs;
+    return stage + os.par * MatStage<S>::BYTES;
+  }
+  __device__ __forceinline__ void op_end(unsigned nseq) {
+    os.par ^= 1u;
+    os.cur_seq = nseq;
+    ++mi;
+  }
+  template <int SRC, int DST, bool TR>
+  __device__ __forceinline__ void mv(int, int) {
+    unsigned nseq;
+    const uint8_t* buf = op_begin(nseq);
+    matvec_stage<S, TR, NG, DIAG>(buf, vlane(), reg<SRC>(), reg<DST>()); asm volatile("" :: "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
+    op_end(nseq);
+  }
+  template <int MODE, int SRC, int DST>
+  __device__ __forceinline__ double leaf(void) {
+    unsigned nseq;
+    const uint8_t* buf = op_begin(nseq);
+    const int vl = vlane();
+    const double tot = leaf_apply<S, MODE, NG>(buf, cslot + os.par * kCodeSlotBytes + 4 * (vl & 15), vl, reg<SRC>(), reg<DST>());
+    asm volatile("" :: "v"(tot), "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
+    op_end(nseq);
+    return tot;
+  }
+  template <int D> __device__ __forceinline__ void lset(int, int) { (void)leaf<LEAF_SET, D, D>(); }
+  template <int SRC, int D> __device__ __forceinline__ void lmul(int, int) { (void)leaf<LEAF_MUL, SRC, D>(); }
+  template <int SRC> __device__ __forceinline__ void ldot(int, int, int row) {
+    const double tot = leaf<LEAF_DOT, SRC, SRC>();
+    pcnt[(size_t)row * kRow + vsidx()] = pc * tot;
+  }
+  // cherry-table ops (cmx_walk.h): the table staged like a leaf operator, its row named by two symbols
+  template <int MODE, int SRC, int DST>
+  __device__ __forceinline__ double cherry(void) {
+    unsigned nseq;
+    const uint8_t* buf = op_begin(nseq);
+    const int vl = vlane();
+    const double tot = cherry_apply<S, MODE, NG>(buf, cslot + os.par * kCodeSlotBytes + 4 * (vl & 15), cslot2 + os.par * kCodeSlotBytes + 4 * (vl & 15),
+                                                 vl, reg<SRC>(), reg<DST>());
+    asm volatile("" :: "v"(tot), "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
+    op_end(nseq);
+    return tot;
+  }
+  template <int D> __device__ __forceinline__ void cset(int, int, int) { (void)cherry<LEAF_SET, D, D>(); }
+  template <int SRC> __device__ __forceinline__ void cdot(int, int, int, int, int row) {
+    const double tot = cherry<LEAF_DOT, SRC, SRC>();
+    pcnt[(size_t)row * kRow + vsidx()] = pc * tot;
+  }
+  // workspace vector -> register: plain global loads straight into the destination register, which the walk has
+  // declared dead (kill) long before -- in the outside pass the two sibling messages of a node are requested before the
+  // first product and first read after it, so their latency hides behind ~100 MFMAs without a landing buffer.  The
+  // loads are compiler-visible (hipcc waits for them before the first use); they are counted in vs like every VMEM
+  // instruction this code issues so that the counted waits of the operator stream let them stay in flight.
+  template <int D>
+  __device__ __forceinline__ void load(int arr, int slot) {
+    {
+      const int vl = vlane();
+      load_vec<VL>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<D>(), vl);
+    }
+    os.vs += kVecInstrs;
+  }
+  template <int SRC>
+  __device__ __forceinline__ void store(int arr, int slot) {
+    {
+      const int vl = vlane();
+      store_vec<VL>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<SRC>(), vl);
+    }
+    os.vs += kVecInstrs;
+  }
+  template <int D, int SRC> __device__ __forceinline__ void mov() {
+#pragma unroll
+    for (int x = 0; x < VL; ++x) reg<D>()[x] = reg<SRC>()[x];
+  }
+  template <int D, int SRC> __device__ __forceinline__ void mul() {
+#pragma unroll
+    for (int x = 0; x < VL; ++x) reg<D>()[x] *= reg<SRC>()[x];
+  }
+  __device__ __forceinline__ void mulup() {
+#pragma unroll
+    for (int x = 0; x < VL; ++x) { R1[x] *= R3[x]; R2[x] *= R3[x]; }
+  }
+  template <int D> __device__ __forceinline__ void setpi() {
+#pragma unroll
+    for (int sb = 0; sb < S / 4; ++sb) {
+      const double pv = pi[(4 * sb + (vlane() >> 4)) % (S / FUSE)];
+#pragma unroll
+      for (int g = 0; g < NG; ++g) reg<D>()[sb * NG + g] = pv;
+    }
+  }
+  template <int SRC> __device__ __forceinline__ void rootl() {
+    // lane l holds state 4 sb + (l >> 4) of its four sites: weight it with that state's frequency
+    if constexpr (FUSE == 1) {
+      double p_[NG];
+#pragma unroll
+      for (int g = 0; g < NG; ++g) p_[g] = 0.0;
+#pragma unroll
+      for (int sb = 0; sb < S / 4; ++sb) {
+        const double pv = pi[4 * sb + (vlane() >> 4)];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) p_[g] = __builtin_fma(pv, reg<SRC>()[sb * NG + g], p_[g]);
+      }
+      Lg[0] = reduce_sites<NG>(p_);
+    } else {   // one 4-state tile per fused class
+      const double pv = pi[vlane() >> 4];
+#pragma unroll
+      for (int sb = 0; sb < FUSE; ++sb) {
+        double p_[NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) p_[g] = pv * reg<SRC>()[sb * NG + g];
+        Lg[sb] = reduce_sites<NG>(p_);
+      }
+    }
+  }
+  __device__ __forceinline__ void dot3(int row) {
+    double p_[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) p_[g] = 0.0;
+#pragma unroll
+    for (int sb = 0; sb < S / 4; ++sb)
+#pragma unroll
+      for (int g = 0; g < NG; ++g) p_[g] = __builtin_fma(R3[sb * NG + g] * R1[sb * NG + g], R2[sb * NG + g], p_[g]);
+    pcnt[(size_t)row * kRow + vsidx()] = pc * reduce_sites<NG>(p_);
+  }
+};
+
+// Maps the 64 sites of this wave (symbol of taxon t at gcodes[t * gstride], per lane) for all rate classes: one walk of
+// the tree (cmx_walk.h) per class.  Classes [c_begin, c_end) are processed; c_after is the class of the first pass that
+// follows this call (its first operator is requested by the last operator op here).  With finalize, on return
+// cnt[(b*K+k)*64 + lane] holds the final counts n(b, site, k) and the scalars are per lane; without (class-split
+// observed mode) only part[] and L_out = sum of p_c L_c over the processed classes are produced.
+// part: [C][B*K][64] per-class joint counts (written once each, summed at the end: no read-modify-write in the loop).
+template <int S, int FUSE, int NG, bool RESOLVED>
+__device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restrict__ wsM, double* __restrict__ wsU,
+                                               double* __restrict__ part, double* __restrict__ cnt, int lds_off,
+                                               const uint8_t* __restrict__ gcodes, size_t gstride, int lane,
+                                               OpState& os, double& L_out, double& pr_out, int& rc_out,
+                                               double& norm_out, int c_begin, int c_end, int c_after, bool finalize) {
+  const DevModel& m = a.m;
+  constexpr bool kTables = DevWalk<S, FUSE, NG, RESOLVED>::kCherryTables;   // (the launcher guarantees m.msched_r then)
+  const ConstModel cm(m, kTables);
+  constexpr int kSites = 16 * NG;      // sites per wave (NG site groups of 16; an S-vector is S / 4 * NG doubles per lane)
+  constexpr int kRow = NG == 3 ? 64 : kSites;   // row length of the wave's per-site scratch arrays
+  // site of this lane inside the wave's block for per-site scalars and arrays: NG = 4: the lane itself; NG = 2: lanes
+  // l and l ^ 16 both carry site 16 (l >> 5) + (l & 15) and do the per-site work redundantly (identical values)
+  const int sidx = NG >= 3 ? lane : (NG == 2 ? (((lane >> 5) << 4) | (lane & 15)) : (lane & 15));
+  const int C = m.C, K = m.K;
+  double Lsum = 0.0, prsum = 0.0, best = -1.0;
+  int bestc = 0;
+  DevWalk<S, FUSE, NG, RESOLVED> be(os, cm);
+  be.pi = m.pi;
+  be.nmv = kTables ? m.nmv_r : m.nmv;
+  be.wsM = wsM;
+  be.wsU = wsU;
+  be.gcodes = gcodes;
+  be.gstride = gstride;
+  be.stage = cmx_smem + lds_off;                                 // two operator buffers
+  be.cslot = be.stage + 2 * MatStage<S>::BYTES;                  // two symbol slots
+  be.cslot2 = be.cslot + 2 * kCodeSlotBytes;                     // ... and two for the second leaf of a cherry-table op
+  be.lds_stage = lds_addr(be.stage);                             // wave-uniform LDS byte addresses (SGPRs)
+  be.lds_codes = lds_addr(be.cslot);
+  be.lds_codes2 = lds_addr(be.cslot2);
+  be.lane = lane;
+  be.c_end = c_end;
+  {  // symbols of op 0 if it is a leaf op (the previous site block could not request them).  Everything this wave
+     // wrote before (simulated symbols) is in L2 first; the request is not counted, so drain it here.
+    const int tx0 = cm.msched[1];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (tx0 >= 0) {
+      if (kTables && (tx0 & 0x40000000)) {
+        code_dma(gcodes + (size_t)(tx0 & 0x7fff) * gstride, be.cslot + os.par * kCodeSlotBytes);
+        code_dma(gcodes + (size_t)((tx0 >> 15) & 0x7fff) * gstride, be.cslot2 + os.par * kCodeSlotBytes);
+      } else {
+        code_dma(gcodes + (size_t)tx0 * gstride, be.cslot + os.par * kCodeSlotBytes);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  for (int c = c_begin; c < c_end; ++c) {
+    // operators of this class and of the class of the pass that follows (its first operator is requested by our last op)
+    be.mat_c = m.MAT + (size_t)c * m.MC * MatStage<S>::UNIT;
+    be.mat_after = m.MAT + (size_t)((c + 1 < c_end) ? c + 1 : c_after) * m.MC * MatStage<S>::UNIT;
+    const double pc = FUSE > 1 ? 1.0 : cm.probs[c];  // fused: the class probabilities are folded into the count operators
+    be.pc = pc;
+    be.c = c;
+    be.pcnt = part + (size_t)c * m.B * K * kRow;   // wave-uniform; the lane's site is added at each use
+    be.begin_pass();
+    walk_pass(be, m.NV, K);
+    if constexpr (FUSE == 1) {
+      const double Lc = be.Lg[0];
+      Lsum += pc * Lc;
+      prsum += cm.rates[c] * pc * Lc;
+      if (pc * Lc > best) { best = pc * Lc; bestc = c; }  // first maximum wins (getRateClassWithMaxPostProbPerSite)
+    } else {
+#pragma unroll
+      for (int g = 0; g < FUSE; ++g) {
+        const int cc = c * FUSE + g;
+        if (cc < m.C0) {
+          const double pg = cm.probs[cc];
+          Lsum += pg * be.Lg[g];
+          prsum += cm.rates[cc] * pg * be.Lg[g];
+          if (pg * be.Lg[g] > best) { best = pg * be.Lg[g]; bestc = cc; }
+        }
+      }
+    }
+  }
+  if (!finalize) {   // class-split mode: the pass's sums, its best class and that class's weight
+    L_out = Lsum;
+    pr_out = prsum;
+    rc_out = bestc;
+    norm_out = best;
+    return;
+  }
+  // ---------------- sum the classes in class order, divide by the site likelihood, norm (computeNormForSite)
+  // Rows r = b*K + k are taken sixteen at a time and classes four at a time so that 64 independent loads are in flight
+  // (this phase is pure L2 latency); the sums run in the same order as a plain (b, k, c) loop nest.
+  double nrm = 0.0, tot = 0.0;
+  const int BK = m.B * K;
+  int kk = 0;  // r % K
+  constexpr int RC = 16;
+  for (int r0 = 0; r0 < BK; r0 += RC) {
+    double v[RC];
+#pragma unroll
+    for (int u = 0; u < RC; ++u) v[u] = 0.0;
+    int c = 0;
+    for (; c + 4 <= C; c += 4) {
+      double t[4][RC];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const double* pp = part + ((size_t)(c + q) * BK + r0) * kRow + sidx;
+#pragma unroll
+        for (int u = 0; u < RC; ++u) t[q][u] = pp[(size_t)(r0 + u < BK ? u : 0) * kRow];
+      }
+#pragma unroll
+      for (int u = 0; u < RC; ++u) v[u] = (((v[u] + t[0][u]) + t[1][u]) + t[2][u]) + t[3][u];
+    }
+    for (; c < C; ++c) {
+      const double* pp = part + ((size_t)c * BK + r0) * kRow + sidx;
+#pragma unroll
+      for (int u = 0; u < RC; ++u) v[u] += pp[(size_t)(r0 + u < BK ? u : 0) * kRow];
+    }
+#pragma unroll
+    for (int u = 0; u < RC; ++u) {
+      if (r0 + u < BK) {
+        const double q = v[u] / Lsum;
+        cnt[(size_t)(r0 + u) * kRow + sidx] = q;
+        tot += q;
+        if (++kk == K) {
+          nrm = __builtin_fma(tot, tot, nrm);
+          tot = 0.0;
+          kk = 0;
+        }
+      }
+    }
+  }
+  L_out = Lsum;
+  pr_out = prsum / Lsum;
+  rc_out = bestc;
+  norm_out = sqrt(nrm);
+}
+
+// site groups of 16 per wave: 4 (64 sites, two waves per SIMD) or 2 (32 sites: the four live S-vectors take 80 registers
+// instead of 160 and three waves fit a SIMD; operators are then staged per 32 sites)
+template <int S>
+constexpr int map_lds_fixed() { return 2 * MatStage<S>::BYTES + 4 * kCodeSlotBytes; }   // stage buffers + symbol slots (two leaves)
+// + the simulator's node states (one byte per node and site) when they fit what is left of the CU's LDS share
+
+template <int S, int MODE, int FUSE, int NG = map_ng(S)>
+__global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void map_kernel(const MapArgs a) {
+  constexpr int VL = S / 4 * NG, kSites = 16 * NG;
+  constexpr int kRow = NG == 3 ? 64 : kSites;
+  const DevModel& m = a.m;
+  // the null's alignments are fully resolved: class-fused nucleotide models walk them with the cherry tables' stream
+  constexpr bool kTables = (MODE == kModeNull || MODE == kModeNullPatterns) && DevWalk<S, FUSE, NG, true>::kCherryTables;
+  const ConstModel cm(m, kTables);
+  const int lane = threadIdx.x & (kWave - 1);
+  const int sidx = NG >= 3 ? lane : (NG == 2 ? (((lane >> 5) << 4) | (lane & 15)) : (lane & 15));   // site of this lane in the wave's block
+  // wave index through readfirstlane: the compiler cannot see that threadIdx.x >> 6 is wave-uniform and would keep every
+  // per-wave base pointer below as a per-lane 64-bit VGPR pair (spilled, and reloaded from scratch in the hot loop)
+  const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int wave = blockIdx.x * kWavesPerBlock + wib;
+  const int nwaves = gridDim.x * kWavesPerBlock;
+  double* wsD = a.ws.D + (size_t)wave * m.NIW * VL * kWave;
+  double* wsU = a.ws.U + (size_t)wave * m.NIW * VL * kWave;
+  double* cnt0 = a.ws.cnt + (size_t)wave * 2 * m.B * m.K * kRow;
+  double* cnt1 = cnt0 + (size_t)m.B * m.K * kRow;
+  double* part = a.ws.part + (size_t)wave * m.C * m.B * m.K * kRow;
+  // LDS per wave: workspace prefetch buffer (S*64*8 B), two operator stage buffers, two symbol slots
+  const int lds_off = wib * a.lds_per_wave;
+  const size_t nblocks = (a.nsites + kSites - 1) / kSites;
+  // request the first op's operator (class 0, entry 0); every op then requests the next one
+  OpState os;
+  os.par = 0;
+  {
+    const int c0 = (MODE == kModeObservedSplit) ? wave % m.C : 0;   // class of this wave's first pass
+    mat_dma<S>(m.MAT + (size_t)c0 * m.MC * MatStage<S>::UNIT + cm.msched[0], cmx_smem + lds_off, lane);
+  }
+  os.vs = MatStage<S>::ROWS;
+  os.cur_seq = os.vs;
+  os.pre_mat = cm.msched[2];   // entry 1 (the stream is padded with copies of its first entries)
+  os.pre_tx = cm.msched[3];
+  if (MODE == kModeObservedSplit) {
+    const size_t ntasks = nblocks * (size_t)m.C, BK = (size_t)m.B * m.K;
+    for (size_t task = wave; task < ntasks; task += nwaves) {
+      const size_t sb = task / m.C;
+      const int c = (int)(task % m.C);
+      const size_t site = sb * kSites + sidx;
+      const size_t s = site < a.nsites ? site : a.nsites - 1;
+      double L, pr, nrm;
+      int rc;
+      map_sites_wave<S, FUSE, NG, false>(a, wsD, wsU, a.split_part + sb * m.C * BK * kSites, nullptr, lds_off, a.aln + s, a.ld, lane, os, L, pr,
+                        rc, nrm, c, c + 1, (int)((task + nwaves) % m.C), false);
+      a.split_lc[task * kSites + sidx] = L;
+      a.split_lc[(ntasks + task) * kSites + sidx] = pr;
+      a.split_lc[(2 * ntasks + task) * kSites + sidx] = nrm;          // weight of the pass's best class
+      a.split_lc[(3 * ntasks + task) * kSites + sidx] = (double)rc;   // ... and its index
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    return;
+  }
+  if constexpr (MODE == kModeNullPatterns) {
+    // lane = pattern p (numbered in first-occurrence order): the column of its first site g, walked exactly as
+    // the null mode walks a site of a pair; per pattern what observed mode writes per site
+    const size_t npat = *a.npat;
+    const size_t nb = (npat + kSites - 1) / kSites;
+    for (size_t sb = wave; sb < nb; sb += nwaves) {
+      const size_t p = sb * kSites + sidx;
+      const bool active = p < npat && sidx < kSites;
+      const size_t g = a.rep_site[active ? p : npat - 1];
+      const size_t rh = g / a.rep_ram, j = g - rh * a.rep_ram;   // rh = rep_local * 2 + h
+      double L, pr, nrm;
+      int rc;
+      // tile sb of the pattern table is this wave's count block: the class-sum epilogue writes the final counts there,
+      // once, with its own row stride (lanes past npat write their clamped copy into the last tile's spare columns)
+      double* tile = a.counts + sb * ((size_t)m.B * m.K * kRow);
+      map_sites_wave<S, FUSE, NG, true>(a, wsD, wsU, part, tile, lds_off, a.supplied + rh * (size_t)m.T * a.rep_ram + j, a.rep_ram,
+                                        lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
+      if (active) {
+        a.post_rate[p] = pr;
+        a.rate_class[p] = rc;
+        a.norm[p] = nrm;
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    return;
+  }
+  for (size_t sb = wave; sb < nblocks; sb += nwaves) {
+    const size_t site = sb * kSites + sidx;
+    const bool active = site < a.nsites && sidx < kSites;
+    const size_t s = active ? site : a.nsites - 1;
+    if (MODE == kModeObserved) {
+      double L, pr, nrm;
+      int rc;
+      map_sites_wave<S, FUSE, NG, false>(a, wsD, wsU, part, cnt0, lds_off, a.aln + s, a.ld, lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
+      if (active) {
+        if (a.logL) a.logL[s] = log(L);
+        if (a.post_rate) a.post_rate[s] = pr;
+        if (a.rate_class) a.rate_class[s] = rc;
+        if (a.norm) a.norm[s] = nrm;
+        if (a.counts)
+          for (int r = 0; r < m.B * m.K; ++r) a.counts[(size_t)r * a.ldc + s] = cnt0[(size_t)r * kRow + sidx];
+      }
+    } else {
+      // null pair q = s: replicate rep, column j; simulated-site index g_h = ((rep*2 + h)*rep_ram + j).
+      // Only the minima over the two batches leave the loop (AnalysisTools.cpp:643-652) -- fewer live registers.
+      double prmin = 0.0, nmin = 0.0;
+      int rcmin = 0;
+      for (int h = 0; h < 2; ++h) {
+        const size_t rep_local = s / a.rep_ram, j = s % a.rep_ram;
+        const uint8_t* gbase;
+        size_t gstride;
+        // the alignments were simulated by simulate_lds_kernel / simulate_blocked_kernel (cmx_null_simulate_dev) or
+        // supplied by the caller: [replicate][batch][taxon][rep_ram]
+        gbase = a.supplied + ((rep_local * 2 + h) * (size_t)m.T) * a.rep_ram + j;
+        gstride = a.rep_ram;
+        double L, pr, nrm;
+        int rc;
+        map_sites_wave<S, FUSE, NG, true>(a, wsD, wsU, part, h ? cnt1 : cnt0, lds_off, gbase, gstride, lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
+        if (h == 0) { prmin = pr; nmin = nrm; rcmin = rc; }
+        else { prmin = pr < prmin ? pr : prmin; nmin = nrm < nmin ? nrm : nmin; rcmin = rc < rcmin ? rc : rcmin; }
+      }
+      const double stat = pair_stat_strided(a.stat_kind, a.stat_param, m.B, m.K, cnt0 + sidx, (size_t)kRow, cnt1 + sidx, (size_t)kRow, a.stat_mean);
+      if (active) {
+        a.null_stat[s] = stat;
+        if (a.null_rcmin) a.null_rcmin[s] = rcmin;
+        if (a.null_prmin) a.null_prmin[s] = prmin;
+        if (a.null_nmin) a.null_nmin[s] = nmin;
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last op left an operator DMA in flight
+}
+
+// LDS per mapping wave: operator stage buffers + symbol slots (nn, mode: the node states of a simulator inside the wave
+// depended on them; not needed any more)
+int map_lds_per_wave(int S, int /*nn*/, int /*mode*/) {
+  return S == 20 ? map_lds_fixed<20>() : (S == 16 ? map_lds_fixed<16>() : map_lds_fixed<4>());
+}
+
+hipError_t launch_map(const MapArgs& a_in, int mode, int grid_blocks, hipStream_t stream) {
+  dim3 grid(grid_blocks), block(kWave * kWavesPerBlock);
+  MapArgs a = a_in;
+  a.lds_per_wave = map_lds_per_wave(a.m.S, a.m.nn, mode);
+  const size_t lds = (size_t)kWavesPerBlock * (size_t)a.lds_per_wave;
+  const int lim = 160 * 1024 / map_waves_per_simd(a.m.S);  // dynamic LDS a workgroup may use (that many workgroups per CU)
+  if ((int)lds > lim) return hipErrorInvalidValue;
+#define CMX_LAUNCH(...) /* S, MODE, FUSE [, NG] */                                                            \
+  do {                                                                                                        \
+    /* per launch: the attribute belongs to the current device (a process may hold contexts on several) */    \
+    const hipError_t ea_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&map_kernel<__VA_ARGS__>),       \
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, lim);              \
+    if (ea_ != hipSuccess) return ea_;                                                                        \
+    hipLaunchKernelGGL((map_kernel<__VA_ARGS__>), grid, block, lds, stream, a);                               \
+  } while (0)
+  // (the null instantiations of the class-fused layouts read the cherry-table walk's stream)
+  if ((mode == kModeNull || mode == kModeNullPatterns) && a.m.fuse > 1 && a.m.msched_r == nullptr) return hipErrorInvalidValue;
+  if (mode == kModeNullPatterns && (!a.rep_site || !a.npat || !a.counts || !a.post_rate || !a.rate_class || !a.norm)) return hipErrorInvalidValue;
+#define CMX_LAUNCH_MODES(S_, F_)                                            \
+  do {                                                                      \
+    if (mode == kModeObserved) CMX_LAUNCH(S_, kModeObserved, F_);           \
+    else if (mode == kModeObservedSplit) CMX_LAUNCH(S_, kModeObservedSplit, F_); \
+    else if (mode == kModeNullPatterns) CMX_LAUNCH(S_, kModeNullPatterns, F_); \
+    else CMX_LAUNCH(S_, kModeNull, F_);                                     \
+  } while (0)
+  // 16-site wave-tasks (one site group): small alignments, four times the waves
+  if (a.m.S == 20 && a.m.fuse == 1 && mode == kModeObservedSplit && a.split_sites == 16) CMX_LAUNCH(20, kModeObservedSplit, 1, 1);
+  else if (a.m.S == 20 && a.m.fuse == 1) CMX_LAUNCH_MODES(20, 1);
+  else if (a.m.S == 20 && a.m.fuse == 5) CMX_LAUNCH_MODES(20, 5);
+  else if (a.m.S == 16 && a.m.fuse == 4) CMX_LAUNCH_MODES(16, 4);
+  else if (a.m.S == 4 && a.m.fuse == 1) CMX_LAUNCH_MODES(4, 1);
+  else return hipErrorInvalidValue;
+#undef CMX_LAUNCH_MODES
+#undef CMX_LAUNCH
+  return hipGetLastError();
+}
+
+// class-split observed mode: sums the per-class results in class order exactly as map_sites_wave's own epilogue does.
+// 64 sites x 16 branch lanes per workgroup (round 4; one thread per site walked B x C dependent loads, 0.2 ms for 2 000
+// sites): thread (site, w) sums the classes of the branches b = w mod 16 and leaves each branch's total in LDS, then the
+// site's first thread adds the squares in branch order -- every sum runs in the order of the plain (b, k, c) loop nest.
+constexpr int kFinBranchLanes = 16, kFinChunk = 128;
+__global__ __launch_bounds__(64 * kFinBranchLanes) void map_finalize_kernel(const MapArgs a) {
+  const DevModel& m = a.m;
+  __shared__ double tots[kFinChunk][64];
+  const int tx = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const size_t s = (size_t)blockIdx.x * 64 + tx;
+  const bool live = s < a.nsites;
+  const size_t sc = live ? s : a.nsites - 1;
+  const size_t kS = (size_t)a.split_sites;   // sites per wave-task of the mapping kernel
+  const size_t sb = sc / kS, lane = sc % kS, BK = (size_t)m.B * m.K;
+  const size_t nblocks = (a.nsites + kS - 1) / kS, ntasks = nblocks * (size_t)m.C;
+  double Lsum = 0.0, prsum = 0.0, best = -1.0;
+  int bestc = 0;
+  for (int c = 0; c < m.C; ++c) {
+    const size_t t = sb * m.C + c;
+    Lsum += a.split_lc[t * kS + lane];
+    prsum += a.split_lc[(ntasks + t) * kS + lane];
+    const double bv = a.split_lc[(2 * ntasks + t) * kS + lane];
+    if (bv > best) { best = bv; bestc = (int)a.split_lc[(3 * ntasks + t) * kS + lane]; }
+  }
+  const double* part = a.split_part + sb * m.C * BK * kS + lane;
+  double nrm = 0.0;
+  for (int b0 = 0; b0 < m.B; b0 += kFinChunk) {
+    const int be = b0 + kFinChunk < m.B ? b0 + kFinChunk : m.B;
+    for (int b = b0 + w; b < be; b += kFinBranchLanes) {
+      double tot = 0.0;
+      for (int k = 0; k < m.K; ++k) {
+        const size_t r = (size_t)b * m.K + k;
+        double v = 0.0;
+        for (int c = 0; c < m.C; ++c) v += part[((size_t)c * BK + r) * kS];
+        v /= Lsum;
+        if (a.counts && live) a.counts[r * a.ldc + s] = v;
+        tot += v;
+      }
+      tots[b - b0][tx] = tot;
+    }
+    __syncthreads();
+    if (w == 0)
+      for (int b = b0; b < be; ++b) nrm = __builtin_fma(tots[b - b0][tx], tots[b - b0][tx], nrm);
+    __syncthreads();
+  }
+  if (w != 0 || !live) return;
+  if (a.logL) a.logL[s] = log(Lsum);
+  if (a.post_rate) a.post_rate[s] = prsum / Lsum;
+  if (a.rate_class) a.rate_class[s] = bestc;
+  if (a.norm) a.norm[s] = sqrt(nrm);
+}
+
+hipError_t launch_map_finalize(const MapArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(map_finalize_kernel, dim3((unsigned)((a.nsites + 63) / 64)), dim3(64 * kFinBranchLanes), 0, stream, a);
+  return hipGetLastError();
+}
+
+// Rows S0 .. S0+A-1 of every transposed leaf operator: sum of the rows of the states compatible with ambiguity id a
+// (what the DR likelihood's leaf initialisation does for B/Z/X/gap).  One thread per (class, leaf operator, a, x);
+// a row has `rowlen` values (= S0, or S0 * fuse for the class-fused nucleotide layout).
+__global__ void extend_leaf_rows_kernel(double* MAT, int C, int MC, int first_leaf, int nleaf, int S0, int rowlen, int A,
+                                        int unit, int stride /* doubles between rows: leaf_row_stride */, const uint32_t* __restrict__ masks) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t total = (size_t)C * nleaf * A * rowlen;
+  if (i >= total) return;
+  const int x = (int)(i % rowlen);
+  const int a = (int)((i / rowlen) % A);
+  const int l = (int)((i / ((size_t)rowlen * A)) % nleaf);
+  const int c = (int)(i / ((size_t)rowlen * A * nleaf));
+  double* M = MAT + ((size_t)c * MC + first_leaf + l) * unit;
+  const uint32_t mk = masks ? masks[S0 + a] : 0xffffffffu;
+  double v = 0.0;
+  for (int z = 0; z < S0; ++z)
+    if ((mk >> z) & 1u) v += M[(size_t)z * stride + x];
+  M[(size_t)(S0 + a) * stride + x] = v;
+}
+
+hipError_t launch_extend_leaf_rows(const DevModel& m, const uint32_t* d_masks, hipStream_t stream) {
+  const int A = max_ambig(m.S0), nleaf = m.T + m.K * m.T;
+  const size_t total = (size_t)m.C * nleaf * A * m.S;
+  hipLaunchKernelGGL(extend_leaf_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, m.MAT, m.C, m.MC,
+                     m.NI + m.NI * m.K, nleaf, m.S0, m.S, A, mat_unit(m.S), leaf_row_stride(m.S), d_masks);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ listed pairs and groups
+// pair_diag_kernel and group_stat_kernel stay in this file: they score pairs through the same per-lane statistic
+// (cmx_pairstat.h) as the null-mode walk, and the code hipcc emits for map_kernel<S, kModeNull> depends on their presence in
+// the translation unit (compiled elsewhere: same registers and scratch, 5 to 63 more instructions).
+// statistic of the pairs (j of data set 1, j of data set 2), j < n, and the minima the null file carries
+// (AnalysisTools.cpp:728-732): counts are branch-major [B*K][ld]
+__global__ void pair_diag_kernel(int kind, double param, int B, int K, const double* __restrict__ c1, size_t ld1,
+                                 const double* __restrict__ c2, size_t ld2, size_t n, const int32_t* __restrict__ rc1,
+                                 const int32_t* __restrict__ rc2, const double* __restrict__ pr1,
+                                 const double* __restrict__ pr2, const double* __restrict__ nm1,
+                                 const double* __restrict__ nm2, double* __restrict__ stat, int32_t* __restrict__ rcmin,
+                                 double* __restrict__ prmin, double* __restrict__ nmin, const double* __restrict__ mv,
+                                 const double* __restrict__ w) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  if (stat) stat[j] = w ? pair_stat_weighted(kind, param, B, K, c1 + j, ld1, c2 + j, ld2, mv, w)
+                        : pair_stat_strided(kind, param, B, K, c1 + j, ld1, c2 + j, ld2, mv);
+  if (rcmin) rcmin[j] = rc1[j] < rc2[j] ? rc1[j] : rc2[j];
+  if (prmin) prmin[j] = pr1[j] < pr2[j] ? pr1[j] : pr2[j];
+  if (nmin) nmin[j] = nm1[j] < nm2[j] ? nm1[j] : nm2[j];
+}
+
+hipError_t launch_pair_diag(int kind, double param, int B, int K, const double* c1, size_t ld1, const double* c2, size_t ld2,
+                            size_t n, const int32_t* rc1, const int32_t* rc2, const double* pr1, const double* pr2,
+                            const double* nm1, const double* nm2, double* stat, int32_t* rcmin, double* prmin, double* nmin,
+                            const double* d_mean, hipStream_t stream, const double* d_w) {
+  hipLaunchKernelGGL(pair_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, kind, param, B, K, c1, ld1,
+                     c2, ld2, n, rc1, rc2, pr1, pr2, nm1, nm2, stat, rcmin, prmin, nmin, d_mean, d_w);
+  return hipGetLastError();
+}
+
+// Statistic of a group of sites, Statistic::getValueForGroup: the smallest pairwise value over the group
+// (AbstractMinimumStatistic, CoMap/Statistics.h:121-133) or, for Compensation, the closed form of Statistics.h:267-294.
+// One wave per group; group g owns sites[offsets[g] .. offsets[g+1]) (columns of the branch-major counts).
+// w (or null): normalised branch weights; the Compensation closed form then sums w t^2 (Statistics.h:275-285) as
+// (weight_factor * t)^2, the pairs use pair_stat_weighted.
+__global__ __launch_bounds__(kWave) void group_stat_kernel(int kind, double param, int B, int K, const double* __restrict__ counts,
+                                                          size_t ld, const int64_t* __restrict__ offsets,
+                                                          const int32_t* __restrict__ sites, double* __restrict__ out,
+                                                          const double* __restrict__ mv, const double* __restrict__ w) {
+  const size_t g = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int32_t* mem = sites + offsets[g];
+  const int m = (int)(offsets[g + 1] - offsets[g]);
+  if (kind == CMX_STAT_COMPENSATION) {
+    double sumnorms = 0.0, sq2 = 0.0;
+    for (int j = 0; j < m; ++j) {
+      double q = 0.0;
+      for (int b = lane; b < B; b += kWave) {
+        double t = 0.0;
+        for (int k = 0; k < K; ++k) t += counts[((size_t)b * K + k) * ld + mem[j]];
+        if (w) t *= weight_factor(kind, w[b]);
+        q += t * t;
+      }
+      for (int off = 32; off; off >>= 1) q += __shfl_xor(q, off);
+      sumnorms += sqrt(q);
+    }
+    for (int b = lane; b < B; b += kWave) {
+      double t = 0.0;
+      for (int j = 0; j < m; ++j)
+        for (int k = 0; k < K; ++k) t += counts[((size_t)b * K + k) * ld + mem[j]];
+      if (w) t *= weight_factor(kind, w[b]);
+      sq2 += t * t;
+    }
+    for (int off = 32; off; off >>= 1) sq2 += __shfl_xor(sq2, off);
+    if (lane == 0) out[g] = 1.0 - sqrt(sq2) / sumnorms;
+    return;
+  }
+  // pairs (i, j), j < i, in the reference's order; "val < mini" with a NaN val never wins, so NaN pairs are skipped
+  double best = __builtin_inf();
+  const int npairs = m * (m - 1) / 2;
+  for (int p = lane; p < npairs; p += kWave) {
+    int i = (int)((1.0 + sqrt(1.0 + 8.0 * (double)p)) / 2.0);
+    while (i * (i - 1) / 2 > p) --i;
+    while ((i + 1) * i / 2 <= p) ++i;
+    const int j = p - i * (i - 1) / 2;
+    const double v = w ? pair_stat_weighted(kind, param, B, K, counts + mem[i], ld, counts + mem[j], ld, mv, w)
+                       : pair_stat_strided(kind, param, B, K, counts + mem[i], ld, counts + mem[j], ld, mv);
+    if (v < best) best = v;
+  }
+  for (int off = 32; off; off >>= 1) {
+    const double o = __shfl_xor(best, off);
+    if (o < best) best = o;
+  }
+  if (lane == 0) out[g] = best;
+}
+
+hipError_t launch_group_stats(int kind, double param, int B, int K, const double* d_counts, size_t ld, const int64_t* d_offsets,
+                              const int32_t* d_sites, size_t ngroups, double* d_out, const double* d_mean, hipStream_t stream,
+                              const double* d_w) {
+  if (ngroups == 0) return hipSuccess;
+  hipLaunchKernelGGL(group_stat_kernel, dim3((unsigned)ngroups), dim3(kWave), 0, stream, kind, param, B, K, d_counts, ld,
+                     d_offsets, d_sites, d_out, d_mean, d_w);
+  return hipGetLastError();
+}
+
+}  // namespace cmx

@@ -7,7 +7,7 @@
 //     of a block (no pseudo-state row for the unknowns: see below), up to 8 k-steps x 2 row tiles x 4 registers (16 k-steps
 //     = 512 taxa at one workgroup per CU), expanded
 //     once per run straight from the symbol bytes.  The k-loop reads only the second alignment's operands from LDS
-//     (2 ds_read_b128 per 4 MFMAs) -- the 8-wave kernel (cmx_kernels.hip, mica_mfma3_kernel) expanded all twelve operand
+//     (2 ds_read_b128 per 4 MFMAs) -- the 8-wave kernel (cmx_mica.hip, mica_mfma3_kernel) expanded all twelve operand
 //     tiles of every tile again, and its busiest SIMDs spent more issue cycles on that than on the matrix products;
 //   * the first operand's "one" is 8, the second's 1: an accumulator holds 8 x count, which IS the LDS address of
 //     f(count) (the table sits at LDS address 0) -- no shift and no add in front of the 64 lookups per lane;
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS > 8 ? 1 
     // (global_load_lds_dwordx4: lane l's 16 bytes land at base + 16 l, the image's order), requested in front of the first
     // half, waited for in front of the next barrier (vmcnt(0)).  Each on the other's road is slower, measured same box: the
     // plain one on DMA 2.95 -> 3.26 ms (the DMA costs the issuing wave more than a register load), the weighted one on
-    // registers 4.48 -> 4.75 ms (256 registers, 12 spilled).  Inline asm for the reason given in cmx_kernels.hip: a DMA the
+    // registers 4.48 -> 4.75 ms (256 registers, 12 spilled).  Inline asm for the reason given in cmx_map.hip: a DMA the
     // compiler knows of makes it wait for every outstanding load before the next LDS read.
     cmx_i4 braw[DMA ? 1 : SPT];
     double s2r = 0.0;
@@ -720,7 +720,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS > 8 ? 1 
 // 1 024 pairs.  Epilogue per lane: the four state rows of a first-alignment column are four consecutive accumulator
 // registers (4 lookups, 3 adds), the four states of a second-alignment column are four neighbouring lanes (two DPP adds
 // within the quad); sixteen sums per lane, 256 pairs per wave, stored as 128-byte row pieces.  The one-column-per-tile
-// kernel this replaces (cmx_kernels.hip, mica_mfma_kernel<4>) used 5 of 32 rows of every operand tile: 12.2 ms for
+// kernel this replaces up to 256 taxa (cmx_mica.hip, mica_mfma_kernel<4>) used 5 of 32 rows of every operand tile: 12.2 ms for
 // 5 000 x 5 000 columns x 256 taxa.
 constexpr int kD4I = 64, kD4J = 16;
 template <unsigned KNOWN, unsigned UNK>
@@ -973,13 +973,9 @@ bool mica4_serves(int A, int Tp, size_t n1, size_t n2) {
 
 hipError_t launch_mica4(int T, const MicaWork* wk, size_t n1, size_t n2, int intra, double* d_mi, double* d_hj, size_t ldo,
                         hipStream_t stream) {
-  static const unsigned chunk = [] {
-    const char* e = getenv("CMX_MICA4_CHUNK");
-    const unsigned c = e ? (unsigned)atoi(e) : 32u;
-    return c < 1 ? 1u : (c > kM4MaxChunk ? kM4MaxChunk : c);
-  }();
-  // two workgroups per CU at a time (254 registers): a multiple of 512
-  static const unsigned grid = [] { const char* e = getenv("CMX_MICA4_GRID"); return e ? (unsigned)atoi(e) : 1024u; }();
+  constexpr unsigned chunk = 32;     // tiles per run
+  static_assert(chunk >= 1 && chunk <= kM4MaxChunk, "one lane of a wave per tile of a run");
+  constexpr unsigned grid = 1024;    // two workgroups per CU at a time (254 registers): a multiple of 512
   const int Tp = wk->Tp;
   if (Tp <= 64) return launch_mica4_ks<2>(T, Tp, wk, n1, n2, intra, d_mi, d_hj, ldo, chunk, grid, stream);
   if (Tp <= 128) return launch_mica4_ks<4>(T, Tp, wk, n1, n2, intra, d_mi, d_hj, ldo, chunk, grid, stream);

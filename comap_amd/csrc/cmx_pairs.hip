@@ -1,0 +1,284 @@
+// pair_gram_kernel (fp64 throughout): all-pairs statistic as X.X^T on v_mfma_f64_16x16x4_f64 with per-statistic epilogues
+//   (CoMap/Statistics.h:164-329; loops CoMap/CoETools.cpp:672-692, 786-810).
+#include <algorithm>
+
+#include "cmx_device.h"
+#include "cmx_pairstat.h"
+
+namespace cmx {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------------------------------------ pair statistics
+// prep: X[b][i] (Bp rows, zero padded) and per-site scalars s (sum of squares) and r (row sum of indicators)
+//   kind 0/4: X = type-0 count - mean;  3: X = type-0 count;  1: X = per-branch total;
+//   2: X = [total >= 1];  5: X = [total >= threshold], r = sum X, s = NaN flag when a total leaves [0, 10000)
+// w (normalised branch weights, or null; kinds 0, 1, 3, 4, 7 only): X_b = weight_factor(kind, w_b) * (the value above),
+// the mean of kind 0/4 is sum w x; the caller then scores kind 0 with the Cosinus epilogue and kind 4 with the scalar
+// product's (no (B-1) factors: DESIGN A.7, weighted)
+__global__ void pair_prep_kernel(int kind, double param, const double* __restrict__ counts, size_t n, size_t ldc, int B,
+                                 int K, double* __restrict__ X, size_t ldx, int Bp, double* __restrict__ sv,
+                                 double* __restrict__ rv, const double* __restrict__ mvec /* [B] or null */, size_t blk,
+                                 const double* __restrict__ w) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  // blk > 0: the sites are `blk`-site blocks side by side (replicates of the clustering null); every block gets its own
+  // [Bp][ldx] operand so that a block's rows stay ldx * 8 bytes apart (not the whole batch's row length: 128 rows
+  // 4 MB apart thrash the TLB and land on one L2 channel)
+  if (blk) X += (i / blk) * ((size_t)Bp * ldx) - (i / blk) * blk;
+  if (w) {
+    const bool centred = kind == 0 || kind == 4;
+    double mean = 0.0;
+    if (centred)
+      for (int b = 0; b < B; ++b) mean += w[b] * (counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0));
+    double s = 0.0, r = 0.0;
+    for (int b = 0; b < B; ++b) {
+      double v;
+      if (centred) v = counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0) - mean;
+      else if (kind == 3) v = counts[(size_t)b * K * ldc + i];
+      else {
+        v = 0.0;
+        for (int k = 0; k < K; ++k) v += counts[((size_t)b * K + k) * ldc + i];
+      }
+      v *= weight_factor(kind, w[b]);
+      X[(size_t)b * ldx + i] = v;
+      s += v * v;
+      r += v;
+    }
+    for (int b = B; b < Bp; ++b) X[(size_t)b * ldx + i] = 0.0;
+    sv[i] = s;
+    rv[i] = r;
+    return;
+  }
+  double mean = 0.0;
+  if (kind == 0 || kind == 4) {   // (CorrectedCorrelation arrives as kind 0 with its mean vector in mvec)
+    for (int b = 0; b < B; ++b) mean += counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0);
+    mean /= B;
+  }
+  double s = 0.0, r = 0.0;
+  bool bad = false;
+  for (int b = 0; b < B; ++b) {
+    double v;
+    if (kind == 0 || kind == 4) v = counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0) - mean;
+    else if (kind == 3 || kind == 9) v = counts[(size_t)b * K * ldc + i];
+    else {
+      double t = 0.0;
+      for (int k = 0; k < K; ++k) t += counts[((size_t)b * K + k) * ldc + i];
+      if (kind == 1 || kind == 7) v = t;
+      else if (kind == 2) v = t >= 1.0 ? 1.0 : 0.0;
+      else {
+        v = t >= param ? 1.0 : 0.0;
+        if (!(t >= 0.0 && t < 10000.0)) bad = true;
+      }
+    }
+    X[(size_t)b * ldx + i] = v;
+    s += v * v;
+    r += v;
+  }
+  for (int b = B; b < Bp; ++b) X[(size_t)b * ldx + i] = 0.0;
+  sv[i] = bad ? __builtin_nan("") : s;
+  rv[i] = r;
+}
+
+hipError_t launch_pair_prep(int kind, double param, const double* d_counts, size_t n, size_t ldc, int B, int K,
+                            double* d_X, size_t ldx, int Bp, double* d_s, double* d_r, const double* d_mvec,
+                            hipStream_t stream, size_t blk, const double* d_w) {
+  const int block = 256;
+  hipLaunchKernelGGL(pair_prep_kernel, dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, stream, kind, param,
+                     d_counts, n, ldc, B, K, d_X, ldx, Bp, d_s, d_r, d_mvec, blk, d_w);
+  return hipGetLastError();
+}
+
+// the factor of a statistic that depends on one site only (fi, fj of pair_epilogue)
+__device__ __forceinline__ double pair_site_factor(int kind, int B, double s) {
+  if (kind == 0) return sqrt(s / (B - 1));
+  if (kind == 3 || kind == 1) return sqrt(s);
+  return 0.0;
+}
+__device__ __forceinline__ double pair_epilogue(int kind, int B, double g, double si, double sj, double ri, double rj, double fi,
+                                                double fj) {
+  switch (kind) {
+    case 0: {
+      const double cov = g / (B - 1);
+      return cov / (fi * fj);
+    }
+    case 4: return g / (B - 1);
+    case 9: return g;
+    case 3: return g / (fi * fj);
+    case 1: {
+      double s3 = si + sj + 2.0 * g;
+      if (s3 < 0.0) s3 = 0.0;
+      return 1.0 - sqrt(s3) / (fi + fj);
+    }
+    case 2: return g;
+    case 5: {
+      if (si != si || sj != sj) return __builtin_nan("");
+      const double np = B;
+      const double cell[4] = {g, ri - g, rj - g, np - ri - rj + g};
+      const double ma[4] = {ri, ri, np - ri, np - ri}, mb[4] = {rj, np - rj, rj, np - rj};
+      double s = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (cell[q] > 0) s += (cell[q] / np) * log(cell[q] * np / (ma[q] * mb[q]));
+      return s / log(2.7182818);
+    }
+  }
+  return __builtin_nan("");
+}
+
+// One wave computes a 64x64 tile of G = X1^T-rows . X2-rows on v_mfma_f64_16x16x4_f64 (A[i][k]: lane = i + 16k,
+// C[row = (lane>>4) + 4r][col = lane & 15]); operands come straight from L2 (X is a few MB), prefetched one k-step
+// ahead; 16 MFMAs per 8 operand loads.
+// Four tiles (four waves) per workgroup: single-wave workgroups made the launch dispatch-bound (262 144 of them for a
+// batch of 256 matrices of 2 000 sites ran at 0.1-0.5 resident waves per SIMD, profiles/r01_cluster_null_pmc_summary.json).
+__global__ __launch_bounds__(4 * kWave) void pair_gram_kernel(int kind, int B, int Bp, const double* __restrict__ X1,
+                                                         const double* __restrict__ s1, const double* __restrict__ r1,
+                                                         size_t n1, size_t ldx1, const double* __restrict__ X2,
+                                                         const double* __restrict__ s2, const double* __restrict__ r2,
+                                                         size_t n2, size_t ldx2, int intra, double* __restrict__ out,
+                                                         size_t ldo, size_t zsite, size_t zout, size_t zx, size_t irow0) {
+  // blockIdx.z: independent blocks of sites (clustering null: one per replicate): per-site vectors side by side
+  // (zsite apart), operands zx apart
+  X1 += blockIdx.z * zx; s1 += blockIdx.z * zsite; r1 += blockIdx.z * zsite;
+  X2 += blockIdx.z * zx; s2 += blockIdx.z * zsite; r2 += blockIdx.z * zsite;
+  out += blockIdx.z * zout;
+  const int lane = threadIdx.x & 63;
+  const size_t ti = blockIdx.y, tj = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const size_t i0 = ti * 64, j0 = tj * 64;
+  if (j0 >= n2) return;
+  const double nanv = __builtin_nan("");
+  // irow0: the rows are rows irow0 .. of the full matrix (row-block / multi-GPU processing); "below the diagonal" is
+  // then j <= irow0 + i.  A tile wholly below it is skipped (intra == 2: the caller never reads it) or NaN-filled.
+  if (intra == 2 && j0 + 63 < irow0 + i0) return;   // (clustering: mirrored distances; row blocks: only j > i is read)
+  if (intra && irow0 == 0 && tj < ti) {  // strictly below the diagonal: NaN fill (reference loop is j > i, CoETools.cpp:680)
+    for (int r = 0; r < 64; ++r) {
+      const size_t i = i0 + r, j = j0 + lane;
+      if (i < n1 && j < n2) out[i * ldo + j] = nanv;
+    }
+    return;
+  }
+  const int li = lane & 15, lk = lane >> 4;
+  size_t ia[4], jb[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    size_t i = i0 + 16 * t + li, j = j0 + 16 * t + li;
+    ia[t] = i < n1 ? i : n1 - 1;
+    jb[t] = j < n2 ? j : n2 - 1;
+  }
+  d4 acc[4][4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[p][q] = (d4){0.0, 0.0, 0.0, 0.0};
+  double a[4], b[4], an[4], bn[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    a[t] = X1[(size_t)lk * ldx1 + ia[t]];
+    b[t] = X2[(size_t)lk * ldx2 + jb[t]];
+  }
+  for (int k0 = 0; k0 < Bp; k0 += 4) {
+    const int kn = (k0 + 4 < Bp) ? k0 + 4 : k0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      an[t] = X1[(size_t)(kn + lk) * ldx1 + ia[t]];
+      bn[t] = X2[(size_t)(kn + lk) * ldx2 + jb[t]];
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[p][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[p], b[q], acc[p][q], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { a[t] = an[t]; b[t] = bn[t]; }
+  }
+  // Epilogue: the per-site factors of the statistic (a square root and a division each) are computed once per row
+  // and column of the tile, not once per pair -- the same operations on the same operands, so the values do not
+  // change, but 64 pairs per lane no longer repeat them (they were three quarters of the kernel's instructions).
+  double sjv[4], rjv[4], fj[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const size_t j = j0 + 16 * q + li;
+    sjv[q] = s2[j < n2 ? j : n2 - 1];
+    rjv[q] = r2[j < n2 ? j : n2 - 1];
+    fj[q] = pair_site_factor(kind, B, sjv[q]);
+  }
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const size_t i = i0 + 16 * p + lk + 4 * r;
+      if (i >= n1) continue;
+      const double si = s1[i], ri = r1[i];
+      const double fi = pair_site_factor(kind, B, si);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const size_t j = j0 + 16 * q + li;
+        if (j < n2) {
+          double v = pair_epilogue(kind, B, acc[p][q][r], si, sjv[q], ri, rjv[q], fi, fj[q]);
+          if (intra && j <= irow0 + i) v = nanv;
+          out[i * ldo + j] = v;
+        }
+      }
+    }
+}
+
+constexpr int kEuclidRows = 8;
+// EuclidianDistance (CoMap/Distance.h:157-171): sqrt(sum_b (tot2_b - tot1_b)^2) over the per-branch totals.  Computed from
+// the differences themselves, not from the Gram matrix: ||a||^2 + ||b||^2 - 2 a.b loses all digits for near-identical
+// vectors.  X = the totals operand of pair_prep_kernel (kind 1), [Bp][ldx]; one thread per pair, row i broadcast.
+__global__ __launch_bounds__(256) void pair_euclid_kernel(int B, const double* __restrict__ X1, size_t n1, size_t ldx1,
+                                                         const double* __restrict__ X2, size_t n2, size_t ldx2, int intra,
+                                                         double* __restrict__ out, size_t ldo, size_t zx,
+                                                         size_t zout) {
+  // one wave = kEuclidRows rows x 64 columns: the column operand is loaded once per branch and used for all rows, the
+  // row operands are wave-uniform (scalar loads); per pair the arithmetic is the same chain of FMAs in branch order
+  X1 += blockIdx.z * zx; X2 += blockIdx.z * zx; out += blockIdx.z * zout;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const size_t i0 = ((size_t)blockIdx.y * 4 + wave) * kEuclidRows, j = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  if (i0 >= n1) return;
+  if (intra == 2 && (size_t)blockIdx.x * 64 + 63 <= i0) return;   // whole tile in the lower triangle: left to the caller
+  const size_t jc = j < n2 ? j : n2 - 1;
+  double d[kEuclidRows];
+#pragma unroll
+  for (int r = 0; r < kEuclidRows; ++r) d[r] = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const double t2 = X2[(size_t)b * ldx2 + jc];
+    const double* row = X1 + (size_t)b * ldx1 + i0;
+#pragma unroll
+    for (int r = 0; r < kEuclidRows; ++r) {
+      const double t = t2 - row[i0 + r < n1 ? r : 0];
+      d[r] = __builtin_fma(t, t, d[r]);
+    }
+  }
+  if (j >= n2) return;
+#pragma unroll
+  for (int r = 0; r < kEuclidRows; ++r) {
+    const size_t i = i0 + r;
+    if (i >= n1 || (intra == 2 && j <= i)) continue;
+    out[i * ldo + j] = (!intra || j > i) ? sqrt(d[r]) : __builtin_nan("");
+  }
+}
+
+// nblk > 1: nblk independent site blocks of n1 (= n2) sites, block z at site offset z * zsite, output at z * zout
+hipError_t launch_pair_gram(int kind, int B, int Bp, const double* d_X1, const double* d_s1, const double* d_r1,
+                            size_t n1, size_t ldx1, const double* d_X2, const double* d_s2, const double* d_r2,
+                            size_t n2, size_t ldx2, int intra, double* d_out, size_t ldo, hipStream_t stream,
+                            size_t nblk, size_t zsite, size_t zout, size_t zx, size_t irow0) {
+  for (size_t z0 = 0; z0 < nblk; z0 += 65535) {     // grid.z limit
+    const unsigned gz = (unsigned)std::min<size_t>(65535, nblk - z0);
+    const size_t so = z0 * zsite, xo = z0 * zx;
+    double* out = d_out + z0 * zout;
+    if (kind == CMX_STAT_EUCLIDIAN_DISTANCE) {
+      hipLaunchKernelGGL(pair_euclid_kernel, dim3((unsigned)((n2 + 63) / 64), (unsigned)((n1 + 4 * kEuclidRows - 1) / (4 * kEuclidRows)), gz), dim3(256), 0, stream, B,
+                         d_X1 + xo, n1, ldx1, d_X2 + xo, n2, ldx2, intra, out, ldo, zx, zout);
+    } else {
+      dim3 grid((unsigned)((n2 + 255) / 256), (unsigned)((n1 + 63) / 64), gz);
+      hipLaunchKernelGGL(pair_gram_kernel, grid, dim3(4 * kWave), 0, stream, kind, B, Bp, d_X1 + xo, d_s1 + so, d_r1 + so, n1,
+                         ldx1, d_X2 + xo, d_s2 + so, d_r2 + so, n2, ldx2, intra, out, ldo, zsite, zout, zx, irow0);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace cmx

@@ -1,0 +1,454 @@
+// The sequence simulators: simulate_kernel, the null's simulate_blocked_kernel / simulate_lds_kernel (the same draws in the
+// layout the null-mode mapping kernel reads) and simulate_continuous_kernel, all on the counter RNG below.
+#include <algorithm>
+
+#include "cmx_device.h"
+#include "cmx_lanes.h"
+
+namespace cmx {
+
+// Philox2x32-10 (Random123): counter = (g_lo, g_hi[14:0] | draw << 15), key = seed_lo ^ seed_hi * 0x9E3779B9 ^ 'CMX2'.
+// Same scheme as oracle/oracle.c (DESIGN.md "RNG").  One 32 x 32 -> 64 multiply per round: the 4x32 variant (two per
+// round, 128 output bits) cost the fused null kernel 4.7 % of its time in quarter-rate integer multiplies.
+// g < 2^47, draw < 2^17.
+//   draw 0 (rate class / continuous rate) and 1 (root state): counter from the site's g, the 64 output bits give one
+//   53-bit uniform (philox_uniform);
+//   draw 2 + node (state at the lower end of a branch): the sites 2k and 2k + 1 SHARE the call with counter g >> 1 and
+//   take its first and second output word as a 32-bit uniform (philox_node_uniform): the node draws are 99 % of a
+//   simulation's calls, a category's probability is resolved to 2^-32 either way, and a thread that holds both sites of
+//   a pair (simulate_lds_kernel) makes one call for two draws.
+__device__ __forceinline__ void philox_words(uint64_t seed, uint64_t g, uint32_t draw, uint32_t& w0, uint32_t& w1) {
+  uint32_t c0 = (uint32_t)g, c1 = ((uint32_t)(g >> 32) & 0x7fffu) | (draw << 15);
+  uint32_t k = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x9E3779B9u) ^ 0x434d5832u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p = (uint64_t)0xD256D193u * (uint64_t)c0;   // one v_mad_u64_u32 instead of v_mul_hi + v_mul_lo
+    c0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p >> 32), k, c1, 0x96);   // three-way xor in one v_bitop3_b32
+    c1 = (uint32_t)p;
+    k += 0x9E3779B9u;
+  }
+  w0 = c0;
+  w1 = c1;
+}
+__device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t g, uint32_t draw) {
+  uint32_t c0, c1;
+  philox_words(seed, g, draw, c0, c1);
+  const uint64_t bits = (((uint64_t)c0 << 32) | c1) >> 11;
+  return (double)bits * (1.0 / 9007199254740992.0);
+}
+__device__ __forceinline__ double philox_node_uniform(uint64_t seed, uint64_t g, uint32_t node) {
+  uint32_t w0, w1;
+  philox_words(seed, g >> 1, 2u + node, w0, w1);
+  return (double)((g & 1) ? w1 : w0) * (1.0 / 4294967296.0);
+}
+
+template <class CumPtr>
+__device__ __forceinline__ int draw_index(double u, CumPtr cum, int n) {
+  int idx = 0;
+  for (int j = 0; j < n - 1; ++j) idx += (u >= cum[j]) ? 1 : 0;
+  return idx;
+}
+// the same index (#{ j < n-1 : u >= cum[j] }, cum non-decreasing) found from a guide table: entry k = the number of
+// leading running sums that are <= k/32, so the scan for a u in [k/32, (k+1)/32) starts there -- one or two reads of the
+// lane's own row instead of n - 1 (the rows are lane-divergent 160-byte gathers: the simulator's whole cost)
+__device__ __forceinline__ int draw_guided(double u, const double* __restrict__ cum, const uint8_t* __restrict__ guide, int n) {
+  int idx = guide[(int)(u * 32.0)];
+  while (idx < n - 1 && u >= cum[idx]) ++idx;
+  return idx;
+}
+
+// ------------------------------------------------------------------------------------------------ stand-alone simulator
+// rep_ram != 0: the n sites are blocks of rep_ram (the replicates of one side of a null, side by side in the alignment);
+// block r holds the global sites g0 + r * gstep ..  (one launch for all replicates of a side: round 3 launched per replicate)
+__global__ void simulate_kernel(const DevModel m, uint64_t seed, uint64_t g0, size_t n, uint8_t* aln, size_t ld,
+                                int32_t* classes, uint8_t* states, size_t rep_ram, uint64_t gstep) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const uint64_t g = rep_ram ? g0 + (uint64_t)(j / rep_ram) * gstep + (uint64_t)(j % rep_ram) : g0 + j;
+  const int S = m.S0;
+  const int c = draw_index(philox_uniform(seed, g, 0), m.cum_probs, m.C0);
+  if (classes) classes[j] = c;
+  states[(size_t)m.root * ld + j] = (uint8_t)draw_index(philox_uniform(seed, g, 1), m.cum_pi, S);
+  for (int node = m.nn - 2; node >= 0; --node) {
+    const int x = states[(size_t)m.parent[node] * ld + j];
+    const size_t row = ((size_t)c * m.nn + node) * S + x;
+    const int y = draw_guided(philox_node_uniform(seed, g, (uint32_t)node), m.CP + row * S, m.CPG + row * 32, S);
+    states[(size_t)node * ld + j] = (uint8_t)y;
+    const int tx = m.taxon_of[node];
+    if (tx >= 0) aln[(size_t)tx * ld + j] = (uint8_t)y;
+  }
+}
+
+hipError_t launch_simulate(const DevModel& m, uint64_t seed, uint64_t g0, size_t n, uint8_t* d_aln, size_t ld,
+                           int32_t* d_classes, uint8_t* d_states, hipStream_t stream, size_t rep_ram, uint64_t gstep) {
+  const int block = 256;
+  const int grid = (int)((n + block - 1) / block);
+  hipLaunchKernelGGL(simulate_kernel, dim3(grid), dim3(block), 0, stream, m, seed, g0, n, d_aln, ld, d_classes, d_states, rep_ram, gstep);
+  return hipGetLastError();
+}
+
+// The null's simulator since round 2 (cmx_null_intra_dev): the SAME draws as simulate_kernel / the fused loop of
+// map_kernel<S, null>, but one thread per site at full occupancy instead of 64 sites inside a mapping wave that holds
+// half a SIMD's registers.  Inside the mapping kernel the simulator was 7.8 % of a wave's time, all of it dependent L2
+// gathers that two waves per SIMD cannot hide; here thousands of waves hide them (cfg3, same box: fused 12.96 ms,
+// mapping of supplied alignments 11.98 ms + this kernel).  Nodes are drawn level by level in groups of four (m.simg),
+// four running sums per round trip of the search, exactly as the fused loop does.
+// Sites s = 0 .. of one null launch: g = g0 + s; (replicate, batch) block s / blk, column s % blk of an alignment stored
+// as [block][taxon][blk] -- the layout map_kernel<S, null> reads supplied alignments in.
+__global__ __launch_bounds__(256) void simulate_blocked_kernel(const DevModel m, uint64_t seed, uint64_t g0, size_t s0, size_t n,
+                                                               size_t blk, uint8_t* __restrict__ aln,
+                                                               uint8_t* __restrict__ states /*[nn][n]*/) {
+  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const size_t s = s0 + j;
+  const uint64_t g = g0 + s;
+  const int S0 = m.S0;
+  uint8_t* out = aln + (s / blk) * (size_t)m.T * blk + s % blk;
+  const int c = draw_index(philox_uniform(seed, g, 0), m.cum_probs, m.C0);
+  states[(size_t)m.root * n + j] = (uint8_t)draw_index(philox_uniform(seed, g, 1), m.cum_pi, S0);
+  for (int gi = 0; gi < m.nsimg; ++gi) {
+    const cmx_cint q = (cmx_cint)m.simg + gi * 16;   // [0..3] node, [4..7] its parent, [8..11] its taxon or -1
+    int x[4], idx[4];
+    double u[4];
+    size_t row[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) x[jj] = states[(size_t)q[4 + jj] * n + j];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) u[jj] = philox_node_uniform(seed, g, (uint32_t)q[jj]);
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      row[jj] = ((size_t)c * m.nn + q[jj]) * S0 + x[jj];
+      idx[jj] = m.CPG[row[jj] * 32 + (int)(u[jj] * 32.0)];
+    }
+    bool any;
+    do {
+      double cv[4][4];
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+        for (int d = 0; d < 4; ++d) cv[jj][d] = m.CP[row[jj] * S0 + idx[jj] + d];   // the table is padded by 4 sums
+      any = false;
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        bool go = true;
+        int adv = 0;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          go = go && idx[jj] + d < S0 - 1 && u[jj] >= cv[jj][d];
+          adv += go ? 1 : 0;
+        }
+        idx[jj] += adv;
+        any |= adv == 4;
+      }
+    } while (any);
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      states[(size_t)q[jj] * n + j] = (uint8_t)idx[jj];
+      if (q[8 + jj] >= 0) out[(size_t)q[8 + jj] * blk] = (uint8_t)idx[jj];
+    }
+  }
+}
+
+// The same simulator with the tables of the node being drawn in LDS.  A draw needs one guide byte and a few running
+// sums of ONE of C * S rows of its node; gathered from L2 by every thread that is ~100 bytes of traffic per draw
+// (2.5e9 draws per target launch: the gather kernel above was L2-bound, 22 ms).  Here a workgroup draws 1 024 sites
+// (four per thread), node by node, parents first: the node's C * S rows (12.8 KB for proteins) and guide bytes are copied
+// into LDS once per workgroup, double-buffered (global -> registers while the current node is drawn, registers -> LDS
+// behind a barrier), and every search runs on LDS.  Same draws, same states as simulate_kernel.
+constexpr int kSimStep = 2;        // running sums per search and LDS round trip in simulate_lds_kernel
+constexpr int kSimLdsChunks = 8;   // 16-byte pieces of a node's tables per thread (256 threads): up to 32 KiB per buffer
+template <int SPT, int NCH /* 16-byte pieces of a node's tables per thread */, int NT /* threads */, int WAVES>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void simulate_lds_kernel(const DevModel m, uint64_t seed, uint64_t g0, size_t s0, size_t n,
+                                                           size_t blk, uint8_t* __restrict__ aln, uint8_t* __restrict__ states) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t sim_smem[];
+  const int S0 = m.S0, C0 = m.C0, tid = threadIdx.x;
+  const int rowb = S0 * 8, tabb = C0 * S0 * rowb, guib = C0 * S0 * 32;       // bytes: one row of sums, all rows, all guides
+  const int bufb = (tabb + guib + 15) & ~15, nch = bufb / 16;
+  // piece q (16 bytes) of node `node`'s tables: the sums of class q / (S0 * rowb / 16) ... are contiguous per class in CP,
+  // the guide bytes per class in CPG
+  auto piece_src = [&](int node, int q) -> const cmx_i4* {
+    const int off = q * 16;
+    if (off < tabb) {
+      const int c = off / (S0 * rowb), r = off % (S0 * rowb);
+      return reinterpret_cast<const cmx_i4*>(reinterpret_cast<const uint8_t*>(m.CP + ((size_t)c * m.nn + node) * S0 * S0) + r);
+    }
+    const int o2 = off - tabb, c = o2 / (S0 * 32), r = o2 % (S0 * 32);
+    return reinterpret_cast<const cmx_i4*>(m.CPG + ((size_t)c * m.nn + node) * S0 * 32 + r);
+  };
+  size_t j[SPT];
+  uint64_t g[SPT];
+  int cls[SPT];
+  uint8_t* out[SPT];
+  bool on[SPT];
+#pragma unroll
+  for (int k = 0; k < SPT; ++k) {
+    // a thread's sites are neighbours: sites 2 q and 2 q + 1 share a Philox call for their node draws (g0 + s0 is even:
+    // launch_simulate_blocked checks it), and their states are neighbouring bytes
+    j[k] = (size_t)blockIdx.x * SPT * NT + (size_t)(SPT * tid + k);
+    on[k] = j[k] < n;
+    // (n is even: a thread's two sites are both inside or both outside; the outside ones repeat the last pair)
+    const size_t jj = on[k] ? j[k] : n - 2 + (k & 1), s = s0 + jj;
+    j[k] = jj;
+    g[k] = g0 + s;
+    out[k] = aln + (s / blk) * (size_t)m.T * blk + s % blk;
+    cls[k] = draw_index(philox_uniform(seed, g[k], 0), m.cum_probs, C0);
+    if (on[k]) states[(size_t)m.root * n + jj] = (uint8_t)draw_index(philox_uniform(seed, g[k], 1), m.cum_pi, S0);
+  }
+  // this thread's pieces of a node's tables: where they start for node 0, and the node's stride (sums: S0 * S0 doubles,
+  // guides: S0 * 32 bytes) -- loop-invariant, so that the node loop adds one 24-bit product instead of dividing and
+  // multiplying per node (quarter-rate 32-bit multiplies were a quarter of the loop's vector cycles)
+  const uint8_t* psrc[NCH];
+  unsigned pstride[NCH];
+  bool pok[NCH];
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    const int q = tid + NT * i;
+    pok[i] = q < nch && q * 16 < tabb + guib;
+    psrc[i] = reinterpret_cast<const uint8_t*>(piece_src(0, pok[i] ? q : 0));
+    pstride[i] = (unsigned)(q * 16 < tabb ? S0 * rowb : S0 * 32);
+  }
+  int crow[SPT];
+#pragma unroll
+  for (int k = 0; k < SPT; ++k) crow[k] = cls[k] * S0;
+  // tables of the first node
+  const cmx_cint ord = (cmx_cint)m.simord;
+  int buf = 0;
+  for (int q = tid; q < nch; q += NT)
+    reinterpret_cast<cmx_i4*>(sim_smem)[q] = (q * 16 < tabb + guib) ? *piece_src(ord[0], q) : cmx_i4{0, 0, 0, 0};
+  __syncthreads();
+  // nodes level by level (m.simord): the parent's state was written a whole level ago, not by the previous iteration
+  for (int it = 0; it < m.nn - 1; ++it) {
+    const int node = ord[it];
+    const bool more = it + 1 < m.nn - 1;
+    cmx_i4 nxt[NCH];
+    if (more) {
+      const int nnode = ord[it + 1];
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        if (pok[i]) nxt[i] = *reinterpret_cast<const cmx_i4*>(psrc[i] + __umul24((unsigned)nnode, pstride[i]));
+      }
+    }
+    const double* T_ = reinterpret_cast<const double*>(sim_smem + (size_t)buf * bufb);
+    const uint8_t* G_ = sim_smem + (size_t)buf * bufb + tabb;
+    const int par = ((cmx_cint)m.parent)[node], tx = ((cmx_cint)m.taxon_of)[node];   // scalar loads: the products with n and blk stay scalar
+    // the SPT searches side by side: parents' states, uniforms, guide bytes, then kSimStep running sums per search and round
+    // trip (a `while (u >= cum[idx]) ++idx` per site is a chain of dependent LDS reads under a divergent branch: 36
+    // branches and 110 scalar instructions per wave and draw).  Reads past a row's end stay inside the buffer (the guide
+    // bytes follow the sums) and are not counted.
+    int x[SPT], idx[SPT];
+    double u[SPT];
+    const double* cum[SPT];
+    // the states of a thread's two sites are neighbouring bytes at an even address (n, j[0] even): one 16-bit access
+    static_assert(SPT % 2 == 0, "sites in pairs");
+    const uint8_t* sp = states + (size_t)par * n;
+#pragma unroll
+    for (int k = 0; k < SPT; k += 2) {
+      const unsigned xx = *reinterpret_cast<const unsigned short*>(sp + (unsigned)j[k]);
+      x[k] = (int)(xx & 0xffu);
+      x[k + 1] = (int)(xx >> 8);
+    }
+#pragma unroll
+    for (int k = 0; k < SPT; k += 2) {
+      // (g[k] is even and g[k + 1] its neighbour -- or g[k] again, the clamped slot behind the last site of an odd n)
+      uint32_t w0, w1;
+      philox_words(seed, g[k] >> 1, 2u + (uint32_t)node, w0, w1);
+      u[k] = (double)((g[k] & 1) ? w1 : w0) * (1.0 / 4294967296.0);
+      if (k + 1 < SPT) {
+        u[k + 1] = (double)((g[k + 1] & 1) ? w1 : w0) * (1.0 / 4294967296.0);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < SPT; ++k) {
+      const int row = crow[k] + x[k];
+      idx[k] = G_[row * 32 + (int)(u[k] * 32.0)];
+      cum[k] = T_ + __mul24(row, S0);
+    }
+    bool any;
+    do {
+      double cv[SPT][kSimStep];
+#pragma unroll
+      for (int k = 0; k < SPT; ++k)
+#pragma unroll
+        for (int d = 0; d < kSimStep; ++d) cv[k][d] = cum[k][idx[k] + d];
+      any = false;
+#pragma unroll
+      for (int k = 0; k < SPT; ++k) {
+        bool go = true;
+        int adv = 0;
+#pragma unroll
+        for (int d = 0; d < kSimStep; ++d) {
+          go = go && idx[k] + d < S0 - 1 && u[k] >= cv[k][d];
+          adv += go ? 1 : 0;
+        }
+        idx[k] += adv;
+        any |= adv == kSimStep;
+      }
+    } while (any);
+    uint8_t* sn = states + (size_t)node * n;
+#pragma unroll
+    for (int k = 0; k < SPT; k += 2)
+      if (on[k]) {
+        *reinterpret_cast<unsigned short*>(sn + (unsigned)j[k]) = (unsigned short)(idx[k] | (idx[k + 1] << 8));
+        if (tx >= 0) {
+          if (((blk | (size_t)(uintptr_t)aln) & 1) == 0) {   // (an even rep_ram: the pair sits in one replicate block, at an even address)
+            *reinterpret_cast<unsigned short*>(out[k] + (size_t)tx * blk) = (unsigned short)(idx[k] | (idx[k + 1] << 8));
+          } else {
+            out[k][(size_t)tx * blk] = (uint8_t)idx[k];
+            out[k + 1][(size_t)tx * blk] = (uint8_t)idx[k + 1];
+          }
+        }
+      }
+    if (more) {
+      __syncthreads();   // nobody reads the other buffer any more (it held the previous node)
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        const int q = tid + NT * i;
+        if (q < nch && q * 16 < tabb + guib) reinterpret_cast<cmx_i4*>(sim_smem + (size_t)(buf ^ 1) * bufb)[q] = nxt[i];
+      }
+      __syncthreads();
+      buf ^= 1;
+    }
+  }
+}
+
+// Tables in LDS (a node's tables are copied once per 1 024 sites) from about two workgroups per CU on (cfg3's 500 000
+// sites: 0.61 ms against the gather kernel's 0.66); a workgroup's walk over the nodes with two barriers each takes
+// ~0.6 ms however few there are, so below that the gather kernel, one thread per site and no barrier, is quicker
+constexpr size_t kSimLdsMinSites = 450000;
+// nsites sites with global indices g0 .. in passes of at most `chunk` (the states scratch holds nn * chunk bytes)
+hipError_t launch_simulate_blocked(const DevModel& m, uint64_t seed, uint64_t g0, size_t nsites, size_t blk, uint8_t* d_aln,
+                                   uint8_t* d_states, size_t chunk, hipStream_t stream) {
+  // tables in LDS when a node's rows + guides fit 8 pieces per thread (every model this engine takes: S <= 20, C <= 8)
+  const size_t bufb = ((size_t)m.C0 * m.S0 * (m.S0 * 8 + 32) + 15) & ~(size_t)15;
+  // (DNA: 512-byte tables that sit in L1 / L2 anyway, and 2 barriers x 511 nodes: gathering is faster, cfg4 step 11.7 vs 13.0 ms)
+  const bool lds = m.S0 > 4 && bufb <= (size_t)kSimLdsChunks * 256 * 16;
+  for (size_t s0 = 0; s0 < nsites; s0 += chunk) {
+    const size_t n = std::min(chunk, nsites - s0);
+    // (the LDS kernel pairs the sites 2 k, 2 k + 1 of the global numbering and stores a pair's symbols as one 16-bit word at
+    // column s0 + j of its replicate block: g0, s0 and n all have to be even, not just g0 + s0)
+    if (lds && n >= kSimLdsMinSites && (g0 & 1) == 0 && (s0 & 1) == 0 && (n & 1) == 0) {
+      // 512 threads with two sites each: 56 registers = eight waves per SIMD (the kernel is bound by vector issue -- half of
+      // it Philox's quarter-rate multiplies -- once enough waves hide the LDS round trips: four sites per thread at three
+      // waves per SIMD 14.8 ms per target step, at five 11.6, this shape 10.2)
+      if (bufb <= (size_t)2 * 512 * 16)
+        hipLaunchKernelGGL((simulate_lds_kernel<2, 2, 512, 8>), dim3((unsigned)((n + 1023) / 1024)), dim3(512), 2 * bufb, stream, m, seed, g0, s0,
+                           n, blk, d_aln, d_states);
+      else
+        hipLaunchKernelGGL((simulate_lds_kernel<4, kSimLdsChunks, 256, 4>), dim3((unsigned)((n + 1023) / 1024)), dim3(256), 2 * bufb, stream, m,
+                           seed, g0, s0, n, blk, d_aln, d_states);
+    }
+    else
+      hipLaunchKernelGGL(simulate_blocked_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, m, seed, g0, s0, n, blk,
+                         d_aln, d_states);
+  }
+  return hipGetLastError();
+}
+
+// ---- simulations.continuous = yes (CoMap/CoMap.cpp:146, 213: NonHomogeneousSequenceSimulator::enableContinuousRates).
+// Every site draws its own rate from the CONTINUOUS Gamma(alpha, beta = alpha) distribution (Invariant(Gamma): rate 0 with
+// probability p_inv, else the Gamma draw divided by 1 - p_inv) and every branch uses exp(Q r t) of that very rate: the
+// row of the parent's state is rebuilt from the generator's eigensystem at each node (S exponentials + S^2 multiply-adds)
+// -- there is no table to look up.  Same counter RNG and draw numbering as the discrete simulator (draw 0 = rate).
+
+__host__ __device__ inline void cmx_gamma_pq(double a, double x, double* p, double* q) {
+  /* regularised incomplete gamma, lower P and upper Q = 1 - P, each from the expansion that gives it without
+   * cancellation: series for x < a + 1 (P), Lentz continued fraction otherwise (Q) */
+  if (x <= 0.0) { *p = 0.0; *q = 1.0; return; }
+  const double pre = exp(-x + a * log(x) - lgamma(a));
+  if (x < a + 1.0) {
+    double term = 1.0 / a, sum = term;
+    for (int n = 1; n < 1000; ++n) {
+      term *= x / (a + n);
+      sum += term;
+      if (fabs(term) < fabs(sum) * 1e-17) break;
+    }
+    *p = sum * pre;
+    *q = 1.0 - *p;
+    return;
+  }
+  const double tiny = 1e-300;
+  double b = x + 1.0 - a, c = 1.0 / tiny, d = 1.0 / b, h = d;
+  for (int i = 1; i < 1000; ++i) {
+    const double an = -(double)i * ((double)i - a);
+    b += 2.0;
+    d = an * d + b;
+    if (fabs(d) < tiny) d = tiny;
+    c = b + an / c;
+    if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    h *= del;
+    if (fabs(del - 1.0) < 1e-16) break;
+  }
+  *q = pre * h;
+  *p = 1.0 - *q;
+}
+/* "x is below the u-quantile": decided on the tail that carries the information (P < u, or Q > 1 - u for u > 1/2) */
+__host__ __device__ inline int cmx_gamma_below(double a, double x, double u) {
+  double p, q;
+  cmx_gamma_pq(a, x, &p, &q);
+  return u <= 0.5 ? p < u : q > 1.0 - u;
+}
+/* quantile of Gamma(shape a, scale 1): bracket [lo, 2 lo] by doubling / halving from 1, then 110 bisection steps
+ * (deterministic, no tolerance test) */
+__host__ __device__ inline double cmx_gamma_quantile(double a, double u) {
+  if (u <= 0.0) return 0.0;
+  double lo = 1.0, hi;
+  if (cmx_gamma_below(a, lo, u)) {
+    for (int i = 0; i < 1100 && cmx_gamma_below(a, 2.0 * lo, u); ++i) lo *= 2.0;
+    hi = 2.0 * lo;
+  } else {
+    hi = lo;
+    lo = 0.5 * hi;
+    for (int i = 0; i < 1070 && !cmx_gamma_below(a, lo, u); ++i) { hi = lo; lo *= 0.5; }
+  }
+  for (int i = 0; i < 110; ++i) {
+    const double mid = 0.5 * (lo + hi);
+    if (cmx_gamma_below(a, mid, u)) lo = mid; else hi = mid;
+  }
+  return 0.5 * (lo + hi);
+}
+
+__global__ void simulate_continuous_kernel(const DevModel m, uint64_t seed, uint64_t g0, size_t n, double alpha, double p_inv,
+                                           uint8_t* aln, size_t ld, double* rates, uint8_t* states) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const uint64_t g = g0 + j;
+  const int S = m.S0;
+  const double u0 = philox_uniform(seed, g, 0);
+  double r = 0.0;
+  if (u0 >= p_inv) r = cmx_gamma_quantile(alpha, (u0 - p_inv) / (1.0 - p_inv)) / alpha / (1.0 - p_inv);
+  if (rates) rates[j] = r;
+  states[(size_t)m.root * ld + j] = (uint8_t)draw_index(philox_uniform(seed, g, 1), m.cum_pi, S);
+  for (int node = m.nn - 2; node >= 0; --node) {
+    const int x = states[(size_t)m.parent[node] * ld + j];
+    const double u = philox_node_uniform(seed, g, (uint32_t)node);
+    const size_t mo = (size_t)m.model_of[node];
+    const double *V = m.eigV + mo * S * S + (size_t)x * S, *Vi = m.eigVi + mo * S * S, *lam = m.eigLam + mo * S;
+    const double rt = r * m.blen[node];
+    double w[kSimContinuousMaxStates];    // V[x][k] exp(lambda_k r t), S <= kPlainStates entries (dynamically indexed: private memory)
+    for (int k = 0; k < S; ++k) w[k] = V[k] * exp(lam[k] * rt);
+    // index = #{ y < S-1 : u >= cum_y } with cum the running sum of the row P(x, .) -- the discrete simulator's rule
+    int idx = 0;
+    double cum = 0.0;
+    for (int y = 0; y < S - 1; ++y) {
+      double pxy = 0.0;
+      for (int k = 0; k < S; ++k) pxy += w[k] * Vi[(size_t)k * S + y];
+      cum += pxy;
+      idx += (u >= cum) ? 1 : 0;
+    }
+    states[(size_t)node * ld + j] = (uint8_t)idx;
+    const int tx = m.taxon_of[node];
+    if (tx >= 0) aln[(size_t)tx * ld + j] = (uint8_t)idx;
+  }
+}
+
+hipError_t launch_simulate_continuous(const DevModel& m, uint64_t seed, uint64_t g0, size_t n, double alpha, double p_inv,
+                                      uint8_t* d_aln, size_t ld, double* d_rates, uint8_t* d_states, hipStream_t stream) {
+  const int block = 128;
+  hipLaunchKernelGGL(simulate_continuous_kernel, dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, stream, m, seed, g0, n,
+                     alpha, p_inv, d_aln, ld, d_rates, d_states);
+  return hipGetLastError();
+}
+
+}  // namespace cmx

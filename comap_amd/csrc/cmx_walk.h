@@ -4,7 +4,7 @@
 //   * host, Numeric backend   (cmx_host_model.cpp): runs the pass in plain doubles from the device layouts, consuming
 //     that stream exactly as the device does, and is compared with a direct pruning computation before a context is
 //     accepted (verify_walk);
-//   * device backend          (cmx_kernels.hip: map_sites_wave): registers are S-vectors of the wave's 64 sites.
+//   * device backend          (cmx_map.hip: map_sites_wave)    : registers are S-vectors of the wave's 64 sites.
 // So the control flow that decides WHICH operator every product / leaf gather applies exists in one place.
 //
 // Algorithm ("message scheme").  M_n = P_n D_n is the message a node sends up its branch, D_n the product

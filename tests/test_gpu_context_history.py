@@ -20,7 +20,7 @@ test_gpu_mi_bounds.py, test_gpu_ancestral.py, test_gpu_codon_alphabets.py); no t
 
 Ops that need not be byte-reproducible (NOT_BYTE_REPRODUCIBLE): mi_columns_unknowns_* and mi_pairs_unknowns_*.
 mi_columns_kernel / mi_pairs_kernel add the fractional weights of ambiguous letters with floating-point atomicAdd
-(comap_amd/csrc/cmx_kernels.hip, `atomicAdd(&joint[...], w)` in both kernels), so the order of the additions, and with
+(comap_amd/csrc/cmx_mica.hip, `atomicAdd(&joint[...], w)` in both kernels), so the order of the additions, and with
 it the last bits, may differ from run to run.  These ops stay in every sequence and are compared with the oracle, at
 the tolerance of test_mi_columns_matches_oracle_with_ambiguity, at every step instead.  Every other op must be equal
 byte for byte on two fresh contexts (first test) -- a difference there is a finding, not an exception.
