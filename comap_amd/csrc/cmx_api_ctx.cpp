@@ -254,14 +254,6 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
     }
     UP(nrec); UP(simg); UP(simord);
     d.nsimg = (int)(h.simg.size() / 16);
-    {  // two zero entries (not prefetchable) after the last load: the kernel reads one entry ahead without a bounds test
-      std::vector<int> ld(h.ldsched);
-      ld.push_back(0);
-      ld.push_back(0);
-      const int* dld = nullptr;
-      CMX_TRY(upload(ctx, ld, &dld));
-      d.ldsched = dld;
-    }
     UP(eigV); UP(eigVi); UP(eigLam); UP(model_of); UP(blen);
     UP(CP); UP(CPG); UP(pi); UP(rates); UP(probs); UP(cum_pi); UP(cum_probs);
 #undef UP
@@ -279,11 +271,8 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
     auto alloc_ws = [&](Workspace* ws, size_t w, size_t* bytes) -> cmx_status {
       const size_t ks = (size_t)map_sites_per_wave(h.dS);   // sites per mapping wave
       const size_t bD = w * h.NIW * h.dS * ks * sizeof(double);
-      // (rows of the per-site scratch arrays: the sites of a wave, or 64 lanes for the 48-site experiment layout)
-      const size_t kr = map_ng(h.dS) == 3 ? 64 : ks;
-      const size_t bC = w * 2 * h.B * h.K * kr * sizeof(double);
-      const size_t bP = w * h.dC * h.B * h.K * kr * sizeof(double);
-      const size_t bS = w * h.nn * ks, bA = w * h.T * ks;
+      const size_t bC = w * 2 * h.B * h.K * ks * sizeof(double);
+      const size_t bP = w * h.dC * h.B * h.K * ks * sizeof(double);
       const bool g = guard_on();
       auto one = [&](const char* nm, void** p, size_t bytes) -> cmx_status {
         HIP_TRY(ctx, hipMalloc(p, bytes + (g ? kGuardBytes : 0)));
@@ -297,10 +286,8 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
       CMX_TRY(one("U", (void**)&ws->U, bD));
       CMX_TRY(one("cnt", (void**)&ws->cnt, bC));
       CMX_TRY(one("part", (void**)&ws->part, bP));
-      CMX_TRY(one("st", (void**)&ws->st, bS));
-      CMX_TRY(one("aln", (void**)&ws->aln, bA));
       ws->waves = (int)w;
-      *bytes += 2 * bD + bC + bP + bS + bA;
+      *bytes += 2 * bD + bC + bP;
       return CMX_OK;
     };
     ctx->ws_bytes = 0;
@@ -326,8 +313,6 @@ void cmx_ctx_destroy(cmx_ctx* ctx) {
     if (ws->U) (void)hipFree(ws->U);
     if (ws->cnt) (void)hipFree(ws->cnt);
     if (ws->part) (void)hipFree(ws->part);
-    if (ws->st) (void)hipFree(ws->st);
-    if (ws->aln) (void)hipFree(ws->aln);
   }
   delete ctx;
 }

@@ -117,12 +117,12 @@ cmx_status map_sites_impl(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, siz
   size_t ks = (size_t)map_sites_per_wave(ctx->hm.dS);
   size_t nblocks = (nsites + ks - 1) / ks;
   const size_t obs_waves = (size_t)max_blocks * kWavesPerBlock;
-  if (nblocks * (size_t)ctx->hm.dC <= obs_waves && ctx->hm.dC > 1 && map_ng(ctx->hm.dS) != 3) {   // (48-site experiment builds: no class split)
+  if (nblocks * (size_t)ctx->hm.dC <= obs_waves && ctx->hm.dC > 1) {
     // small alignment: one (site block, class) per wave, classes summed by a second kernel (same arithmetic order)
     // Proteins, when even that leaves most of the chip idle: 16-site blocks (one site group per wave) -- four times the
     // tasks, a quarter of the matrix work per operator op, and a wave's slices of the workspaces are a quarter as large,
     // so 4 * obs_waves of them fit the same allocation
-    if (ctx->hm.dS == 20 && ctx->hm.fuse == 1 && ks == 64 && ((nsites + 15) / 16) * (size_t)ctx->hm.dC <= 4 * obs_waves) {
+    if (ctx->hm.dS == 20 && ctx->hm.fuse == 1 && ((nsites + 15) / 16) * (size_t)ctx->hm.dC <= 4 * obs_waves) {
       ks = 16;
       nblocks = (nsites + ks - 1) / ks;
     }

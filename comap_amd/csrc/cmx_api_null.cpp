@@ -140,9 +140,9 @@ static cmx_status null_patterns_dev(cmx_ctx* ctx, MapArgs a, size_t nrep, size_t
   CMX_TRY(scratch(ctx, "pat_incl", cap, &b.incl));
   CMX_TRY(scratch(ctx, "pat_of", cap, &b.pat_of));
   CMX_TRY(scratch(ctx, "pat_site", cap, &b.rep_site));
-  // tile-major: a mapping wave's ks patterns are one [B*K][kr] block, the last tile whole (its spare columns are written)
-  const size_t ks = (size_t)map_sites_per_wave(h.dS), kr = map_ng(h.dS) == 3 ? 64 : ks, ntiles = (cap + ks - 1) / ks;
-  CMX_TRY(scratch(ctx, "pat_cnt", BK * kr * ntiles, &cnt));
+  // tile-major: a mapping wave's ks patterns are one [B*K][ks] block, the last tile whole (its spare columns are written)
+  const size_t ks = (size_t)map_sites_per_wave(h.dS), ntiles = (cap + ks - 1) / ks;
+  CMX_TRY(scratch(ctx, "pat_cnt", BK * ks * ntiles, &cnt));
   // Correlation / Covariance: the pairs are scored in one pass from per-pattern moments (pair_stat_moments)
   const bool moments = a.stat_kind == CMX_STAT_CORRELATION || a.stat_kind == CMX_STAT_COVARIANCE;
   double *pmean = nullptr, *pss = nullptr;
@@ -176,8 +176,8 @@ static cmx_status null_patterns_dev(cmx_ctx* ctx, MapArgs a, size_t nrep, size_t
     const size_t blocks_needed = ((n + ks - 1) / ks + kWavesPerBlock - 1) / kWavesPerBlock;
     HIP_TRY(ctx, launch_map(a, kModeNullPatterns, (int)std::min<size_t>(blocks_needed, (size_t)ctx->grid_blocks), (hipStream_t)stream));
     if (moments)
-      HIP_TRY(ctx, launch_null_pattern_moments(h.B, h.K, cnt, (int)ks, (int)kr, a.npat, n, pmean, pss, (hipStream_t)stream));
-    HIP_TRY(ctx, launch_null_pattern_pairs(a.stat_kind, a.stat_param, h.B, h.K, cnt, (int)ks, (int)kr, pmean, pss, pr, rc, nm, b.pat_of, rep_ram, n / 2,
+      HIP_TRY(ctx, launch_null_pattern_moments(h.B, h.K, cnt, (int)ks, (int)ks, a.npat, n, pmean, pss, (hipStream_t)stream));
+    HIP_TRY(ctx, launch_null_pattern_pairs(a.stat_kind, a.stat_param, h.B, h.K, cnt, (int)ks, (int)ks, pmean, pss, pr, rc, nm, b.pat_of, rep_ram, n / 2,
                                            a.stat_mean, o.stat, o.rcmin, o.prmin, o.nmin, (hipStream_t)stream));
   }
   return CMX_OK;
@@ -229,7 +229,7 @@ cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint
   Stat sk;
   CMX_TRY(resolve_stat(ctx, kind, params, stream, &sk));
   a.stat_kind = kind; a.stat_param = sk.param; a.stat_mean = sk.d_mean;
-  a.seed = seed; a.rep_begin = rep_begin; a.rep_ram = rep_ram; a.supplied = d_supplied;
+  a.rep_ram = rep_ram; a.supplied = d_supplied;
   a.null_stat = d_stat; a.null_rcmin = d_rcmin; a.null_prmin = d_prmin; a.null_nmin = d_nmin;
   const size_t reps_per_pass = null_pattern_reps(ctx, rep_ram);
   if (reps_per_pass) return null_patterns_dev(ctx, a, rep_end - rep_begin, reps_per_pass, stream);

@@ -23,10 +23,7 @@ namespace cmx {
 
 namespace {
 
-#ifndef HC_THREADS
-#define HC_THREADS 512
-#endif
-constexpr int kHcThreads = HC_THREADS;
+constexpr int kHcThreads = 512;
 constexpr int kHcWaves = kHcThreads / kWave;
 constexpr int kHcMaxPerThread = (CMX_CLUSTER_MAX_SITES + kHcThreads - 1) / kHcThreads;   // columns of a row per thread
 constexpr int kHcSeg = 512;       // columns of one rescan unit: 8 loads in flight per lane

@@ -23,20 +23,15 @@ constexpr int kSimContinuousMaxStates = 64;
 // (42 / 34 dwords) moves the period to 32 rows: no two rows of an operator share a bank.
 constexpr int leaf_row_stride(int S) { return S + 1; }             // doubles per row of a transposed leaf operator
 constexpr int mat_unit(int S) { return (S + max_ambig(S)) * leaf_row_stride(S); }   // doubles per device matrix
-#ifndef CMX_WAVES_PER_SIMD
-#define CMX_WAVES_PER_SIMD 2       // resident mapping waves per SIMD for 20 states (1: 512-register budget, 2: 256)
-#endif
-#ifndef CMX_WAVES_PER_SIMD_S4
-#define CMX_WAVES_PER_SIMD_S4 3    // nucleotide vectors are 8 registers: the kernel is latency-bound, more waves help
-#endif
-#ifndef CMX_NG
-#define CMX_NG 4                   // site groups of 16 per mapping wave for >= 16 device states: 4 (64 sites) or 2 (32 sites)
-#endif
-constexpr int map_ng(int S) { return S >= 16 ? CMX_NG : 4; }
+// A mapping wave walks four site groups of 16: lane = site.  (The 16-site class-split launch of small alignments is the one
+// other shape, one site group; fewer groups per wave with more waves per SIMD were measured and rejected)
+constexpr int map_ng(int) { return 4; }
 constexpr int map_sites_per_wave(int S) { return 16 * map_ng(S); }
+// Resident mapping waves per SIMD: nucleotide vectors are 8 registers, the kernel is latency-bound and more waves help;
+// the other layouts need the 256-register budget of two waves.
 // (three waves per SIMD were tried for the 16-state class-fused nucleotide layout -- vectors of 32 registers: at 168
 // registers the kernel spills 213 of them and the cfg 4 launch went from 7.7 to 10.7 ms)
-constexpr int map_waves_per_simd(int S) { return S == 4 ? CMX_WAVES_PER_SIMD_S4 : ((map_ng(S) == 2 || map_ng(S) == 3) ? 3 : CMX_WAVES_PER_SIMD); }
+constexpr int map_waves_per_simd(int S) { return S == 4 ? 3 : 2; }
 
 // Device-resident model + tree program.  All pointers are device pointers.
 struct DevModel {
@@ -58,7 +53,7 @@ struct DevModel {
   int nmv;                 // number of pairs
   const int* msched_r;     // the cherry-table walk's stream (class-fused nucleotide models, resolved alignments: the null), or null
   int nmv_r;
-  const int* ldsched;      // [nloads + 2] workspace loads: bit 31 prefetchable, bit 30 array (0 M, 1 U), low 24 bits slot
+  const int* ldsched;      // unused (null): the load schedule stays on the host; the slot keeps the kernel-argument layout
   // simulator: running sums of the rows of P, [C][nn][S(x)][S], and a 32-entry guide table per row (see draw_guided)
   const double* CP;
   const uint8_t* CPG;      // [C][nn][S(x)][32]
@@ -88,8 +83,8 @@ struct Workspace {
   double* U;        // [waves][NIW][S][64]  outside messages arriving at internal nodes
   double* cnt;      // [waves][2][B*K][64]  final counts of the wave's sites (two batches for the null)
   double* part;     // [waves][C][B*K][64]  per-class joint counts, summed in class order at the end
-  uint8_t* st;      // [waves][nn][64]      simulated states
-  uint8_t* aln;     // [waves][T][64]       simulated leaf states
+  uint8_t* st;      // unused (null): no wave simulates its own sites any more; the slot keeps the kernel-argument layout
+  uint8_t* aln;     // unused (null): as st
   int waves;
 };
 
@@ -121,8 +116,9 @@ struct MapArgs {
   int stat_kind;
   double stat_param;       // discrete-MI threshold
   const double* stat_mean; // CorrectedCorrelation: [2][B] mean vectors of the two operands (device), else null
-  uint64_t seed;
-  size_t rep_begin, rep_ram;
+  uint64_t seed;           // unused: the alignments are simulated before the launch; the slot keeps the kernel-argument layout
+  size_t rep_begin;        // unused: as seed
+  size_t rep_ram;
   const uint8_t* supplied; // [nrep][2][T][rep_ram] or null
   double* null_stat;       // [nsites]
   int32_t* null_rcmin;
@@ -132,12 +128,15 @@ struct MapArgs {
   // of every pattern, and the number of patterns (device; the grid is sized for every site its own pattern)
   const uint32_t* rep_site;
   const uint32_t* npat;
-  // ... counts is then the tile-major pattern table: tile p / kSites is [B*K][kRow] doubles, pattern p its column p % kSites
-  // (kSites patterns per wave, kRow the wave's row stride: the block map_sites_wave's epilogue writes)
+  // ... counts is then the tile-major pattern table: tile p / kSites is [B*K][kSites] doubles, pattern p its column p % kSites
+  // (kSites patterns per wave: the block map_sites_wave's epilogue writes)
 };
+// The code hipcc emits for the mapping kernels depends on where these structures' fields sit in the kernel argument
+// (DESIGN.md 4.5.4): an unused field keeps its slot.
+static_assert(sizeof(DevModel) == 256 && sizeof(Workspace) == 56 && sizeof(MapArgs) == 512 && offsetof(MapArgs, rep_site) == 496,
+              "kernel-argument layout of the mapping kernels");
 
 // launchers by source file (cmx_map.hip; pair_diag and group_stats are there for map_kernel's sake)
-int map_lds_per_wave(int S, int nn, int mode);
 hipError_t launch_map(const MapArgs& a, int mode, int grid_blocks, hipStream_t stream);
 hipError_t launch_map_finalize(const MapArgs& a, hipStream_t stream);
 // fills rows S.. of every leaf operator from d_masks[S .. S+max_ambig(S)) (null: every state compatible)

@@ -1,8 +1,9 @@
 // The mapping walk: hand-written gfx950 (CDNA4) kernels.  fp64 throughout (the reference computes in double and its
 // DR likelihood has no per-node rescaling, CoMap/CoETools.cpp:244).
 //
-// map_kernel<S, MODE>
-//   one wavefront = 64 sites (lane == site) x all rate classes in turn; four independent waves per workgroup.
+// map_kernel<S, MODE, FUSE, NG>
+//   one wavefront = 64 sites (lane == site, NG = 4 site groups of 16) x all rate classes in turn; four independent waves
+//   per workgroup.  (NG = 1: the 16-site wave-tasks of the class-split launch for small alignments.)
 //   Replaces, per site: DRHomogeneousTreeLikelihood::initialize (post-order "inside" pass), the pre-order
 //   "outside" pass, LegacySubstitutionMappingTools::computeSubstitutionVectors and computeNormForSite
 //   (call sites CoMap/CoETools.cpp:397, CoMap/AnalysisTools.cpp:592-612; algorithm SURVEY.md A.2/A.3/A.6).
@@ -12,11 +13,12 @@
 //   a layout where lane = (state inside a 4-state tile, site of a group of 16).
 //   Matrices are packed host-side in 4x4 blocks so that one copy serves both P.d (inside) and P^T.u (outside).
 //   Inside vectors / outside messages that must survive go to a per-wave HBM workspace as [S/2][lane][2]: every
-//   access is one fully coalesced 1 KiB row; loads are prefetched into LDS by DMA under a host-built schedule.
+//   access is one fully coalesced 1 KiB row; they come back by plain global loads into registers the walk has declared
+//   dead long before (DevWalk::load).  LDS holds, per wave, two operator stage buffers and four symbol slots.
 //   DESIGN.md 4.1 has the full description and the measurements.
 //   MODE == kModeNull: map (x2 batches) -> per-pair statistic of AnalysisTools::getNullDistributionIntraDR
 //   (CoMap/AnalysisTools.cpp:587-653) per wave, on alignments simulated beforehand by simulate_lds_kernel /
-//   simulate_blocked_kernel at full occupancy (round 1 simulated inside the mapping wave).
+//   simulate_blocked_kernel at full occupancy.
 //   MODE == kModeNullPatterns: the same walk over the null's distinct columns, one lane per pattern; the pairs are scored
 //   by null_pattern_pairs_kernel (cmx_null_patterns.hip).
 #include "cmx_device.h"
@@ -60,7 +62,7 @@ constexpr int kCodeSlotBytes = 4 * kWave;  // one dword per lane
 
 // LDS-DMA is issued through inline asm on purpose.  hipcc models __builtin_amdgcn_global_load_lds as a write to
 // LDS that any later ds_read may alias, and puts s_waitcnt vmcnt(0) in front of the next LDS read: with one dynamic LDS
-// array every operator, workspace vector and symbol would then be waited for right after the NEXT one was requested,
+// array every operator and symbol would then be waited for right after the NEXT one was requested,
 // i.e. the whole L2/HBM latency exposed once per op.  An asm DMA is invisible to that bookkeeping; the ordering
 // between a DMA and the LDS reads of its data is kept by the counted waits below (wait_vm), and compiler-issued
 // vmcnt waits for its own loads only become stricter (it undercounts what is in flight).
@@ -124,6 +126,11 @@ __device__ __forceinline__ void code_dma(const uint8_t* p, uint8_t* slot) { code
 // s_waitcnt vmcnt(n) needs an immediate: pick the largest supported threshold <= allowed (waiting for more is safe)
 template <int N>
 __device__ __forceinline__ void waitcnt_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
+template <int BASE>
+__device__ __forceinline__ void wait_vm_from(int v /* 0 .. 6 */) {   // vmcnt(BASE + v), as a tree of wave-uniform branches
+  if (v <= 3) { if (v <= 1) { if (v == 0) waitcnt_vm<BASE>(); else waitcnt_vm<BASE + 1>(); } else { if (v == 2) waitcnt_vm<BASE + 2>(); else waitcnt_vm<BASE + 3>(); } }
+  else { if (v == 4) waitcnt_vm<BASE + 4>(); else if (v == 5) waitcnt_vm<BASE + 5>(); else waitcnt_vm<BASE + 6>(); }
+}
 template <int S, int VL>
 __device__ __forceinline__ void wait_vm(int allowed) {
   // what can have been issued after X: the next operator (1 .. R DMA rows, +1 with symbols) and up to three workspace
@@ -134,16 +141,10 @@ __device__ __forceinline__ void wait_vm(int allowed) {
   static_assert(R + 1 + 2 * H < 64, "vmcnt is a 6-bit counter");
   static_assert(R + 1 <= 6, "operator rows + symbols");
   const int v = allowed % H < 7 ? allowed % H : 6, q = allowed / H;   // (H >= 7 for every instantiation but S = 4: there v < H anyway)
-  if (q == 0) {
-    if (v <= 3) { if (v <= 1) { if (v == 0) waitcnt_vm<0>(); else waitcnt_vm<1>(); } else { if (v == 2) waitcnt_vm<2>(); else waitcnt_vm<3>(); } }
-    else { if (v == 4) waitcnt_vm<4>(); else if (v == 5) waitcnt_vm<5>(); else waitcnt_vm<6>(); }
-  } else if (q == 1) {
-    if (v <= 3) { if (v <= 1) { if (v == 0) waitcnt_vm<H>(); else waitcnt_vm<H + 1>(); } else { if (v == 2) waitcnt_vm<H + 2>(); else waitcnt_vm<H + 3>(); } }
-    else { if (v == 4) waitcnt_vm<H + 4>(); else if (v == 5) waitcnt_vm<H + 5>(); else waitcnt_vm<H + 6>(); }
-  } else if (q == 2 && 2 * H + 6 < 64) {
-    if (v <= 3) { if (v <= 1) { if (v == 0) waitcnt_vm<2 * H>(); else waitcnt_vm<2 * H + 1>(); } else { if (v == 2) waitcnt_vm<2 * H + 2>(); else waitcnt_vm<2 * H + 3>(); } }
-    else { if (v == 4) waitcnt_vm<2 * H + 4>(); else if (v == 5) waitcnt_vm<2 * H + 5>(); else waitcnt_vm<2 * H + 6>(); }
-  } else {
+  if (q == 0) wait_vm_from<0>(v);
+  else if (q == 1) wait_vm_from<H>(v);
+  else if (q == 2 && 2 * H + 6 < 64) wait_vm_from<2 * H>(v);
+  else {
     // three vectors or more in flight: whatever the counter can still tell apart (it saturates at 63)
     constexpr int TOP = (3 * H + 4 < 64) ? 3 * H : (2 * H + 6 < 64 ? 2 * H + 6 : 2 * H);
     waitcnt_vm<TOP>();
@@ -174,22 +175,6 @@ __device__ __forceinline__ double reduce_sites(const double (&p)[NG]) {
     double k0 = p0 + p2, k1 = p1 + p3;   // site groups 0 / 1 in the lower half of the wave, 2 / 3 in the upper
     swap16(k0, k1);            // even rows: own k0, partner's k0    | odd rows: partner's k1, own k1
     return k0 + k1;            // site group lane >> 4: lane l holds site l
-  } else if constexpr (NG == 3) {
-    // three site groups (48 sites per wave, three waves per SIMD): the four-group exchange with an empty fourth group;
-    // lanes 48 .. 63 end with nothing of interest
-    double p0 = p[0], p1 = p[1], p2 = p[2], p3 = 0.0;
-    swap32(p0, p2);
-    swap32(p1, p3);
-    double k0 = p0 + p2, k1 = p1 + p3;
-    swap16(k0, k1);
-    return k0 + k1;
-  } else if constexpr (NG == 2) {
-    // two site groups (32 sites per wave): lanes l and l ^ 16 both end with the total of site 16 (l >> 5) + (l & 15)
-    double p0 = p[0], p1 = p[1];
-    swap32(p0, p1);            // lanes < 32: own p0, partner's p0   | lanes >= 32: partner's p1, own p1
-    double k = p0 + p1, q = k;
-    swap16(k, q);              // even rows: k own, q = partner's (odd row) k   | odd rows: k = partner's, q own
-    return k + q;
   } else {
     // one site group (16 sites per wave, small alignments): all four lanes l, l ^ 16, l ^ 32, l ^ 48 end with the total of site l & 15
     static_assert(NG == 1, "site groups per wave");
@@ -246,23 +231,13 @@ __device__ __forceinline__ void matvec_stage(const uint8_t* buf, int lane, const
 // lane l needs, for each site group g, element 4 sb + (l >> 4) of the row named by the symbol of site 16 g + (l & 15).
 // SET out = row, MUL out = row o in (in may be out), DOT returns sum_x in[x] * row[x] of site l (reduce_sites).
 enum { LEAF_SET = 0, LEAF_MUL = 1, LEAF_DOT = 2 };
+// r[g]: the lane's values of site group g's row (rows are stored state-in-tile major: state 4 sb + s4 at position
+// s4 * NB + sb, cmx_host_model.cpp).  Per site group the row values and their use: the reads of the next group do not
+// depend on anything computed for the previous one.
 template <int S, int MODE, int NG>
-__device__ __forceinline__ double leaf_apply(const uint8_t* buf, const uint8_t* codes /* slot + 4 * (lane & 15) */, int lane,
-                                             const double (&in)[S / 4 * NG], double (&out)[S / 4 * NG]) {
+__device__ __forceinline__ double rows_apply(const double* const (&r)[NG], const double (&in)[S / 4 * NG], double (&out)[S / 4 * NG]) {
   constexpr int NB = S / 4;
   double part[NG];
-  // all symbols first (one LDS round trip), then per site group the row values and their use: the reads of the next
-  // group do not depend on anything computed for the previous one
-  unsigned code[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) code[g] = codes[g * (NG == 3 ? 64 : 256 / NG)];   // one dword per LANE in the slot, group g at 64 / NG * g (three groups: as four)
-  const double* r[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const unsigned row = code[g] < (unsigned)MatStage<S>::NROW ? code[g] : (unsigned)(MatStage<S>::NROW - 1);
-    // rows are stored state-in-tile major: state 4 sb + s4 at position s4 * NB + sb (cmx_host_model.cpp)
-    r[g] = reinterpret_cast<const double*>(buf + row * (leaf_row_stride(S) * 8)) + (lane >> 4) * NB;
-  }
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
     part[g] = 0.0;
@@ -279,43 +254,42 @@ __device__ __forceinline__ double leaf_apply(const uint8_t* buf, const uint8_t* 
   if (MODE != LEAF_DOT) return 0.0;
   return reduce_sites<NG>(part);
 }
+// where the lane's values of row `row` of a staged leaf operator or cherry table start
+template <int S>
+__device__ __forceinline__ const double* stage_row(const uint8_t* buf, unsigned row, int lane) {
+  return reinterpret_cast<const double*>(buf + row * (leaf_row_stride(S) * 8)) + (lane >> 4) * (S / 4);
+}
+template <int S, int MODE, int NG>
+__device__ __forceinline__ double leaf_apply(const uint8_t* buf, const uint8_t* codes /* slot + 4 * (lane & 15) */, int lane,
+                                             const double (&in)[S / 4 * NG], double (&out)[S / 4 * NG]) {
+  // all symbols first (one LDS round trip): one dword per LANE in the slot, group g at 64 / NG * g
+  unsigned code[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) code[g] = codes[g * (256 / NG)];
+  const double* r[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g)
+    r[g] = stage_row<S>(buf, code[g] < (unsigned)MatStage<S>::NROW ? code[g] : (unsigned)(MatStage<S>::NROW - 1), lane);
+  return rows_apply<S, MODE, NG>(r, in, out);
+}
 
 // Row of a cherry table (cmx_walk.h): the row is named by the symbols of the cherry's two leaves, 4 * symbol(l1) + symbol(l2)
 // (fully resolved alignments only: both symbols are states of the 4-letter alphabet), the columns are a leaf row's.
 template <int S, int MODE, int NG>
 __device__ __forceinline__ double cherry_apply(const uint8_t* buf, const uint8_t* codes1, const uint8_t* codes2, int lane,
                                                const double (&in)[S / 4 * NG], double (&out)[S / 4 * NG]) {
-  constexpr int NB = S / 4;
-  double part[NG];
   unsigned c1[NG], c2[NG];
 #pragma unroll
-  for (int g = 0; g < NG; ++g) { c1[g] = codes1[g * (NG == 3 ? 64 : 256 / NG)]; c2[g] = codes2[g * (NG == 3 ? 64 : 256 / NG)]; }
+  for (int g = 0; g < NG; ++g) { c1[g] = codes1[g * (256 / NG)]; c2[g] = codes2[g * (256 / NG)]; }
   const double* r[NG];
 #pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const unsigned row = ((c1[g] & 3u) << 2) | (c2[g] & 3u);
-    r[g] = reinterpret_cast<const double*>(buf + row * (leaf_row_stride(S) * 8)) + (lane >> 4) * NB;
-  }
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    part[g] = 0.0;
-    double v[NB];
-#pragma unroll
-    for (int sb = 0; sb < NB; ++sb) v[sb] = r[g][sb];
-#pragma unroll
-    for (int sb = 0; sb < NB; ++sb) {
-      if (MODE == LEAF_SET) out[sb * NG + g] = v[sb];
-      else part[g] = __builtin_fma(in[sb * NG + g], v[sb], part[g]);
-    }
-  }
-  if (MODE != LEAF_DOT) return 0.0;
-  return reduce_sites<NG>(part);
+  for (int g = 0; g < NG; ++g) r[g] = stage_row<S>(buf, ((c1[g] & 3u) << 2) | (c2[g] & 3u), lane);
+  return rows_apply<S, MODE, NG>(r, in, out);
 }
 
 // ------------------------------------------------------------------------------------------------ small helpers
 // Workspace vectors are stored as [S/2][64 lanes][2 doubles]: one 16-byte access per lane and row, 1 KiB per
-// wave-instruction, the same image in HBM and (for prefetched vectors) in LDS.  An odd length (16-site tasks: S = 5) ends
-// with a row of single doubles.
+// wave-instruction.  An odd length (16-site tasks: S = 5) ends with a row of single doubles.
 // (Round 4 tried [S][64] with 64-bit accesses: hipcc puts v_mov copies and the s_waitcnt for them right behind the 128-bit
 // loads at 3 of the 5 load sites of map_kernel<20, null> -- the loaded quads do not match the registers the vector's phi
 // with the other arms of the child switch got -- and 64-bit loads remove copies and early waits alike.  Twice the VMEM
@@ -344,25 +318,6 @@ __device__ __forceinline__ void store_vec(double* p, const double (&v)[S], int l
   if constexpr (S % 2) p[(size_t)(S / 2) * 2 * kWave - lane] = v[S - 1];
 }
 
-// asynchronous HBM -> LDS copy of one workspace vector (S/2 LDS-DMA instructions, no VGPR destination)
-template <int S>
-__device__ __forceinline__ void prefetch_vec_lds(const double* p /* slice base + 2*lane */, uint8_t* lds /* wave-uniform */) {
-  constexpr int R = S / 2;
-  const uint32_t l = lds_addr(lds);
-#pragma unroll
-  for (int i = 0; i + 4 <= R; i += 4) dma_rows16<4>(p + (size_t)i * 2 * kWave, l + i * 1024);
-  if constexpr (R % 4 != 0) dma_rows16<R % 4>(p + (size_t)(R / 4) * 4 * 2 * kWave, l + (R / 4) * 4 * 1024);
-}
-template <int S>
-__device__ __forceinline__ void read_vec_lds(const uint8_t* lds /* wave-uniform */, int lane, double (&v)[S]) {
-#pragma unroll
-  for (int i = 0; i < S / 2; ++i) {
-    const d2 t = *reinterpret_cast<const d2*>(lds + (size_t)(i * kWave + lane) * 16);
-    v[2 * i] = t[0];
-    v[2 * i + 1] = t[1];
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ mapping core
 extern __shared__ __attribute__((aligned(16))) uint8_t cmx_smem[];
 
@@ -373,20 +328,17 @@ __device__ __forceinline__ void sload_rec(cmx_cint p, cmx_i16& r) {
 }
 
 struct ConstModel {
-  cmx_cint taxon_of, parent, nrec, msched, ldsched;
-  cmx_cdbl pi, rates, probs, cum_pi, cum_probs;
+  cmx_cint nrec, msched;
+  cmx_cdbl rates, probs;
   // tables: the cherry-table walk's operator stream (class-fused nucleotide models on resolved alignments)
   __device__ __forceinline__ explicit ConstModel(const DevModel& m, bool tables = false)
-      : taxon_of((cmx_cint)m.taxon_of), parent((cmx_cint)m.parent), nrec((cmx_cint)m.nrec),
-        msched((cmx_cint)(tables ? m.msched_r : m.msched)), ldsched((cmx_cint)m.ldsched), pi((cmx_cdbl)m.pi), rates((cmx_cdbl)m.rates),
-        probs((cmx_cdbl)m.probs), cum_pi((cmx_cdbl)m.cum_pi), cum_probs((cmx_cdbl)m.cum_probs) {}
+      : nrec((cmx_cint)m.nrec), msched((cmx_cint)(tables ? m.msched_r : m.msched)), rates((cmx_cdbl)m.rates),
+        probs((cmx_cdbl)m.probs) {}
 };
 // Operator-stream bookkeeping of a wave (wave-uniform, lives across site blocks).  vs counts the VMEM instructions this
 // code issued and knows about (DMA rows, vector stores); an asynchronous transfer remembers vs right after its issue,
 // and "wait for X" is s_waitcnt vmcnt(vs - X_seq): VMEM completes in order, so the instructions issued after X may stay
 // in flight.  Instructions that are not counted only make the wait stricter.
-// (The phase timers, the ablation switches and the round-1 fused-simulator arrangement that produced the figures quoted in
-// DESIGN.md were stripped from this file in round 3: scripts/experiments/ablations/README.md names the tagged source.)
 struct OpState {
   int pre_mat, pre_tx;  // op-stream entry of the NEXT op, loaded one op early (its latency hides behind the current op)
   unsigned par;      // stage buffer / code slot of the current operator op
@@ -395,22 +347,18 @@ struct OpState {
 };
 
 // Device backend of the tree walk (cmx_walk.h): registers R0..R3 are S-vectors of the wave's sites in the matrix-core
-// layout.  The walk names what it wants; the operator stream (m.msched) and the load schedule (m.ldsched) -- recorded
-// from the same walk on the host and checked numerically there -- say where it is.
+// layout.  The walk names what it wants, workspace slots included; the operator stream (m.msched) -- recorded from the
+// same walk on the host and checked numerically there -- says where the operators are.
 // RESOLVED: every symbol of the alignment is a state (the null's simulated or supplied alignments): leaf ops then stage the
 // S0 state rows of the transposed operator only, not its ambiguity rows
 template <int S, int FUSE, int NG, bool RESOLVED>
 struct DevWalk {
   static constexpr int VL = S / 4 * NG, kSites = 16 * NG;
-  static constexpr int kRow = NG == 3 ? 64 : kSites;   // lanes per row of the wave's per-site scratch arrays (three groups: lanes 48 .. 63 own unused columns)
   static constexpr bool DIAG = FUSE > 1 && S / FUSE == 4;
   static constexpr int kProductBytes = DIAG ? (S / 4) * 128 : MatStage<S>::BYTES;                      // diagonal tiles come first
   static constexpr int kLeafBytes = RESOLVED ? (S / FUSE) * leaf_row_stride(S) * 8 : MatStage<S>::BYTES;
-#ifndef CMX_NO_CHERRY_TABLES
-#define CMX_NO_CHERRY_TABLES 0     // 1: A/B builds without the cherry tables (scripts/ab_libs.sh)
-#endif
   static constexpr int kVecInstrs = (VL + 1) / 2;   // VMEM instructions of one workspace vector
-  static constexpr bool kCherryTables = RESOLVED && DIAG && !CMX_NO_CHERRY_TABLES;   // cmx_walk.h: cset / cdot instead of a cherry's operator ops
+  static constexpr bool kCherryTables = RESOLVED && DIAG;   // cmx_walk.h: cset / cdot instead of a cherry's operator ops
   static constexpr int kCherryBytes = 16 * leaf_row_stride(S) * 8;   // a table's 16 rows (one per symbol pair)
   static constexpr int kCherryFlag = 0x40000000;                     // stream entry: taxon of l1 | taxon of l2 << 15 | flag
   static_assert(kCherryBytes <= MatStage<S>::BYTES, "a cherry table fits a stage buffer");
@@ -444,7 +392,7 @@ struct DevWalk {
   // site of the lane inside the wave's block (see map_sites_wave)
   __device__ __forceinline__ int vsidx() const {
     const int l = vlane();
-    return NG >= 3 ? l : (NG == 2 ? (((l >> 5) << 4) | (l & 15)) : (l & 15));
+    return NG == 4 ? l : (l & 15);
   }
   template <int I>
   __device__ __forceinline__ double (&reg())[VL] {
@@ -470,18 +418,11 @@ struct DevWalk {
   template <int R>
   __device__ __forceinline__ void kill() {
     double(&r)[VL] = reg<R>();
-    static_assert(VL == 4 || VL == 5 || VL == 8 || VL == 12 || VL == 15 || VL == 16 || VL == 20, "kill() names every element in one statement");
-    if constexpr (VL == 12)
-      asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]), "=v"(r[5]), "=v"(r[6]), "=v"(r[7]), "=v"(r[8]), "=v"(r[9]), "=v"(r[10]), "=v"(r[11]));
-    else if constexpr (VL == 15)
-      asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]), "=v"(r[5]), "=v"(r[6]), "=v"(r[7]), "=v"(r[8]), "=v"(r[9]), "=v"(r[10]), "=v"(r[11]), "=v"(r[12]), "=v"(r[13]), "=v"(r[14]));
-    else
+    static_assert(VL == 4 || VL == 5 || VL == 16 || VL == 20, "kill() names every element in one statement");
     if constexpr (VL == 5)
       asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]));
     else if constexpr (VL == 4)
       asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]));
-    else if constexpr (VL == 8)
-      asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]), "=v"(r[5]), "=v"(r[6]), "=v"(r[7]));
     else if constexpr (VL == 16)
       asm volatile("" : "=v"(r[0]), "=v"(r[1]), "=v"(r[2]), "=v"(r[3]), "=v"(r[4]), "=v"(r[5]), "=v"(r[6]), "=v"(r[7]), "=v"(r[8]),
                         "=v"(r[9]), "=v"(r[10]), "=v"(r[11]), "=v"(r[12]), "=v"(r[13]), "=v"(r[14]), "=v"(r[15]));
@@ -548,38 +489,30 @@ struct DevWalk {
     matvec_stage<S, TR, NG, DIAG>(buf, vlane(), reg<SRC>(), reg<DST>()); asm volatile("" :: "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
     op_end(nseq);
   }
-  template <int MODE, int SRC, int DST>
-  __device__ __forceinline__ double leaf(void) {
+  // a leaf op, or a cherry-table op (cmx_walk.h): the table is staged like a leaf operator, its row named by two symbols
+  template <bool CHERRY, int MODE, int SRC, int DST>
+  __device__ __forceinline__ double row_op() {
     unsigned nseq;
     const uint8_t* buf = op_begin(nseq);
     const int vl = vlane();
-    const double tot = leaf_apply<S, MODE, NG>(buf, cslot + os.par * kCodeSlotBytes + 4 * (vl & 15), vl, reg<SRC>(), reg<DST>());
+    const uint8_t* codes = cslot + os.par * kCodeSlotBytes + 4 * (vl & 15);
+    double tot;
+    if constexpr (CHERRY) tot = cherry_apply<S, MODE, NG>(buf, codes, cslot2 + os.par * kCodeSlotBytes + 4 * (vl & 15), vl, reg<SRC>(), reg<DST>());
+    else tot = leaf_apply<S, MODE, NG>(buf, codes, vl, reg<SRC>(), reg<DST>());
     asm volatile("" :: "v"(tot), "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
     op_end(nseq);
     return tot;
   }
-  template <int D> __device__ __forceinline__ void lset(int, int) { (void)leaf<LEAF_SET, D, D>(); }
-  template <int SRC, int D> __device__ __forceinline__ void lmul(int, int) { (void)leaf<LEAF_MUL, SRC, D>(); }
+  template <int D> __device__ __forceinline__ void lset(int, int) { (void)row_op<false, LEAF_SET, D, D>(); }
+  template <int SRC, int D> __device__ __forceinline__ void lmul(int, int) { (void)row_op<false, LEAF_MUL, SRC, D>(); }
   template <int SRC> __device__ __forceinline__ void ldot(int, int, int row) {
-    const double tot = leaf<LEAF_DOT, SRC, SRC>();
-    pcnt[(size_t)row * kRow + vsidx()] = pc * tot;
+    const double tot = row_op<false, LEAF_DOT, SRC, SRC>();
+    pcnt[(size_t)row * kSites + vsidx()] = pc * tot;
   }
-  // cherry-table ops (cmx_walk.h): the table staged like a leaf operator, its row named by two symbols
-  template <int MODE, int SRC, int DST>
-  __device__ __forceinline__ double cherry(void) {
-    unsigned nseq;
-    const uint8_t* buf = op_begin(nseq);
-    const int vl = vlane();
-    const double tot = cherry_apply<S, MODE, NG>(buf, cslot + os.par * kCodeSlotBytes + 4 * (vl & 15), cslot2 + os.par * kCodeSlotBytes + 4 * (vl & 15),
-                                                 vl, reg<SRC>(), reg<DST>());
-    asm volatile("" :: "v"(tot), "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
-    op_end(nseq);
-    return tot;
-  }
-  template <int D> __device__ __forceinline__ void cset(int, int, int) { (void)cherry<LEAF_SET, D, D>(); }
+  template <int D> __device__ __forceinline__ void cset(int, int, int) { (void)row_op<true, LEAF_SET, D, D>(); }
   template <int SRC> __device__ __forceinline__ void cdot(int, int, int, int, int row) {
-    const double tot = cherry<LEAF_DOT, SRC, SRC>();
-    pcnt[(size_t)row * kRow + vsidx()] = pc * tot;
+    const double tot = row_op<true, LEAF_DOT, SRC, SRC>();
+    pcnt[(size_t)row * kSites + vsidx()] = pc * tot;
   }
   // workspace vector -> register: plain global loads straight into the destination register, which the walk has
   // declared dead (kill) long before -- in the outside pass the two sibling messages of a node are requested before the
@@ -654,7 +587,7 @@ struct DevWalk {
     for (int sb = 0; sb < S / 4; ++sb)
 #pragma unroll
       for (int g = 0; g < NG; ++g) p_[g] = __builtin_fma(R3[sb * NG + g] * R1[sb * NG + g], R2[sb * NG + g], p_[g]);
-    pcnt[(size_t)row * kRow + vsidx()] = pc * reduce_sites<NG>(p_);
+    pcnt[(size_t)row * kSites + vsidx()] = pc * reduce_sites<NG>(p_);
   }
 };
 
@@ -674,10 +607,9 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
   constexpr bool kTables = DevWalk<S, FUSE, NG, RESOLVED>::kCherryTables;   // (the launcher guarantees m.msched_r then)
   const ConstModel cm(m, kTables);
   constexpr int kSites = 16 * NG;      // sites per wave (NG site groups of 16; an S-vector is S / 4 * NG doubles per lane)
-  constexpr int kRow = NG == 3 ? 64 : kSites;   // row length of the wave's per-site scratch arrays
-  // site of this lane inside the wave's block for per-site scalars and arrays: NG = 4: the lane itself; NG = 2: lanes
-  // l and l ^ 16 both carry site 16 (l >> 5) + (l & 15) and do the per-site work redundantly (identical values)
-  const int sidx = NG >= 3 ? lane : (NG == 2 ? (((lane >> 5) << 4) | (lane & 15)) : (lane & 15));
+  // site of this lane inside the wave's block for per-site scalars and arrays: NG = 4: the lane itself; NG = 1: lanes
+  // l, l ^ 16, l ^ 32 and l ^ 48 all carry site l & 15 and do the per-site work redundantly (identical values)
+  const int sidx = NG == 4 ? lane : (lane & 15);
   const int C = m.C, K = m.K;
   double Lsum = 0.0, prsum = 0.0, best = -1.0;
   int bestc = 0;
@@ -717,7 +649,7 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
     const double pc = FUSE > 1 ? 1.0 : cm.probs[c];  // fused: the class probabilities are folded into the count operators
     be.pc = pc;
     be.c = c;
-    be.pcnt = part + (size_t)c * m.B * K * kRow;   // wave-uniform; the lane's site is added at each use
+    be.pcnt = part + (size_t)c * m.B * K * kSites;   // wave-uniform; the lane's site is added at each use
     be.begin_pass();
     walk_pass(be, m.NV, K);
     if constexpr (FUSE == 1) {
@@ -761,23 +693,23 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
       double t[4][RC];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const double* pp = part + ((size_t)(c + q) * BK + r0) * kRow + sidx;
+        const double* pp = part + ((size_t)(c + q) * BK + r0) * kSites + sidx;
 #pragma unroll
-        for (int u = 0; u < RC; ++u) t[q][u] = pp[(size_t)(r0 + u < BK ? u : 0) * kRow];
+        for (int u = 0; u < RC; ++u) t[q][u] = pp[(size_t)(r0 + u < BK ? u : 0) * kSites];
       }
 #pragma unroll
       for (int u = 0; u < RC; ++u) v[u] = (((v[u] + t[0][u]) + t[1][u]) + t[2][u]) + t[3][u];
     }
     for (; c < C; ++c) {
-      const double* pp = part + ((size_t)c * BK + r0) * kRow + sidx;
+      const double* pp = part + ((size_t)c * BK + r0) * kSites + sidx;
 #pragma unroll
-      for (int u = 0; u < RC; ++u) v[u] += pp[(size_t)(r0 + u < BK ? u : 0) * kRow];
+      for (int u = 0; u < RC; ++u) v[u] += pp[(size_t)(r0 + u < BK ? u : 0) * kSites];
     }
 #pragma unroll
     for (int u = 0; u < RC; ++u) {
       if (r0 + u < BK) {
         const double q = v[u] / Lsum;
-        cnt[(size_t)(r0 + u) * kRow + sidx] = q;
+        cnt[(size_t)(r0 + u) * kSites + sidx] = q;
         tot += q;
         if (++kk == K) {
           nrm = __builtin_fma(tot, tot, nrm);
@@ -793,22 +725,22 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
   norm_out = sqrt(nrm);
 }
 
-// site groups of 16 per wave: 4 (64 sites, two waves per SIMD) or 2 (32 sites: the four live S-vectors take 80 registers
-// instead of 160 and three waves fit a SIMD; operators are then staged per 32 sites)
+// LDS per mapping wave: two operator stage buffers + four symbol slots (two per leaf of a cherry-table op)
 template <int S>
-constexpr int map_lds_fixed() { return 2 * MatStage<S>::BYTES + 4 * kCodeSlotBytes; }   // stage buffers + symbol slots (two leaves)
-// + the simulator's node states (one byte per node and site) when they fit what is left of the CU's LDS share
+constexpr int map_lds_fixed() { return 2 * MatStage<S>::BYTES + 4 * kCodeSlotBytes; }
+static int map_lds_per_wave(int S) {
+  return S == 20 ? map_lds_fixed<20>() : (S == 16 ? map_lds_fixed<16>() : map_lds_fixed<4>());
+}
 
 template <int S, int MODE, int FUSE, int NG = map_ng(S)>
 __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void map_kernel(const MapArgs a) {
   constexpr int VL = S / 4 * NG, kSites = 16 * NG;
-  constexpr int kRow = NG == 3 ? 64 : kSites;
   const DevModel& m = a.m;
   // the null's alignments are fully resolved: class-fused nucleotide models walk them with the cherry tables' stream
   constexpr bool kTables = (MODE == kModeNull || MODE == kModeNullPatterns) && DevWalk<S, FUSE, NG, true>::kCherryTables;
   const ConstModel cm(m, kTables);
   const int lane = threadIdx.x & (kWave - 1);
-  const int sidx = NG >= 3 ? lane : (NG == 2 ? (((lane >> 5) << 4) | (lane & 15)) : (lane & 15));   // site of this lane in the wave's block
+  const int sidx = NG == 4 ? lane : (lane & 15);   // site of this lane in the wave's block
   // wave index through readfirstlane: the compiler cannot see that threadIdx.x >> 6 is wave-uniform and would keep every
   // per-wave base pointer below as a per-lane 64-bit VGPR pair (spilled, and reloaded from scratch in the hot loop)
   const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -816,10 +748,10 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
   const int nwaves = gridDim.x * kWavesPerBlock;
   double* wsD = a.ws.D + (size_t)wave * m.NIW * VL * kWave;
   double* wsU = a.ws.U + (size_t)wave * m.NIW * VL * kWave;
-  double* cnt0 = a.ws.cnt + (size_t)wave * 2 * m.B * m.K * kRow;
-  double* cnt1 = cnt0 + (size_t)m.B * m.K * kRow;
-  double* part = a.ws.part + (size_t)wave * m.C * m.B * m.K * kRow;
-  // LDS per wave: workspace prefetch buffer (S*64*8 B), two operator stage buffers, two symbol slots
+  double* cnt0 = a.ws.cnt + (size_t)wave * 2 * m.B * m.K * kSites;
+  double* cnt1 = cnt0 + (size_t)m.B * m.K * kSites;
+  double* part = a.ws.part + (size_t)wave * m.C * m.B * m.K * kSites;
+  // LDS per wave: two operator stage buffers, then four symbol slots (map_lds_fixed)
   const int lds_off = wib * a.lds_per_wave;
   const size_t nblocks = (a.nsites + kSites - 1) / kSites;
   // request the first op's operator (class 0, entry 0); every op then requests the next one
@@ -859,14 +791,14 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
     const size_t nb = (npat + kSites - 1) / kSites;
     for (size_t sb = wave; sb < nb; sb += nwaves) {
       const size_t p = sb * kSites + sidx;
-      const bool active = p < npat && sidx < kSites;
+      const bool active = p < npat;
       const size_t g = a.rep_site[active ? p : npat - 1];
       const size_t rh = g / a.rep_ram, j = g - rh * a.rep_ram;   // rh = rep_local * 2 + h
       double L, pr, nrm;
       int rc;
       // tile sb of the pattern table is this wave's count block: the class-sum epilogue writes the final counts there,
       // once, with its own row stride (lanes past npat write their clamped copy into the last tile's spare columns)
-      double* tile = a.counts + sb * ((size_t)m.B * m.K * kRow);
+      double* tile = a.counts + sb * ((size_t)m.B * m.K * kSites);
       map_sites_wave<S, FUSE, NG, true>(a, wsD, wsU, part, tile, lds_off, a.supplied + rh * (size_t)m.T * a.rep_ram + j, a.rep_ram,
                                         lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
       if (active) {
@@ -880,7 +812,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
   }
   for (size_t sb = wave; sb < nblocks; sb += nwaves) {
     const size_t site = sb * kSites + sidx;
-    const bool active = site < a.nsites && sidx < kSites;
+    const bool active = site < a.nsites;
     const size_t s = active ? site : a.nsites - 1;
     if (MODE == kModeObserved) {
       double L, pr, nrm;
@@ -892,7 +824,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
         if (a.rate_class) a.rate_class[s] = rc;
         if (a.norm) a.norm[s] = nrm;
         if (a.counts)
-          for (int r = 0; r < m.B * m.K; ++r) a.counts[(size_t)r * a.ldc + s] = cnt0[(size_t)r * kRow + sidx];
+          for (int r = 0; r < m.B * m.K; ++r) a.counts[(size_t)r * a.ldc + s] = cnt0[(size_t)r * kSites + sidx];
       }
     } else {
       // null pair q = s: replicate rep, column j; simulated-site index g_h = ((rep*2 + h)*rep_ram + j).
@@ -913,7 +845,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
         if (h == 0) { prmin = pr; nmin = nrm; rcmin = rc; }
         else { prmin = pr < prmin ? pr : prmin; nmin = nrm < nmin ? nrm : nmin; rcmin = rc < rcmin ? rc : rcmin; }
       }
-      const double stat = pair_stat_strided(a.stat_kind, a.stat_param, m.B, m.K, cnt0 + sidx, (size_t)kRow, cnt1 + sidx, (size_t)kRow, a.stat_mean);
+      const double stat = pair_stat_strided(a.stat_kind, a.stat_param, m.B, m.K, cnt0 + sidx, (size_t)kSites, cnt1 + sidx, (size_t)kSites, a.stat_mean);
       if (active) {
         a.null_stat[s] = stat;
         if (a.null_rcmin) a.null_rcmin[s] = rcmin;
@@ -925,47 +857,43 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last op left an operator DMA in flight
 }
 
-// LDS per mapping wave: operator stage buffers + symbol slots (nn, mode: the node states of a simulator inside the wave
-// depended on them; not needed any more)
-int map_lds_per_wave(int S, int /*nn*/, int /*mode*/) {
-  return S == 20 ? map_lds_fixed<20>() : (S == 16 ? map_lds_fixed<16>() : map_lds_fixed<4>());
+template <int S, int MODE, int FUSE, int NG = map_ng(S)>
+static hipError_t launch_map_as(const MapArgs& a, dim3 grid, dim3 block, size_t lds, int lim, hipStream_t stream) {
+  // per launch: the attribute belongs to the current device (a process may hold contexts on several)
+  const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&map_kernel<S, MODE, FUSE, NG>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+  if (ea != hipSuccess) return ea;
+  hipLaunchKernelGGL((map_kernel<S, MODE, FUSE, NG>), grid, block, lds, stream, a);
+  return hipGetLastError();
+}
+template <int S, int FUSE>
+static hipError_t launch_map_mode(int mode, const MapArgs& a, dim3 grid, dim3 block, size_t lds, int lim, hipStream_t stream) {
+  switch (mode) {
+    case kModeObserved: return launch_map_as<S, kModeObserved, FUSE>(a, grid, block, lds, lim, stream);
+    case kModeObservedSplit: return launch_map_as<S, kModeObservedSplit, FUSE>(a, grid, block, lds, lim, stream);
+    case kModeNullPatterns: return launch_map_as<S, kModeNullPatterns, FUSE>(a, grid, block, lds, lim, stream);
+    default: return launch_map_as<S, kModeNull, FUSE>(a, grid, block, lds, lim, stream);
+  }
 }
 
 hipError_t launch_map(const MapArgs& a_in, int mode, int grid_blocks, hipStream_t stream) {
   dim3 grid(grid_blocks), block(kWave * kWavesPerBlock);
   MapArgs a = a_in;
-  a.lds_per_wave = map_lds_per_wave(a.m.S, a.m.nn, mode);
+  a.lds_per_wave = map_lds_per_wave(a.m.S);
   const size_t lds = (size_t)kWavesPerBlock * (size_t)a.lds_per_wave;
   const int lim = 160 * 1024 / map_waves_per_simd(a.m.S);  // dynamic LDS a workgroup may use (that many workgroups per CU)
   if ((int)lds > lim) return hipErrorInvalidValue;
-#define CMX_LAUNCH(...) /* S, MODE, FUSE [, NG] */                                                            \
-  do {                                                                                                        \
-    /* per launch: the attribute belongs to the current device (a process may hold contexts on several) */    \
-    const hipError_t ea_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&map_kernel<__VA_ARGS__>),       \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, lim);              \
-    if (ea_ != hipSuccess) return ea_;                                                                        \
-    hipLaunchKernelGGL((map_kernel<__VA_ARGS__>), grid, block, lds, stream, a);                               \
-  } while (0)
   // (the null instantiations of the class-fused layouts read the cherry-table walk's stream)
   if ((mode == kModeNull || mode == kModeNullPatterns) && a.m.fuse > 1 && a.m.msched_r == nullptr) return hipErrorInvalidValue;
   if (mode == kModeNullPatterns && (!a.rep_site || !a.npat || !a.counts || !a.post_rate || !a.rate_class || !a.norm)) return hipErrorInvalidValue;
-#define CMX_LAUNCH_MODES(S_, F_)                                            \
-  do {                                                                      \
-    if (mode == kModeObserved) CMX_LAUNCH(S_, kModeObserved, F_);           \
-    else if (mode == kModeObservedSplit) CMX_LAUNCH(S_, kModeObservedSplit, F_); \
-    else if (mode == kModeNullPatterns) CMX_LAUNCH(S_, kModeNullPatterns, F_); \
-    else CMX_LAUNCH(S_, kModeNull, F_);                                     \
-  } while (0)
   // 16-site wave-tasks (one site group): small alignments, four times the waves
-  if (a.m.S == 20 && a.m.fuse == 1 && mode == kModeObservedSplit && a.split_sites == 16) CMX_LAUNCH(20, kModeObservedSplit, 1, 1);
-  else if (a.m.S == 20 && a.m.fuse == 1) CMX_LAUNCH_MODES(20, 1);
-  else if (a.m.S == 20 && a.m.fuse == 5) CMX_LAUNCH_MODES(20, 5);
-  else if (a.m.S == 16 && a.m.fuse == 4) CMX_LAUNCH_MODES(16, 4);
-  else if (a.m.S == 4 && a.m.fuse == 1) CMX_LAUNCH_MODES(4, 1);
-  else return hipErrorInvalidValue;
-#undef CMX_LAUNCH_MODES
-#undef CMX_LAUNCH
-  return hipGetLastError();
+  if (a.m.S == 20 && a.m.fuse == 1 && mode == kModeObservedSplit && a.split_sites == 16)
+    return launch_map_as<20, kModeObservedSplit, 1, 1>(a, grid, block, lds, lim, stream);
+  if (a.m.S == 20 && a.m.fuse == 1) return launch_map_mode<20, 1>(mode, a, grid, block, lds, lim, stream);
+  if (a.m.S == 20 && a.m.fuse == 5) return launch_map_mode<20, 5>(mode, a, grid, block, lds, lim, stream);
+  if (a.m.S == 16 && a.m.fuse == 4) return launch_map_mode<16, 4>(mode, a, grid, block, lds, lim, stream);
+  if (a.m.S == 4 && a.m.fuse == 1) return launch_map_mode<4, 1>(mode, a, grid, block, lds, lim, stream);
+  return hipErrorInvalidValue;
 }
 
 // class-split observed mode: sums the per-class results in class order exactly as map_sites_wave's own epilogue does.

@@ -226,9 +226,9 @@ __global__ __launch_bounds__(256) void mica_codes_kernel(int A, int T, int Tp, c
                                                          const uint8_t* __restrict__ aln, size_t ld, uint8_t* __restrict__ codes,
                                                          uint8_t* __restrict__ flag, uint8_t* __restrict__ gap, double* __restrict__ S,
                                                          int* __restrict__ anyflag, size_t n, size_t npad /* columns behind n that get "no row" codes */) {
-  constexpr int kRow = 68;               // bytes per taxon of the tile: 17 dwords, so that a column is read conflict-free
+  constexpr int kTileRow = 68;           // bytes per taxon of the tile: 17 dwords, so that a column is read conflict-free
   constexpr int kCnt = 35;               // counts per column (states, the unknown; odd stride)
-  __shared__ __attribute__((aligned(4))) uint8_t tile[64 * kRow];
+  __shared__ __attribute__((aligned(4))) uint8_t tile[64 * kTileRow];
   __shared__ int cnt[64 * kCnt];
   __shared__ int amb[64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -250,13 +250,13 @@ __global__ __launch_bounds__(256) void mica_codes_kernel(int A, int T, int Tp, c
         }
         if (c <= (unsigned)A) atomicAdd(&cnt[lane * kCnt + (int)c], 1);
       }
-      tile[tl * kRow + lane] = (uint8_t)c;
+      tile[tl * kTileRow + lane] = (uint8_t)c;
     }
     __syncthreads();
 #pragma unroll 4
     for (int r = 0; r < 16; ++r) {       // wave w: columns 4 r + w, one taxon per lane
       const int col = 4 * r + w;
-      if (i0 + col < n + npad && tc + lane < Tp) codes[(i0 + col) * (size_t)Tp + tc + lane] = tile[lane * kRow + col];
+      if (i0 + col < n + npad && tc + lane < Tp) codes[(i0 + col) * (size_t)Tp + tc + lane] = tile[lane * kTileRow + col];
     }
     __syncthreads();
   }

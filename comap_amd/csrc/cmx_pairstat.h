@@ -179,9 +179,4 @@ __device__ inline double pair_stat_weighted(int kind, double param, int B, int K
   return pair_stat_strided(kind, param, B, K, c1, ld1, c2, ld2, mv);
 }
 
-__device__ __forceinline__ double pair_stat_lane(int kind, double param, int B, int K, const double* __restrict__ c1,
-                                                 const double* __restrict__ c2) {
-  return pair_stat_strided(kind, param, B, K, c1, (size_t)kWave, c2, (size_t)kWave);
-}
-
 }  // namespace cmx
