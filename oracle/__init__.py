@@ -66,6 +66,44 @@ class Model:
         self.method, self.nonneg = int(method), int(bool(nonneg))
         self.naive_W = None if naive_W is None else _f64(naive_W)
         self.nn, self.T, self.B = len(self.parent), len(self.lot), len(self.parent) - 1
+        # the same model written as a set of one generator (the form the C entry points take)
+        self.Qs, self.pis, self.Bks = self.Q[None], self.pi[None], self.Bk[None]
+        self.model_of_branch, self.root_freqs = np.zeros(self.nn, dtype=np.int32), self.pi
+
+
+class ModelSet:
+    """Non-homogeneous model set (DRNonHomogeneousTreeLikelihood, CoMap/CoETools.cpp:126-206): Qs [M, S, S], pis [M, S],
+    Bks [M, K, S, S] (None: the total register of every generator), model_of_branch [nn] (the generator of the branch
+    above each node; the root's entry is not used), root_freqs [S].  The tree is used as rooted.  Accepted wherever a
+    Model is."""
+
+    def __init__(self, parent, blen, leaf_of_taxon, Qs, pis, rates, probs, model_of_branch, root_freqs, Bks=None,
+                 method=METHOD_UNIF, nonneg=True, naive_W=None):
+        self.parent, self.blen, self.lot = _i32(parent), _f64(blen), _i32(leaf_of_taxon)
+        self.Qs, self.pis, self.rates, self.probs = _f64(Qs), _f64(pis), _f64(rates), _f64(probs)
+        self.M, self.S = self.pis.shape
+        self.C = len(self.rates)
+        assert self.Qs.shape == (self.M, self.S, self.S)
+        if Bks is None:
+            Bks = self.Qs.copy()
+            Bks[:, np.arange(self.S), np.arange(self.S)] = 0.0
+        self.Bks = _f64(Bks).reshape(self.M, -1, self.S, self.S)
+        self.K = self.Bks.shape[1]
+        self.model_of_branch, self.root_freqs = _i32(model_of_branch), _f64(root_freqs)
+        self.method, self.nonneg = int(method), int(bool(nonneg))
+        self.naive_W = None if naive_W is None else _f64(naive_W)
+        self.nn, self.T, self.B = len(self.parent), len(self.lot), len(self.parent) - 1
+        assert len(self.model_of_branch) == self.nn and len(self.root_freqs) == self.S
+        assert 0 <= self.model_of_branch.min() and self.model_of_branch.max() < self.M
+
+
+def _set_args(m, with_bks=True):
+    """(nmod, Qs, pis[, Bks], model_of, rootf) of a Model or a ModelSet as the entry points of oracle.c take them"""
+    D = ctypes.c_double
+    a = [len(m.pis), _p(m.Qs, D), _p(m.pis, D)]
+    if with_bks:
+        a.append(_p(m.Bks, D))
+    return a + [_p(m.model_of_branch, ctypes.c_int), _p(m.root_freqs, D)]
 
 
 def default_masks(S):
@@ -88,9 +126,8 @@ def map_sites(m, aln, masks=None):
     rc = np.zeros(N, dtype=np.int32)
     D, I, U8, U32 = ctypes.c_double, ctypes.c_int, ctypes.c_uint8, ctypes.c_uint32
     lib().orc_map_sites(m.nn, _p(m.parent, I), _p(m.blen, D), m.T, _p(m.lot, I), ctypes.c_long(N), _p(aln, U8),
-                        _p(masks, U32), m.S, m.C, m.K, _p(m.Q, D), _p(m.pi, D), _p(m.rates, D), _p(m.probs, D),
-                        _p(m.Bk, D), m.method, m.nonneg, _p(m.naive_W, D), _p(counts, D), _p(logL, D), _p(pr, D),
-                        _p(rc, I), _p(norm, D))
+                            _p(masks, U32), m.S, m.C, m.K, *_set_args(m), _p(m.rates, D), _p(m.probs, D), m.method,
+                            m.nonneg, _p(m.naive_W, D), _p(counts, D), _p(logL, D), _p(pr, D), _p(rc, I), _p(norm, D))
     return dict(counts=counts, logL=logL, post_rate=pr, rate_class=rc, norm=norm)
 
 
@@ -105,10 +142,10 @@ def map_sites_noavg(m, aln, masks=None):
     norm, margin = np.zeros(N), np.zeros((N, m.B))
     arg = np.zeros((N, m.B), dtype=np.int32)
     D, I, U8, U32 = ctypes.c_double, ctypes.c_int, ctypes.c_uint8, ctypes.c_uint32
-    lib().orc_map_sites_noavg(m.nn, _p(m.parent, I), _p(m.blen, D), m.T, _p(m.lot, I), ctypes.c_long(N), _p(aln, U8),
-                              _p(masks, U32), m.S, m.C, m.K, _p(m.Q, D), _p(m.pi, D), _p(m.rates, D), _p(m.probs, D),
-                              _p(m.Bk, D), m.method, m.nonneg, _p(m.naive_W, D), _p(counts, D), _p(norm, D), _p(arg, I),
-                              _p(margin, D))
+    lib().orc_map_sites_noavg(m.nn, _p(m.parent, I), _p(m.blen, D), m.T, _p(m.lot, I), ctypes.c_long(N),
+                                  _p(aln, U8), _p(masks, U32), m.S, m.C, m.K, *_set_args(m), _p(m.rates, D),
+                                  _p(m.probs, D), m.method, m.nonneg, _p(m.naive_W, D), _p(counts, D), _p(norm, D),
+                                  _p(arg, I), _p(margin, D))
     return dict(counts=counts, norm=norm, argmax=arg, margin=margin)
 
 
@@ -124,32 +161,42 @@ def map_sites_marginal(m, aln, average, masks=None, want_post=False):
     anc = np.zeros((N, m.nn), dtype=np.int32)
     post = np.zeros((N, m.nn, m.C, m.S)) if want_post else None
     D, I, U8, U32 = ctypes.c_double, ctypes.c_int, ctypes.c_uint8, ctypes.c_uint32
-    lib().orc_map_sites_marginal(m.nn, _p(m.parent, I), _p(m.blen, D), m.T, _p(m.lot, I), ctypes.c_long(N), _p(aln, U8),
-                                 _p(masks, U32), m.S, m.C, m.K, _p(m.Q, D), _p(m.pi, D), _p(m.rates, D), _p(m.probs, D),
-                                 _p(m.Bk, D), m.method, m.nonneg, _p(m.naive_W, D), int(bool(average)), _p(counts, D),
-                                 _p(norm, D), _p(post, D) if want_post else None, _p(anc, I), _p(margin, D))
+    lib().orc_map_sites_marginal(m.nn, _p(m.parent, I), _p(m.blen, D), m.T, _p(m.lot, I), ctypes.c_long(N),
+                                     _p(aln, U8), _p(masks, U32), m.S, m.C, m.K, *_set_args(m), _p(m.rates, D),
+                                     _p(m.probs, D), m.method, m.nonneg, _p(m.naive_W, D), int(bool(average)),
+                                     _p(counts, D), _p(norm, D), _p(post, D) if want_post else None, _p(anc, I),
+                                     _p(margin, D))
     return dict(counts=counts, norm=norm, anc=anc, margin=margin, post=post)
 
 
-def simulate(m, seed, g0, n):
+FRAGILE = 1e-9      # a simulated site with a draw closer than this to a boundary of its cumulative row is "fragile"
+
+
+def simulate(m, seed, g0, n, want_near=False):
+    """-> (aln [T, n], classes [n]) and, with want_near, near [n]: per site the smallest |u - cum_j| over all its draws
+    (class, root, every node).  Another implementation's cumulative rows differ from these in their last digits, so a
+    site with near < FRAGILE may legitimately come out differently there."""
     aln = np.zeros((m.T, n), dtype=np.uint8)
     cls = np.zeros(n, dtype=np.int32)
+    near = np.zeros(n) if want_near else None
     D, I = ctypes.c_double, ctypes.c_int
-    lib().orc_simulate(m.nn, _p(m.parent, I), _p(m.blen, D), m.T, _p(m.lot, I), m.S, m.C, _p(m.Q, D), _p(m.pi, D),
-                       _p(m.rates, D), _p(m.probs, D), ctypes.c_uint64(seed), ctypes.c_uint64(g0), ctypes.c_long(n),
-                       _p(aln, ctypes.c_uint8), _p(cls, I))
-    return aln, cls
+    lib().orc_simulate(m.nn, _p(m.parent, I), _p(m.blen, D), m.T, _p(m.lot, I), m.S, m.C, *_set_args(m, False),
+                           _p(m.rates, D), _p(m.probs, D), ctypes.c_uint64(seed), ctypes.c_uint64(g0), ctypes.c_long(n),
+                           _p(aln, ctypes.c_uint8), _p(cls, I), _p(near, D))
+    return (aln, cls, near) if want_near else (aln, cls)
 
 
-def simulate_continuous(m, seed, g0, n, alpha, p_inv=0.0):
-    """simulations.continuous = yes: -> (aln [T, n], rates [n])"""
+def simulate_continuous(m, seed, g0, n, alpha, p_inv=0.0, want_near=False):
+    """simulations.continuous = yes: -> (aln [T, n], rates [n]) and, with want_near, near [n] as in simulate (root and
+    node draws; the rate is a quantile, not a draw from a cumulative row)"""
     aln = np.zeros((m.T, n), dtype=np.uint8)
     rates = np.zeros(n)
+    near = np.zeros(n) if want_near else None
     D, I = ctypes.c_double, ctypes.c_int
-    lib().orc_simulate_continuous(m.nn, _p(m.parent, I), _p(m.blen, D), m.T, _p(m.lot, I), m.S, _p(m.Q, D), _p(m.pi, D),
-                                  D(alpha), D(p_inv), ctypes.c_uint64(seed), ctypes.c_uint64(g0), ctypes.c_long(n),
-                                  _p(aln, ctypes.c_uint8), _p(rates, D))
-    return aln, rates
+    lib().orc_simulate_continuous(m.nn, _p(m.parent, I), _p(m.blen, D), m.T, _p(m.lot, I), m.S, *_set_args(m, False),
+                                      D(alpha), D(p_inv), ctypes.c_uint64(seed), ctypes.c_uint64(g0), ctypes.c_long(n),
+                                      _p(aln, ctypes.c_uint8), _p(rates, D), _p(near, D))
+    return (aln, rates, near) if want_near else (aln, rates)
 
 
 def gamma_quantile(a, u):
@@ -223,11 +270,10 @@ def null_intra(m, kind, seed, rep_begin, rep_end, repRAM, supplied=None, params=
         supplied = np.ascontiguousarray(supplied, dtype=np.uint8)
         assert supplied.shape == (rep_end - rep_begin, 2, m.T, repRAM)
     D, I = ctypes.c_double, ctypes.c_int
-    lib().orc_null_intra(m.nn, _p(m.parent, I), _p(m.blen, D), m.T, _p(m.lot, I), m.S, m.C, m.K, _p(m.Q, D),
-                         _p(m.pi, D), _p(m.rates, D), _p(m.probs, D), _p(m.Bk, D), m.method, m.nonneg, kind,
-                         _p(params, D), ctypes.c_uint64(seed), ctypes.c_long(rep_begin), ctypes.c_long(rep_end),
-                         ctypes.c_long(repRAM), _p(supplied, ctypes.c_uint8), _p(stat, D), _p(rcmin, I), _p(prmin, D),
-                         _p(nmin, D))
+    lib().orc_null_intra(m.nn, _p(m.parent, I), _p(m.blen, D), m.T, _p(m.lot, I), m.S, m.C, m.K, *_set_args(m),
+                             _p(m.rates, D), _p(m.probs, D), m.method, m.nonneg, kind, _p(params, D),
+                             ctypes.c_uint64(seed), ctypes.c_long(rep_begin), ctypes.c_long(rep_end), ctypes.c_long(repRAM),
+                             _p(supplied, ctypes.c_uint8), _p(stat, D), _p(rcmin, I), _p(prmin, D), _p(nmin, D))
     return dict(stat=stat, rcmin=rcmin, prmin=prmin, nmin=nmin)
 
 

@@ -192,31 +192,49 @@ static void joint_count_matrix(int S, const double* J, const double* P, int nonn
   }
 }
 
+/* Non-homogeneous model set (DRNonHomogeneousTreeLikelihood, CoMap/CoETools.cpp:126-206): M reversible generators Qs [M][S][S]
+ * with their frequencies pis [M][S] and registers Bks [M][K][S][S]; model_of[node] names the generator of the branch above
+ * the node (NULL: generator 0 everywhere), rootf [S] are the frequencies at the root of the tree, which stays rooted.  A
+ * homogeneous model is the set with nmod = 1, model_of all 0 and rootf = pi: every entry point below takes a set.
+ * eigen_set: M blocks of lam [S], V [S][S], Vinv [S][S]. */
+static double* eigen_set(int M, int S, const double* Qs, const double* pis) {
+  size_t blk = (size_t)S + 2 * (size_t)S * S;
+  double* e = (double*)malloc(sizeof(double) * blk * M);
+  for (int m = 0; m < M; m++)
+    orc_eigen_reversible(S, Qs + (size_t)m * S * S, pis + (size_t)m * S, e + m * blk, e + m * blk + S, e + m * blk + S + (size_t)S * S);
+  return e;
+}
+#define SET_OF(b) (model_of ? model_of[b] : 0)
+/* the generator of branch b: its eigensystem, its Q and its registers */
+#define SET_EIG(b) const double* lam = eig + (size_t)SET_OF(b) * ((size_t)S + 2 * (size_t)S2), *V = lam + S, *Vinv = V + S2
+#define SET_GEN(b) const double* Q = Qs + (size_t)SET_OF(b) * S2; const double* Bk = Bks + (size_t)SET_OF(b) * K * S2
+
 /* DRHomogeneousTreeLikelihood::initialize + getLogLikelihoodPerSite / getPosteriorRatePerSite /
  * getRateClassWithMaxPostProbPerSite (A.2, A.5) followed by
  * LegacySubstitutionMappingTools::computeSubstitutionVectors(average, joint) (A.3) and computeNormForSite (A.6).
  * method: 0 uniformization, 1 decomposition, 2 naive (N(x,y) = W(x,y)[x != y]).
  * counts is site-major [N][B][K] == mapping[i][b][k] (CoMap/Statistics.h:154-160). */
 int orc_map_sites(int nn, const int* parent, const double* blen, int T, const int* leaf_of_taxon, long N,
-                  const uint8_t* aln, const uint32_t* masks, int S, int C, int K, const double* Q, const double* pi,
-                  const double* rates, const double* probs, const double* Bk, int method, int nonneg,
-                  const double* naiveW, double* counts, double* logL, double* post_rate, int* rate_class,
-                  double* norm) {
+                  const uint8_t* aln, const uint32_t* masks, int S, int C, int K, int nmod, const double* Qs,
+                  const double* pis, const double* Bks, const int* model_of, const double* rootf, const double* rates,
+                  const double* probs, int method, int nonneg, const double* naiveW, double* counts, double* logL,
+                  double* post_rate, int* rate_class, double* norm) {
   int B = nn - 1, root = nn - 1, S2 = S * S;
   int *first, *next;
   child_lists(nn, parent, &first, &next);
   int* taxon_of = (int*)malloc(sizeof(int) * nn);
   for (int i = 0; i < nn; i++) taxon_of[i] = -1;
   for (int t = 0; t < T; t++) taxon_of[leaf_of_taxon[t]] = t;
-  double* lam = (double*)malloc(sizeof(double) * (S + 2 * S2));
-  double *V = lam + S, *Vinv = V + S2;
-  orc_eigen_reversible(S, Q, pi, lam, V, Vinv);
+  double* eig = eigen_set(nmod, S, Qs, pis);
+  const double* pi = rootf;
   /* per branch x class: P and (P o N^k) */
   double* P = (double*)malloc(sizeof(double) * (size_t)B * C * S2);
   double* PN = (double*)malloc(sizeof(double) * (size_t)B * C * K * S2);
   double* Jtmp = (double*)malloc(sizeof(double) * S2);
   for (int b = 0; b < B; b++)
     for (int c = 0; c < C; c++) {
+      SET_EIG(b);
+      SET_GEN(b);
       double t = blen[b] * rates[c];
       double* Pbc = P + ((size_t)b * C + c) * S2;
       orc_transition(S, lam, V, Vinv, t, Pbc);
@@ -326,7 +344,7 @@ int orc_map_sites(int nn, const int* parent, const double* blen, int T, const in
     }
     norm[i] = sqrt(nrm);
   }
-  free(D); free(U); free(Lc); free(P); free(PN); free(Jtmp); free(lam); free(taxon_of); free(first); free(next);
+  free(D); free(U); free(Lc); free(P); free(PN); free(Jtmp); free(eig); free(taxon_of); free(first); free(next);
   return 0;
 }
 
@@ -345,23 +363,25 @@ int orc_map_sites(int nn, const int* parent, const double* blen, int T, const in
  * margin[i*B + b] = (best - second best) / best of pxy: where it is below ~1e-9 another implementation may pick the
  * other cell; the parity tests skip those entries. */
 int orc_map_sites_noavg(int nn, const int* parent, const double* blen, int T, const int* leaf_of_taxon, long N,
-                        const uint8_t* aln, const uint32_t* masks, int S, int C, int K, const double* Q, const double* pi,
-                        const double* rates, const double* probs, const double* Bk, int method, int nonneg,
-                        const double* naiveW, double* counts, double* norm, int* argmax_xy, double* margin) {
+                        const uint8_t* aln, const uint32_t* masks, int S, int C, int K, int nmod, const double* Qs,
+                        const double* pis, const double* Bks, const int* model_of, const double* rootf,
+                        const double* rates, const double* probs, int method, int nonneg, const double* naiveW,
+                        double* counts, double* norm, int* argmax_xy, double* margin) {
   int B = nn - 1, root = nn - 1, S2 = S * S;
   int *first, *next;
   child_lists(nn, parent, &first, &next);
   int* taxon_of = (int*)malloc(sizeof(int) * nn);
   for (int i = 0; i < nn; i++) taxon_of[i] = -1;
   for (int t = 0; t < T; t++) taxon_of[leaf_of_taxon[t]] = t;
-  double* lam = (double*)malloc(sizeof(double) * (S + 2 * S2));
-  double *V = lam + S, *Vinv = V + S2;
-  orc_eigen_reversible(S, Q, pi, lam, V, Vinv);
+  double* eig = eigen_set(nmod, S, Qs, pis);
+  const double* pi = rootf;
   double* P = (double*)malloc(sizeof(double) * (size_t)B * C * S2);
   double* N1 = (double*)malloc(sizeof(double) * (size_t)B * K * S2);   /* N^k(x, y; t_b) at rate 1 */
   double* Jtmp = (double*)malloc(sizeof(double) * S2 * 2);
   double* P1 = Jtmp + S2;
   for (int b = 0; b < B; b++) {
+    SET_EIG(b);
+    SET_GEN(b);
     for (int c = 0; c < C; c++) orc_transition(S, lam, V, Vinv, blen[b] * rates[c], P + ((size_t)b * C + c) * S2);
     orc_transition(S, lam, V, Vinv, blen[b], P1);
     for (int k = 0; k < K; k++) {
@@ -457,7 +477,7 @@ int orc_map_sites_noavg(int nn, const int* parent, const double* blen, int T, co
     }
     norm[i] = sqrt(nrm);
   }
-  free(D); free(U); free(pxy); free(P); free(N1); free(Jtmp); free(lam); free(taxon_of); free(first); free(next);
+  free(D); free(U); free(pxy); free(P); free(N1); free(Jtmp); free(eig); free(taxon_of); free(first); free(next);
   return 0;
 }
 
@@ -480,19 +500,18 @@ int orc_map_sites_noavg(int nn, const int* parent, const double* blen, int T, co
  * post (optional): [N][nn][C][S]; anc (optional): [N][nn]; margin (optional, [N][nn]): (best - second) / best of the
  * marginal state posterior -- where it is tiny another implementation may pick the other state. */
 int orc_map_sites_marginal(int nn, const int* parent, const double* blen, int T, const int* leaf_of_taxon, long N,
-                           const uint8_t* aln, const uint32_t* masks, int S, int C, int K, const double* Q, const double* pi,
-                           const double* rates, const double* probs, const double* Bk, int method, int nonneg,
-                           const double* naiveW, int average, double* counts, double* norm, double* post, int* anc,
-                           double* margin) {
+                           const uint8_t* aln, const uint32_t* masks, int S, int C, int K, int nmod, const double* Qs,
+                           const double* pis, const double* Bks, const int* model_of, const double* rootf,
+                           const double* rates, const double* probs, int method, int nonneg, const double* naiveW,
+                           int average, double* counts, double* norm, double* post, int* anc, double* margin) {
   int B = nn - 1, root = nn - 1, S2 = S * S;
   int *first, *next;
   child_lists(nn, parent, &first, &next);
   int* taxon_of = (int*)malloc(sizeof(int) * nn);
   for (int i = 0; i < nn; i++) taxon_of[i] = -1;
   for (int t = 0; t < T; t++) taxon_of[leaf_of_taxon[t]] = t;
-  double* lam = (double*)malloc(sizeof(double) * (S + 2 * S2));
-  double *V = lam + S, *Vinv = V + S2;
-  orc_eigen_reversible(S, Q, pi, lam, V, Vinv);
+  double* eig = eigen_set(nmod, S, Qs, pis);
+  const double* pi = rootf;
   double* P = (double*)malloc(sizeof(double) * (size_t)B * C * S2);
   /* conditional counts N^k(x, y; t): per class at r_c t_b (slots 0 .. C-1) and at t_b itself (slot C) */
   double* NC = (double*)malloc(sizeof(double) * (size_t)B * (C + 1) * K * S2);
@@ -500,6 +519,8 @@ int orc_map_sites_marginal(int nn, const int* parent, const double* blen, int T,
   double* Pt = Jtmp + S2;
   for (int b = 0; b < B; b++)
     for (int c = 0; c <= C; c++) {
+      SET_EIG(b);
+      SET_GEN(b);
       double t = blen[b] * (c < C ? rates[c] : 1.0);
       orc_transition(S, lam, V, Vinv, t, Pt);
       if (c < C) memcpy(P + ((size_t)b * C + c) * S2, Pt, sizeof(double) * S2);
@@ -636,7 +657,7 @@ int orc_map_sites_marginal(int nn, const int* parent, const double* blen, int T,
     }
     norm[i] = sqrt(nrm);
   }
-  free(D); free(U); free(st); free(P); free(NC); free(Jtmp); free(lam); free(taxon_of); free(first); free(next);
+  free(D); free(U); free(st); free(P); free(NC); free(Jtmp); free(eig); free(taxon_of); free(first); free(next);
   return 0;
 }
 
@@ -686,44 +707,51 @@ double orc_node_uniform(uint64_t seed, uint64_t g, uint32_t node) {
   return (double)w[g & 1] * (1.0 / 4294967296.0);
 }
 
-static int draw_index(double u, const double* p, int n) {
+/* index = #{ j < n-1 : u >= cum_j }.  *near (optional) is lowered to the smallest |u - cum_j| met: a draw that close to
+ * a boundary of its cumulative row may fall on the other side in an implementation whose row differs in the last digits */
+static int draw_index(double u, const double* p, int n, double* near) {
   double cum = 0;
   int idx = 0;
   for (int j = 0; j < n - 1; j++) {
     cum += p[j];
     if (u >= cum) idx = j + 1;
+    if (near && fabs(u - cum) < *near) *near = fabs(u - cum);
   }
   return idx;
 }
 
-/* NonHomogeneousSequenceSimulator::simulate(n) restated (homogeneous model, discrete rates):
- * aln[t*n + j]; global site indices g0 .. g0+n-1. */
-void orc_simulate(int nn, const int* parent, const double* blen, int T, const int* leaf_of_taxon, int S, int C,
-                  const double* Q, const double* pi, const double* rates, const double* probs, uint64_t seed,
-                  uint64_t g0, long n, uint8_t* aln, int* classes) {
+/* NonHomogeneousSequenceSimulator::simulate(n) restated (discrete rates): aln[t*n + j]; global site indices g0 .. g0+n-1.
+ * The root state comes from rootf, the state below branch `node` from row x of exp(Q_{model_of[node]} r_c t_node).
+ * near (optional, [n]): per site the smallest |u - cum_j| over all its draws (class, root, every node). */
+void orc_simulate(int nn, const int* parent, const double* blen, int T, const int* leaf_of_taxon, int S, int C, int nmod,
+                  const double* Qs, const double* pis, const int* model_of, const double* rootf, const double* rates,
+                  const double* probs, uint64_t seed, uint64_t g0, long n, uint8_t* aln, int* classes, double* near) {
   int S2 = S * S, B = nn - 1, root = nn - 1;
-  double* lam = (double*)malloc(sizeof(double) * (S + 2 * S2));
-  double *V = lam + S, *Vinv = V + S2;
-  orc_eigen_reversible(S, Q, pi, lam, V, Vinv);
+  double* eig = eigen_set(nmod, S, Qs, pis);
+  const double* pi = rootf;
   double* P = (double*)malloc(sizeof(double) * (size_t)B * C * S2);
-  for (int b = 0; b < B; b++)
+  for (int b = 0; b < B; b++) {
+    SET_EIG(b);
     for (int c = 0; c < C; c++) orc_transition(S, lam, V, Vinv, blen[b] * rates[c], P + ((size_t)b * C + c) * S2);
+  }
   int* taxon_of = (int*)malloc(sizeof(int) * nn);
   for (int i = 0; i < nn; i++) taxon_of[i] = -1;
   for (int t = 0; t < T; t++) taxon_of[leaf_of_taxon[t]] = t;
   uint8_t* st = (uint8_t*)malloc(nn);
   for (long j = 0; j < n; j++) {
     uint64_t g = g0 + (uint64_t)j;
-    int c = draw_index(orc_uniform(seed, g, 0), probs, C);
+    double d = 1.0, *nr = near ? &d : 0;
+    int c = draw_index(orc_uniform(seed, g, 0), probs, C, nr);
     if (classes) classes[j] = c;
-    st[root] = (uint8_t)draw_index(orc_uniform(seed, g, 1), pi, S);
+    st[root] = (uint8_t)draw_index(orc_uniform(seed, g, 1), pi, S, nr);
     for (int node = nn - 2; node >= 0; node--) { /* parents have larger ids (post-order) */
       int x = st[parent[node]];
-      st[node] = (uint8_t)draw_index(orc_node_uniform(seed, g, (uint32_t)node), P + ((size_t)node * C + c) * S2 + (size_t)x * S, S);
+      st[node] = (uint8_t)draw_index(orc_node_uniform(seed, g, (uint32_t)node), P + ((size_t)node * C + c) * S2 + (size_t)x * S, S, nr);
       if (taxon_of[node] >= 0) aln[(size_t)taxon_of[node] * n + j] = st[node];
     }
+    if (near) near[j] = d;
   }
-  free(st); free(taxon_of); free(P); free(lam);
+  free(st); free(taxon_of); free(P); free(eig);
 }
 
 /* ------------------------------------------------------------------ simulations.continuous = yes (CoMap/CoMap.cpp:146, 213)
@@ -791,12 +819,13 @@ double orc_gamma_quantile(double a, double u) {
 }
 
 void orc_simulate_continuous(int nn, const int* parent, const double* blen, int T, const int* leaf_of_taxon, int S,
-                             const double* Q, const double* pi, double alpha, double p_inv, uint64_t seed, uint64_t g0,
-                             long n, uint8_t* aln, double* rates) {
+                             int nmod, const double* Qs, const double* pis, const int* model_of, const double* rootf,
+                             double alpha, double p_inv, uint64_t seed, uint64_t g0, long n, uint8_t* aln,
+                             double* rates, double* near) {
   int S2 = S * S, root = nn - 1;
-  double* lam = (double*)malloc(sizeof(double) * (S + 3 * S2));
-  double *V = lam + S, *Vinv = V + S2, *P = Vinv + S2;
-  orc_eigen_reversible(S, Q, pi, lam, V, Vinv);
+  double* eig = eigen_set(nmod, S, Qs, pis);
+  double* P = (double*)malloc(sizeof(double) * S);
+  const double* pi = rootf;
   int* taxon_of = (int*)malloc(sizeof(int) * nn);
   for (int i = 0; i < nn; i++) taxon_of[i] = -1;
   for (int t = 0; t < T; t++) taxon_of[leaf_of_taxon[t]] = t;
@@ -806,15 +835,23 @@ void orc_simulate_continuous(int nn, const int* parent, const double* blen, int 
     double u0 = orc_uniform(seed, g, 0), r = 0.0;
     if (u0 >= p_inv) r = orc_gamma_quantile(alpha, (u0 - p_inv) / (1.0 - p_inv)) / alpha / (1.0 - p_inv);
     if (rates) rates[j] = r;
-    st[root] = (uint8_t)draw_index(orc_uniform(seed, g, 1), pi, S);
+    double d = 1.0, *nr = near ? &d : 0;   /* the rate is no draw from a cumulative row: draw 0 has no boundary here */
+    st[root] = (uint8_t)draw_index(orc_uniform(seed, g, 1), pi, S, nr);
     for (int node = nn - 2; node >= 0; node--) {
       int x = st[parent[node]];
-      orc_transition(S, lam, V, Vinv, blen[node] * r, P);   /* getPij_t(d * rate) of this very site */
-      st[node] = (uint8_t)draw_index(orc_node_uniform(seed, g, (uint32_t)node), P + (size_t)x * S, S);
+      SET_EIG(node);
+      const double t = blen[node] * r;
+      for (int y = 0; y < S; y++) {   /* row x of getPij_t(d * rate) of this very site, summed as orc_transition sums it */
+        double s = 0;
+        for (int k = 0; k < S; k++) s += V[x * S + k] * exp(lam[k] * t) * Vinv[k * S + y];
+        P[y] = s;
+      }
+      st[node] = (uint8_t)draw_index(orc_node_uniform(seed, g, (uint32_t)node), P, S, nr);
       if (taxon_of[node] >= 0) aln[(size_t)taxon_of[node] * n + j] = st[node];
     }
+    if (near) near[j] = d;
   }
-  free(st); free(taxon_of); free(lam);
+  free(st); free(taxon_of); free(P); free(eig);
 }
 
 /* ------------------------------------------------------------------ Domain (CoMap/Domain.cpp:46-59, 113-122) */
@@ -942,10 +979,10 @@ void orc_pair_stats_inter(int kind, long N1, long N2, int B, int K, const double
  * score site j of batch 1 against site j of batch 2.  Replicates rep_begin..rep_end-1; global simulated-site
  * index g = ((rep*2 + batch) * repRAM + j).  Outputs have (rep_end-rep_begin)*repRAM entries. */
 void orc_null_intra(int nn, const int* parent, const double* blen, int T, const int* leaf_of_taxon, int S, int C,
-                    int K, const double* Q, const double* pi, const double* rates, const double* probs,
-                    const double* Bk, int method, int nonneg, int kind, const double* sparams, uint64_t seed,
-                    long rep_begin, long rep_end, long repRAM, const uint8_t* supplied, double* stat, int* rcmin,
-                    double* prmin, double* nmin) {
+                    int K, int nmod, const double* Qs, const double* pis, const double* Bks, const int* model_of,
+                    const double* rootf, const double* rates, const double* probs, int method, int nonneg, int kind,
+                    const double* sparams, uint64_t seed, long rep_begin, long rep_end, long repRAM,
+                    const uint8_t* supplied, double* stat, int* rcmin, double* prmin, double* nmin) {
   int B = nn - 1;
   uint8_t* aln = (uint8_t*)malloc((size_t)T * repRAM);
   uint32_t* masks = (uint32_t*)malloc(sizeof(uint32_t) * 256);
@@ -963,10 +1000,10 @@ void orc_null_intra(int nn, const int* parent, const double* blen, int T, const 
     for (int h = 0; h < 2; h++) {
       const uint8_t* a = aln;
       if (supplied) a = supplied + ((size_t)(rep - rep_begin) * 2 + h) * T * repRAM;
-      else orc_simulate(nn, parent, blen, T, leaf_of_taxon, S, C, Q, pi, rates, probs, seed,
-                        ((uint64_t)rep * 2 + h) * (uint64_t)repRAM, repRAM, aln, 0);
-      orc_map_sites(nn, parent, blen, T, leaf_of_taxon, repRAM, a, masks, S, C, K, Q, pi, rates, probs, Bk, method,
-                    nonneg, 0, cnt[h], ll, pr[h], rc[h], nr[h]);
+      else orc_simulate(nn, parent, blen, T, leaf_of_taxon, S, C, nmod, Qs, pis, model_of, rootf, rates, probs, seed,
+                        ((uint64_t)rep * 2 + h) * (uint64_t)repRAM, repRAM, aln, 0, 0);
+      orc_map_sites(nn, parent, blen, T, leaf_of_taxon, repRAM, a, masks, S, C, K, nmod, Qs, pis, Bks, model_of, rootf,
+                    rates, probs, method, nonneg, 0, cnt[h], ll, pr[h], rc[h], nr[h]);
     }
     for (long j = 0; j < repRAM; j++) {
       size_t o = (size_t)(rep - rep_begin) * repRAM + j;

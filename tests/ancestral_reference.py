@@ -126,3 +126,33 @@ def model_set(S, seed):
         pis.append(pi)
     rf = rng.uniform(0.5, 1.5, S)
     return np.array(Qs), np.array(pis), rf / rf.sum()
+
+
+def brute_force_joint(parent, blen, lot, Qs, rates, probs, root_freqs, aln, masks=None, model_of_branch=None):
+    """every assignment of states to ALL nodes (a leaf takes the states compatible with its code), per site and class ->
+    dict(L [N] site likelihood, pair [nn, C, N, S, S] Pr(class c, father = x, node = y, data) of every branch,
+    node [nn, C, N, S] Pr(class c, node = x, data)); divide by L for the posteriors"""
+    parent = np.asarray(parent)
+    nn = len(parent)
+    pi = np.asarray(root_freqs, dtype=np.float64)
+    S, C = len(pi), len(rates)
+    P = transition_matrices(parent, blen, Qs, rates, model_of_branch)
+    e = _leaf_vectors(aln, S, masks)
+    N = e.shape[1]
+    taxon = {int(n): t for t, n in enumerate(lot)}
+    root = int(np.flatnonzero(parent < 0)[0])
+    L, pair, node = np.zeros(N), np.zeros((nn, C, N, S, S)), np.zeros((nn, C, N, S))
+    for i in range(N):
+        allowed = [np.flatnonzero(e[taxon[n], i]) if n in taxon else range(S) for n in range(nn)]
+        for st in itertools.product(*allowed):
+            for c in range(C):
+                w = probs[c] * pi[st[root]]
+                for b in range(nn):
+                    if parent[b] >= 0:
+                        w *= P[c, b, st[parent[b]], st[b]]
+                L[i] += w
+                for b in range(nn):
+                    node[b, c, i, st[b]] += w
+                    if parent[b] >= 0:
+                        pair[b, c, i, st[parent[b]], st[b]] += w
+    return dict(L=L, pair=pair, node=node)

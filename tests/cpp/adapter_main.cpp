@@ -1,6 +1,10 @@
 // Test driver for include/comap_mi355x_adapter.hpp (the C++ mirror of the reference's interface).
 //   adapter_main domain <lo> <hi> <n> <x>...         -> prints getIndex(x) or -1 per x (host logic only, no GPU)
 //   adapter_main run <input.bin> <output.bin>        -> getVectors + computeIntraStats with null on the GPU
+//   adapter_main mapnull <input.bin> <output.bin>    -> getVectors + getNullDistributionIntraDR, homogeneous or under a model set (GPU);
+//      input.bin: header, tree as for "run"; int32 M; M == 0: f64 Q[S*S], pi[S]; M > 0: f64 Qs[M*S*S], pis[M*S], int32
+//      modelOfBranch[nn], f64 rootFrequencies[S]; then f64 rates[C], probs[C]; uint8 aln[T*N]
+//      output.bin: f64 counts[N*B]; then per null pair f64 stat, prMin, nMin; int32 rcMin
 //   adapter_main groups <tree.bin>                   -> ClusterTools::getGroups + io::writeGroups to stdout (host only);
 //      tree.bin: int32 n, maxGroupSize; int32 merge[2(n-1)]; f64 dmax, stat, nmin [n-1]; int32 coords[n], isConstant[n]
 //   adapter_main cluster <input.bin> <method> <maxsize>   -> ClusterTools::cluster + getGroups + writeGroups of the observed data (GPU)
@@ -96,6 +100,45 @@ int main(int argc, char** argv) {
       wr(out, mapping->data(), static_cast<size_t>(N) * eng.getNumberOfBranches());
       cmx::Vdouble norms = cmx::AnalysisTools::computeNorms(*mapping);
       wr(out, norms.data(), norms.size());
+      return 0;
+    }
+    if (argc == 4 && std::strcmp(argv[1], "mapnull") == 0) {
+      std::ifstream in(argv[2], std::ios::binary);
+      int32_t h[8], M;
+      uint64_t seed;
+      rd(in, h, 8);
+      rd(in, &seed, 1);
+      const int nn = h[0], T = h[1], S = h[2], C = h[3], N = h[4];
+      cmx::TreeArrays t;
+      cmx::ModelArrays m;
+      t.parent.resize(nn); t.branchLengths.resize(nn); t.leafOfTaxon.resize(T);
+      rd(in, t.parent.data(), nn); rd(in, t.branchLengths.data(), nn); rd(in, t.leafOfTaxon.data(), T);
+      rd(in, &M, 1);
+      m.nbStates = S;
+      if (M == 0) {
+        m.generator.resize(S * S); m.frequencies.resize(S);
+        rd(in, m.generator.data(), S * S); rd(in, m.frequencies.data(), S);
+      } else {   // SubstitutionModelSet: one generator per branch, a root frequency set
+        m.generators.resize(static_cast<size_t>(M) * S * S); m.generatorFrequencies.resize(static_cast<size_t>(M) * S);
+        m.modelOfBranch.resize(nn); m.rootFrequencies.resize(S);
+        rd(in, m.generators.data(), m.generators.size()); rd(in, m.generatorFrequencies.data(), m.generatorFrequencies.size());
+        rd(in, m.modelOfBranch.data(), nn); rd(in, m.rootFrequencies.data(), S);
+      }
+      m.rates.resize(C); m.rateProbabilities.resize(C);
+      rd(in, m.rates.data(), C); rd(in, m.rateProbabilities.data(), C);
+      std::vector<uint8_t> aln(static_cast<size_t>(T) * N);
+      rd(in, aln.data(), aln.size());
+      cmx::Engine eng(t, m, 0);
+      auto mapping = cmx::CoETools::getVectors(eng, aln.data(), N);
+      cmx::CorrelationStatistic stat;
+      std::vector<cmx::NullDistributionRow> rows;
+      cmx::AnalysisTools::getNullDistributionIntraDR(eng, stat, seed, h[5], h[6], &rows, nullptr, nullptr);
+      std::ofstream out(argv[3], std::ios::binary);
+      wr(out, mapping->data(), static_cast<size_t>(N) * eng.getNumberOfBranches());
+      for (const auto& r : rows) {
+        double v[3] = {r.stat, r.prMin, r.nMin};
+        wr(out, v, 3); wr(out, &r.rcMin, 1);
+      }
       return 0;
     }
     if (argc == 3 && std::strcmp(argv[1], "groups") == 0) {   // host only: a clustering tree -> the groups table

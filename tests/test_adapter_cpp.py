@@ -250,3 +250,39 @@ def test_cpp_analysis_tools_matrices(adapter_exe, tmp_path, n1, n2, dim):
         rel_close(np.diag(ind), np.diag(cor(a, b)), 1e-9, 1e-12)
     else:
         assert "DimensionException" in r.stdout and "independant comparisons" in r.stdout
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["p20x4", "n4x4", "homogeneous"])
+def test_cpp_model_arrays_equal_the_python_engine(adapter_exe, tmp_path, name):
+    """ModelArrays::generators / generatorFrequencies / rootFrequencies / modelOfBranch (a SubstitutionModelSet) and the
+    homogeneous ModelArrays::generator / frequencies: the mapping and one null through the adapter are the bytes the Python
+    engine gives for the same model -- both are thin over the same C-ABI calls; the numbers themselves are held against
+    the model-set oracle in tests/test_gpu_model_sets.py"""
+    import model_sets as ms
+    c = ms.case("p20x4" if name == "homogeneous" else name)
+    N, rep_cpu, rep_ram, seed = 70, 2, 50, 777
+    aln = ms.alignment(c, N)
+    nn, T, S, C = len(c["parent"]), len(c["lot"]), c["S"], c["C"]
+    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
+    with open(inp, "wb") as f:
+        f.write(struct.pack("<8i", nn, T, S, C, N, rep_cpu, rep_ram, 1) + struct.pack("<Q", seed))
+        f.write(c["parent"].astype(np.int32).tobytes() + c["blen"].tobytes() + c["lot"].astype(np.int32).tobytes())
+        if name == "homogeneous":
+            f.write(struct.pack("<i", 0) + c["Qs"][1].tobytes() + c["pis"][1].tobytes())
+            eng = engine.Engine(c["parent"], c["blen"], c["lot"], c["Qs"][1], c["pis"][1], c["rates"], c["probs"])
+        else:
+            f.write(struct.pack("<i", 3) + c["Qs"].tobytes() + c["pis"].tobytes() + c["mob"].astype(np.int32).tobytes() + c["root"].tobytes())
+            eng = ms.engine_of(c)
+        f.write(c["rates"].tobytes() + c["probs"].tobytes() + aln.tobytes())
+    subprocess.check_call([adapter_exe, "mapnull", str(inp), str(outp)])
+    raw = open(outp, "rb").read()
+    B = nn - 1
+    counts = np.frombuffer(raw, dtype="<f8", count=N * B).reshape(N, B, 1)
+    rec = np.dtype([("stat", "<f8"), ("pr", "<f8"), ("nm", "<f8"), ("rc", "<i4")])
+    rows = np.frombuffer(raw, dtype=rec, count=rep_cpu * rep_ram, offset=N * B * 8)
+    assert len(raw) == N * B * 8 + rep_cpu * rep_ram * rec.itemsize
+    assert np.array_equal(counts, eng.map_sites(aln)["counts"])
+    nl = eng.null_intra(engine.STAT_CORRELATION, seed, 0, rep_cpu, rep_ram)
+    assert np.array_equal(rows["stat"], nl["stat"], equal_nan=True) and np.array_equal(rows["rc"], nl["rcmin"])
+    assert np.array_equal(rows["pr"], nl["prmin"]) and np.array_equal(rows["nm"], nl["nmin"])
