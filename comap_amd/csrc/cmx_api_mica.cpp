@@ -20,6 +20,22 @@ static cmx_status default_mi_masks(cmx_ctx* ctx, int nalpha, const uint32_t** d_
   return CMX_OK;
 }
 
+// the scratch of alignment k = 1, 2 that `path` reads (or writes: the classification kernels fill C, flag, gap and S on every path)
+static cmx_status mica_side_scratch(cmx_ctx* ctx, MicaPath path, int Tp, int k, MicaSide* s) {
+  const std::string t = std::to_string(k);
+  const size_t n = s->n, codes = (size_t)Tp * (n + kMicaCodePad);
+  if (path == kMicaDna1) CMX_TRY(scratch(ctx, ("mica_H" + t).c_str(), 32 * (size_t)Tp * n, &s->H));
+  CMX_TRY(scratch(ctx, ("mica_C" + t).c_str(), codes, &s->C));
+  CMX_TRY(scratch(ctx, ("mica_f" + t).c_str(), n, &s->flag));
+  CMX_TRY(scratch(ctx, ("mica_g" + t).c_str(), n, &s->gap));
+  CMX_TRY(scratch(ctx, ("mica_S" + t).c_str(), n, &s->S));
+  if (path != kMicaProtein4) return CMX_OK;
+  CMX_TRY(scratch(ctx, ("mica_info" + t).c_str(), mica4_info_words(n), &s->info));
+  CMX_TRY(scratch(ctx, ("mica_order" + t).c_str(), n, &s->order));
+  CMX_TRY(scratch(ctx, ("mica_Cs" + t).c_str(), codes, &s->Cs));
+  return scratch(ctx, ("mica_Ss" + t).c_str(), n, &s->Ss);
+}
+
 cmx_status cmx_mi_columns_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* d_masks, const uint8_t* d_aln1,
                               size_t n1, size_t ld1, const uint8_t* d_aln2, size_t n2, size_t ld2, double* d_mi,
                               double* d_hjoint, size_t ldo, double* d_h1, double* d_h2, void* stream) {
@@ -31,44 +47,21 @@ cmx_status cmx_mi_columns_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_
   if (!d_aln1 || !d_mi || !d_hjoint || ntaxa < 1 || n1 == 0 || n2 == 0 || ld1 < n1 || ld2 < n2 || ldo < n2)
     return fail(ctx, CMX_ERR_INVALID, "cmx_mi_columns: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // MFMA path (one-hot Gram) whenever the c ln c table fits the kernel's LDS; columns with ambiguous symbols are
-  // left to the LDS-table kernel pair by pair
-  MicaWork w{};
-  const bool mfma = ntaxa <= 2047;   // table + operand buffers within 64 KiB of LDS
-  if (mfma) {
-    w.Tp = (ntaxa + 31) / 32 * 32;
-    const size_t hb = 32 * (size_t)w.Tp;
-    const bool needH = mica_needs_onehot(nalpha, w.Tp);   // 32 Tp bytes per column: only where a kernel reads them
-    CMX_TRY(scratch(ctx, "mica_H1", needH ? hb * n1 : 16, &w.H1));
-    CMX_TRY(scratch(ctx, "mica_C1", (size_t)w.Tp * (n1 + kMicaCodePad), &w.C1));
-    CMX_TRY(scratch(ctx, "mica_f1", n1, &w.flag1));
-    CMX_TRY(scratch(ctx, "mica_g1", n1, &w.gap1));
-    CMX_TRY(scratch(ctx, "mica_S1", n1, &w.S1));
-    if (!intra) {
-      CMX_TRY(scratch(ctx, "mica_H2", needH ? hb * n2 : 16, &w.H2));
-      CMX_TRY(scratch(ctx, "mica_C2", (size_t)w.Tp * (n2 + kMicaCodePad), &w.C2));
-      CMX_TRY(scratch(ctx, "mica_f2", n2, &w.flag2));
-      CMX_TRY(scratch(ctx, "mica_g2", n2, &w.gap2));
-      CMX_TRY(scratch(ctx, "mica_S2", n2, &w.S2));
-    }
-    CMX_TRY(scratch(ctx, "mica_ftab", ((size_t)(ntaxa + 1) + 2 * ((size_t)nalpha * nalpha * ntaxa + 1) + 2), &w.ftab));
+  // the MFMA paths (one-hot Gram) serve the columns without partial ambiguity codes, the LDS-table kernel the pairs of the
+  // others
+  MicaWork w{{{n1}, {n2}}};   // the column counts; every pointer null
+  w.Tp = mica_padded_taxa(ntaxa);
+  const MicaPath path = mica_path(nalpha, ntaxa, n1, n2);
+  if (path != kMicaTables && path != kMicaRefused) {
+    CMX_TRY(mica_side_scratch(ctx, path, w.Tp, 1, &w.s[0]));
+    if (intra) w.s[1] = w.s[0];
+    else CMX_TRY(mica_side_scratch(ctx, path, w.Tp, 2, &w.s[1]));
+    CMX_TRY(scratch(ctx, "mica_ftab", mica_ftab_entries(nalpha, ntaxa), &w.ftab));
     CMX_TRY(scratch(ctx, "mica_any", 1, &w.anyflag));
-    if (nalpha == 20) {   // block info of the four-wave kernel, padded to whole tiles of 12 columns
-      CMX_TRY(scratch(ctx, "mica_info1", ((n1 + 11) / 12 * 4 + 4), &w.info1));
-      CMX_TRY(scratch(ctx, "mica_order1", n1, &w.order1));
-      CMX_TRY(scratch(ctx, "mica_Cs1", (size_t)w.Tp * (n1 + kMicaCodePad), &w.Cs1));
-      CMX_TRY(scratch(ctx, "mica_Ss1", n1, &w.Ss1));
-      if (mica4_serves(nalpha, w.Tp, n1, intra ? n1 : n2)) CMX_TRY(scratch(ctx, "mica_img2", mica4_image_bytes(w.Tp, intra ? n1 : n2), &w.img2));
-      if (!intra) {
-        CMX_TRY(scratch(ctx, "mica_info2", ((n2 + 11) / 12 * 4 + 4), &w.info2));
-        CMX_TRY(scratch(ctx, "mica_order2", n2, &w.order2));
-        CMX_TRY(scratch(ctx, "mica_Cs2", (size_t)w.Tp * (n2 + kMicaCodePad), &w.Cs2));
-        CMX_TRY(scratch(ctx, "mica_Ss2", n2, &w.Ss2));
-      }
-    }
+    if (path == kMicaProtein4) CMX_TRY(scratch(ctx, "mica_img2", mica4_image_bytes(w.Tp, n2), &w.img2));
   }
-  HIP_TRY(ctx, launch_mi_columns(nalpha, ntaxa, d_masks, d_aln1, n1, ld1, d_aln2, n2, ld2, intra ? 1 : 0, d_mi, d_hjoint,
-                                 ldo, d_h1, intra ? nullptr : d_h2, mfma ? &w : nullptr, (hipStream_t)stream));
+  HIP_TRY(ctx, launch_mi_columns(nalpha, ntaxa, d_masks, d_aln1, ld1, d_aln2, ld2, intra ? 1 : 0, d_mi, d_hjoint, ldo, d_h1,
+                                 intra ? nullptr : d_h2, w, (hipStream_t)stream));
   return CMX_OK;
 }
 

@@ -306,35 +306,48 @@ hipError_t launch_inter_rows(const double* d_stat, size_t ldo, size_t n2, const 
 hipError_t launch_mi_pairs(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t ld1, const uint8_t* d_aln2,
                            size_t ld2, const int64_t* d_idx1, const int64_t* d_idx2, size_t npairs, double* d_mi,
                            double* d_hj, hipStream_t stream);
-// scratch of the MFMA Mica path (all device pointers; a null H1 = LDS-table kernel only)
+// The column stage.  mica_path alone decides which kernels serve a call -- the LDS-table kernel only; beside it the four-wave
+// or the eight-wave protein kernel, the four-wave or the one-column-per-tile nucleotide kernel; or none (hipErrorInvalidValue):
+// cmx_mi_columns_dev requests scratch from it, launch_mi_columns dispatches on it.  Every size the host shares with a Mica
+// kernel is a function beside that kernel (mica_ftab_entries, mica4_info_words, mica4_image_bytes, the *_lds_bytes).
+enum MicaPath { kMicaTables, kMicaProtein4, kMicaProtein8, kMicaDna4, kMicaDna1, kMicaRefused };
+MicaPath mica_path(int A, int T, size_t n1, size_t n2);
+constexpr int mica_padded_taxa(int T) { return (T + 31) / 32 * 32; }   // whole MFMA steps of 32 taxa
 constexpr int kMicaLdsF2 = 4096;   // entries of f2 the weighted four-wave kernel keeps in LDS (m < 4096: cells of up to ten taxa)
-constexpr int kMicaCodePad = 64;   // columns of "no row" symbols behind the last column of C1 / C2 (the four-wave kernels read whole tiles: 12 / 64 columns)
-struct MicaWork {
-  int8_t *H1, *H2;         // one-hot [n][32][Tp] int8 where mica_needs_onehot (the one-column-per-tile kernel), else a 16-byte stand-in
-  uint8_t *C1, *C2;        // [n + kMicaCodePad][Tp] one-hot row of each taxon (state, A = unknown, 255 = none): the packed protein kernel's operands
-  uint8_t *flag1, *flag2;  // [n] column has ambiguous symbols other than "unknown" (-> LDS-table kernel)
-  uint8_t *gap1, *gap2;    // [n] column has unknowns (gap / X / N: compatible with every state; handled on the matrix cores)
-  double *S1, *S2;         // [n] sum_a f(count_a)
-  double* ftab;            // [T + 1] c ln c, then [A*A*T + 1] f2[m] = (m / A^2) ln(m / A^2) (pairs with unknowns), then 0 and f2[M0 ..] again
-  int* anyflag;            // some column of either alignment has ambiguous symbols
-  unsigned *info1, *info2;   // per block of three SORTED columns: not-served and has-unknowns bits (cmx_mica4.hip; NULL: not used)
-  unsigned *order1, *order2; // [n] original column of a sorted position (columns without unknowns first, stable)
-  uint8_t *Cs1, *Cs2;        // [n + kMicaCodePad][Tp] symbol bytes in sorted order
-  double *Ss1, *Ss2;         // [n] column sums in sorted order
-  void* img2;                // mica4_image_bytes(Tp, n2): the second alignment's expanded operands by tile (cmx_mica4.hip)
-  int Tp;                  // T rounded up to a multiple of 32 (taxa per MFMA step)
+constexpr int kMicaCodePad = 64;   // columns of "no row" symbols behind the last column of C / Cs (the four-wave kernels read whole tiles: 12 / 64 columns)
+// scratch of one alignment on the MFMA paths (device pointers; null where the path does not read it)
+struct MicaSide {
+  size_t n;          // columns
+  int8_t* H;         // [n][32][Tp] one-hot int8 (kMicaDna1)
+  uint8_t* C;        // [n + kMicaCodePad][Tp] one-hot row of each taxon (state, A = unknown, 63 = none)
+  uint8_t* flag;     // [n] column has ambiguous symbols other than "unknown" (-> LDS-table kernel)
+  uint8_t* gap;      // [n] column has unknowns (gap / X / N: compatible with every state; handled on the matrix cores)
+  double* S;         // [n] sum_a f(count_a)
+  unsigned* info;    // [mica4_info_words(n)] per block of three SORTED columns: not-served and has-unknowns bits (kMicaProtein4, as the four below)
+  unsigned* order;   // [n] original column of a sorted position (columns without unknowns first, stable)
+  uint8_t* Cs;       // [n + kMicaCodePad][Tp] symbol bytes in sorted order
+  double* Ss;        // [n] column sums in sorted order
 };
-bool mica_needs_onehot(int A, int Tp);   // whether launch_mi_columns reads MicaWork::H1 / H2 for this alphabet
-hipError_t launch_mi_columns(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t n1, size_t ld1,
-                             const uint8_t* d_aln2, size_t n2, size_t ld2, int intra, double* d_mi, double* d_hj,
-                             size_t ldo, double* d_h1, double* d_h2, const MicaWork* work, hipStream_t stream);
-// (cmx_mica4.hip) the four-wave protein kernel (unknowns included; partial ambiguity codes are not served)
-bool mica4_serves(int A, int Tp, size_t n1, size_t n2);
+struct MicaWork {
+  MicaSide s[2];     // the two alignments (n always set, the rest as mica_path(A, T, s[0].n, s[1].n) needs it); intra layout: s[1] == s[0]
+  double* ftab;      // [mica_ftab_entries(A, T)] (mica_ftable_kernel)
+  int* anyflag;      // some column of either alignment has ambiguous symbols
+  void* img2;        // [mica4_image_bytes(Tp, s[1].n)] the second alignment's expanded operands by tile (kMicaProtein4)
+  int Tp;            // mica_padded_taxa(T)
+};
+size_t mica_ftab_entries(int A, int T);
+// dynamic LDS beyond the 64 KiB a kernel may use unasked
+template <class K>
+hipError_t mica_allow_lds(K* kernel, size_t bytes) {
+  if (bytes <= 64 * 1024) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+hipError_t launch_mi_columns(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t ld1, const uint8_t* d_aln2,
+                             size_t ld2, int intra, double* d_mi, double* d_hj, size_t ldo, double* d_h1, double* d_h2,
+                             const MicaWork& work, hipStream_t stream);
+// (cmx_mica4.hip) the four-wave kernels (unknowns included; partial ambiguity codes are not served): proteins, nucleotides
+size_t mica4_info_words(size_t n);
 size_t mica4_image_bytes(int Tp, size_t n2);
-hipError_t launch_mica4(int T, const MicaWork* wk, size_t n1, size_t n2, int intra, double* d_mi, double* d_hj, size_t ldo,
-                        hipStream_t stream);
-// the four-wave nucleotide kernel (unknowns included; partial ambiguity codes are not served)
-bool mica_dna4_serves(int A, int Tp, size_t n1, size_t n2);
-hipError_t launch_mica_dna4(int T, const MicaWork* wk, size_t n1, size_t n2, int intra, double* d_mi, double* d_hj, size_t ldo,
-                            hipStream_t stream);
+hipError_t launch_mica4(int T, const MicaWork& wk, int intra, double* d_mi, double* d_hj, size_t ldo, hipStream_t stream);
+hipError_t launch_mica_dna4(int T, const MicaWork& wk, int intra, double* d_mi, double* d_hj, size_t ldo, hipStream_t stream);
 }  // namespace cmx

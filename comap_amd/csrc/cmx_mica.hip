@@ -294,6 +294,8 @@ __global__ void mica_ftable_kernel(int T, int A, double* __restrict__ f, int* __
     if (c >= M0) hi[c - M0 + 1] = fv;
   }
 }
+// the three tables: T + 1 entries of f, A^2 T + 1 of f2, and room for a zero and all of f2 again
+size_t mica_ftab_entries(int A, int T) { return (size_t)(T + 1) + 2 * ((size_t)A * A * T + 1) + 2; }
 
 // One workgroup (8 waves) per 8 x 4 tile of column pairs (8 columns of the first alignment, 4 of the second), wave w owns
 // the 2 x 2 sub-tile (rows 2*(w/2).., columns 2*(w%2)..): 64 accumulator registers, so that two workgroups share a CU
@@ -464,6 +466,10 @@ __global__ __launch_bounds__(512, 2) void mica_mfma_kernel(int T, int Tp, const 
     }
   }
 }
+// mica_smem of mica_mfma_kernel: f[0 .. T], two buffers of twelve operand tiles
+static size_t mica_mfma_lds_bytes(int T) {
+  return (((size_t)(T + 1) * 8 + 15) & ~(size_t)15) + 2 * (kMicaTileI + kMicaTileJ) * 64 * sizeof(cmx_i4);
+}
 
 // ---- protein alphabet, packed tiles.  A column needs 21 one-hot rows (20 states + the pseudo-state of unknowns), a
 // 32-row MFMA tile per column wastes a third of the rows and (32/21)^2 of the matrix work AND of the table epilogue.
@@ -487,7 +493,8 @@ __device__ __forceinline__ void mica3_tile(int T, int Tp, const uint8_t* __restr
   double* ftab = reinterpret_cast<double*>(mica_smem);                       // [T + 1]
   cmx_i4* ops = reinterpret_cast<cmx_i4*>(mica_smem + (((size_t)(T + 1) * 8 + 15) & ~(size_t)15));  // [4][12][64]
   constexpr int NOP = 12, NI = 8;   // operand tiles per k-step: 8 of the first alignment (4 blocks), 4 of the second
-  uint8_t* codes = reinterpret_cast<uint8_t*>(ops + 4 * NOP * 64) + 16384;   // the unknowns' path lays 8 x 8 KiB over the operand buffers + 16 KiB          // [18][Tp]: the tile's columns, one byte per taxon
+  // [18][Tp]: the tile's columns, one byte per taxon (16 KiB behind the operand buffers: the unknowns' path lays 8 x 8 KiB over both)
+  uint8_t* codes = reinterpret_cast<uint8_t*>(ops + 4 * NOP * 64) + 16384;
   double* Scol = reinterpret_cast<double*>(codes + (size_t)(kMica3I + kMica3J) * Tp);   // [18] S of the tile's columns (12 + 6)
   int* fcol = reinterpret_cast<int*>(Scol + 18);   // [18] bit 0 partial ambiguity codes, bit 1 unknowns, bit 2 past the end
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wi = w >> 1, wj = w & 1;
@@ -699,15 +706,22 @@ __device__ __forceinline__ void mica3_tile(int T, int Tp, const uint8_t* __restr
       const uint8_t *__restrict__ gap2, const double *__restrict__ S2, const double *__restrict__ ftab_g, int intra,             \
       double *__restrict__ mi, double *__restrict__ hj, size_t ldo, unsigned ntx
 #define CMX_MICA3_ARGS T, Tp, C1, n1, flag1, gap1, S1, C2, n2, flag2, gap2, S2, ftab_g, intra, mi, hj, ldo, ntx
-// the proteins the four-wave kernel does not serve: more than 512 taxa, or operands past its 31-bit offsets (mica4_serves, cmx_mica4.hip)
+// the proteins the four-wave kernel does not serve: more than 512 taxa, or operands past its 31-bit offsets (mica_path)
 __global__ __launch_bounds__(512, 4) void mica_mfma3_kernel(CMX_MICA3_PARAMS, unsigned ntiles, unsigned per_xcd) {
   // XCD-aware tile order.  Workgroups are dealt to the 8 XCDs round-robin (blockIdx.x % 8) and each XCD has its own L2:
   // XCD x takes a contiguous run of the row-major tile order, so that the tiles which complete an output cache line (a
-  // tile writes 48-byte pieces of 12 rows) and re-read the same symbol columns meet in one L2.  At 5000 x 5000 x 256 the
-  // launch time did not change (6.31 ms either way): kept for the traffic, not for the time.
+  // tile writes 48-byte pieces of 12 rows) and re-read the same symbol columns meet in one L2.  Measured while this kernel
+  // still served 256 taxa: at 5000 x 5000 columns the launch time did not change (6.31 ms either way).  Kept for the
+  // traffic, not for the time.
   const unsigned tlin = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
   if ((blockIdx.x >> 3) >= per_xcd || tlin >= ntiles) return;
   mica3_tile(CMX_MICA3_ARGS, tlin);
+}
+// mica_smem of mica_mfma3_kernel: f[0 .. T], four buffers of twelve operand tiles, 16 KiB (the unknowns' path lays 8 x 8 KiB
+// over them), the tile's 18 symbol columns, their 18 sums and (20 slots for) their 18 flag words
+static size_t mica_mfma3_lds_bytes(int T, int Tp) {
+  return (((size_t)(T + 1) * 8 + 15) & ~(size_t)15) + 4 * 12 * 64 * sizeof(cmx_i4) + 16384 + (size_t)(kMica3I + kMica3J) * Tp +
+         18 * sizeof(double) + 20 * sizeof(int);
 }
 // Column entropies (SiteTools::entropy per site; Mica.cpp:349-361 h1 / h2).  Two columns per wave, lane 32 c + a = state a of
 // column c: every state's frequency is summed over the taxa in taxon order by its own lane and the A terms are added in
@@ -741,68 +755,72 @@ __global__ __launch_bounds__(64) void column_entropy_kernel(int T, const uint32_
   if (a == 0 && i < n) h[i] = s;
 }
 
-// the one-hot matrices H [n][32][Tp] are operands of the one-column-per-tile kernel only: nucleotides above 256 taxa
-bool mica_needs_onehot(int A, int Tp) { return A == 4 && Tp > 256; }
+// Which kernels serve a call.  Above 2 047 taxa the c ln c table and the operand buffers pass 64 KiB of LDS (and the eight-wave
+// kernel's 16-bit counts their range): LDS tables alone.  Proteins: the four-wave kernel holds up to sixteen k-steps = 512
+// taxa of operands in registers and addresses the symbol arrays and one operand image with 31-bit byte offsets; the
+// eight-wave kernel takes the rest.  Nucleotides: the four-wave kernel up to eight k-steps = 256 taxa (its whole weighted
+// table in LDS), the same 31-bit offsets -- past them nothing serves the call; the one-column-per-tile kernel above 256 taxa.
+MicaPath mica_path(int A, int T, size_t n1, size_t n2) {
+  if (T > 2047) return kMicaTables;
+  const int Tp = mica_padded_taxa(T);
+  const bool off31 = (std::max(n1, n2) + kMicaCodePad) * (size_t)Tp < 0x7fffffffull;
+  if (A == 20) return Tp <= 512 && off31 && mica4_image_bytes(Tp, n2) / 2 < 0x7fffffffull ? kMicaProtein4 : kMicaProtein8;
+  if (Tp > 256) return kMicaDna1;
+  return off31 ? kMicaDna4 : kMicaRefused;
+}
 
-hipError_t launch_mi_columns(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t n1, size_t ld1,
-                             const uint8_t* d_aln2, size_t n2, size_t ld2, int intra, double* d_mi, double* d_hj,
-                             size_t ldo, double* d_h1, double* d_h2, const MicaWork* work, hipStream_t stream) {
+hipError_t launch_mi_columns(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t ld1, const uint8_t* d_aln2,
+                             size_t ld2, int intra, double* d_mi, double* d_hj, size_t ldo, double* d_h1, double* d_h2,
+                             const MicaWork& work, hipStream_t stream) {
   if (A != 20 && A != 4) return hipErrorInvalidValue;
-  const size_t ntiles = ((n2 + 15) / 16) * n1;
-  dim3 grid((unsigned)std::min<size_t>(ntiles, 8192));
-  const size_t lds = sizeof(double) * A * A * 16;
-  const int* anyf = (work && work->H1) ? work->anyflag : nullptr;
-  // MFMA path for the columns without ambiguous symbols (work->H1 etc. non-null); the LDS kernel then only serves
-  // the pairs that involve an ambiguous column.
-  const uint8_t *f1 = nullptr, *f2 = nullptr;
-  if (work && work->H1) {
-    const int Tp = work->Tp;
-    hipLaunchKernelGGL(mica_ftable_kernel, dim3((unsigned)((A * A * T) / 256 + 1)), dim3(256), 0, stream, T, A, work->ftab, work->anyflag);
-    auto classify = [&](const uint8_t* aln, size_t n, size_t ld, int8_t* H, uint8_t* C, uint8_t* flag, uint8_t* gap, double* S) {
-      if (mica_needs_onehot(A, Tp))
-        hipLaunchKernelGGL(mica_onehot_kernel, dim3((unsigned)(n + kMicaCodePad)), dim3(256), 0, stream, A, T, Tp, d_masks, aln, ld, H, C, flag, gap,
-                           S, work->anyflag, n);
-      else   // codes, flags and column sums only (the packed kernels expand the symbol bytes themselves): 64 columns per workgroup
-        hipLaunchKernelGGL(mica_codes_kernel, dim3((unsigned)((n + kMicaCodePad + 63) / 64)), dim3(256), 0, stream, A, T, Tp, d_masks, aln, ld, C, flag,
-                           gap, S, work->anyflag, n, (size_t)kMicaCodePad);
-    };
-    classify(d_aln1, n1, ld1, work->H1, work->C1, work->flag1, work->gap1, work->S1);
-    if (!intra) classify(d_aln2, n2, ld2, work->H2, work->C2, work->flag2, work->gap2, work->S2);
-    const size_t lds2 = (((size_t)(T + 1) * 8 + 15) & ~(size_t)15) + 2 * (kMicaTileI + kMicaTileJ) * 64 * sizeof(cmx_i4);
-    if (A == 20 && mica4_serves(A, Tp, n1, n2) && work->info1 && work->img2) {
-      // proteins up to 512 taxa: the four-wave kernel (cmx_mica4.hip), unknowns included
-      const hipError_t e4 = launch_mica4(T, work, n1, n2, intra, d_mi, d_hj, ldo, stream);
-      if (e4 != hipSuccess) return e4;
-    } else if (A == 20) {
-      // the proteins it does not serve: the eight-wave packed kernel
+  const MicaSide &s1 = work.s[0], &s2 = work.s[1];
+  const size_t n1 = s1.n, n2 = s2.n;
+  const int Tp = work.Tp;
+  const MicaPath path = mica_path(A, T, n1, n2);
+  // codes, flags, column sums (and, for the one-column-per-tile kernel, the one-hot matrices) of one alignment
+  auto classify = [&](const uint8_t* aln, size_t ld, const MicaSide& s) {
+    if (path == kMicaDna1)
+      hipLaunchKernelGGL(mica_onehot_kernel, dim3((unsigned)(s.n + kMicaCodePad)), dim3(256), 0, stream, A, T, Tp, d_masks, aln, ld, s.H, s.C,
+                         s.flag, s.gap, s.S, work.anyflag, s.n);
+    else   // the packed kernels expand the symbol bytes themselves: 64 columns per workgroup
+      hipLaunchKernelGGL(mica_codes_kernel, dim3((unsigned)((s.n + kMicaCodePad + 63) / 64)), dim3(256), 0, stream, A, T, Tp, d_masks, aln, ld,
+                         s.C, s.flag, s.gap, s.S, work.anyflag, s.n, (size_t)kMicaCodePad);
+  };
+  // the MFMA paths serve the columns without partial ambiguity codes, the LDS-table kernel behind them the pairs that
+  // involve a flagged column; kMicaTables has no flags (null) and that kernel serves every pair
+  if (path != kMicaTables && path != kMicaRefused) {
+    hipLaunchKernelGGL(mica_ftable_kernel, dim3((unsigned)((A * A * T) / 256 + 1)), dim3(256), 0, stream, T, A, work.ftab, work.anyflag);
+    classify(d_aln1, ld1, s1);
+    if (!intra) classify(d_aln2, ld2, s2);
+  }
+  hipError_t e = hipSuccess;
+  switch (path) {
+    case kMicaTables: break;
+    case kMicaRefused: return hipErrorInvalidValue;
+    case kMicaProtein4: e = launch_mica4(T, work, intra, d_mi, d_hj, ldo, stream); break;
+    case kMicaDna4: e = launch_mica_dna4(T, work, intra, d_mi, d_hj, ldo, stream); break;
+    case kMicaProtein8: {
       const unsigned ntx = (unsigned)((n2 + kMica3J - 1) / kMica3J), nty = (unsigned)((n1 + kMica3I - 1) / kMica3I);
       const unsigned ntiles = ntx * nty, per_xcd = (ntiles + 7) / 8;
-      const size_t lds3 = lds2 + 2 * (kMica3I / 3 * 2 + kMica3J / 3 * 2) * 64 * sizeof(cmx_i4) + 16384 + (size_t)(kMica3I + kMica3J) * Tp + 18 * sizeof(double) + 20 * sizeof(int);
-      if (lds3 > 64 * 1024) {
-        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&mica_mfma3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-        if (ea != hipSuccess) return ea;
-      }
-      hipLaunchKernelGGL(mica_mfma3_kernel, dim3(8 * per_xcd), dim3(512), lds3, stream, T, Tp, work->C1, n1,
-                         work->flag1, work->gap1, work->S1, intra ? work->C1 : work->C2, n2, intra ? work->flag1 : work->flag2,
-                         intra ? work->gap1 : work->gap2, intra ? work->S1 : work->S2, work->ftab, intra, d_mi, d_hj, ldo, ntx, ntiles, per_xcd);
-    } else if (Tp <= 256) {
-      // nucleotides up to 256 taxa: the four-wave nucleotide kernel (cmx_mica4.hip), unknowns included (no one-hot matrices exist here)
-      if (!mica_dna4_serves(A, Tp, n1, n2)) return hipErrorInvalidValue;
-      const hipError_t e4 = launch_mica_dna4(T, work, n1, n2, intra, d_mi, d_hj, ldo, stream);
-      if (e4 != hipSuccess) return e4;
-    } else {
-      // nucleotides above 256 taxa: the one-column-per-tile kernel on the one-hot matrices
-      dim3 g2((unsigned)((n2 + kMicaTileJ - 1) / kMicaTileJ), (unsigned)((n1 + kMicaTileI - 1) / kMicaTileI));
-      hipLaunchKernelGGL(mica_mfma_kernel<4>, g2, dim3(512), lds2, stream, T, Tp, work->H1, n1,
-                         work->flag1, work->gap1, work->S1, intra ? work->H1 : work->H2, n2, intra ? work->flag1 : work->flag2,
-                         intra ? work->gap1 : work->gap2, intra ? work->S1 : work->S2, work->ftab, intra, d_mi, d_hj, ldo);
+      const size_t lds = mica_mfma3_lds_bytes(T, Tp);
+      if ((e = mica_allow_lds(&mica_mfma3_kernel, lds)) != hipSuccess) break;
+      hipLaunchKernelGGL(mica_mfma3_kernel, dim3(8 * per_xcd), dim3(512), lds, stream, T, Tp, s1.C, n1, s1.flag, s1.gap, s1.S, s2.C, n2,
+                         s2.flag, s2.gap, s2.S, work.ftab, intra, d_mi, d_hj, ldo, ntx, ntiles, per_xcd);
+      break;
     }
-    f1 = work->flag1;
-    f2 = intra ? work->flag1 : work->flag2;
+    case kMicaDna1: {
+      dim3 grid((unsigned)((n2 + kMicaTileJ - 1) / kMicaTileJ), (unsigned)((n1 + kMicaTileI - 1) / kMicaTileI));
+      hipLaunchKernelGGL(mica_mfma_kernel<4>, grid, dim3(512), mica_mfma_lds_bytes(T), stream, T, Tp, s1.H, n1, s1.flag, s1.gap, s1.S,
+                         s2.H, n2, s2.flag, s2.gap, s2.S, work.ftab, intra, d_mi, d_hj, ldo);
+      break;
+    }
   }
+  if (e != hipSuccess) return e;
   // the LDS-table kernel, then the column entropies
+  const size_t ntiles = ((n2 + 15) / 16) * n1;
   auto tables = [&](auto columns, auto entropy) {
-    hipLaunchKernelGGL(columns, grid, dim3(64), lds, stream, T, d_masks, d_aln1, n1, ld1, d_aln2, n2, ld2, intra, d_mi, d_hj, ldo, f1, f2, anyf);
+    hipLaunchKernelGGL(columns, dim3((unsigned)std::min<size_t>(ntiles, 8192)), dim3(64), sizeof(double) * A * A * 16, stream, T, d_masks,
+                       d_aln1, n1, ld1, d_aln2, n2, ld2, intra, d_mi, d_hj, ldo, s1.flag, s2.flag, work.anyflag);
     if (d_h1) hipLaunchKernelGGL(entropy, dim3((unsigned)((n1 + 1) / 2)), dim3(64), 0, stream, T, d_masks, d_aln1, n1, ld1, d_h1);
     if (d_h2) hipLaunchKernelGGL(entropy, dim3((unsigned)((n2 + 1) / 2)), dim3(64), 0, stream, T, d_masks, d_aln2, n2, ld2, d_h2);
   };

@@ -4,9 +4,9 @@
 //   * persistent workgroups of FOUR waves (one per SIMD), each walking a run of tiles of 12 columns of the first
 //     alignment x 3 columns of the second; wave w owns the 3 x 3 pairs of its block of three first-alignment columns;
 //   * the first alignment's operands held in REGISTERS for the whole run: three columns x 20 states = 60 of the 64 rows
-//     of a block (no pseudo-state row for the unknowns: see below), up to 8 k-steps x 2 row tiles x 4 registers (16 k-steps
-//     = 512 taxa at one workgroup per CU), expanded
-//     once per run straight from the symbol bytes.  The k-loop reads only the second alignment's operands from LDS
+//     of a block (no pseudo-state row for the unknowns: see below), up to 16 k-steps x 2 row tiles x 4 registers (eight
+//     k-steps = 256 taxa at two workgroups per CU, sixteen = 512 taxa at one), expanded once per run straight from the
+//     symbol bytes.  The k-loop reads only the second alignment's operands from LDS
 //     (2 ds_read_b128 per 4 MFMAs) -- the 8-wave kernel (cmx_mica.hip, mica_mfma3_kernel) expanded all twelve operand
 //     tiles of every tile again, and its busiest SIMDs spent more issue cycles on that than on the matrix products;
 //   * the first operand's "one" is 8, the second's 1: an accumulator holds 8 x count, which IS the LDS address of
@@ -41,9 +41,6 @@
 //
 // Pairs with a column that carries PARTIAL ambiguity codes (B, Z, R, Y ...) are left to the LDS-table kernel
 // (launch_mi_columns).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <type_traits>
 #include <utility>
 
@@ -128,7 +125,7 @@ __global__ __launch_bounds__(1024) void mica_sort_columns_kernel(const uint8_t* 
   for (size_t i0 = 0; i0 < n; i0 += 1024) {
     const size_t i = i0 + tid;
     const bool in = i < n, g = in && gap[i] != 0, c = in && !g;
-    const unsigned long long mc = __ballot(c), mg = __ballot(g);
+    const unsigned long long mc = __ballot(c);
     if (lane == 0) { wsum[w] = (unsigned)__popcll(mc); }
     __syncthreads();
     unsigned offc = 0, totc = 0;
@@ -136,8 +133,7 @@ __global__ __launch_bounds__(1024) void mica_sort_columns_kernel(const uint8_t* 
     // (the others: position in the chunk minus the clean ones before it)
     const unsigned before = (unsigned)(64 * w + lane), cleanb = offc + (unsigned)__popcll(mc & ((1ull << lane) - 1ull));
     if (c) order[base[0] + cleanb] = (unsigned)i;
-    if (g) order[base[1] + (before - cleanb) - 0u] = (unsigned)i;
-    (void)mg;
+    if (g) order[base[1] + (before - cleanb)] = (unsigned)i;
     __syncthreads();
     if (tid == 0) {
       const unsigned inchunk = (unsigned)((n - i0) < 1024 ? (n - i0) : 1024);
@@ -158,7 +154,7 @@ __global__ __launch_bounds__(256) void mica_gather_columns_kernel(const unsigned
   }
   const size_t i = order[k];
   for (int t = threadIdx.x; t < Tp / 16; t += 256) {
-    // mica_onehot_kernel's codes (unknown = 20, no row = 63) -> this file's (kM4Unknown, kM4None)
+    // mica_codes_kernel's codes (unknown = 20, no row = 63) -> this file's (kM4Unknown, kM4None)
     cmx_i4 x = reinterpret_cast<const cmx_i4*>(C + i * (size_t)Tp)[t];
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
@@ -184,6 +180,11 @@ __global__ void mica_blockinfo_kernel(const unsigned* __restrict__ order, const 
   }
   info[k] = v;
 }
+// MicaSide::info: the blocks of a side padded to whole tiles of twelve columns (blocks past the end: all three columns "not
+// served"), then four spare words; the first of them is mica_sort_columns_kernel's "some column has unknowns"
+static size_t m4_info_blocks(size_t n) { return (n + kM4I - 1) / kM4I * (kM4I / 3); }
+size_t mica4_info_words(size_t n) { return m4_info_blocks(n) + 4; }
+static unsigned* m4_anygap(const MicaSide& s) { return s.info + m4_info_blocks(s.n); }
 // intra layout: NaN wherever j <= i (the kernels below write each unordered pair once, at (min, max) of its columns)
 __global__ void mica_nan_lower_kernel(size_t n, double* __restrict__ mi, double* __restrict__ hj, size_t ldo) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
@@ -876,37 +877,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
+// k-steps of 32 taxa a four-wave instantiation holds in operand registers (Tp <= 32 KS), and f(integral_constant<int, KS>)
+static int m4_ksteps(int Tp) { return Tp <= 64 ? 2 : (Tp <= 128 ? 4 : (Tp <= 256 ? 8 : 16)); }
+template <int MAXKS, class F>
+static hipError_t m4_with_ksteps(int Tp, F&& f) {
+  switch (m4_ksteps(Tp)) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+  }
+  if constexpr (MAXKS >= 16) return f(std::integral_constant<int, 16>{});
+  return hipErrorInvalidValue;   // (mica_path sends no such call here)
+}
 size_t mica_dna4_lds_bytes(int T, int KS) {
   return (((size_t)(16 * T + 1) * 8 + 15) & ~(size_t)15) + (size_t)2 * 2 * KS * 64 * sizeof(cmx_i4) + (kD4I + 2 * kD4J) * sizeof(double) +
          (kD4I + 2 * kD4J) * sizeof(int);
 }
-template <int KS>
-static hipError_t launch_mica_dna4_ks(int T, int Tp, const MicaWork* wk, size_t n1, size_t n2, int intra, double* d_mi, double* d_hj,
-                                      size_t ldo, unsigned chunk, unsigned grid, hipStream_t stream) {
-  const size_t lds = mica_dna4_lds_bytes(T, KS);
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mica_dna4_kernel<KS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const unsigned nJ = (unsigned)((n2 + kD4J - 1) / kD4J), nI = (unsigned)((n1 + kD4I - 1) / kD4I);
-  const unsigned nchunks = (nJ + chunk - 1) / chunk, nruns = nI * nchunks;
-  if (intra) hipLaunchKernelGGL(mica_nan_lower_kernel, dim3((unsigned)((n1 + 255) / 256), (unsigned)n1), dim3(256), 0, stream, n1, d_mi, d_hj, ldo);
-  hipLaunchKernelGGL(mica_dna4_kernel<KS>, dim3(grid < nruns ? grid : nruns), dim3(256), lds, stream, T, Tp, wk->C1, n1, wk->flag1, wk->S1,
-                     intra ? wk->C1 : wk->C2, n2, intra ? wk->flag1 : wk->flag2, intra ? wk->S1 : wk->S2, wk->ftab, intra, d_mi, d_hj, ldo, nJ,
-                     chunk, nchunks, nruns);
-  return hipGetLastError();
-}
-// nucleotides, Tp <= 256 (eight k-steps of operand registers; the whole weighted table in LDS), byte offsets within 31 bits
-bool mica_dna4_serves(int A, int Tp, size_t n1, size_t n2) {
-  return A == 4 && Tp <= 256 && (std::max(n1, n2) + kMicaCodePad) * (size_t)Tp < 0x7fffffffull;
-}
-hipError_t launch_mica_dna4(int T, const MicaWork* wk, size_t n1, size_t n2, int intra, double* d_mi, double* d_hj, size_t ldo,
-                            hipStream_t stream) {
+// nucleotides: up to eight k-steps of operand registers, the whole weighted table in LDS
+hipError_t launch_mica_dna4(int T, const MicaWork& wk, int intra, double* d_mi, double* d_hj, size_t ldo, hipStream_t stream) {
   const unsigned chunk = 16, grid = 512;   // 16 tiles of 64 x 16 columns per run; two workgroups per CU
-  const int Tp = wk->Tp;
-  if (Tp <= 64) return launch_mica_dna4_ks<2>(T, Tp, wk, n1, n2, intra, d_mi, d_hj, ldo, chunk, grid, stream);
-  if (Tp <= 128) return launch_mica_dna4_ks<4>(T, Tp, wk, n1, n2, intra, d_mi, d_hj, ldo, chunk, grid, stream);
-  return launch_mica_dna4_ks<8>(T, Tp, wk, n1, n2, intra, d_mi, d_hj, ldo, chunk, grid, stream);
+  const MicaSide &s1 = wk.s[0], &s2 = wk.s[1];
+  return m4_with_ksteps<8>(wk.Tp, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    const size_t lds = mica_dna4_lds_bytes(T, KS);
+    if (const hipError_t e = mica_allow_lds(&mica_dna4_kernel<KS>, lds); e != hipSuccess) return e;
+    const unsigned nJ = (unsigned)((s2.n + kD4J - 1) / kD4J), nI = (unsigned)((s1.n + kD4I - 1) / kD4I);
+    const unsigned nchunks = (nJ + chunk - 1) / chunk, nruns = nI * nchunks;
+    if (intra) hipLaunchKernelGGL(mica_nan_lower_kernel, dim3((unsigned)((s1.n + 255) / 256), (unsigned)s1.n), dim3(256), 0, stream, s1.n, d_mi, d_hj, ldo);
+    hipLaunchKernelGGL(mica_dna4_kernel<KS>, dim3(grid < nruns ? grid : nruns), dim3(256), lds, stream, T, wk.Tp, s1.C, s1.n, s1.flag, s1.S,
+                       s2.C, s2.n, s2.flag, s2.S, wk.ftab, intra, d_mi, d_hj, ldo, nJ, chunk, nchunks, nruns);
+    return hipGetLastError();
+  });
 }
 
 size_t mica4_lds_bytes(int T, int KS, bool weighted) {
@@ -914,75 +915,45 @@ size_t mica4_lds_bytes(int T, int KS, bool weighted) {
   return (((size_t)(weighted ? M0 + 1 : T + 1) * 8 + 15) & ~(size_t)15) + (size_t)2 * 2 * KS * 64 * sizeof(cmx_i4) + 16 * sizeof(double) + 16 * sizeof(unsigned) +
          (weighted ? 4 * kM4Corr * sizeof(double) + 4 * m4_qcap(KS) * sizeof(unsigned) : 0) + 4 * kM4FinBytes;
 }
+// MicaWork::img2: two images (plain, weighted; mica4_image_kernel) of 2 KS KiB per tile of three columns of the second alignment
+size_t mica4_image_bytes(int Tp, size_t n2) { return 2 * ((n2 + kM4J - 1) / kM4J) * (size_t)(2 * m4_ksteps(Tp)) * 64 * sizeof(cmx_i4); }
 
-template <int KS, bool WEIGHTED>
-static hipError_t launch_mica4_one(int T, int Tp, const MicaWork* wk, size_t n1, size_t n2, int intra, double* d_mi, double* d_hj,
-                                   size_t ldo, unsigned nJ, unsigned chunk, unsigned nchunks, unsigned nruns, unsigned grid,
-                                   hipStream_t stream) {
-  const size_t lds = mica4_lds_bytes(T, KS, WEIGHTED);
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mica_mfma4_kernel<KS, WEIGHTED>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  // the second alignment's operand image of this instantiation (its two halves of wk->img2)
-  cmx_i4* img = reinterpret_cast<cmx_i4*>(wk->img2) + (WEIGHTED ? (size_t)nJ * 2 * KS * 64 : 0);
-  hipLaunchKernelGGL((mica4_image_kernel<KS, WEIGHTED>), dim3(nJ), dim3(256), 0, stream, Tp, intra ? wk->Cs1 : wk->Cs2, img);
-  hipLaunchKernelGGL((mica_mfma4_kernel<KS, WEIGHTED>), dim3(grid < nruns ? grid : nruns), dim3(256), lds, stream, T, Tp, wk->Cs1, n1,
-                     wk->info1, wk->Ss1, img, n2, intra ? wk->info1 : wk->info2, intra ? wk->Ss1 : wk->Ss2,
-                     wk->order1, intra ? wk->order1 : wk->order2, wk->ftab, intra, d_mi, d_hj, ldo, nJ, chunk, nchunks, nruns,
-                     wk->info1 + (n1 + 11) / 12 * 4, intra ? wk->info1 + (n1 + 11) / 12 * 4 : wk->info2 + (n2 + 11) / 12 * 4);
-  return hipGetLastError();
+// a side's columns sorted (those without unknowns first), its symbol bytes and sums gathered in that order, its block info
+static void m4_prepare_side(const MicaSide& s, int Tp, size_t nblocks, hipStream_t stream) {
+  hipLaunchKernelGGL(mica_sort_columns_kernel, dim3(1), dim3(1024), 0, stream, s.gap, s.n, s.order, m4_anygap(s));
+  hipLaunchKernelGGL(mica_gather_columns_kernel, dim3((unsigned)(s.n + kMicaCodePad)), dim3(256), 0, stream, s.order, s.n, Tp, s.C, s.S, s.Cs, s.Ss);
+  hipLaunchKernelGGL(mica_blockinfo_kernel, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, stream, s.order, s.flag, s.gap, s.n, nblocks, s.info);
 }
 
-template <int KS>
-static hipError_t launch_mica4_ks(int T, int Tp, const MicaWork* wk, size_t n1, size_t n2, int intra, double* d_mi, double* d_hj,
-                                  size_t ldo, unsigned chunk, unsigned grid, hipStream_t stream) {
-  const unsigned nJ = (unsigned)((n2 + kM4J - 1) / kM4J), nI = (unsigned)((n1 + kM4I - 1) / kM4I);
-  const unsigned nchunks = (nJ + chunk - 1) / chunk, nruns = nI * nchunks;
-  // block info, padded to whole tiles (blocks past the end: all three columns "not served")
-  const size_t nb1 = (size_t)nI * (kM4I / 3), nb2 = nJ;
-  // (the info arrays have four words to spare behind the blocks of the four-wave tiling: the first holds "some column has unknowns")
-  hipLaunchKernelGGL(mica_sort_columns_kernel, dim3(1), dim3(1024), 0, stream, wk->gap1, n1, wk->order1, wk->info1 + (n1 + 11) / 12 * 4);
-  hipLaunchKernelGGL(mica_gather_columns_kernel, dim3((unsigned)(n1 + kMicaCodePad)), dim3(256), 0, stream, wk->order1, n1, Tp, wk->C1, wk->S1,
-                     wk->Cs1, wk->Ss1);
-  hipLaunchKernelGGL(mica_blockinfo_kernel, dim3((unsigned)((nb1 + 255) / 256)), dim3(256), 0, stream, wk->order1, wk->flag1, wk->gap1, n1, nb1,
-                     wk->info1);
-  if (!intra) {
-    hipLaunchKernelGGL(mica_sort_columns_kernel, dim3(1), dim3(1024), 0, stream, wk->gap2, n2, wk->order2, wk->info2 + (n2 + 11) / 12 * 4);
-    hipLaunchKernelGGL(mica_gather_columns_kernel, dim3((unsigned)(n2 + kMicaCodePad)), dim3(256), 0, stream, wk->order2, n2, Tp, wk->C2, wk->S2,
-                       wk->Cs2, wk->Ss2);
-    hipLaunchKernelGGL(mica_blockinfo_kernel, dim3((unsigned)((nb2 + 255) / 256)), dim3(256), 0, stream, wk->order2, wk->flag2, wk->gap2, n2, nb2,
-                       wk->info2);
-  } else {
-    hipLaunchKernelGGL(mica_nan_lower_kernel, dim3((unsigned)((n1 + 255) / 256), (unsigned)n1), dim3(256), 0, stream, n1, d_mi, d_hj, ldo);
-  }
-  hipError_t e = launch_mica4_one<KS, false>(T, Tp, wk, n1, n2, intra, d_mi, d_hj, ldo, nJ, chunk, nchunks, nruns, grid, stream);
-  if (e == hipSuccess) e = launch_mica4_one<KS, true>(T, Tp, wk, n1, n2, intra, d_mi, d_hj, ldo, nJ, chunk, nchunks, nruns, grid, stream);
-  return e;
-}
-
-// proteins, Tp <= 256 (eight k-steps of operand registers), byte offsets within 31 bits; the caller serves the pairs with
-// partial ambiguity codes
-static int mica4_ksteps(int Tp) { return Tp <= 64 ? 2 : (Tp <= 128 ? 4 : (Tp <= 256 ? 8 : 16)); }
-// bytes of MicaWork::img2: two images (plain, weighted) of 2 KS KB per tile of three columns of the second alignment
-size_t mica4_image_bytes(int Tp, size_t n2) { return 2 * ((n2 + kM4J - 1) / kM4J) * (size_t)(2 * mica4_ksteps(Tp)) * 1024; }
-bool mica4_serves(int A, int Tp, size_t n1, size_t n2) {
-  return A == 20 && Tp <= 512 && (std::max(n1, n2) + kMicaCodePad) * (size_t)Tp < 0x7fffffffull && mica4_image_bytes(Tp, n2) / 2 < 0x7fffffffull;
-}
-
-hipError_t launch_mica4(int T, const MicaWork* wk, size_t n1, size_t n2, int intra, double* d_mi, double* d_hj, size_t ldo,
-                        hipStream_t stream) {
+// proteins: up to sixteen k-steps of operand registers (the sixteen at one workgroup per CU: the pipelined tile loop keeps a
+// lone wave's matrix core and vector unit busy together); the caller serves the pairs with partial ambiguity codes
+hipError_t launch_mica4(int T, const MicaWork& wk, int intra, double* d_mi, double* d_hj, size_t ldo, hipStream_t stream) {
   constexpr unsigned chunk = 32;     // tiles per run
   static_assert(chunk >= 1 && chunk <= kM4MaxChunk, "one lane of a wave per tile of a run");
   constexpr unsigned grid = 1024;    // two workgroups per CU at a time (254 registers): a multiple of 512
-  const int Tp = wk->Tp;
-  if (Tp <= 64) return launch_mica4_ks<2>(T, Tp, wk, n1, n2, intra, d_mi, d_hj, ldo, chunk, grid, stream);
-  if (Tp <= 128) return launch_mica4_ks<4>(T, Tp, wk, n1, n2, intra, d_mi, d_hj, ldo, chunk, grid, stream);
-  if (Tp <= 256) return launch_mica4_ks<8>(T, Tp, wk, n1, n2, intra, d_mi, d_hj, ldo, chunk, grid, stream);
-  // 257 .. 512 taxa: sixteen k-steps of operand registers, one workgroup per CU (the pipelined tile loop keeps a lone wave's
-  // matrix core and vector unit busy together)
-  return launch_mica4_ks<16>(T, Tp, wk, n1, n2, intra, d_mi, d_hj, ldo, chunk, grid, stream);
+  const MicaSide &s1 = wk.s[0], &s2 = wk.s[1];
+  return m4_with_ksteps<16>(wk.Tp, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    const unsigned nJ = (unsigned)((s2.n + kM4J - 1) / kM4J), nI = (unsigned)((s1.n + kM4I - 1) / kM4I);
+    const unsigned nchunks = (nJ + chunk - 1) / chunk, nruns = nI * nchunks;
+    // the first side's block info covers whole tiles of twelve columns, the second's its tiles of three
+    m4_prepare_side(s1, wk.Tp, m4_info_blocks(s1.n), stream);
+    if (!intra) m4_prepare_side(s2, wk.Tp, nJ, stream);
+    else hipLaunchKernelGGL(mica_nan_lower_kernel, dim3((unsigned)((s1.n + 255) / 256), (unsigned)s1.n), dim3(256), 0, stream, s1.n, d_mi, d_hj, ldo);
+    auto one = [&](auto wc) {   // an instantiation: its image of the second alignment's operands (its half of img2), then its tiles
+      constexpr bool WEIGHTED = decltype(wc)::value;
+      const size_t lds = mica4_lds_bytes(T, KS, WEIGHTED);
+      if (const hipError_t e = mica_allow_lds(&mica_mfma4_kernel<KS, WEIGHTED>, lds); e != hipSuccess) return e;
+      cmx_i4* img = reinterpret_cast<cmx_i4*>(static_cast<uint8_t*>(wk.img2) + (WEIGHTED ? mica4_image_bytes(wk.Tp, s2.n) / 2 : 0));
+      hipLaunchKernelGGL((mica4_image_kernel<KS, WEIGHTED>), dim3(nJ), dim3(256), 0, stream, wk.Tp, s2.Cs, img);
+      hipLaunchKernelGGL((mica_mfma4_kernel<KS, WEIGHTED>), dim3(grid < nruns ? grid : nruns), dim3(256), lds, stream, T, wk.Tp, s1.Cs, s1.n,
+                         s1.info, s1.Ss, img, s2.n, s2.info, s2.Ss, s1.order, s2.order, wk.ftab, intra, d_mi, d_hj, ldo, nJ, chunk, nchunks,
+                         nruns, m4_anygap(s1), m4_anygap(s2));
+      return hipGetLastError();
+    };
+    const hipError_t e = one(std::false_type{});
+    return e == hipSuccess ? one(std::true_type{}) : e;
+  });
 }
 
 }  // namespace cmx

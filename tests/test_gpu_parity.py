@@ -1253,6 +1253,47 @@ def test_mica_four_wave_nucleotide_kernel_against_oracle(T, n1, n2):
     assert np.isnan(gi["mi"][np.tril_indices(n2)]).all() and np.isnan(gi["hjoint"][np.tril_indices(n2)]).all()
 
 
+def test_mi_columns_one_context_serves_every_path_in_turn_and_back():
+    """One model-less context through the five paths of the column stage and back to the first: four-wave protein (40
+    taxa), eight-wave protein (600), four-wave nucleotide (40), one-column-per-tile nucleotide (300), LDS tables only (2 048
+    taxa, 5 x 4 columns).  Each visit is a rectangle call and an intra call; the unknowns are in the second alignment only on
+    one visit and in the first only on the next, and each alignment has one column with a partial ambiguity code.  The
+    context's scratch buffers keep their names from path to path and only grow, so a path that reads a buffer another path
+    sized or filled shows here: every result is the oracle's and, bit for bit, that of the same call on a fresh context."""
+    visits = [(20, 40, 30, 25), (20, 600, 30, 25), (4, 40, 30, 25), (4, 300, 30, 25), (4, 2048, 5, 4), (20, 40, 30, 25)]
+    eng = engine.Engine()
+    for k, (A, T, n1, n2) in enumerate(visits):
+        rng = np.random.default_rng(1000 + k)
+        masks = oracle.default_masks(A).copy()
+        masks[A + 1] = 0b101                                    # partial ambiguity: two states
+        base = rng.integers(0, A, size=(T, 1))
+
+        def draw(n, p, unknowns):
+            a = np.where(rng.random((T, n)) < p, base, rng.integers(0, A, size=(T, n))).astype(np.uint8)
+            if unknowns:
+                gapped = rng.random(n) < 0.3
+                gapped[0] = True
+                a[(rng.random((T, n)) < 0.2) & gapped[None, :]] = A
+                a[:, n // 2] = A                                   # a column of unknowns only
+            return a
+
+        a1, a2 = draw(n1, 0.6, k % 2 == 1), draw(n2, 0.4, k % 2 == 0)
+        a1[rng.integers(0, T, 3), n1 // 4] = A + 1
+        a2[rng.integers(0, T, 3), n2 - 1] = A + 1
+        for x, y in ((a1, a2), (a2, None)):
+            g = eng.mi_columns(x, y, A, masks=masks[: A + 2])
+            f = engine.Engine().mi_columns(x, y, A, masks=masks[: A + 2])
+            o = oracle.mi_columns(x, x if y is None else y, A, masks)
+            for key in ("mi", "hjoint"):
+                if y is None:
+                    iu = np.triu_indices(x.shape[1], 1)
+                    rel_close(g[key][iu], o[key][iu], 1e-6, 1e-10)
+                    assert np.isnan(g[key][np.tril_indices(x.shape[1])]).all()
+                else:
+                    rel_close(g[key], o[key], 1e-6, 1e-10)
+                assert np.array_equal(g[key], f[key], equal_nan=True), (k, key, y is None)
+
+
 @pytest.mark.parametrize("dim,n1,n2", [(5, 7, 4), (125, 70, 33), (64, 130, 130), (2, 3, 3)])
 def test_analysis_tools_vector_matrices(dim, n1, n2):
     """AnalysisTools::compute{ScalarProduct,Cosinus,Correlation,Covariance}Matrix (CoMap/AnalysisTools.cpp:102-339) on the
