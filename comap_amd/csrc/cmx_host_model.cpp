@@ -162,9 +162,9 @@ void build_records(HostModel* hm) {
 
 namespace {
 // ---- Recorder: the operator stream (matrix index in a class block, taxon or -1) and the workspace loads of a pass
-template <bool CT>
+template <bool CT, bool CR>
 struct Recorder {
-  static constexpr bool kCherryTables = CT;
+  static constexpr bool kCherryTables = CT, kCherryRows = CR;
   HostModel* hm;
   long t = 0;
   std::vector<long> store_time[2];
@@ -196,6 +196,7 @@ struct Recorder {
   template <int S> void store(int arr, int slot) { store_time[arr][slot] = t++; if (!CT) hm->n_stores++; }
   template <int D, int S> void mov() {}
   template <int D, int S> void mul() {}
+  template <int D, int A, int B> void prod() {}
   void mulup() {}
   template <int D> void setpi() {}
   template <int S> void rootl() {}
@@ -205,9 +206,9 @@ struct Recorder {
 
 // ---- Numeric: the pass in plain doubles for one site, operators read from HostModel::MAT in their device layouts
 // and selected by the recorded stream exactly as the device selects them; every register starts as NaN.
-template <bool CT>
+template <bool CT, bool CR>
 struct Numeric {
-  static constexpr bool kCherryTables = CT;
+  static constexpr bool kCherryTables = CT, kCherryRows = CR;
   const HostModel& hm;
   int dS, NB;
   size_t MU;
@@ -320,6 +321,7 @@ struct Numeric {
   }
   template <int D, int S> void mov() { R[D] = R[S]; }
   template <int D, int S> void mul() { for (int x = 0; x < dS; ++x) R[D][x] *= R[S][x]; }
+  template <int D, int A, int B> void prod() { for (int x = 0; x < dS; ++x) R[D][x] = R[A][x] * R[B][x]; }
   void mulup() { for (int x = 0; x < dS; ++x) { R[1][x] *= R[3][x]; R[2][x] *= R[3][x]; } }
   template <int D> void setpi() { for (int x = 0; x < dS; ++x) R[D][x] = hm.pi[x % hm.S]; }
   template <int S> void rootl() {
@@ -328,6 +330,35 @@ struct Numeric {
   void dot3(int row) { double s = 0; for (int x = 0; x < dS; ++x) s += R[3][x] * R[1][x] * R[2][x]; count_row(row, s); }
   template <int Rg> void kill() { R[Rg].assign(dS, std::nan("")); }   // a killed register must not be read again
 };
+
+// the plain stream and the load schedule: the row-reusing cherry visit (cmx_walk.h, kCherryRows) for unfused models
+template <bool CR>
+void record_plain(HostModel* hm) {
+  Recorder<false, CR> rc(hm);
+  walk_pass(rc, hm->NV, hm->K);
+  for (size_t j = 0; j < rc.loads.size(); ++j) {
+    const auto& e = rc.loads[j];
+    unsigned w = (unsigned)e.slot | (e.arr ? 0x40000000u : 0u);
+    // prefetchable: its producer store is issued before the previous load (where the prefetch is issued)
+    if (j > 0 && e.src >= 0 && e.src < rc.loads[j - 1].t) w |= 0x80000000u;
+    hm->ldsched.push_back((int)w);
+  }
+}
+
+// what verify_walk keeps of a numeric pass
+struct NumericResult {
+  std::string err;
+  size_t mi = 0, fi = 0;
+  std::vector<int> code;
+  std::vector<double> cnt, Lg;
+  std::vector<char> counted;
+};
+template <bool CT, bool CR>
+NumericResult run_numeric(const HostModel& hm) {
+  Numeric<CT, CR> nm(hm);
+  walk_pass(nm, hm.NV, hm.K);
+  return {nm.err, nm.mi, nm.fi, nm.code, nm.cnt, nm.Lg, nm.counted};
+}
 }  // namespace
 
 // records -> operator stream + load schedule (with prefetchability) by a dry run of the walk
@@ -337,18 +368,11 @@ void record_walk(HostModel* hm) {
   hm->ldsched.clear();
   hm->n_loads = hm->n_stores = hm->n_products = hm->n_leaf_ops = hm->n_products_r = hm->n_leaf_ops_r = 0;
   if (hm->cherry_base > 0) {   // the cherry-table walk's own operator stream (same loads and stores)
-    Recorder<true> rt(hm);
+    Recorder<true, false> rt(hm);
     walk_pass(rt, hm->NV, hm->K);
   }
-  Recorder<false> rc(hm);
-  walk_pass(rc, hm->NV, hm->K);
-  for (size_t j = 0; j < rc.loads.size(); ++j) {
-    const Recorder<false>::Ld& e = rc.loads[j];
-    unsigned w = (unsigned)e.slot | (e.arr ? 0x40000000u : 0u);
-    // prefetchable: its producer store is issued before the previous load (where the prefetch is issued)
-    if (j > 0 && e.src >= 0 && e.src < rc.loads[j - 1].t) w |= 0x80000000u;
-    hm->ldsched.push_back((int)w);
-  }
+  if (hm->fuse == 1) record_plain<true>(hm);
+  else record_plain<false>(hm);
 }
 
 // Runs the walk numerically for one random site of device class 0 and compares site likelihood and all joint counts
@@ -357,16 +381,15 @@ std::string verify_walk(const HostModel& hm) {
   const int S = hm.S, F = hm.fuse, K = hm.K, nn = hm.nn, B = hm.B, root = hm.root;
   const size_t S2 = (size_t)S * S;
   if ((int)hm.nrec.size() != hm.NV * 16) return "tree-walk self-check failed: record table size";
-  Numeric<false> nm(hm);
-  walk_pass(nm, hm.NV, K);
+  const NumericResult nm = F == 1 ? run_numeric<false, true>(hm) : run_numeric<false, false>(hm);
   if (!nm.err.empty()) return nm.err;
   if (2 * nm.mi != hm.msched.size()) return "tree-walk self-check failed: unused operators in the stream";
   if (nm.fi != hm.ldsched.size()) return "tree-walk self-check failed: unused workspace loads in the schedule";
   // the cherry-table walk: same site, same reference
-  Numeric<true> nt(hm);
+  NumericResult nt;
   const bool tables = !hm.msched_r.empty();
   if (tables) {
-    walk_pass(nt, hm.NV, K);
+    nt = run_numeric<true, false>(hm);
     if (!nt.err.empty()) return nt.err + " (cherry-table walk)";
     if (2 * nt.mi != hm.msched_r.size()) return "tree-walk self-check failed: unused operators in the cherry-table stream";
     if (nt.fi != hm.ldsched.size()) return "tree-walk self-check failed: the cherry-table walk loads other workspace vectors";
@@ -480,6 +503,7 @@ std::string build_host_model(const cmx_model* model, const cmx_tree* tree, HostM
   }
   if (nchild[nn - 1] < 2) return "the root needs at least two children";
   hm->NI = (int)hm->int_post.size();
+  hm->fuse = (S == 4 && C >= 4) ? (C == 4 ? 4 : 5) : 1;   // (before record_walk: it chooses the cherry visit of the plain stream)
   if (!hm->plain) {
     build_records(hm);
     // cherry tables only for the class-fused nucleotide layout (16 symbol pairs; 400 for proteins would not fit a stage buffer)
@@ -646,7 +670,6 @@ std::string build_host_model(const cmx_model* model, const cmx_tree* tree, HostM
   //   [.., + ncherry*(1+3K))     cherry tables of the class-fused nucleotide layout (cmx_walk.h), 16 rows (symbol pair) each
   const int MC = hm->plain ? 0 : NI + NI * K + T + K * T + hm->ncherry * (1 + 3 * K);
   hm->MC = MC;
-  hm->fuse = (S == 4 && C >= 4) ? (C == 4 ? 4 : 5) : 1;
   const int F = hm->fuse;
   const int dS = S * F, dC = (C + F - 1) / F;
   hm->dS = dS;

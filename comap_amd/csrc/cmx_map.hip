@@ -359,6 +359,7 @@ struct DevWalk {
   static constexpr int kLeafBytes = RESOLVED ? (S / FUSE) * leaf_row_stride(S) * 8 : MatStage<S>::BYTES;
   static constexpr int kVecInstrs = (VL + 1) / 2;   // VMEM instructions of one workspace vector
   static constexpr bool kCherryTables = RESOLVED && DIAG;   // cmx_walk.h: cset / cdot instead of a cherry's operator ops
+  static constexpr bool kCherryRows = FUSE == 1;            // cmx_walk.h: a cherry's outside visit keeps its leaf rows in registers
   static constexpr int kCherryBytes = 16 * leaf_row_stride(S) * 8;   // a table's 16 rows (one per symbol pair)
   static constexpr int kCherryFlag = 0x40000000;                     // stream entry: taxon of l1 | taxon of l2 << 15 | flag
   static_assert(kCherryBytes <= MatStage<S>::BYTES, "a cherry table fits a stage buffer");
@@ -542,6 +543,10 @@ struct DevWalk {
   template <int D, int SRC> __device__ __forceinline__ void mul() {
 #pragma unroll
     for (int x = 0; x < VL; ++x) reg<D>()[x] *= reg<SRC>()[x];
+  }
+  template <int D, int A, int B> __device__ __forceinline__ void prod() {
+#pragma unroll
+    for (int x = 0; x < VL; ++x) reg<D>()[x] = reg<A>()[x] * reg<B>()[x];
   }
   __device__ __forceinline__ void mulup() {
 #pragma unroll

@@ -55,7 +55,14 @@ enum { OPER_P = -1 };         // which operator of a branch: OPER_P = transition
 //   rec(v, int (&r)[16])
 //   lset<D>(leaf, which); lmul<S, D>(leaf, which)  [D = S o row];  ldot<S>(leaf, which, row)  [count]
 //   mv<S, D, TR>(node, which)  [D = M S or M^T S];  load<D>(arr, slot); store<S>(arr, slot)
-//   mov<D, S>(); mul<D, S>() [D *= S]; mulup() [R1 *= R3, R2 *= R3]; setpi<D>(); rootl<S>(); dot3(row); kill<R>()
+//   mov<D, S>(); mul<D, S>() [D *= S]; prod<D, A, B>() [D = A o B]; mulup() [R1 *= R3, R2 *= R3]; setpi<D>(); rootl<S>();
+//   dot3(row)  [count = sum R3 o R1 o R2]; kill<R>()
+//   static constexpr bool kCherryRows  (unfused models; a backend with cherry tables never reaches it): the outside visit
+//   of an inlined cherry gathers each of its two leaf rows A = P_l1[:, s1], Bv = P_l2[:, s2] ONCE and keeps it in a
+//   register the visit leaves dead anyway -- 2 + 2 K leaf ops as child B, 2 + 3 K as child A (whose sibling's outside
+//   message still occupies R1), instead of 2 + 4 K.  Every product and every sum keeps its operands (IEEE multiplication
+//   commutes; dot3 and ldot both compute fma((W o A), Bv, sum) over the same state order), so the counts are the same bits.
+//   Class-fused nucleotide models keep the plain visit: their null runs on the cherry tables.
 template <class BE>
 CMX_HD void walk_cherry_message(BE& be, int node, int l1, int l2) {   // M of an inlined cherry -> R1, through R3
   if constexpr (BE::kCherryTables) {
@@ -112,6 +119,42 @@ CMX_HD void walk_child_dispose(BE& be, const int (&r)[16], int K) {
     }
     // cherry: its visit happens here, with U in R0; handed-over child: U stays in R0 for the next node
     be.template mov<0, UR>();
+    if constexpr (BE::kCherryRows) {
+      if (kind == KIND_CHERRY) {
+        // R0 = U_c.  Child B: R1, R2, R3 are dead, both rows stay (A in R1, Bv in R2) and the cherry's own count is the
+        // node's dot3.  Child A: R1 holds U_b for the sibling's turn, so only A stays (R2) and Bv is gathered where used.
+        const int l1 = r[o + CH_L1], l2 = r[o + CH_L2];
+        constexpr int RA = SIDE ? 1 : 2;
+        be.template kill<RA>();
+        be.template lset<RA>(l1, OPER_P);                            // A = M_l1
+        if (SIDE) {
+          be.template kill<2>();
+          be.template lset<2>(l2, OPER_P);                           // Bv = M_l2
+        }
+        for (int k = 0; k <= K; ++k) {
+          be.template kill<3>();
+          be.template mv<0, 3, true>(node, k < K ? k : OPER_P);      // W = J_c^T U_c, at last Up_c = P_c^T U_c
+          if (k < K) {
+            if (SIDE) {
+              be.dot3(node * K + k);                                 // count_c = sum W o M_l1 o M_l2
+            } else {
+              be.template mul<3, 2>();                               // W o M_l1
+              be.template ldot<3>(l2, OPER_P, node * K + k);
+            }
+          }
+        }
+        // U_l2 first, so that A dies before the gathers of l1's counts and, as child A, Up_c with the gather of Bv: U_l1
+        // first keeps all four registers live around K + 1 more leaf ops (48 spilled VGPRs against 19)
+        be.template kill<0>();
+        be.template prod<0, 3, RA>();                                // U_l2 = Up_c o M_l1
+        for (int k = 0; k < K; ++k) be.template ldot<0>(l2, k, l2 * K + k);
+        be.template kill<0>();
+        if (SIDE) be.template prod<0, 3, 2>();                       // U_l1 = Up_c o M_l2
+        else be.template lmul<3, 0>(l2, OPER_P);
+        for (int k = 0; k < K; ++k) be.template ldot<0>(l1, k, l1 * K + k);
+        return;
+      }
+    }
     if (kind == KIND_CHERRY) {
       const int l1 = r[o + CH_L1], l2 = r[o + CH_L2];
       for (int k = 0; k <= K; ++k) {
@@ -210,6 +253,14 @@ CMX_HD void walk_pass(BE& be, int NV, int K) {
     // ---- outside messages of the children
     be.mulup();                                     // R1 = U_b, R2 = U_a
     walk_child_dispose<0>(be, r, K);
+    if constexpr (BE::kCherryRows) {
+      // child A's turn is over: its outside message, Up and whatever a cherry's visit left are dead on every arm.  The
+      // visit defines R0, R2 and R3; without these kills the compiler carries them, merged with the other arms' old
+      // values, to the kills at the top of the loop and spills around EVERY node's mulup (+7 % launch time)
+      be.template kill<0>();
+      be.template kill<2>();
+      be.template kill<3>();
+    }
     walk_child_dispose<1>(be, r, K);
   }
 }
