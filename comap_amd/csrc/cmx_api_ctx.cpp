@@ -18,6 +18,7 @@ std::mutex g_guard_mu;
 std::vector<std::string> g_guard_failures;
 std::map<std::string, size_t> g_guard_shrink;
 
+std::atomic<int> g_lds_slot{1};         // cmx_debug_lds_slot: 0 = the mapping walk's LDS slot is planned empty (A/B runs, tests)
 std::atomic<int> g_pat_hash_bits{64};   // (tests force collisions with it)
 
 bool guard_on() {
@@ -177,6 +178,7 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
   }
   if (model) {
     int code = CMX_OK;
+    ctx->hm.lds_slot = g_lds_slot.load() != 0;
     std::string msg = build_host_model(model, tree, &ctx->hm, &code);
     if (!msg.empty()) {
       ctx->err = msg;
@@ -340,9 +342,10 @@ cmx_status cmx_get_transition_matrices(const cmx_ctx* ctx, double* P) {
 
 cmx_status cmx_debug_walk(const cmx_model* model, const cmx_tree* tree, int32_t* nrec, size_t nrec_cap, size_t* nrec_n,
                           int32_t* ldsched, size_t ld_cap, size_t* ld_n, int32_t* msched, size_t m_cap, size_t* m_n,
-                          int32_t* slot_of_node, uint64_t* stats /*[7]: loads, stores, products, leaf ops per pass; products, leaf ops of the cherry-table walk, cherries with tables*/) {
+                          int32_t* slot_of_node, uint64_t* stats /*[8]: loads, stores, products, leaf ops per pass; products, leaf ops of the cherry-table walk, cherries with tables; LDS-slot transfers*/) {
   HostModel hm;
   int code = CMX_OK;
+  hm.lds_slot = g_lds_slot.load() != 0;
   const std::string msg = build_host_model(model, tree, &hm, &code);
   if (!msg.empty()) {
     g_create_error = msg;
@@ -360,6 +363,7 @@ cmx_status cmx_debug_walk(const cmx_model* model, const cmx_tree* tree, int32_t*
   if (stats) {
     stats[0] = hm.n_loads; stats[1] = hm.n_stores; stats[2] = hm.n_products; stats[3] = hm.n_leaf_ops;
     stats[4] = hm.n_products_r; stats[5] = hm.n_leaf_ops_r; stats[6] = hm.msched_r.empty() ? 0 : (uint64_t)hm.ncherry;
+    stats[7] = (uint64_t)hm.n_lds_loads | ((uint64_t)hm.n_lds_stores << 20) | ((uint64_t)hm.n_lds_copies << 40);
   }
   return CMX_OK;
 }
@@ -382,6 +386,12 @@ cmx_status cmx_scratch_check(cmx_ctx* ctx) {
 int cmx_debug_scratch_guard(int on) {
   const int was = guard_on() ? 1 : 0;
   if (on >= 0) g_guard.store(on ? 1 : 0);
+  return was;
+}
+
+int cmx_debug_lds_slot(int on) {
+  const int was = g_lds_slot.load();
+  if (on >= 0) g_lds_slot.store(on ? 1 : 0);
   return was;
 }
 

@@ -32,6 +32,10 @@ constexpr int map_sites_per_wave(int S) { return 16 * map_ng(S); }
 // (three waves per SIMD were tried for the 16-state class-fused nucleotide layout -- vectors of 32 registers: at 168
 // registers the kernel spills 213 of them and the cfg 4 launch went from 7.7 to 10.7 ms)
 constexpr int map_waves_per_simd(int S) { return S == 4 ? 3 : 2; }
+// Which mapping instantiations keep one workspace vector per wave in LDS (cmx_walk.h, kLdsSlot): the 64-site walk of the
+// 20-state unfused layout.  9 088 B of stage buffers and symbol slots + 10 240 B = 19 328 B per wave, 77 312 B per
+// workgroup, two workgroups per CU.
+constexpr bool map_lds_slot(int S, int fuse, int ng) { return S == 20 && fuse == 1 && ng == 4; }
 
 // Device-resident model + tree program.  All pointers are device pointers.
 struct DevModel {

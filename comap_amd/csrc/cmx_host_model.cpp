@@ -165,6 +165,7 @@ namespace {
 template <bool CT, bool CR>
 struct Recorder {
   static constexpr bool kCherryTables = CT, kCherryRows = CR;
+  static constexpr bool kLdsSlot = !CT;   // the plain walk follows the plan's flags; the cherry-table walk has none (fused models)
   HostModel* hm;
   long t = 0;
   std::vector<long> store_time[2];
@@ -194,6 +195,10 @@ struct Recorder {
   template <int S, int D, bool TR> void mv(int node, int which) { op(mat_internal(node, which), -1); (CT ? hm->n_products_r : hm->n_products)++; }
   template <int D> void load(int arr, int slot) { loads.push_back({arr, slot, t++, store_time[arr][slot]}); if (!CT) hm->n_loads++; }
   template <int S> void store(int arr, int slot) { store_time[arr][slot] = t++; if (!CT) hm->n_stores++; }
+  // transfers the LDS slot serves: still loads and stores of the walk (n_loads, n_stores, ldsched), counted beside them
+  template <int D> void lload(int arr, int slot) { load<D>(arr, slot); hm->n_lds_loads++; }
+  template <int S> void lstore(int arr, int slot) { store<S>(arr, slot); hm->n_lds_stores++; }
+  template <int S> void lcopy(int, int) { ++t; hm->n_lds_copies++; }
   template <int D, int S> void mov() {}
   template <int D, int S> void mul() {}
   template <int D, int A, int B> void prod() {}
@@ -209,6 +214,9 @@ struct Recorder {
 template <bool CT, bool CR>
 struct Numeric {
   static constexpr bool kCherryTables = CT, kCherryRows = CR;
+  static constexpr bool kLdsSlot = !CT;
+  std::vector<double> lds;                 // the LDS slot: a fifth vector, NaN until written and again after each read
+  int lds_arr = -1, lds_slot = -1;         // its occupant
   const HostModel& hm;
   int dS, NB;
   size_t MU;
@@ -221,6 +229,7 @@ struct Numeric {
   explicit Numeric(const HostModel& h) : hm(h), dS(h.dS), NB(h.dS / 4), MU((size_t)mat_unit(h.dS)), blk(h.MAT.data()) {
     const double nan = std::nan("");
     for (auto& r : R) r.assign(dS, nan);
+    lds.assign(dS, nan);
     ws[0].assign((size_t)h.NIW * dS, nan);
     ws[1].assign((size_t)h.NIW * dS, nan);
     cnt.assign((size_t)h.B * h.K, nan);
@@ -319,6 +328,23 @@ struct Numeric {
     if (slot < 0 || slot >= hm.NIW) return fail("workspace slot out of range");
     std::copy(R[S].begin(), R[S].end(), &ws[arr][(size_t)slot * dS]);
   }
+  template <int D> void lload(int arr, int slot) {
+    if (fi >= hm.ldsched.size()) return fail("more workspace loads than scheduled");
+    const int w = hm.ldsched[fi++];
+    if (((w >> 30) & 1) != arr || (w & 0xffffff) != slot) return fail("load " + std::to_string(fi - 1) + " names the wrong vector");
+    if (lds_arr != arr || lds_slot != slot) return fail("load " + std::to_string(fi - 1) + " finds the LDS slot empty or holding another vector");
+    R[D] = lds;
+    lds.assign(dS, std::nan(""));
+    lds_arr = lds_slot = -1;
+  }
+  template <int S> void lstore(int arr, int slot) {
+    if (slot < 0 || slot >= hm.NIW) return fail("workspace slot out of range");
+    if (lds_arr >= 0) return fail("the LDS slot is written while it holds a vector nobody has read");
+    lds = R[S];
+    lds_arr = arr;
+    lds_slot = slot;
+  }
+  template <int S> void lcopy(int arr, int slot) { lstore<S>(arr, slot); }
   template <int D, int S> void mov() { R[D] = R[S]; }
   template <int D, int S> void mul() { for (int x = 0; x < dS; ++x) R[D][x] *= R[S][x]; }
   template <int D, int A, int B> void prod() { for (int x = 0; x < dS; ++x) R[D][x] = R[A][x] * R[B][x]; }
@@ -345,6 +371,32 @@ void record_plain(HostModel* hm) {
   }
 }
 
+// ---- SlotProbe: the workspace transfers of a pass with the record that issues each, in the Recorder's program-order time
+struct SlotProbe {
+  static constexpr bool kCherryTables = false, kCherryRows = true, kLdsSlot = false;
+  const HostModel* hm;
+  long t = 0;
+  int cur = -1;
+  struct Ev { int arr, slot, v; long t; };
+  std::vector<Ev> stores, loads;
+  explicit SlotProbe(const HostModel* h) : hm(h) {}
+  void rec(int v, int (&r)[16]) { cur = v; for (int i = 0; i < 16; ++i) r[i] = hm->nrec[(size_t)v * 16 + i]; }
+  template <int D> void lset(int, int) { ++t; }
+  template <int S, int D> void lmul(int, int) { ++t; }
+  template <int S> void ldot(int, int, int) { ++t; }
+  template <int S, int D, bool TR> void mv(int, int) { ++t; }
+  template <int D> void load(int arr, int slot) { loads.push_back({arr, slot, cur, t++}); }
+  template <int S> void store(int arr, int slot) { stores.push_back({arr, slot, cur, t++}); }
+  template <int D, int S> void mov() {}
+  template <int D, int S> void mul() {}
+  template <int D, int A, int B> void prod() {}
+  void mulup() {}
+  template <int D> void setpi() {}
+  template <int S> void rootl() {}
+  void dot3(int) {}
+  template <int R> void kill() {}
+};
+
 // what verify_walk keeps of a numeric pass
 struct NumericResult {
   std::string err;
@@ -361,12 +413,63 @@ NumericResult run_numeric(const HostModel& hm) {
 }
 }  // namespace
 
+// Which workspace vectors go through the wave's one LDS slot (cmx_walk.h, kLdsSlot) instead of HBM.  Candidates, at a node
+// whose child A is a visited node: (inside) M_a, stored at A's visit and loaded at the node's -- the HBM store stays, the
+// outside pass needs it, so the slot saves the load: weight 1; (outside) U_a, stored at the node's visit and loaded at A's --
+// neither transfer happens: weight 2.  A candidate occupies the slot from its store to its load in program order; the plan
+// is the set of disjoint intervals of largest weight (weighted interval scheduling), written as FLAG_LDS_* bits of the
+// records.  Only the 20-state unfused layout has a device backend with a slot; no other model is planned.
+void plan_lds_slot(HostModel* hm) {
+  for (int v = 0; v < hm->NV; ++v)
+    hm->nrec[(size_t)v * 16 + REC_FLAGS] &= ~(FLAG_LDS_M_PUT | FLAG_LDS_M_GET | FLAG_LDS_UA_PUT | FLAG_LDS_U_GET);
+  if (!hm->lds_slot || hm->S != 20 || hm->fuse != 1) return;
+  SlotProbe pb(hm);
+  walk_pass(pb, hm->NV, hm->K);
+  std::vector<const SlotProbe::Ev*> st[2];
+  st[0].assign(hm->NIW, nullptr);
+  st[1].assign(hm->NIW, nullptr);
+  for (const auto& e : pb.stores) st[e.arr][e.slot] = &e;   // every vector is written once
+  struct Iv { long s, e; int w, put_v, get_v, put_flag, get_flag; };
+  std::vector<Iv> iv;
+  std::vector<char> m_loaded(hm->NIW, 0);
+  auto child_a = [&](int v, int slot) {
+    const int* r = &hm->nrec[(size_t)v * 16];
+    return r[REC_A + CH_KIND] == KIND_STORED && r[REC_A + CH_SLOT] == slot;
+  };
+  for (const auto& l : pb.loads) {
+    const SlotProbe::Ev* s = st[l.arr][l.slot];
+    if (!s || s->t >= l.t) continue;
+    if (l.arr == WS_M) {   // the first load of a message is the inside pass's
+      if (!m_loaded[l.slot] && child_a(l.v, l.slot)) iv.push_back({s->t, l.t, 1, s->v, l.v, FLAG_LDS_M_PUT, FLAG_LDS_M_GET});
+      m_loaded[l.slot] = 1;
+    } else if (child_a(s->v, l.slot) && hm->nrec[(size_t)l.v * 16 + REC_SLOT] == l.slot) {
+      iv.push_back({s->t, l.t, 2, s->v, l.v, FLAG_LDS_UA_PUT, FLAG_LDS_U_GET});
+    }
+  }
+  std::sort(iv.begin(), iv.end(), [](const Iv& a, const Iv& b) { return a.e < b.e; });
+  const size_t n = iv.size();
+  std::vector<long> best(n + 1, 0);          // best[i]: largest weight among the first i intervals
+  std::vector<size_t> prev(n, 0);            // intervals that end before interval i starts
+  for (size_t i = 0; i < n; ++i) {
+    prev[i] = (size_t)(std::lower_bound(iv.begin(), iv.begin() + i, iv[i].s, [](const Iv& a, long s) { return a.e < s; }) - iv.begin());
+    best[i + 1] = std::max(best[i], best[prev[i]] + iv[i].w);
+  }
+  for (size_t i = n; i > 0;) {
+    if (best[i] == best[i - 1]) { --i; continue; }
+    const Iv& x = iv[i - 1];
+    hm->nrec[(size_t)x.put_v * 16 + REC_FLAGS] |= x.put_flag;
+    hm->nrec[(size_t)x.get_v * 16 + REC_FLAGS] |= x.get_flag;
+    i = prev[i - 1];
+  }
+}
+
 // records -> operator stream + load schedule (with prefetchability) by a dry run of the walk
 void record_walk(HostModel* hm) {
   hm->msched.clear();
   hm->msched_r.clear();
   hm->ldsched.clear();
   hm->n_loads = hm->n_stores = hm->n_products = hm->n_leaf_ops = hm->n_products_r = hm->n_leaf_ops_r = 0;
+  hm->n_lds_loads = hm->n_lds_stores = hm->n_lds_copies = 0;
   if (hm->cherry_base > 0) {   // the cherry-table walk's own operator stream (same loads and stores)
     Recorder<true, false> rt(hm);
     walk_pass(rt, hm->NV, hm->K);
@@ -506,6 +609,7 @@ std::string build_host_model(const cmx_model* model, const cmx_tree* tree, HostM
   hm->fuse = (S == 4 && C >= 4) ? (C == 4 ? 4 : 5) : 1;   // (before record_walk: it chooses the cherry visit of the plain stream)
   if (!hm->plain) {
     build_records(hm);
+    plan_lds_slot(hm);
     // cherry tables only for the class-fused nucleotide layout (16 symbol pairs; 400 for proteins would not fit a stage buffer)
     // (a fused model without a single cherry still gets the second stream -- identical to the first: the null's kernel
     // instantiation reads it unconditionally)

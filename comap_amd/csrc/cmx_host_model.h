@@ -52,12 +52,17 @@ struct HostModel {
   std::vector<int> msched_r;    // operator stream of the cherry-table walk; entry (matrix, taxon | 0x40000000 | tx1 | tx2 << 15 | -1)
   // per class pass, for traffic / flop accounting (_r: the cherry-table walk)
   size_t n_loads = 0, n_stores = 0, n_products = 0, n_leaf_ops = 0, n_products_r = 0, n_leaf_ops_r = 0;
+  // LDS slot of the mapping wave (cmx_walk.h, kLdsSlot).  lds_slot is an input of build_host_model: false = plan nothing.
+  // Of n_loads / n_stores, the transfers the slot serves instead of HBM; n_lds_copies: messages written to both.
+  bool lds_slot = true;
+  size_t n_lds_loads = 0, n_lds_stores = 0, n_lds_copies = 0;
 };
 
 // The walk of a rate-class pass lives in cmx_walk.h.  build_records: the per-node records it reads; record_walk: the
 // operator stream and load schedule the device follows (a dry run of the walk); verify_walk: the walk run numerically
 // on the host from the device layouts against a direct pruning computation (empty string when they agree).
 void build_records(HostModel* hm);
+void plan_lds_slot(HostModel* hm);   // after build_records, before record_walk: sets the FLAG_LDS_* bits of the records
 void record_walk(HostModel* hm);
 std::string verify_walk(const HostModel& hm);
 

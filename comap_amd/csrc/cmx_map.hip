@@ -14,7 +14,8 @@
 //   Matrices are packed host-side in 4x4 blocks so that one copy serves both P.d (inside) and P^T.u (outside).
 //   Inside vectors / outside messages that must survive go to a per-wave HBM workspace as [S/2][lane][2]: every
 //   access is one fully coalesced 1 KiB row; they come back by plain global loads into registers the walk has declared
-//   dead long before (DevWalk::load).  LDS holds, per wave, two operator stage buffers and four symbol slots.
+//   dead long before (DevWalk::load).  LDS holds, per wave, two operator stage buffers and four symbol slots; the 64-site
+//   protein walk adds one workspace vector (DevWalk::kLdsSlot) for the short-lived vectors the host's plan names.
 //   DESIGN.md 4.1 has the full description and the measurements.
 //   MODE == kModeNull: map (x2 batches) -> per-pair statistic of AnalysisTools::getNullDistributionIntraDR
 //   (CoMap/AnalysisTools.cpp:587-653) per wave, on alignments simulated beforehand by simulate_lds_kernel /
@@ -360,6 +361,9 @@ struct DevWalk {
   static constexpr int kVecInstrs = (VL + 1) / 2;   // VMEM instructions of one workspace vector
   static constexpr bool kCherryTables = RESOLVED && DIAG;   // cmx_walk.h: cset / cdot instead of a cherry's operator ops
   static constexpr bool kCherryRows = FUSE == 1;            // cmx_walk.h: a cherry's outside visit keeps its leaf rows in registers
+  // cmx_walk.h: one workspace vector per wave stays in LDS where the records say so (the 64-site protein walk in all its
+  // modes; the 16-site shape shares the records and ignores the bits, like every backend without a slot)
+  static constexpr bool kLdsSlot = map_lds_slot(S, FUSE, NG);
   static constexpr int kCherryBytes = 16 * leaf_row_stride(S) * 8;   // a table's 16 rows (one per symbol pair)
   static constexpr int kCherryFlag = 0x40000000;                     // stream entry: taxon of l1 | taxon of l2 << 15 | flag
   static_assert(kCherryBytes <= MatStage<S>::BYTES, "a cherry table fits a stage buffer");
@@ -372,7 +376,7 @@ struct DevWalk {
   double *wsM, *wsU, *pcnt;
   const uint8_t* gcodes;
   size_t gstride;
-  uint8_t *stage, *cslot, *cslot2;
+  uint8_t *stage, *cslot, *cslot2, *vslot;
   uint32_t lds_stage, lds_codes, lds_codes2;
   int lane, c, c_end;
   double pc;
@@ -536,6 +540,33 @@ struct DevWalk {
     }
     os.vs += kVecInstrs;
   }
+  // LDS slot (kLdsSlot): the vector in the workspace layout [VL/2][64 lanes][2], one 16-byte access per lane and row (no
+  // bank conflict).  Plain accesses: the compiler's own lgkmcnt waits cover them, and they are not VMEM, so os.vs does
+  // not count them.
+  template <int D>
+  __device__ __forceinline__ void lload(int, int) {
+    static_assert(kLdsSlot && VL % 2 == 0, "LDS slot");
+    const d2* p = reinterpret_cast<const d2*>(vslot) + vlane();
+#pragma unroll
+    for (int i = 0; i < VL / 2; ++i) {
+      const d2 t = p[i * kWave];
+      reg<D>()[2 * i] = t[0];
+      reg<D>()[2 * i + 1] = t[1];
+    }
+  }
+  template <int SRC>
+  __device__ __forceinline__ void lstore(int, int) {
+    static_assert(kLdsSlot && VL % 2 == 0, "LDS slot");
+    d2* p = reinterpret_cast<d2*>(vslot) + vlane();
+#pragma unroll
+    for (int i = 0; i < VL / 2; ++i) {
+      d2 t;
+      t[0] = reg<SRC>()[2 * i];
+      t[1] = reg<SRC>()[2 * i + 1];
+      p[i * kWave] = t;
+    }
+  }
+  template <int SRC> __device__ __forceinline__ void lcopy(int arr, int slot) { lstore<SRC>(arr, slot); }
   template <int D, int SRC> __device__ __forceinline__ void mov() {
 #pragma unroll
     for (int x = 0; x < VL; ++x) reg<D>()[x] = reg<SRC>()[x];
@@ -628,6 +659,7 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
   be.stage = cmx_smem + lds_off;                                 // two operator buffers
   be.cslot = be.stage + 2 * MatStage<S>::BYTES;                  // two symbol slots
   be.cslot2 = be.cslot + 2 * kCodeSlotBytes;                     // ... and two for the second leaf of a cherry-table op
+  be.vslot = be.cslot2 + 2 * kCodeSlotBytes;                     // ... and, with kLdsSlot, one workspace vector
   be.lds_stage = lds_addr(be.stage);                             // wave-uniform LDS byte addresses (SGPRs)
   be.lds_codes = lds_addr(be.cslot);
   be.lds_codes2 = lds_addr(be.cslot2);
@@ -730,12 +762,16 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
   norm_out = sqrt(nrm);
 }
 
-// LDS per mapping wave: two operator stage buffers + four symbol slots (two per leaf of a cherry-table op)
+// LDS per mapping wave: two operator stage buffers + four symbol slots (two per leaf of a cherry-table op), and one
+// workspace vector of ng site groups for the instantiations with an LDS slot (DevWalk::kLdsSlot)
 template <int S>
-constexpr int map_lds_fixed() { return 2 * MatStage<S>::BYTES + 4 * kCodeSlotBytes; }
-static int map_lds_per_wave(int S) {
-  return S == 20 ? map_lds_fixed<20>() : (S == 16 ? map_lds_fixed<16>() : map_lds_fixed<4>());
+constexpr int map_lds_fixed(int fuse, int ng) {
+  return 2 * MatStage<S>::BYTES + 4 * kCodeSlotBytes + (map_lds_slot(S, fuse, ng) ? S / 4 * ng * kWave * 8 : 0);
 }
+static int map_lds_per_wave(int S, int fuse, int ng) {
+  return S == 20 ? map_lds_fixed<20>(fuse, ng) : (S == 16 ? map_lds_fixed<16>(fuse, ng) : map_lds_fixed<4>(fuse, ng));
+}
+static_assert(kWavesPerBlock * map_lds_fixed<20>(1, 4) <= 160 * 1024 / map_waves_per_simd(20), "the protein walk's workgroup fits its share of a CU's LDS");
 
 template <int S, int MODE, int FUSE, int NG = map_ng(S)>
 __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void map_kernel(const MapArgs a) {
@@ -756,7 +792,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
   double* cnt0 = a.ws.cnt + (size_t)wave * 2 * m.B * m.K * kSites;
   double* cnt1 = cnt0 + (size_t)m.B * m.K * kSites;
   double* part = a.ws.part + (size_t)wave * m.C * m.B * m.K * kSites;
-  // LDS per wave: two operator stage buffers, then four symbol slots (map_lds_fixed)
+  // LDS per wave: two operator stage buffers, then four symbol slots, then the vector slot if any (map_lds_fixed)
   const int lds_off = wib * a.lds_per_wave;
   const size_t nblocks = (a.nsites + kSites - 1) / kSites;
   // request the first op's operator (class 0, entry 0); every op then requests the next one
@@ -884,7 +920,8 @@ static hipError_t launch_map_mode(int mode, const MapArgs& a, dim3 grid, dim3 bl
 hipError_t launch_map(const MapArgs& a_in, int mode, int grid_blocks, hipStream_t stream) {
   dim3 grid(grid_blocks), block(kWave * kWavesPerBlock);
   MapArgs a = a_in;
-  a.lds_per_wave = map_lds_per_wave(a.m.S);
+  const bool split16 = a.m.S == 20 && a.m.fuse == 1 && mode == kModeObservedSplit && a.split_sites == 16;
+  a.lds_per_wave = map_lds_per_wave(a.m.S, a.m.fuse, split16 ? 1 : map_ng(a.m.S));
   const size_t lds = (size_t)kWavesPerBlock * (size_t)a.lds_per_wave;
   const int lim = 160 * 1024 / map_waves_per_simd(a.m.S);  // dynamic LDS a workgroup may use (that many workgroups per CU)
   if ((int)lds > lim) return hipErrorInvalidValue;
@@ -892,7 +929,7 @@ hipError_t launch_map(const MapArgs& a_in, int mode, int grid_blocks, hipStream_
   if ((mode == kModeNull || mode == kModeNullPatterns) && a.m.fuse > 1 && a.m.msched_r == nullptr) return hipErrorInvalidValue;
   if (mode == kModeNullPatterns && (!a.rep_site || !a.npat || !a.counts || !a.post_rate || !a.rate_class || !a.norm)) return hipErrorInvalidValue;
   // 16-site wave-tasks (one site group): small alignments, four times the waves
-  if (a.m.S == 20 && a.m.fuse == 1 && mode == kModeObservedSplit && a.split_sites == 16)
+  if (split16)
     return launch_map_as<20, kModeObservedSplit, 1, 1>(a, grid, block, lds, lim, stream);
   if (a.m.S == 20 && a.m.fuse == 1) return launch_map_mode<20, 1>(mode, a, grid, block, lds, lim, stream);
   if (a.m.S == 20 && a.m.fuse == 5) return launch_map_mode<20, 5>(mode, a, grid, block, lds, lim, stream);

@@ -16,6 +16,9 @@
 // their message is rebuilt from two leaf gathers and one product where needed and their three branches are counted
 // where their outside message is produced.  A node's LAST visited child hands its message over in registers (R1 on the
 // way up, R0 on the way down); everything else goes through the per-wave workspace, written once.
+// At a node whose two children are both visited, child A's vectors are short-lived: M_a is stored a few visits before the
+// node's inside visit loads it, U_a is stored at the node's outside visit and loaded a few visits later.  A backend with
+// kLdsSlot keeps ONE such vector at a time on chip; which ones, the host plans per tree (FLAG_LDS_*).
 //
 // Registers: R0..R3.  Only R1 (inside) / R0 (outside) are live from one node to the next; the backends' kill<R>() tells
 // a compiler so.  Templates name registers at compile time; the device maps them to VGPR arrays.
@@ -39,7 +42,13 @@ enum { KIND_LEAF = 0, KIND_STORED = 1, KIND_CHERRY = 2 };
 enum { FLAG_PSEUDO = 1,       // zero-length branch of a split multifurcation
        FLAG_HAND = 2,         // child B is the node visited right before (inside) / right after (outside) this one
        FLAG_U_HANDED = 4,     // this node's outside message arrives in R0 (its parent is the node visited right before it)
-       FLAG_ROOT = 8 };
+       FLAG_ROOT = 8,
+       // LDS slot (backends with kLdsSlot; the host's plan, cmx_host_model.cpp: plan_lds_slot).  Other backends ignore the
+       // bits: the workspace slots stay allocated and a flagged transfer is a valid plain one.
+       FLAG_LDS_M_PUT = 16,   // inside: this node's message also goes to the wave's LDS slot (its parent reads it there)
+       FLAG_LDS_M_GET = 32,   // inside: M_a comes from the LDS slot, not from WS_M
+       FLAG_LDS_UA_PUT = 64,  // outside: U_a goes to the LDS slot and not to WS_U
+       FLAG_LDS_U_GET = 128 };// outside: this node's U comes from the LDS slot, not from WS_U
 enum { WS_M = 0, WS_U = 1 };  // workspace arrays: messages of the inside pass, outside messages
 enum { OPER_P = -1 };         // which operator of a branch: OPER_P = transition matrix, k >= 0 = count operator k
 
@@ -57,6 +66,9 @@ enum { OPER_P = -1 };         // which operator of a branch: OPER_P = transition
 //   mv<S, D, TR>(node, which)  [D = M S or M^T S];  load<D>(arr, slot); store<S>(arr, slot)
 //   mov<D, S>(); mul<D, S>() [D *= S]; prod<D, A, B>() [D = A o B]; mulup() [R1 *= R3, R2 *= R3]; setpi<D>(); rootl<S>();
 //   dot3(row)  [count = sum R3 o R1 o R2]; kill<R>()
+//   static constexpr bool kLdsSlot: the wave has ONE on-chip slot of a workspace vector.  Where the records say so (FLAG_LDS_*)
+//   lstore<S>(arr, slot) / lload<D>(arr, slot) take the place of store / load -- same registers on both arms -- and
+//   lcopy<S>(arr, slot) follows a store whose vector has a second, early reader.  A slot read frees the slot.
 //   static constexpr bool kCherryRows  (unfused models; a backend with cherry tables never reaches it): the outside visit
 //   of an inlined cherry gathers each of its two leaf rows A = P_l1[:, s1], Bv = P_l2[:, s2] ONCE and keeps it in a
 //   register the visit leaves dead anyway -- 2 + 2 K leaf ops as child B, 2 + 3 K as child A (whose sibling's outside
@@ -103,7 +115,12 @@ CMX_HD void walk_child_dispose(BE& be, const int (&r)[16], int K) {
   if (kind == KIND_LEAF) {
     for (int k = 0; k < K; ++k) be.template ldot<UR>(node, k, node * K + k);
   } else if (kind == KIND_STORED && !(SIDE && (r[REC_FLAGS] & FLAG_HAND))) {
-    be.template store<UR>(WS_U, r[o + CH_SLOT]);
+    if constexpr (BE::kLdsSlot && SIDE == 0) {
+      if (r[REC_FLAGS] & FLAG_LDS_UA_PUT) be.template lstore<UR>(WS_U, r[o + CH_SLOT]);
+      else be.template store<UR>(WS_U, r[o + CH_SLOT]);
+    } else {
+      be.template store<UR>(WS_U, r[o + CH_SLOT]);
+    }
   } else {
     if constexpr (BE::kCherryTables) {
       if (kind == KIND_CHERRY) {
@@ -193,7 +210,12 @@ CMX_HD void walk_pass(BE& be, int NV, int K) {
       if (ka == KIND_LEAF) {
         be.template lset<0>(r[REC_A + CH_NODE], OPER_P);
       } else if (ka == KIND_STORED) {
-        be.template load<0>(WS_M, r[REC_A + CH_SLOT]);
+        if constexpr (BE::kLdsSlot) {
+          if (flags & FLAG_LDS_M_GET) be.template lload<0>(WS_M, r[REC_A + CH_SLOT]);
+          else be.template load<0>(WS_M, r[REC_A + CH_SLOT]);
+        } else {
+          be.template load<0>(WS_M, r[REC_A + CH_SLOT]);
+        }
       } else if constexpr (BE::kCherryTables) {
         be.template cset<0>(r[REC_A + CH_NODE], r[REC_A + CH_L1], r[REC_A + CH_L2]);
       } else {
@@ -219,6 +241,9 @@ CMX_HD void walk_pass(BE& be, int NV, int K) {
       if (flags & FLAG_PSEUDO) be.template mov<1, 0>();                 // zero-length branch: M = D
       else be.template mv<0, 1, false>(r[REC_NODE], OPER_P);
       be.template store<1>(WS_M, r[REC_SLOT]);
+      if constexpr (BE::kLdsSlot) {
+        if (flags & FLAG_LDS_M_PUT) be.template lcopy<1>(WS_M, r[REC_SLOT]);
+      }
     }
   }
   // ------------------------------------------------------------------ outside pass + joint counts
@@ -231,7 +256,12 @@ CMX_HD void walk_pass(BE& be, int NV, int K) {
     be.template kill<3>();
     if (!(flags & FLAG_U_HANDED)) {
       be.template kill<0>();
-      if (!(flags & FLAG_ROOT)) be.template load<0>(WS_U, r[REC_SLOT]);
+      if constexpr (BE::kLdsSlot) {
+        if (flags & FLAG_LDS_U_GET) be.template lload<0>(WS_U, r[REC_SLOT]);
+        else if (!(flags & FLAG_ROOT)) be.template load<0>(WS_U, r[REC_SLOT]);
+      } else {
+        if (!(flags & FLAG_ROOT)) be.template load<0>(WS_U, r[REC_SLOT]);
+      }
     }
     // ---- messages of the children: M_b -> R2, M_a -> R1 (stored ones: the device only ISSUES the loads here; they are
     // first read by the count below, after the first product)

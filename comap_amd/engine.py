@@ -58,7 +58,7 @@ EXPORTS = [
     "cmx_group_stats", "cmx_group_stats_dev", "cmx_candidate_groups", "cmx_debug_candidate_cursor",
     "cmx_hclust", "cmx_hclust_dev", "cmx_cluster_sites", "cmx_cluster_sites_dev", "cmx_cluster_null",
     "cmx_intra_compact_range_dev", "cmx_intra_gram_prefetch_dev", "cmx_expand_compact_rows", "cmx_vector_matrix",
-    "cmx_scratch_check", "cmx_debug_scratch_guard", "cmx_debug_scratch_guard_failures", "cmx_debug_scratch_shrink",
+    "cmx_scratch_check", "cmx_debug_lds_slot", "cmx_debug_scratch_guard", "cmx_debug_scratch_guard_failures", "cmx_debug_scratch_shrink",
     "cmx_set_null_patterns", "cmx_null_pattern_count", "cmx_debug_null_hash_bits",
 ]
 # clustering.distance / clustering.method options of the reference (CoMap/CoMap.cpp:402-428, :460-472)
@@ -76,6 +76,13 @@ def scratch_guard(on=None):
     (None = query); returns the previous state"""
     lib = load_library()
     return bool(lib.cmx_debug_scratch_guard(ctypes.c_int(-1 if on is None else int(bool(on)))))
+
+
+def lds_slot(on=None):
+    """cmx_debug_lds_slot (include/comap_mi355x.h): whether contexts (and debug_walk) created from now on plan the mapping
+    walk's LDS slot (None = query); returns the previous state.  Off = every workspace vector goes through HBM."""
+    lib = load_library()
+    return bool(lib.cmx_debug_lds_slot(ctypes.c_int(-1 if on is None else int(bool(on)))))
 
 
 def scratch_guard_failures(clear=False):
@@ -233,8 +240,9 @@ def _sz(x):
 
 def debug_walk(parent, blen, leaf_of_taxon, Q, pi, rates, probs, Bk=None):
     """Host-side compilation of the tree into what the mapping kernel's walk reads (no GPU): dict(nrec[NV,16], ldsched,
-    msched[nops,2], slot[nnodes], loads, stores, products, leaf_ops, products_tables, leaf_ops_tables, cherry_tables) --
-    counts are per rate-class pass; *_tables: the walk of resolved alignments with cherry tables (class-fused nucleotide
+    msched[nops,2], slot[nnodes], loads, stores, products, leaf_ops, products_tables, leaf_ops_tables, cherry_tables,
+    lds_loads, lds_stores, lds_copies) -- counts are per rate-class pass; lds_loads / lds_stores: those of `loads` / `stores`
+    that the wave's LDS slot serves instead of HBM, lds_copies: messages written to both (cmx_walk.h, kLdsSlot); *_tables: the walk of resolved alignments with cherry tables (class-fused nucleotide
     models; cherry_tables = 0: no such walk).  The call fails if the engine's numerical self-check of either walk does."""
     lib = load_library()
     keep = [np.ascontiguousarray(parent, dtype=np.int32), _f64(blen), np.ascontiguousarray(leaf_of_taxon, dtype=np.int32),
@@ -257,7 +265,8 @@ def debug_walk(parent, blen, leaf_of_taxon, Q, pi, rates, probs, Bk=None):
     return dict(nrec=nrec[: n1.value].reshape(-1, 16).copy(), ldsched=ld[: n2.value].copy(),
                 msched=ms[: n3.value].reshape(-1, 2).copy(), slot=slot, loads=int(stats[0]), stores=int(stats[1]),
                 products=int(stats[2]), leaf_ops=int(stats[3]), products_tables=int(stats[4]), leaf_ops_tables=int(stats[5]),
-                cherry_tables=int(stats[6]))
+                cherry_tables=int(stats[6]), lds_loads=int(stats[7]) & 0xfffff, lds_stores=(int(stats[7]) >> 20) & 0xfffff,
+                lds_copies=(int(stats[7]) >> 40) & 0xfffff)
 
 
 def debug_candidate_cursor(norm_windows, analysable, min_sim, norms, max_trials):

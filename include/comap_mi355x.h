@@ -149,9 +149,15 @@ void cmx_debug_scratch_shrink(const char* name, size_t bytes);
 cmx_status cmx_debug_walk(const cmx_model* model, const cmx_tree* tree, int32_t* nrec, size_t nrec_cap, size_t* nrec_n,
                           int32_t* ldsched, size_t ld_cap, size_t* ld_n, int32_t* msched, size_t m_cap, size_t* m_n,
                           int32_t* slot_of_node /*[nnodes] or NULL*/,
-                          uint64_t* stats /*[7] or NULL: workspace loads, stores, matrix products, leaf ops per pass; products and
+                          uint64_t* stats /*[8] or NULL: workspace loads, stores, matrix products, leaf ops per pass; products and
                                             leaf ops of the cherry-table walk (resolved alignments of class-fused nucleotide
-                                            models), cherries with tables (0: that walk is the first one)*/);
+                                            models), cherries with tables (0: that walk is the first one); [7]: of those loads
+                                            and stores, the ones the wave's LDS slot serves instead of HBM (loads in bits 0-19,
+                                            stores in bits 20-39) and the messages written to both (bits 40-59)*/);
+/* The mapping walk keeps short-lived workspace vectors in one LDS slot per wave where the tree allows it (20-state models;
+ * results are the same bits either way).  cmx_debug_lds_slot(0) makes contexts created from now on plan the slot empty, i.e.
+ * every vector goes through HBM (A/B runs, tests).  on < 0: query only; returns the previous state.  Process-wide, host only. */
+int cmx_debug_lds_slot(int on);
 
 /* ---- substitution mapping: replaces DRHomogeneousTreeLikelihood::initialize + getLogLikelihoodPerSite /
  * getPosteriorRatePerSite / getRateClassWithMaxPostProbPerSite + computeSubstitutionVectors + computeNormForSite
