@@ -215,50 +215,36 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
     d.S = h.dS; d.C = h.dC; d.S0 = h.S; d.C0 = h.C; d.fuse = h.fuse; d.K = h.K; d.nn = h.nn; d.B = h.B; d.T = h.T; d.NI = h.NI; d.NIW = h.NIW; d.NV = h.NV; d.root = h.root;
 #define UP(field) CMX_TRY(upload(ctx, h.field, &d.field))
     UP(taxon_of); UP(parent);
-    if (h.plain) {
-      // alphabets other than 4 / 20 states: simulator tables and tree only; the sites are mapped by the plain kernels of
-      // cmx_variants.hip on scratch buffers (map_plain below), no operator stream, no per-wave workspaces
-      UP(simg); UP(simord);
-      d.nsimg = (int)(h.simg.size() / 16);
-      UP(eigV); UP(eigVi); UP(eigLam); UP(model_of); UP(blen);
-      UP(CP); UP(CPG); UP(pi); UP(rates); UP(probs); UP(cum_pi); UP(cum_probs);
-      return CMX_OK;
-    }
-    {
+    if (!h.plain) {
+      // (alphabets other than 4 / 20 states get none of this: their sites are mapped by the plain kernels of cmx_variants.hip
+      // on scratch buffers -- map_plain -- with no operator stream and no per-wave workspaces)
       const double* mat = nullptr;
       CMX_TRY(upload(ctx, h.MAT, &mat));
       d.MAT = const_cast<double*>(mat);
-    }
-    d.MC = h.MC;
-    {  // device copy of the operator stream: operator indices premultiplied to element offsets, and the first two entries
-       // repeated after the last one so that "the entry two ops ahead" never needs a wrap test
-      std::vector<int> ms(h.msched);
-      const int unit = mat_unit(h.dS);
-      for (size_t i = 0; i < ms.size(); i += 2) ms[i] *= unit;
-      const size_t n2 = ms.size();
-      for (size_t i = 0; i < 4; ++i) ms.push_back(ms[i % n2]);
-      const int* dms = nullptr;
-      CMX_TRY(upload(ctx, ms, &dms));
-      d.msched = dms;
-      d.nmv = (int)(h.msched.size() / 2);
+      d.MC = h.MC;
+      // device copy of an operator stream: operator indices premultiplied to element offsets, and the first two entries
+      // repeated after the last one so that "the entry two ops ahead" never needs a wrap test
+      auto up_stream = [&](const std::vector<int>& stream, const int** dev, int* nmv) -> cmx_status {
+        std::vector<int> ms(stream);
+        const int unit = mat_unit(h.dS);
+        for (size_t i = 0; i < ms.size(); i += 2) ms[i] *= unit;
+        const size_t n2 = ms.size();
+        for (size_t i = 0; i < 4; ++i) ms.push_back(ms[i % n2]);
+        *nmv = (int)(stream.size() / 2);
+        return upload(ctx, ms, dev);
+      };
+      CMX_TRY(up_stream(h.msched, &d.msched, &d.nmv));
       d.msched_r = nullptr;
       d.nmv_r = 0;
-      if (!h.msched_r.empty()) {   // the cherry-table walk's stream, prepared the same way
-        std::vector<int> mr(h.msched_r);
-        for (size_t i = 0; i < mr.size(); i += 2) mr[i] *= unit;
-        const size_t nr = mr.size();
-        for (size_t i = 0; i < 4; ++i) mr.push_back(mr[i % nr]);
-        const int* dmr = nullptr;
-        CMX_TRY(upload(ctx, mr, &dmr));
-        d.msched_r = dmr;
-        d.nmv_r = (int)(h.msched_r.size() / 2);
-      }
+      if (!h.msched_r.empty()) CMX_TRY(up_stream(h.msched_r, &d.msched_r, &d.nmv_r));   // the cherry-table walk's stream
+      UP(nrec);
     }
-    UP(nrec); UP(simg); UP(simord);
+    UP(simg); UP(simord);
     d.nsimg = (int)(h.simg.size() / 16);
     UP(eigV); UP(eigVi); UP(eigLam); UP(model_of); UP(blen);
     UP(CP); UP(CPG); UP(pi); UP(rates); UP(probs); UP(cum_pi); UP(cum_probs);
 #undef UP
+    if (h.plain) return CMX_OK;   // simulator tables and tree only
     // ambiguity rows of the leaf operators: default "every state compatible" until a call brings a mask table
     HIP_TRY(ctx, launch_extend_leaf_rows(d, nullptr, nullptr));
     HIP_TRY(ctx, hipDeviceSynchronize());

@@ -315,8 +315,6 @@ cmx_status cmx_simulate(cmx_ctx* ctx, uint64_t seed, uint64_t g0, size_t n, uint
   return download(ctx, classes_out, d_cls, n);
 }
 
-static_assert(kPlainStates <= kSimContinuousMaxStates, "simulate_continuous_kernel's per-thread row must hold the largest alphabet");
-
 cmx_status cmx_simulate_continuous_dev(cmx_ctx* ctx, uint64_t seed, uint64_t g0, size_t n, double gamma_alpha, double p_invariant,
                                        uint8_t* d_aln, size_t ld, double* d_rates, void* stream) {
   CMX_TRY(need_model(ctx));

@@ -6,23 +6,12 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "cmx_layout.h"
+
 namespace cmx {
 
 constexpr int kWave = 64;           // gfx950 wavefront
 constexpr int kWavesPerBlock = 4;   // mapping kernels: 4 independent waves per 256-thread workgroup
-// Ambiguous symbols (alignment codes >= S) are served from extra rows S .. S+A-1 appended to every transposed leaf
-// operator: row S+a = sum of the rows of the states compatible with ambiguity id a (filled per call from the caller's
-// mask table, default "every state").  A = 12 for nucleotides (IUPAC + gap), 4 for proteins (B, Z, J, X/gap).
-constexpr int max_ambig(int S) { return S == 4 ? 12 : 4; }
-// simulate_continuous_kernel keeps one row of the transition matrix per thread: the largest alphabet a context takes
-// (== kPlainStates of cmx_host_model.h; cmx_api.cpp asserts it)
-constexpr int kSimContinuousMaxStates = 64;
-// A transposed leaf operator is read row by row, the row named by a site's symbol: sixteen sites of a lane group read
-// sixteen rows at once.  With rows of S doubles (40 dwords for S = 20, 32 for the class-fused 16) rows 8 (2) apart fall
-// on the same LDS banks -- 61 % of the mapping kernel's LDS cycles were bank conflicts.  One double of padding per row
-// (42 / 34 dwords) moves the period to 32 rows: no two rows of an operator share a bank.
-constexpr int leaf_row_stride(int S) { return S + 1; }             // doubles per row of a transposed leaf operator
-constexpr int mat_unit(int S) { return (S + max_ambig(S)) * leaf_row_stride(S); }   // doubles per device matrix
 // A mapping wave walks four site groups of 16: lane = site.  (The 16-site class-split launch of small alignments is the one
 // other shape, one site group; fewer groups per wave with more waves per SIMD were measured and rejected)
 constexpr int map_ng(int) { return 4; }
@@ -46,11 +35,11 @@ struct DevModel {
   // tree (wave-uniform, read through the scalar cache; simulator only)
   const int* taxon_of;     // [nn]  alignment row of a leaf, -1 for internal nodes
   const int* parent;       // [nn]
-  // matrices, [C][MC][mat_unit(S)]: per class a block of packed P | packed (P o N^k) | leaf P^T | leaf (P o N^k)^T
-  // (cmx_host_model.cpp); a matrix use DMAs mat_unit(S)*8 bytes from MAT + (class*MC + index)*mat_unit(S) into LDS
+  // matrices, [C][MC][mat_unit(S)]: per class a block of packed P | packed (P o N^k) | leaf P^T | leaf (P o N^k)^T | cherry
+  // tables (cmx_layout.h: ClassBlock); a matrix use DMAs mat_unit(S)*8 bytes from MAT + (class*MC + index)*mat_unit(S) into LDS
   double* MAT;
   int MC;
-  // tree walk of one rate-class pass (cmx_walk.h; built and checked by cmx_host_model.cpp)
+  // tree walk of one rate-class pass (cmx_walk.h; built by cmx_host_tree.cpp, checked by cmx_host_verify.cpp)
   const int* nrec;         // [NV][16] per-visited-node records
   const int* msched;       // operator uses in program order: pairs (element offset in the class block, taxon or -1),
                            // followed by copies of its first two pairs (the op two ahead is read without a wrap test)

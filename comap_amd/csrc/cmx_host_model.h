@@ -9,10 +9,9 @@
 #include <vector>
 
 #include "../../include/comap_mi355x.h"
+#include "cmx_layout.h"
 
 namespace cmx {
-
-constexpr int kPlainStates = 64;   // device state count of the plain path (alphabets other than 4 / 20 states, up to 64)
 
 struct HostModel {
   int S = 0, C = 0, K = 0, nn = 0, B = 0, T = 0, NI = 0, root = 0;
@@ -30,8 +29,8 @@ struct HostModel {
   std::vector<double> PN;   // [C][B][K][S*S] P o N^k
   std::vector<double> N1;   // [B][K][S*S] N^k at the branch length itself (rate 1): the no-averaging mapping
   std::vector<double> NC;   // [C][B][K][S*S] N^k at r_c t_b (conditional, not P o N): the marginal mapping (nijt.joint = no)
-  std::vector<double> MAT;  // [C][MC][S*S]     device matrices: packed P | packed PN | leaf P^T | leaf PN^T (cmx_host_model.cpp)
-  int MC = 0;               // matrices per (device) class block = NI + NI*K + T + K*T
+  std::vector<double> MAT;  // [dC][MC][mat_unit(dS)] device matrices: packed P | packed PN | leaf P^T | leaf PN^T | cherry tables (block())
+  int MC = 0;               // matrices per (device) class block = block().count(); 0 on the plain path
   std::vector<double> eigV, eigVi, eigLam;   // [NM][S*S], [NM][S*S], [NM][S]: right / left eigenvectors and eigenvalues of the generators
   std::vector<int> model_of;                  // [B] generator of each branch (all 0 for a homogeneous model)
   std::vector<double> CP;   // [C][nn][S][S]    running row sums of P
@@ -42,14 +41,15 @@ struct HostModel {
   int NIW = 0;              // workspace slots: NI + pseudo nodes of split multifurcations
   std::vector<int> nrec;    // [NV][16] per-visited-node records (cmx_walk.h)
   std::vector<int> msched;  // operator uses of one class pass in program order: (matrix index, taxon or -1) pairs
-  std::vector<int> ldsched; // workspace loads of one class pass: bit 31 prefetchable, bit 30 array, low 24 bits slot
+  std::vector<int> ldsched; // workspace loads of one class pass: load_word(array, slot, prefetchable)
   // Cherry tables (cmx_walk.h; class-fused nucleotide models only): an inlined cherry's message and outside visit as rows
   // of 1 + 3 K tables indexed by its two leaves' symbols, for fully resolved alignments (the null's).  The tables follow
   // the leaf operators in a class block (matrix index cherry_base + cherry_of[node] * (1 + 3 K) + table); the walk that
   // uses them has its own operator stream.  ncherry = 0: no tables (proteins, nucleotide models with < 4 classes).
   std::vector<int> cherry_of;   // [nn] cherry index of an inlined cherry node, else -1
   int ncherry = 0, cherry_base = 0;
-  std::vector<int> msched_r;    // operator stream of the cherry-table walk; entry (matrix, taxon | 0x40000000 | tx1 | tx2 << 15 | -1)
+  std::vector<int> msched_r;    // operator stream of the cherry-table walk; entry (matrix, taxon | cherry_entry(tx1, tx2) | -1)
+  ClassBlock block() const { return {NI, K, T, ncherry}; }   // where an operator sits in a class block of MAT
   // per class pass, for traffic / flop accounting (_r: the cherry-table walk)
   size_t n_loads = 0, n_stores = 0, n_products = 0, n_leaf_ops = 0, n_products_r = 0, n_leaf_ops_r = 0;
   // LDS slot of the mapping wave (cmx_walk.h, kLdsSlot).  lds_slot is an input of build_host_model: false = plan nothing.
@@ -59,14 +59,15 @@ struct HostModel {
 };
 
 // The walk of a rate-class pass lives in cmx_walk.h.  build_records: the per-node records it reads; record_walk: the
-// operator stream and load schedule the device follows (a dry run of the walk); verify_walk: the walk run numerically
-// on the host from the device layouts against a direct pruning computation (empty string when they agree).
+// operator stream and load schedule the device follows (a dry run of the walk) -- both in cmx_host_tree.cpp; verify_walk
+// (cmx_host_verify.cpp): the walk run numerically on the host from the device layouts against a direct pruning
+// computation (empty string when they agree).
 void build_records(HostModel* hm);
 void plan_lds_slot(HostModel* hm);   // after build_records, before record_walk: sets the FLAG_LDS_* bits of the records
 void record_walk(HostModel* hm);
 std::string verify_walk(const HostModel& hm);
 
-// returns empty string on success, otherwise the error message (status in *code)
+// (cmx_host_model.cpp) returns empty string on success, otherwise the error message (status in *code)
 std::string build_host_model(const cmx_model* model, const cmx_tree* tree, HostModel* out, int* code);
 
 }  // namespace cmx

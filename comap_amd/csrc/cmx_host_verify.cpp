@@ -1,0 +1,253 @@
+// Host model, the self-check (see cmx_host_model.h): the walk of cmx_walk.h run numerically from the device layouts and
+// through the recorded streams, against a direct pruning computation on the tree itself.  Plain C++17, no device code.
+#include "cmx_host_parts.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace cmx {
+namespace {
+
+// ---- Numeric: the pass in plain doubles for one site, operators read from HostModel::MAT in their device layouts
+// and selected by the recorded stream exactly as the device selects them; every register starts as NaN.
+template <bool CT, bool CR>
+struct Numeric {
+  static constexpr bool kCherryTables = CT, kCherryRows = CR;
+  static constexpr bool kLdsSlot = !CT;
+  std::vector<double> lds;                 // the LDS slot: a fifth vector, NaN until written and again after each read
+  int lds_arr = -1, lds_slot = -1;         // its occupant
+  const HostModel& hm;
+  const ClassBlock mats;
+  int dS, NB;
+  size_t MU;
+  const double* blk;
+  std::vector<int> code;                   // symbol per taxon
+  std::vector<double> R[4], ws[2], cnt, Lg;
+  std::vector<char> counted;
+  size_t mi = 0, fi = 0;
+  std::string err;
+  explicit Numeric(const HostModel& h) : hm(h), mats(h.block()), dS(h.dS), NB(h.dS / 4), MU((size_t)mat_unit(h.dS)), blk(h.MAT.data()) {
+    const double nan = std::nan("");
+    for (auto& r : R) r.assign(dS, nan);
+    lds.assign(dS, nan);
+    ws[0].assign((size_t)h.NIW * dS, nan);
+    ws[1].assign((size_t)h.NIW * dS, nan);
+    cnt.assign((size_t)h.B * h.K, nan);
+    counted.assign((size_t)h.B * h.K, 0);
+    Lg.assign(h.fuse, nan);
+    code.resize(h.T);
+    for (int t = 0; t < h.T; ++t) {      // splitmix-style hash of the taxon index: no global RNG state
+      uint64_t z = 0x9E3779B97F4A7C15ull * (uint64_t)(t + 1);
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;
+      code[t] = (int)(z % (uint64_t)h.S);
+    }
+  }
+  void fail(const std::string& m) { if (err.empty()) err = "tree-walk self-check failed: " + m; }
+  void rec(int v, int (&r)[16]) const { copy_record(hm, v, r); }
+  // the operator the stream stages for this op; `want` = what the walk asked for
+  const std::vector<int>& stream() const { return CT ? hm.msched_r : hm.msched; }
+  int staged(int want_mat, int want_tx) {
+    if (2 * mi + 1 >= stream().size()) { fail("more operator uses than the stream holds"); return -1; }
+    const int mat = stream()[2 * mi], tx = stream()[2 * mi + 1];
+    ++mi;
+    if (mat < 0 || mat >= hm.MC) { fail("operator index out of range"); return -1; }
+    if (mat != want_mat || tx != want_tx) { fail("op " + std::to_string(mi - 1) + " finds the wrong operator staged"); return -1; }
+    return mat;
+  }
+  int leaf_mat(int leaf, int which) {
+    if (leaf < 0 || leaf >= hm.nn || hm.taxon_of[leaf] < 0) { fail("leaf op on a non-leaf"); return -1; }
+    const int tx = hm.taxon_of[leaf];
+    return staged(mats.leaf(tx, which), tx);
+  }
+  // cherry tables: row = 4 * symbol(l1) + symbol(l2), columns as in a leaf row
+  int cherry_mat(int node, int l1, int l2, int table) {
+    if (node < 0 || node >= hm.nn || hm.cherry_of[node] < 0 || table < 0 || table > 3 * hm.K) { fail("cherry op on a node without tables"); return -1; }
+    return staged(mats.cherry(hm.cherry_of[node], table), cherry_entry(hm.taxon_of[l1], hm.taxon_of[l2]));
+  }
+  double cherryrow(int mat, int l1, int l2, int X) const {
+    return blk[(size_t)mat * MU + (size_t)(4 * code[hm.taxon_of[l1]] + code[hm.taxon_of[l2]]) * leaf_row_stride(dS) + leaf_col(X, dS)];
+  }
+  template <int D> void cset(int node, int l1, int l2) {
+    const int mat = cherry_mat(node, l1, l2, 0);
+    if (mat < 0) return;
+    for (int x = 0; x < dS; ++x) R[D][x] = cherryrow(mat, l1, l2, x);
+  }
+  template <int S> void cdot(int node, int l1, int l2, int table, int row) {
+    const int mat = cherry_mat(node, l1, l2, table);
+    if (mat < 0) return;
+    double s = 0;
+    for (int x = 0; x < dS; ++x) s += R[S][x] * cherryrow(mat, l1, l2, x);
+    count_row(row, s);
+  }
+  double leafrow(int mat, int leaf, int X) const { return blk[(size_t)mat * MU + (size_t)code[hm.taxon_of[leaf]] * leaf_row_stride(dS) + leaf_col(X, dS)]; }
+  double packed(int mat, int r, int c) const {
+    if (hm.fuse > 1)   // diagonal tiles only (pack_blocks), the others are exact zeros of the block-diagonal operator
+      return r / 4 == c / 4 ? blk[(size_t)mat * MU + (size_t)(r / 4) * 16 + (r % 4) * 4 + c % 4] : 0.0;
+    return blk[(size_t)mat * MU + ((size_t)(r / 4) * NB + c / 4) * 16 + (r % 4) * 4 + c % 4];
+  }
+  void count_row(int row, double v) {
+    if (row < 0 || row >= hm.B * hm.K) return fail("count row out of range");
+    if (counted[row]) return fail("branch counted twice");
+    counted[row] = 1;
+    cnt[row] = v;
+  }
+  template <int D> void lset(int leaf, int which) {
+    const int mat = leaf_mat(leaf, which);
+    if (mat < 0) return;
+    for (int x = 0; x < dS; ++x) R[D][x] = leafrow(mat, leaf, x);
+  }
+  template <int S, int D> void lmul(int leaf, int which) {
+    const int mat = leaf_mat(leaf, which);
+    if (mat < 0) return;
+    for (int x = 0; x < dS; ++x) R[D][x] = R[S][x] * leafrow(mat, leaf, x);
+  }
+  template <int S> void ldot(int leaf, int which, int row) {
+    const int mat = leaf_mat(leaf, which);
+    if (mat < 0) return;
+    double s = 0;
+    for (int x = 0; x < dS; ++x) s += R[S][x] * leafrow(mat, leaf, x);
+    count_row(row, s);
+  }
+  template <int S, int D, bool TR> void mv(int node, int which) {
+    if (node < 0 || node >= hm.nn || hm.slot[node] < 0) return fail("product on a leaf or pseudo branch");
+    const int mat = staged(mats.internal(hm.slot[node], which), -1);
+    if (mat < 0) return;
+    std::vector<double> out(dS, 0.0);
+    for (int r = 0; r < dS; ++r)
+      for (int c = 0; c < dS; ++c) out[r] += (TR ? packed(mat, c, r) : packed(mat, r, c)) * R[S][c];
+    R[D] = out;
+  }
+  // the next word of the load schedule names this vector
+  bool scheduled(int arr, int slot) {
+    if (fi >= hm.ldsched.size()) { fail("more workspace loads than scheduled"); return false; }
+    const int w = hm.ldsched[fi++];
+    if (load_word_array(w) != arr || load_word_slot(w) != slot) { fail("load " + std::to_string(fi - 1) + " names the wrong vector"); return false; }
+    return true;
+  }
+  template <int D> void load(int arr, int slot) {
+    if (slot < 0 || slot >= hm.NIW) return fail("workspace slot out of range");
+    if (!scheduled(arr, slot)) return;
+    R[D].assign(&ws[arr][(size_t)slot * dS], &ws[arr][(size_t)slot * dS] + dS);
+  }
+  template <int S> void store(int arr, int slot) {
+    if (slot < 0 || slot >= hm.NIW) return fail("workspace slot out of range");
+    std::copy(R[S].begin(), R[S].end(), &ws[arr][(size_t)slot * dS]);
+  }
+  template <int D> void lload(int arr, int slot) {
+    if (!scheduled(arr, slot)) return;
+    if (lds_arr != arr || lds_slot != slot) return fail("load " + std::to_string(fi - 1) + " finds the LDS slot empty or holding another vector");
+    R[D] = lds;
+    lds.assign(dS, std::nan(""));
+    lds_arr = lds_slot = -1;
+  }
+  template <int S> void lstore(int arr, int slot) {
+    if (slot < 0 || slot >= hm.NIW) return fail("workspace slot out of range");
+    if (lds_arr >= 0) return fail("the LDS slot is written while it holds a vector nobody has read");
+    lds = R[S];
+    lds_arr = arr;
+    lds_slot = slot;
+  }
+  template <int S> void lcopy(int arr, int slot) { lstore<S>(arr, slot); }
+  template <int D, int S> void mov() { R[D] = R[S]; }
+  template <int D, int S> void mul() { for (int x = 0; x < dS; ++x) R[D][x] *= R[S][x]; }
+  template <int D, int A, int B> void prod() { for (int x = 0; x < dS; ++x) R[D][x] = R[A][x] * R[B][x]; }
+  void mulup() { for (int x = 0; x < dS; ++x) { R[1][x] *= R[3][x]; R[2][x] *= R[3][x]; } }
+  template <int D> void setpi() { for (int x = 0; x < dS; ++x) R[D][x] = hm.pi[x % hm.S]; }
+  template <int S> void rootl() {
+    for (int g = 0; g < hm.fuse; ++g) { double s = 0; for (int x = 0; x < hm.S; ++x) s += hm.pi[x] * R[S][g * hm.S + x]; Lg[g] = s; }
+  }
+  void dot3(int row) { double s = 0; for (int x = 0; x < dS; ++x) s += R[3][x] * R[1][x] * R[2][x]; count_row(row, s); }
+  template <int Rg> void kill() { R[Rg].assign(dS, std::nan("")); }   // a killed register must not be read again
+};
+
+// what verify_walk keeps of a numeric pass
+struct NumericResult {
+  std::string err;
+  size_t mi = 0, fi = 0;
+  std::vector<int> code;
+  std::vector<double> cnt, Lg;
+  std::vector<char> counted;
+};
+template <bool CT, bool CR>
+NumericResult run_numeric(const HostModel& hm) {
+  Numeric<CT, CR> nm(hm);
+  walk_pass(nm, hm.NV, hm.K);
+  return {nm.err, nm.mi, nm.fi, nm.code, nm.cnt, nm.Lg, nm.counted};
+}
+
+bool close(double a, double b) { return std::fabs(a - b) <= 1e-9 * (std::fabs(a) + std::fabs(b)) + 1e-290; }
+
+// site likelihoods and joint counts of a numeric pass against the direct computation; tables: the cherry-table walk's wording
+std::string compare(const NumericResult& nm, const std::vector<double>& Lref, const std::vector<double>& ref, int classes, int K, bool tables) {
+  const std::string head = "tree-walk self-check failed: ";
+  for (int g = 0; g < classes; ++g)
+    if (!close(nm.Lg[g], Lref[g])) return head + (tables ? "site likelihood of the cherry-table walk differs from the direct computation" : "site likelihood differs from the direct computation");
+  for (size_t r = 0; r < ref.size(); ++r) {
+    if (!nm.counted[r]) return head + (tables ? "the cherry-table walk never counts a branch" : "a branch is never counted");
+    if (!close(nm.cnt[r], ref[r])) return head + (tables ? "cherry-table count of branch " : "joint count of branch ") + std::to_string(r / K) + " differs from the direct computation";
+  }
+  return std::string();
+}
+}  // namespace
+
+// Runs the walk numerically for one random site of device class 0 and compares site likelihood and all joint counts
+// with a direct pruning computation from the row-major hm.P / hm.PN.  Empty string when they agree.
+std::string verify_walk(const HostModel& hm) {
+  const int S = hm.S, F = hm.fuse, K = hm.K, nn = hm.nn, B = hm.B, root = hm.root;
+  const size_t S2 = (size_t)S * S;
+  if ((int)hm.nrec.size() != hm.NV * 16) return "tree-walk self-check failed: record table size";
+  const NumericResult nm = F == 1 ? run_numeric<false, true>(hm) : run_numeric<false, false>(hm);
+  if (!nm.err.empty()) return nm.err;
+  if (2 * nm.mi != hm.msched.size()) return "tree-walk self-check failed: unused operators in the stream";
+  if (nm.fi != hm.ldsched.size()) return "tree-walk self-check failed: unused workspace loads in the schedule";
+  // the cherry-table walk: same site, same reference
+  NumericResult nt;
+  const bool tables = !hm.msched_r.empty();
+  if (tables) {
+    nt = run_numeric<true, false>(hm);
+    if (!nt.err.empty()) return nt.err + " (cherry-table walk)";
+    if (2 * nt.mi != hm.msched_r.size()) return "tree-walk self-check failed: unused operators in the cherry-table stream";
+    if (nt.fi != hm.ldsched.size()) return "tree-walk self-check failed: the cherry-table walk loads other workspace vectors";
+  }
+  const std::vector<int>& code = nm.code;
+  std::vector<double> ref((size_t)B * K, 0.0), Lref(F, 0.0);
+  for (int g = 0; g < F && g < hm.C; ++g) {   // true classes g of device class 0
+    std::vector<double> D((size_t)nn * S), M((size_t)nn * S), U((size_t)nn * S), Up((size_t)nn * S);
+    for (int n = 0; n < nn; ++n) {
+      double* Dn = &D[(size_t)n * S];
+      if (hm.taxon_of[n] >= 0) for (int x = 0; x < S; ++x) Dn[x] = x == code[hm.taxon_of[n]] ? 1.0 : 0.0;
+      else { for (int x = 0; x < S; ++x) Dn[x] = 1.0; for (int e : children(hm, n)) for (int x = 0; x < S; ++x) Dn[x] *= M[(size_t)e * S + x]; }
+      if (n != root) {
+        const double* P = &hm.P[((size_t)g * B + n) * S2];
+        for (int x = 0; x < S; ++x) { double s = 0; for (int z = 0; z < S; ++z) s += P[(size_t)x * S + z] * Dn[z]; M[(size_t)n * S + x] = s; }
+      }
+    }
+    for (int x = 0; x < S; ++x) { Lref[g] += hm.pi[x] * D[(size_t)root * S + x]; Up[(size_t)root * S + x] = hm.pi[x]; }
+    const double wgt = F > 1 ? hm.probs[g] : 1.0;   // fused: class probabilities are folded into the count operators
+    for (int f = nn - 1; f >= 0; --f) {
+      if (hm.taxon_of[f] >= 0) continue;
+      const std::vector<int> c = children(hm, f);
+      for (int n : c) {
+        double* Un = &U[(size_t)n * S];
+        for (int x = 0; x < S; ++x) Un[x] = Up[(size_t)f * S + x];
+        for (int m : c) if (m != n) for (int x = 0; x < S; ++x) Un[x] *= M[(size_t)m * S + x];
+        for (int k = 0; k < K; ++k) {
+          const double* PN = &hm.PN[(((size_t)g * B + n) * K + k) * S2];
+          double tot = 0;
+          for (int x = 0; x < S; ++x) { double s = 0; for (int y = 0; y < S; ++y) s += PN[(size_t)x * S + y] * D[(size_t)n * S + y]; tot += Un[x] * s; }
+          ref[(size_t)n * K + k] += wgt * tot;
+        }
+        if (hm.taxon_of[n] < 0) {
+          const double* P = &hm.P[((size_t)g * B + n) * S2];
+          for (int z = 0; z < S; ++z) { double s = 0; for (int x = 0; x < S; ++x) s += P[(size_t)x * S + z] * Un[x]; Up[(size_t)n * S + z] = s; }
+        }
+      }
+    }
+  }
+  const int classes = std::min(F, hm.C);
+  std::string bad = compare(nm, Lref, ref, classes, K, false);
+  if (bad.empty() && tables) bad = compare(nt, Lref, ref, classes, K, true);
+  return bad;
+}
+
+}  // namespace cmx

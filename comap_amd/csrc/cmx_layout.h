@@ -1,0 +1,58 @@
+// The layouts host and device agree on (internal).  Plain C++17, no HIP: the host model (cmx_host_*.cpp) builds with any
+// C++ compiler from this header, the device sources get it through cmx_device.h.
+#pragma once
+
+namespace cmx {
+
+// device state count of the plain path (alphabets other than 4 / 20 states, up to 64): the largest alphabet a context takes.
+// The plain kernels of cmx_variants.hip run at this many states and simulate_continuous_kernel keeps one row of the
+// transition matrix of this length per thread.
+constexpr int kPlainStates = 64;
+
+// Ambiguous symbols (alignment codes >= S) are served from extra rows S .. S+A-1 appended to every transposed leaf
+// operator: row S+a = sum of the rows of the states compatible with ambiguity id a (filled per call from the caller's
+// mask table, default "every state").  A = 12 for nucleotides (IUPAC + gap), 4 for proteins (B, Z, J, X/gap).
+constexpr int max_ambig(int S) { return S == 4 ? 12 : 4; }
+// A transposed leaf operator is read row by row, the row named by a site's symbol: sixteen sites of a lane group read
+// sixteen rows at once.  With rows of S doubles (40 dwords for S = 20, 32 for the class-fused 16) rows 8 (2) apart fall
+// on the same LDS banks -- 61 % of the mapping kernel's LDS cycles were bank conflicts.  One double of padding per row
+// (42 / 34 dwords) moves the period to 32 rows: no two rows of an operator share a bank.
+constexpr int leaf_row_stride(int S) { return S + 1; }             // doubles per row of a transposed leaf operator
+constexpr int mat_unit(int S) { return (S + max_ambig(S)) * leaf_row_stride(S); }   // doubles per device matrix
+// The column of device state X in a row of a leaf operator or cherry table: state-in-tile major, so that the values one
+// lane of the matrix-core layout needs from a row are contiguous.
+constexpr int leaf_col(int X, int dS) { return (X % 4) * (dS / 4) + X / 4; }
+
+// A class block of HostModel::MAT / DevModel::MAT: per device class one run of count() matrices of mat_unit doubles.
+// `which` names an operator of a branch as in cmx_walk.h: OPER_P (< 0) = transition matrix, k >= 0 = count operator k.
+//   [0, NI)                        P of internal edges, 4x4-block packed (matrix-vector products), by operator slot
+//   [NI, NI + NI*K)                P o N^k of internal edges, packed, index slot*K + k
+//   [first_leaf(), + T)            P of leaf edges transposed, [z][x] = P[x][z] (per-lane row gather by observed symbol)
+//   [.., + K*T)                    P o N^k of leaf edges transposed, index k*T + taxon
+//   [cherry_base(), + ncherry*(1+3K))  cherry tables of the class-fused nucleotide layout (cmx_walk.h), 16 rows (symbol pair) each
+struct ClassBlock {
+  int NI, K, T, ncherry;
+  constexpr int internal(int slot, int which) const { return which < 0 ? slot : NI + slot * K + which; }
+  constexpr int first_leaf() const { return NI + NI * K; }
+  constexpr int leaf(int taxon, int which) const { return which < 0 ? first_leaf() + taxon : first_leaf() + T + which * T + taxon; }
+  constexpr int cherry_base() const { return first_leaf() + T + K * T; }
+  constexpr int cherry(int cherry_index, int table) const { return cherry_base() + cherry_index * (1 + 3 * K) + table; }
+  constexpr int count() const { return cherry_base() + ncherry * (1 + 3 * K); }
+};
+
+// Operator stream entry of a cherry-table op: the taxa of the cherry's two leaves beside the flag (a leaf op's entry is
+// its taxon, a product's -1).  A taxon has 15 bits: a tree has at most 65535 nodes (build_host_model), so a binary tree
+// at most 32768 leaves.
+constexpr int kCherryFlag = 0x40000000;
+constexpr int cherry_entry(int taxon1, int taxon2) { return kCherryFlag | taxon1 | (taxon2 << 15); }
+constexpr int cherry_taxon1(int entry) { return entry & 0x7fff; }
+constexpr int cherry_taxon2(int entry) { return (entry >> 15) & 0x7fff; }
+
+// Load-schedule word of a workspace load: bit 31 prefetchable, bit 30 array (WS_M / WS_U), low 24 bits slot
+constexpr int load_word(int arr, int slot, bool prefetchable) {
+  return (int)((unsigned)slot | (arr ? 0x40000000u : 0u) | (prefetchable ? 0x80000000u : 0u));
+}
+constexpr int load_word_array(int w) { return (w >> 30) & 1; }
+constexpr int load_word_slot(int w) { return w & 0xffffff; }
+
+}  // namespace cmx

@@ -233,7 +233,7 @@ __device__ __forceinline__ void matvec_stage(const uint8_t* buf, int lane, const
 // SET out = row, MUL out = row o in (in may be out), DOT returns sum_x in[x] * row[x] of site l (reduce_sites).
 enum { LEAF_SET = 0, LEAF_MUL = 1, LEAF_DOT = 2 };
 // r[g]: the lane's values of site group g's row (rows are stored state-in-tile major: state 4 sb + s4 at position
-// s4 * NB + sb, cmx_host_model.cpp).  Per site group the row values and their use: the reads of the next group do not
+// s4 * NB + sb, cmx_layout.h: leaf_col).  Per site group the row values and their use: the reads of the next group do not
 // depend on anything computed for the previous one.
 template <int S, int MODE, int NG>
 __device__ __forceinline__ double rows_apply(const double* const (&r)[NG], const double (&in)[S / 4 * NG], double (&out)[S / 4 * NG]) {
@@ -365,7 +365,6 @@ struct DevWalk {
   // modes; the 16-site shape shares the records and ignores the bits, like every backend without a slot)
   static constexpr bool kLdsSlot = map_lds_slot(S, FUSE, NG);
   static constexpr int kCherryBytes = 16 * leaf_row_stride(S) * 8;   // a table's 16 rows (one per symbol pair)
-  static constexpr int kCherryFlag = 0x40000000;                     // stream entry: taxon of l1 | taxon of l2 << 15 | flag
   static_assert(kCherryBytes <= MatStage<S>::BYTES, "a cherry table fits a stage buffer");
   double R0[VL], R1[VL], R2[VL], R3[VL];
   OpState& os;
@@ -464,8 +463,8 @@ struct DevWalk {
     }
     if (etx >= 0 && (more || c + 1 < c_end)) {
       if (kCherryTables && (etx & kCherryFlag)) {
-        code_dma_l(gcodes + (size_t)(etx & 0x7fff) * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
-        code_dma_l(gcodes + (size_t)((etx >> 15) & 0x7fff) * gstride, lds_codes2 + (os.par ^ 1u) * kCodeSlotBytes);
+        code_dma_l(gcodes + (size_t)cherry_taxon1(etx) * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
+        code_dma_l(gcodes + (size_t)cherry_taxon2(etx) * gstride, lds_codes2 + (os.par ^ 1u) * kCodeSlotBytes);
         issued += 2;
       } else {
         code_dma_l(gcodes + (size_t)etx * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
@@ -671,8 +670,8 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (tx0 >= 0) {
       if (kTables && (tx0 & 0x40000000)) {
-        code_dma(gcodes + (size_t)(tx0 & 0x7fff) * gstride, be.cslot + os.par * kCodeSlotBytes);
-        code_dma(gcodes + (size_t)((tx0 >> 15) & 0x7fff) * gstride, be.cslot2 + os.par * kCodeSlotBytes);
+        code_dma(gcodes + (size_t)cherry_taxon1(tx0) * gstride, be.cslot + os.par * kCodeSlotBytes);
+        code_dma(gcodes + (size_t)cherry_taxon2(tx0) * gstride, be.cslot2 + os.par * kCodeSlotBytes);
       } else {
         code_dma(gcodes + (size_t)tx0 * gstride, be.cslot + os.par * kCodeSlotBytes);
       }
@@ -1019,7 +1018,7 @@ hipError_t launch_extend_leaf_rows(const DevModel& m, const uint32_t* d_masks, h
   const int A = max_ambig(m.S0), nleaf = m.T + m.K * m.T;
   const size_t total = (size_t)m.C * nleaf * A * m.S;
   hipLaunchKernelGGL(extend_leaf_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, m.MAT, m.C, m.MC,
-                     m.NI + m.NI * m.K, nleaf, m.S0, m.S, A, mat_unit(m.S), leaf_row_stride(m.S), d_masks);
+                     ClassBlock{m.NI, m.K, m.T, 0}.first_leaf(), nleaf, m.S0, m.S, A, mat_unit(m.S), leaf_row_stride(m.S), d_masks);
   return hipGetLastError();
 }
 

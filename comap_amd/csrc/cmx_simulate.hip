@@ -426,7 +426,7 @@ __global__ void simulate_continuous_kernel(const DevModel m, uint64_t seed, uint
     const size_t mo = (size_t)m.model_of[node];
     const double *V = m.eigV + mo * S * S + (size_t)x * S, *Vi = m.eigVi + mo * S * S, *lam = m.eigLam + mo * S;
     const double rt = r * m.blen[node];
-    double w[kSimContinuousMaxStates];    // V[x][k] exp(lambda_k r t), S <= kPlainStates entries (dynamically indexed: private memory)
+    double w[kPlainStates];    // V[x][k] exp(lambda_k r t), S <= kPlainStates entries (dynamically indexed: private memory)
     for (int k = 0; k < S; ++k) w[k] = V[k] * exp(lam[k] * rt);
     // index = #{ y < S-1 : u >= cum_y } with cum the running sum of the row P(x, .) -- the discrete simulator's rule
     int idx = 0;

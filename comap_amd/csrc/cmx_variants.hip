@@ -18,8 +18,6 @@
 
 namespace cmx {
 
-constexpr int kPlainStatesDev = 64;   // == kPlainStates (cmx_host_model.h): padded state count of the plain path
-
 namespace {
 
 template <int S>
@@ -322,14 +320,14 @@ hipError_t launch_map_noavg(NoAvgArgs a, size_t nsites_total, double* scratch, d
       hipLaunchKernelGGL(noavg_outside_kernel<4>, dim3(gx, a.C), dim3(256), 0, stream, a);
       if (a.mode == kVariantNoAvg) hipLaunchKernelGGL(noavg_pick_kernel<4>, dim3(gx, a.B), dim3(256), 0, stream, a);
       else hipLaunchKernelGGL(marginal_kernel<4>, dim3(gx, a.B), dim3(256), 0, stream, a);
-    } else if (a.S == kPlainStatesDev) {
-      hipLaunchKernelGGL(noavg_inside_kernel<kPlainStatesDev>, dim3(gx, a.C), dim3(256), 0, stream, a);
-      if (a.logL || a.post_rate || a.rate_class) hipLaunchKernelGGL(site_scalars_kernel<kPlainStatesDev>, dim3(gx), dim3(256), 0, stream, a);
+    } else if (a.S == kPlainStates) {
+      hipLaunchKernelGGL(noavg_inside_kernel<kPlainStates>, dim3(gx, a.C), dim3(256), 0, stream, a);
+      if (a.logL || a.post_rate || a.rate_class) hipLaunchKernelGGL(site_scalars_kernel<kPlainStates>, dim3(gx), dim3(256), 0, stream, a);
       if (a.counts) {
-        hipLaunchKernelGGL(noavg_outside_kernel<kPlainStatesDev>, dim3(gx, a.C), dim3(256), 0, stream, a);
-        if (a.mode == kVariantJoint) hipLaunchKernelGGL(joint_kernel<kPlainStatesDev>, dim3(gx, a.B), dim3(256), 0, stream, a);
-        else if (a.mode == kVariantNoAvg) hipLaunchKernelGGL(noavg_pick_kernel<kPlainStatesDev>, dim3(gx, a.B), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(marginal_kernel<kPlainStatesDev>, dim3(gx, a.B), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(noavg_outside_kernel<kPlainStates>, dim3(gx, a.C), dim3(256), 0, stream, a);
+        if (a.mode == kVariantJoint) hipLaunchKernelGGL(joint_kernel<kPlainStates>, dim3(gx, a.B), dim3(256), 0, stream, a);
+        else if (a.mode == kVariantNoAvg) hipLaunchKernelGGL(noavg_pick_kernel<kPlainStates>, dim3(gx, a.B), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(marginal_kernel<kPlainStates>, dim3(gx, a.B), dim3(256), 0, stream, a);
       }
     } else {
       return hipErrorInvalidValue;
@@ -361,10 +359,10 @@ hipError_t launch_ancestral(NoAvgArgs a, size_t nsites_total, double* scratch, c
       hipLaunchKernelGGL(noavg_inside_kernel<4>, dim3(gx, a.C), dim3(256), 0, stream, a);
       hipLaunchKernelGGL(noavg_outside_kernel<4>, dim3(gx, a.C), dim3(256), 0, stream, a);
       hipLaunchKernelGGL(ancestral_kernel<4>, dim3(gx, n_inner), dim3(256), 0, stream, a, o);
-    } else if (a.S == kPlainStatesDev) {
-      hipLaunchKernelGGL(noavg_inside_kernel<kPlainStatesDev>, dim3(gx, a.C), dim3(256), 0, stream, a);
-      hipLaunchKernelGGL(noavg_outside_kernel<kPlainStatesDev>, dim3(gx, a.C), dim3(256), 0, stream, a);
-      hipLaunchKernelGGL(ancestral_kernel<kPlainStatesDev>, dim3(gx, n_inner), dim3(256), 0, stream, a, o);
+    } else if (a.S == kPlainStates) {
+      hipLaunchKernelGGL(noavg_inside_kernel<kPlainStates>, dim3(gx, a.C), dim3(256), 0, stream, a);
+      hipLaunchKernelGGL(noavg_outside_kernel<kPlainStates>, dim3(gx, a.C), dim3(256), 0, stream, a);
+      hipLaunchKernelGGL(ancestral_kernel<kPlainStates>, dim3(gx, n_inner), dim3(256), 0, stream, a, o);
     } else {
       return hipErrorInvalidValue;
     }

@@ -1,7 +1,7 @@
 // The tree walk of one rate-class pass of the mapping kernel, written ONCE and instantiated three times:
-//   * host, Recorder backend  (cmx_host_model.cpp): lists the operators and workspace loads in program order -- the
+//   * host, Recorder backend  (cmx_host_tree.cpp): lists the operators and workspace loads in program order -- the
 //     operator stream and the load schedule the device follows;
-//   * host, Numeric backend   (cmx_host_model.cpp): runs the pass in plain doubles from the device layouts, consuming
+//   * host, Numeric backend   (cmx_host_verify.cpp): runs the pass in plain doubles from the device layouts, consuming
 //     that stream exactly as the device does, and is compared with a direct pruning computation before a context is
 //     accepted (verify_walk);
 //   * device backend          (cmx_map.hip: map_sites_wave)    : registers are S-vectors of the wave's 64 sites.
@@ -24,8 +24,8 @@
 // a compiler so.  Templates name registers at compile time; the device maps them to VGPR arrays.
 #pragma once
 
-#ifdef __HIPCC__
-#define CMX_HD __host__ __device__ __forceinline__
+#ifdef __HIPCC__   // (the host model's sources include no HIP header: __forceinline__, which is this, is spelled out)
+#define CMX_HD __host__ __device__ inline __attribute__((always_inline))
 #else
 #define CMX_HD inline
 #endif
@@ -43,7 +43,7 @@ enum { FLAG_PSEUDO = 1,       // zero-length branch of a split multifurcation
        FLAG_HAND = 2,         // child B is the node visited right before (inside) / right after (outside) this one
        FLAG_U_HANDED = 4,     // this node's outside message arrives in R0 (its parent is the node visited right before it)
        FLAG_ROOT = 8,
-       // LDS slot (backends with kLdsSlot; the host's plan, cmx_host_model.cpp: plan_lds_slot).  Other backends ignore the
+       // LDS slot (backends with kLdsSlot; the host's plan, cmx_host_tree.cpp: plan_lds_slot).  Other backends ignore the
        // bits: the workspace slots stay allocated and a flagged transfer is a valid plain one.
        FLAG_LDS_M_PUT = 16,   // inside: this node's message also goes to the wave's LDS slot (its parent reads it there)
        FLAG_LDS_M_GET = 32,   // inside: M_a comes from the LDS slot, not from WS_M

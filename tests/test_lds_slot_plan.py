@@ -1,4 +1,4 @@
-"""The plan of the mapping walk's LDS slot (cmx_walk.h kLdsSlot, cmx_host_model.cpp plan_lds_slot), no GPU.
+"""The plan of the mapping walk's LDS slot (cmx_walk.h kLdsSlot, cmx_host_tree.cpp plan_lds_slot), no GPU.
 
 A wave keeps ONE workspace vector on chip.  At a node whose child A is a visited node two vectors are short-lived:
 

@@ -1,6 +1,6 @@
 """Host logic without a GPU: what the mapping kernel's tree walk reads (node records, operator stream, workspace-load
 schedule) is compiled and self-checked by cmx_debug_walk for many tree shapes -- binary, caterpillar, star, random
-multifurcations.  The self-check (verify_walk, cmx_host_model.cpp) runs the SAME walk (cmx_walk.h) numerically on the
+multifurcations.  The self-check (verify_walk, cmx_host_verify.cpp) runs the SAME walk (cmx_walk.h) numerically on the
 host, from the device matrix layouts and through the recorded operator stream, and compares site likelihood and every
 joint count with a direct pruning computation on the original (not binarised) tree."""
 import numpy as np
