@@ -61,11 +61,10 @@ static cmx_status cluster_batch_dev(cmx_ctx* ctx, int dist_kind, int linkage, co
   // grid.z slice.  (The tree's "Stat" property below stays unweighted, Distance.h:403-421.)
   Stat sk;
   PairOperand x;
-  const int Bp = pair_Bp(h.B);
   CMX_TRY(resolve_stat(ctx, stat_kind, nullptr, st, &sk));
   CMX_TRY(pair_operand(ctx, sk, d_counts, batch * n, ldc, "1", st, &x, n));
-  HIP_TRY(ctx, launch_pair_gram(gram_kind(sk.gk, sk.d_w), h.B, Bp, x.X, x.s, x.r, n, x.ldx, x.X, x.s, x.r, n, x.ldx, 2 /* upper triangle only */, D, n,
-                                st, batch, n, n * n, (size_t)Bp * x.ldx));
+  const PairOperand rep = x.rows(0, n);   // the first replicate; the others follow at the batch's strides
+  HIP_TRY(ctx, launch_pair_gram(sk, rep, rep, kPairUpperRows, D, n, GramBatch{batch, n, n * n, (size_t)pair_Bp(h.B) * x.ldx}, 0, st));
   HIP_TRY(ctx, launch_dist_finish(dist_kind, D, n, n, n * n, batch, st));
   if (d_dist_out) HIP_TRY(ctx, hipMemcpyAsync(d_dist_out, D, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));
   CMX_TRY(cmx_hclust_dev(ctx, linkage, D, n, n, batch, d_merge, d_dmax, d_size, st));

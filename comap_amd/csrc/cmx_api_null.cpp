@@ -85,18 +85,18 @@ static cmx_status null_unfused_dev(cmx_ctx* ctx1, cmx_ctx* ctx2, int kind, const
   }
   Stat sk;
   CMX_TRY(resolve_stat(ctx1, kind, params, stream, &sk));
-  if (sk.mi()) {
+  const SiteCols cols[2] = {{rc[0], pr[0], nm[0]}, {rc[1], pr[1], nm[1]}};
+  const PairOut out{d_stat, d_rcmin, d_prmin, d_nmin};
+  if (sk.mi()) {   // the statistic from the class words; the diagonal kernel writes the minima only
     PairOperand a, b;
     CMX_TRY(pair_operand(ctx1, sk, cnt[0], n, n, "n1", st, &a));
     CMX_TRY(pair_operand(ctx1, sk, cnt[1], n, n, "n2", st, &b));
-    HIP_TRY(ctx1, launch_mi_pairs_diag(sk.B, a.cls, a.bad, a.ldx, b.cls, b.bad, b.ldx, n, d_stat, st));
-    HIP_TRY(ctx1, launch_pair_diag(kind, 0.0, sk.B, sk.K, cnt[0], n, cnt[1], n, n, rc[0], rc[1], pr[0], pr[1], nm[0], nm[1], nullptr, d_rcmin,
-                                   d_prmin, d_nmin, nullptr, st));   // the minima only
+    HIP_TRY(ctx1, launch_mi_pairs_diag(sk.B, a, b, n, d_stat, st));
+    HIP_TRY(ctx1, launch_pair_diag(sk, cnt[0], n, cols[0], cnt[1], n, cols[1], n, PairOut{nullptr, d_rcmin, d_prmin, d_nmin}, st));
     return CMX_OK;
   }
   // branch weights: ctx1's (the reference scores both data sets with one Statistic object, AnalysisTools.cpp:728)
-  HIP_TRY(ctx1, launch_pair_diag(kind, sk.param, sk.B, sk.K, cnt[0], n, cnt[1], n, n, rc[0], rc[1], pr[0], pr[1], nm[0], nm[1], d_stat, d_rcmin,
-                                 d_prmin, d_nmin, sk.d_mean, st, sk.d_w));
+  HIP_TRY(ctx1, launch_pair_diag(sk, cnt[0], n, cols[0], cnt[1], n, cols[1], n, out, st));
   return CMX_OK;
 }
 
@@ -122,8 +122,8 @@ static size_t null_pattern_reps(const cmx_ctx* ctx, size_t rep_ram) {
   return std::min(budget / per_rep, ((size_t)1 << 31) / (2 * rep_ram));   // (32-bit site indices)
 }
 
-// a.supplied / a.rep_ram / a.stat_* / a.null_* describe the whole null; passes of whole replicates, sized evenly
-static cmx_status null_patterns_dev(cmx_ctx* ctx, MapArgs a, size_t nrep, size_t reps_max, void* stream) {
+// a.supplied / a.rep_ram / a.null_* describe the whole null, sk its statistic; passes of whole replicates, sized evenly
+static cmx_status null_patterns_dev(cmx_ctx* ctx, const Stat& sk, MapArgs a, size_t nrep, size_t reps_max, void* stream) {
   const HostModel& h = ctx->hm;
   const size_t rep_ram = a.rep_ram, T = (size_t)h.T, BK = (size_t)h.B * h.K, rowb = null_pattern_row_bytes(h.T);
   const size_t npass = (nrep + reps_max - 1) / reps_max, reps = (nrep + npass - 1) / npass;
@@ -144,7 +144,7 @@ static cmx_status null_patterns_dev(cmx_ctx* ctx, MapArgs a, size_t nrep, size_t
   const size_t ks = (size_t)map_sites_per_wave(h.dS), ntiles = (cap + ks - 1) / ks;
   CMX_TRY(scratch(ctx, "pat_cnt", BK * ks * ntiles, &cnt));
   // Correlation / Covariance: the pairs are scored in one pass from per-pattern moments (pair_stat_moments)
-  const bool moments = a.stat_kind == CMX_STAT_CORRELATION || a.stat_kind == CMX_STAT_COVARIANCE;
+  const bool moments = sk.kind == CMX_STAT_CORRELATION || sk.kind == CMX_STAT_COVARIANCE;
   double *pmean = nullptr, *pss = nullptr;
   if (moments) {
     CMX_TRY(scratch(ctx, "pat_mean", cap, &pmean));
@@ -162,12 +162,11 @@ static cmx_status null_patterns_dev(cmx_ctx* ctx, MapArgs a, size_t nrep, size_t
     ctx->null_mapped_dev = true;
   }
   const uint8_t* sup = a.supplied;
-  const NullOut out{a.null_stat, a.null_rcmin, a.null_prmin, a.null_nmin};
+  const PairOut out{a.null_stat, a.null_rcmin, a.null_prmin, a.null_nmin};
   a.counts = cnt; a.ldc = 0; a.post_rate = pr; a.rate_class = rc; a.norm = nm;
   a.rep_site = b.rep_site;
   for (size_t r0 = 0; r0 < nrep; r0 += reps) {
     const size_t r1 = std::min(nrep, r0 + reps), n = (r1 - r0) * 2 * rep_ram;
-    const NullOut o = out.at(r0 * rep_ram);
     a.supplied = sup + r0 * 2 * T * rep_ram;
     HIP_TRY(ctx, launch_null_patterns(a.supplied, h.T, rep_ram, n, hash_bits, b, (hipStream_t)stream));
     // the pattern count stays on the device: the grid is sized for every site its own pattern, the waves read the count
@@ -177,8 +176,8 @@ static cmx_status null_patterns_dev(cmx_ctx* ctx, MapArgs a, size_t nrep, size_t
     HIP_TRY(ctx, launch_map(a, kModeNullPatterns, (int)std::min<size_t>(blocks_needed, (size_t)ctx->grid_blocks), (hipStream_t)stream));
     if (moments)
       HIP_TRY(ctx, launch_null_pattern_moments(h.B, h.K, cnt, (int)ks, (int)ks, a.npat, n, pmean, pss, (hipStream_t)stream));
-    HIP_TRY(ctx, launch_null_pattern_pairs(a.stat_kind, a.stat_param, h.B, h.K, cnt, (int)ks, (int)ks, pmean, pss, pr, rc, nm, b.pat_of, rep_ram, n / 2,
-                                           a.stat_mean, o.stat, o.rcmin, o.prmin, o.nmin, (hipStream_t)stream));
+    HIP_TRY(ctx, launch_null_pattern_pairs(sk, cnt, (int)ks, (int)ks, pmean, pss, SiteCols{rc, pr, nm}, b.pat_of, rep_ram, n / 2, out.at(r0 * rep_ram),
+                                           (hipStream_t)stream));
   }
   return CMX_OK;
 }
@@ -200,7 +199,7 @@ cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (ctx->null_depth == 0) { ctx->null_mapped_host = 0; ctx->null_mapped_dev = false; }
-  const NullOut out{d_stat, d_rcmin, d_prmin, d_nmin};
+  const PairOut out{d_stat, d_rcmin, d_prmin, d_nmin};
   if (!d_supplied) {
     // simulate first, at full occupancy, then map the alignments as "supplied" ones: the same draws, the same results
     // as a simulator inside the mapping waves (round 1; 7.8 % of the launch there, latency nobody could hide).  The
@@ -211,7 +210,7 @@ cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint
       cmx_status s = CMX_OK;
       ++ctx->null_depth;
       for (size_t r0 = rep_begin; r0 < rep_end && s == CMX_OK; r0 += reps_per_pass) {
-        const NullOut o = out.at((r0 - rep_begin) * rep_ram);
+        const PairOut o = out.at((r0 - rep_begin) * rep_ram);
         s = cmx_null_intra_dev(ctx, kind, params, seed, r0, std::min(rep_end, r0 + reps_per_pass), rep_ram, nullptr, o.stat, o.rcmin, o.prmin,
                                o.nmin, stream);
       }
@@ -232,7 +231,7 @@ cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint
   a.rep_ram = rep_ram; a.supplied = d_supplied;
   a.null_stat = d_stat; a.null_rcmin = d_rcmin; a.null_prmin = d_prmin; a.null_nmin = d_nmin;
   const size_t reps_per_pass = null_pattern_reps(ctx, rep_ram);
-  if (reps_per_pass) return null_patterns_dev(ctx, a, rep_end - rep_begin, reps_per_pass, stream);
+  if (reps_per_pass) return null_patterns_dev(ctx, sk, a, rep_end - rep_begin, reps_per_pass, stream);
   const size_t ks = (size_t)map_sites_per_wave(ctx->hm.dS);
   const size_t blocks_needed = ((a.nsites + ks - 1) / ks + kWavesPerBlock - 1) / kWavesPerBlock;
   const int grid = (int)std::min<size_t>(blocks_needed, (size_t)ctx->grid_blocks);
@@ -251,12 +250,12 @@ cmx_status cmx_null_intra_continuous_dev(cmx_ctx* ctx, int kind, const double* p
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t T = (size_t)ctx->hm.T, per_rep = 2 * T * rep_ram;
   const size_t reps_per_pass = std::max<size_t>(1, kNullAlnPassBytes / per_rep);   // (not the tests' override)
-  const NullOut out{d_stat, d_rcmin, d_prmin, d_nmin};
+  const PairOut out{d_stat, d_rcmin, d_prmin, d_nmin};
   uint8_t* d_aln;
   CMX_TRY(scratch(ctx, "null_aln", std::min(reps_per_pass, rep_end - rep_begin) * per_rep, &d_aln));
   for (size_t r0 = rep_begin; r0 < rep_end; r0 += reps_per_pass) {
     const size_t r1 = std::min(rep_end, r0 + reps_per_pass);
-    const NullOut o = out.at((r0 - rep_begin) * rep_ram);
+    const PairOut o = out.at((r0 - rep_begin) * rep_ram);
     for (size_t r = r0; r < r1; ++r)
       for (int h = 0; h < 2; ++h)   // [replicate][batch][taxon][rep_ram]; simulated-site index g = (rep * 2 + batch) * rep_ram + j
         CMX_TRY(cmx_simulate_continuous_dev(ctx, seed, ((uint64_t)r * 2 + h) * rep_ram, rep_ram, gamma_alpha, p_invariant,
@@ -274,12 +273,12 @@ cmx_status cmx_null_intra_continuous(cmx_ctx* ctx, int kind, const double* param
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t n = (rep_end - rep_begin) * rep_ram;
   TmpDev tmp;
-  NullOut d;
-  CMX_TRY(d.alloc(ctx, tmp, n));
+  PairOut d;
+  CMX_TRY(alloc_out(ctx, tmp, n, &d));
   CMX_TRY(cmx_null_intra_continuous_dev(ctx, kind, params, seed, rep_begin, rep_end, rep_ram, gamma_alpha, p_invariant, d.stat, d.rcmin, d.prmin,
                                         d.nmin, nullptr));
   HIP_TRY(ctx, hipDeviceSynchronize());
-  return d.fetch(ctx, n, {stat, rcmin, prmin, nmin});
+  return fetch_out(ctx, n, d, {stat, rcmin, prmin, nmin});
 }
 
 cmx_status cmx_null_intra(cmx_ctx* ctx, int kind, const double* params, uint64_t seed, size_t rep_begin, size_t rep_end,
@@ -291,17 +290,17 @@ cmx_status cmx_null_intra(cmx_ctx* ctx, int kind, const double* params, uint64_t
   const size_t n = (rep_end - rep_begin) * rep_ram;
   TmpDev tmp;
   uint8_t* d_sup = nullptr;
-  NullOut d;
+  PairOut d;
   if (supplied) {
     const size_t bytes = (rep_end - rep_begin) * 2 * (size_t)ctx->hm.T * rep_ram;
     for (size_t i = 0; i < bytes; ++i)
       if (supplied[i] >= (unsigned)ctx->hm.S) return fail(ctx, CMX_ERR_INVALID, "cmx_null_intra: supplied alignments must be fully resolved");
     CMX_TRY(tmp.upload(ctx, &d_sup, supplied, bytes));
   }
-  CMX_TRY(d.alloc(ctx, tmp, n));
+  CMX_TRY(alloc_out(ctx, tmp, n, &d));
   CMX_TRY(cmx_null_intra_dev(ctx, kind, params, seed, rep_begin, rep_end, rep_ram, d_sup, d.stat, d.rcmin, d.prmin, d.nmin, nullptr));
   HIP_TRY(ctx, hipDeviceSynchronize());
-  return d.fetch(ctx, n, {stat, rcmin, prmin, nmin});
+  return fetch_out(ctx, n, d, {stat, rcmin, prmin, nmin});
 }
 
 cmx_status cmx_null_inter_dev(cmx_ctx* ctx1, cmx_ctx* ctx2, int kind, const double* params, uint64_t seed,
@@ -317,11 +316,11 @@ cmx_status cmx_null_inter(cmx_ctx* ctx1, cmx_ctx* ctx2, int kind, const double* 
   HIP_TRY(ctx1, hipSetDevice(ctx1->device));
   const size_t n = (rep_end - rep_begin) * rep_ram;
   TmpDev tmp;
-  NullOut d;
-  CMX_TRY(d.alloc(ctx1, tmp, n));
+  PairOut d;
+  CMX_TRY(alloc_out(ctx1, tmp, n, &d));
   CMX_TRY(cmx_null_inter_dev(ctx1, ctx2, kind, params, seed, rep_begin, rep_end, rep_ram, d.stat, d.rcmin, d.prmin, d.nmin, nullptr));
   HIP_TRY(ctx1, hipDeviceSynchronize());
-  return d.fetch(ctx1, n, {stat, rcmin, prmin, nmin});
+  return fetch_out(ctx1, n, d, {stat, rcmin, prmin, nmin});
 }
 
 cmx_status cmx_null_pattern_count(cmx_ctx* ctx, unsigned long long* count) {

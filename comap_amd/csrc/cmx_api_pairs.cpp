@@ -55,26 +55,24 @@ cmx_status pair_operand(cmx_ctx* ctx, const Stat& sk, const double* d_counts, si
   if (sk.mi()) {
     CMX_TRY(scratch(ctx, (std::string("mi_cls_") + slot).c_str(), (size_t)sk.B * o.ldx, &o.cls));
     CMX_TRY(scratch(ctx, (std::string("mi_bad_") + slot).c_str(), n, &o.bad));
-    HIP_TRY(ctx, launch_mi_classify(d_counts, n, ldc, sk.B, sk.K, sk.d_bounds, sk.nb, o.cls, o.ldx, o.bad, st));
+    HIP_TRY(ctx, launch_mi_classify(sk, d_counts, n, ldc, o, st));
   } else {
     const bool own = std::strcmp(slot, "gram") == 0, second = std::strcmp(slot, "2") == 0;
     const std::string pre = own ? "gram_" : "pair_", suf = own ? "1" : slot;
-    const int Bp = pair_Bp(sk.B);
-    CMX_TRY(scratch(ctx, (pre + "X" + suf).c_str(), Bp * o.ldx * (block ? n / block : 1), &o.X));
+    CMX_TRY(scratch(ctx, (pre + "X" + suf).c_str(), pair_Bp(sk.B) * o.ldx * (block ? n / block : 1), &o.X));
     CMX_TRY(scratch(ctx, (pre + "s" + suf).c_str(), n, &o.s));
     CMX_TRY(scratch(ctx, (pre + "r" + suf).c_str(), n, &o.r));
-    HIP_TRY(ctx, launch_pair_prep(sk.gk, sk.param, d_counts, n, ldc, sk.B, sk.K, o.X, o.ldx, Bp, o.s, o.r,
-                                  sk.d_mean && second ? sk.d_mean + sk.B : sk.d_mean, st, block, sk.d_w));
+    HIP_TRY(ctx, launch_pair_prep(sk, d_counts, n, ldc, sk.d_mean && second ? sk.d_mean + sk.B : sk.d_mean, block, o, st));
   }
   *out = o;
   return CMX_OK;
 }
 
-cmx_status pair_block(cmx_ctx* ctx, const Stat& sk, const PairOperand& a, size_t i0, size_t rb, const PairOperand& b, int mode, double* out,
-                      size_t ldo, hipStream_t st) {
-  if (sk.mi()) HIP_TRY(ctx, launch_mi_pairs_block(sk.B, a.cls + i0, a.bad + i0, rb, a.ldx, b.cls, b.bad, b.n, b.ldx, mode, out, ldo, i0, st));
-  else HIP_TRY(ctx, launch_pair_gram(gram_kind(sk.gk, sk.d_w), sk.B, pair_Bp(sk.B), a.X + i0, a.s + i0, a.r + i0, rb, a.ldx, b.X, b.s, b.r, b.n, b.ldx,
-                                     mode, out, ldo, st, 1, 0, 0, 0, mode == 2 ? i0 : 0));
+cmx_status pair_block(cmx_ctx* ctx, const Stat& sk, const PairOperand& a, size_t i0, size_t rb, const PairOperand& b, PairMode mode,
+                      double* out, size_t ldo, hipStream_t st) {
+  if (sk.mi()) HIP_TRY(ctx, launch_mi_pairs_block(sk.B, a.rows(i0, rb), b, mode, out, ldo, i0, st));
+  else HIP_TRY(ctx, launch_pair_gram(sk, a.rows(i0, rb), b, mode, out, ldo, GramBatch{1, 0, 0, 0} /* one block of sites: no grid.z strides */,
+                                     mode == kPairUpperRows ? i0 : 0, st));
   return CMX_OK;
 }
 
@@ -96,7 +94,7 @@ cmx_status cmx_pair_stats_dev(cmx_ctx* ctx, int kind, const double* params, cons
   CMX_TRY(pair_operand(ctx, sk, d_counts1, n1, ld1, "1", st, &a));
   if (intra) b = a;
   else CMX_TRY(pair_operand(ctx, sk, d_counts2, n2, ld2, "2", st, &b));
-  return pair_block(ctx, sk, a, 0, n1, b, intra ? 1 : 0, d_out, ldo, st);
+  return pair_block(ctx, sk, a, 0, n1, b, intra ? kPairOneSet : kPairRectangle, d_out, ldo, st);
 }
 
 // AnalysisTools::compute*Matrix (AnalysisTools.cpp:102-339): the same operand preparation, Gram kernel and epilogues as
@@ -123,8 +121,8 @@ cmx_status cmx_vector_matrix(cmx_ctx* ctx, int kind, size_t dim, const double* v
   else d2 = d1;
   if (independent) {   // AnalysisTools.cpp:150-157: j runs over i alone
     CMX_TRY(tmp.alloc(ctx, &d_out, n1));
-    HIP_TRY(ctx, launch_pair_diag(kind, 0.0, sk.B, 1, d1, n1, d2, n2, n1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_out, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr));
+    const PairOut diag{d_out};   // the statistic alone: no columns, no minima
+    HIP_TRY(ctx, launch_pair_diag(sk, d1, n1, SiteCols{}, d2, n2, SiteCols{}, n1, diag, nullptr));
     std::vector<double> dg(n1);
     CMX_TRY(download(ctx, dg.data(), d_out, n1));
     std::fill(out, out + n1 * n2, 0.0);
@@ -137,7 +135,7 @@ cmx_status cmx_vector_matrix(cmx_ctx* ctx, int kind, size_t dim, const double* v
   else CMX_TRY(pair_operand(ctx, sk, d2, n2, n2, "2", nullptr, &b));
   CMX_TRY(tmp.alloc(ctx, &d_out, n1 * n2));
   // the full rectangle (one-set form too: the reference fills both triangles and the diagonal)
-  CMX_TRY(pair_block(ctx, sk, a, 0, n1, b, 0, d_out, n2, nullptr));
+  CMX_TRY(pair_block(ctx, sk, a, 0, n1, b, kPairRectangle, d_out, n2, nullptr));
   HIP_TRY(ctx, hipDeviceSynchronize());
   CMX_TRY(download(ctx, out, d_out, n1 * n2));
   if (one) {
@@ -211,7 +209,7 @@ cmx_status cmx_intra_pvalues_dev(cmx_ctx* ctx, const double* d_stat, size_t ldo,
   hipStream_t st = (hipStream_t)stream;
   NullTable nt;
   CMX_TRY(prepare_null(ctx, d_norms, n, nclasses, d_null_stat, d_null_nmin, nnull, st, &nt));
-  HIP_TRY(ctx, launch_pvalues(d_stat, ldo, d_norms, n, nt, d_pvalue, d_nsim, st));
+  HIP_TRY(ctx, launch_pvalues(d_stat, ldo, d_norms, n, nt, d_pvalue, d_nsim, 0, n, st));
   return CMX_OK;
 }
 
@@ -239,6 +237,23 @@ cmx_status cmx_intra_pvalues(cmx_ctx* ctx, const double* stat, const double* nor
 }
 
 // ------------------------------------------------------------------------------------------------ compacted rows
+// The compaction of statistics into rows runs in two phases: without a temporary a row launcher only reports the size of the
+// scan's.  rows(scan, i0, rb): an entry point's call of its launcher for the rows [i0, i0 + rb).  open() acquires "rows_count",
+// makes the sizing call (rows [0, rb_max)) and acquires "rows_scan"; after that every call of the pass compacts a block.
+template <class Launch>
+struct RowPass {
+  Launch rows;
+  RowScan scan;
+  cmx_status open(cmx_ctx* ctx, size_t count_words, size_t rb_max) {
+    CMX_TRY(scratch(ctx, "rows_count", count_words, &scan.rowcount));
+    HIP_TRY(ctx, rows(scan, 0, rb_max));
+    return scratch(ctx, "rows_scan", scan.tmp_bytes ? scan.tmp_bytes : 16, &scan.tmp);
+  }
+  hipError_t operator()(size_t i0, size_t rb) { return rows(scan, i0, rb); }
+};
+template <class Launch>
+static RowPass<Launch> row_pass(Launch rows) { return {rows, {}}; }
+
 cmx_status cmx_intra_rows_dev(cmx_ctx* ctx, const double* d_stat, size_t ldo, const double* d_pvalue, const int32_t* d_nsim,
                               size_t n, const int32_t* d_rate_class, const double* d_post_rate, const double* d_norm,
                               const cmx_pair_filters* filters, cmx_pair_row* d_rows, size_t capacity, uint64_t* d_count,
@@ -250,18 +265,50 @@ cmx_status cmx_intra_rows_dev(cmx_ctx* ctx, const double* d_stat, size_t ldo, co
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   cmx_pair_filters f{0, -1, 0.0, -1.0, 0.0};
   if (filters) f = *filters;
-  // the compaction runs in two phases: without a temporary it only reports the size of the scan's
-  unsigned long long *rowcount, *count = reinterpret_cast<unsigned long long*>(d_count);
-  CMX_TRY(scratch(ctx, "rows_count", n * kPairRowSegs + 1, &rowcount));
-  size_t tmp_bytes = 0;
-  void* tmp = nullptr;
-  auto rows = [&] {
-    return launch_pair_rows(d_stat, ldo, d_pvalue, d_nsim, n, d_rate_class, d_post_rate, d_norm, f, rowcount, tmp, tmp_bytes, d_rows, capacity,
-                            count, (hipStream_t)stream);
-  };
-  HIP_TRY(ctx, rows());
-  CMX_TRY(scratch(ctx, "rows_scan", tmp_bytes ? tmp_bytes : 16, &tmp));
-  HIP_TRY(ctx, rows());
+  const SiteCols cols{d_rate_class, d_post_rate, d_norm};
+  auto rows = row_pass([&](RowScan& scan, size_t i0, size_t rb) {   // the whole matrix, the p-values given, nothing before its rows
+    return launch_pair_rows(d_stat, ldo, d_pvalue, d_nsim, n, cols, f, scan, d_rows, capacity, reinterpret_cast<unsigned long long*>(d_count), i0,
+                            rb, nullptr, nullptr, (hipStream_t)stream);
+  });
+  CMX_TRY(rows.open(ctx, n * kPairRowSegs + 1, n));
+  HIP_TRY(ctx, rows(0, n));
+  return CMX_OK;
+}
+
+// What cmx_intra_rows_range_dev and cmx_intra_compact_range_dev are given alike, in the order of their own parameter lists, and
+// what both make of it before their row loops: the statistic, the operand of the Gram kernel for all n sites (both sides of
+// every pair), the null index, the row block.
+struct RowRange {
+  int kind;
+  const double *params, *d_counts;
+  size_t n, ldc;
+  const double *d_norm, *d_null_stat, *d_null_nmin;
+  size_t nnull;
+  int nclasses;
+  size_t row_begin, row_end;
+  Stat sk;
+  PairOperand x;
+  NullTable nt{};   // sorted == nullptr: no null given, as the row launchers read it
+  size_t RB = 0;
+};
+// the checks of entry point `who`, in its order; outputs_ok: its own pointers
+static cmx_status row_range_check(cmx_ctx* ctx, const std::string& who, const RowRange& r, bool outputs_ok) {
+  CMX_TRY(need_model(ctx));
+  CMX_TRY(check_kind(ctx, r.kind));
+  if (!r.d_counts || r.n == 0 || r.ldc < r.n || !r.d_norm || !outputs_ok || r.n > 0x7fffffffull || r.row_begin > r.row_end || r.row_end > r.n ||
+      (r.d_null_stat && (!r.d_null_nmin || r.nclasses < 1 || r.nclasses > 64)) || r.nnull > 0xfffffff0ull)
+    return fail(ctx, CMX_ERR_INVALID, who + ": bad arguments");
+  if (ctx->hm.B < 2) return fail(ctx, CMX_ERR_INVALID, who + ": need at least two branches");
+  if (r.kind == CMX_STAT_EUCLIDIAN_DISTANCE) return fail(ctx, CMX_ERR_UNSUPPORTED, who + ": EuclidianDistance is a distance, not a statistic");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return CMX_OK;
+}
+// kept: the Gram blocks are there already, no operand is prepared
+static cmx_status row_range_prepare(cmx_ctx* ctx, RowRange& r, const double* kept, hipStream_t st) {
+  CMX_TRY(resolve_stat(ctx, r.kind, r.params, st, &r.sk));
+  if (!kept) CMX_TRY(pair_operand(ctx, r.sk, r.d_counts, r.n, r.ldc, "1", st, &r.x));
+  if (r.d_null_stat) CMX_TRY(prepare_null(ctx, r.d_norm, r.n, r.nclasses, r.d_null_stat, r.d_null_nmin, r.nnull, st, &r.nt));
+  r.RB = pair_row_block(r.n, r.row_end - r.row_begin);
   return CMX_OK;
 }
 
@@ -274,47 +321,28 @@ cmx_status cmx_intra_rows_range_dev(cmx_ctx* ctx, int kind, const double* params
                                     const double* d_null_stat, const double* d_null_nmin, size_t nnull, int nclasses,
                                     const cmx_pair_filters* filters, size_t row_begin, size_t row_end, cmx_pair_row* d_rows,
                                     size_t capacity, uint64_t* d_count, void* stream) {
-  CMX_TRY(need_model(ctx));
-  CMX_TRY(check_kind(ctx, kind));
-  const bool with_null = d_null_stat != nullptr;
-  if (!d_counts || n == 0 || ldc < n || !d_rate_class || !d_post_rate || !d_norm || !d_count || (capacity && !d_rows) ||
-      n > 0x7fffffffull || row_begin > row_end || row_end > n || (with_null && (!d_null_nmin || nclasses < 1 || nclasses > 64)) ||
-      nnull > 0xfffffff0ull)
-    return fail(ctx, CMX_ERR_INVALID, "cmx_intra_rows_range: bad arguments");
-  const HostModel& h = ctx->hm;
-  if (h.B < 2) return fail(ctx, CMX_ERR_INVALID, "cmx_intra_rows_range: need at least two branches");
-  if (kind == CMX_STAT_EUCLIDIAN_DISTANCE) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_intra_rows_range: EuclidianDistance is a distance, not a statistic");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  RowRange r{kind, params, d_counts, n, ldc, d_norm, d_null_stat, d_null_nmin, nnull, nclasses, row_begin, row_end};
+  CMX_TRY(row_range_check(ctx, "cmx_intra_rows_range", r, d_rate_class && d_post_rate && d_count && !(capacity && !d_rows)));
   hipStream_t st = (hipStream_t)stream;
   cmx_pair_filters f{0, -1, 0.0, -1.0, 0.0};
   if (filters) f = *filters;
   HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
   if (row_begin == row_end) return CMX_OK;
-  // operand of the Gram kernel for all n sites (both sides of every pair)
-  Stat sk;
-  PairOperand x;
-  CMX_TRY(resolve_stat(ctx, kind, params, stream, &sk));
-  CMX_TRY(pair_operand(ctx, sk, d_counts, n, ldc, "1", st, &x));
-  NullTable nt{};
-  if (with_null) CMX_TRY(prepare_null(ctx, d_norm, n, nclasses, d_null_stat, d_null_nmin, nnull, st, &nt));
+  CMX_TRY(row_range_prepare(ctx, r, nullptr, st));
   // row blocks: dense scratch = the f64 statistic; the p-values are looked up by the pass that writes the rows, for the
-  // pairs it writes.  That pass in two phases: without a temporary it only reports the size of the scan's
-  const size_t RB = pair_row_block(n, row_end - row_begin);
+  // pairs it writes, and every block's rows go behind those already counted
   double* blk_stat;
-  unsigned long long *rowcount, *count = reinterpret_cast<unsigned long long*>(d_count);
-  CMX_TRY(scratch(ctx, "blk_stat", RB * n, &blk_stat));
-  CMX_TRY(scratch(ctx, "rows_count", RB * kPairRowSegs + 1, &rowcount));
-  size_t tmp_bytes = 0;
-  void* tmp = nullptr;
-  auto rows = [&](size_t i0, size_t rb) {
-    return launch_pair_rows(blk_stat, n, nullptr, nullptr, n, d_rate_class, d_post_rate, d_norm, f, rowcount, tmp, tmp_bytes, d_rows, capacity, count,
-                            st, i0, rb, tmp ? count : nullptr, tmp && with_null ? &nt : nullptr);
-  };
-  HIP_TRY(ctx, rows(0, RB));
-  CMX_TRY(scratch(ctx, "rows_scan", tmp_bytes ? tmp_bytes : 16, &tmp));
-  for (size_t i0 = row_begin; i0 < row_end; i0 += RB) {
-    const size_t rb = std::min(RB, row_end - i0);
-    CMX_TRY(pair_block(ctx, sk, x, i0, rb, x, 2, blk_stat, n, st));
+  unsigned long long* count = reinterpret_cast<unsigned long long*>(d_count);
+  CMX_TRY(scratch(ctx, "blk_stat", r.RB * n, &blk_stat));
+  const SiteCols cols{d_rate_class, d_post_rate, d_norm};
+  auto rows = row_pass([&](RowScan& scan, size_t i0, size_t rb) {
+    return launch_pair_rows(blk_stat, n, nullptr, nullptr, n, cols, f, scan, d_rows, capacity, count, i0, rb, scan.tmp ? count : nullptr,
+                            &r.nt, st);
+  });
+  CMX_TRY(rows.open(ctx, r.RB * kPairRowSegs + 1, r.RB));
+  for (size_t i0 = row_begin; i0 < row_end; i0 += r.RB) {
+    const size_t rb = std::min(r.RB, row_end - i0);
+    CMX_TRY(pair_block(ctx, r.sk, r.x, i0, rb, r.x, kPairUpperRows, blk_stat, n, st));
     HIP_TRY(ctx, rows(i0, rb));
   }
   return CMX_OK;
@@ -345,7 +373,7 @@ cmx_status cmx_intra_gram_prefetch_dev(cmx_ctx* ctx, int kind, const double* d_c
   CMX_TRY(pair_operand(ctx, sk, d_counts, n, ldc, "gram", st, &x));
   CMX_TRY(scratch(ctx, "gram_kept", nblk * RB * n, &kept));
   for (size_t i0 = row_begin; i0 < row_end; i0 += RB)
-    CMX_TRY(pair_block(ctx, sk, x, i0, std::min(RB, row_end - i0), x, 2, kept + (i0 - row_begin) * n, n, st));
+    CMX_TRY(pair_block(ctx, sk, x, i0, std::min(RB, row_end - i0), x, kPairUpperRows, kept + (i0 - row_begin) * n, n, st));
   ctx->gram_kept = {true, kind, d_counts, n, ldc, row_begin, row_end, kept};
   return CMX_OK;
 }
@@ -354,38 +382,23 @@ cmx_status cmx_intra_compact_range_dev(cmx_ctx* ctx, int kind, const double* par
                                        const double* d_norm, const double* d_null_stat, const double* d_null_nmin, size_t nnull,
                                        int nclasses, size_t row_begin, size_t row_end, cmx_pair_compact* d_out, size_t capacity,
                                        void* stream) {
-  CMX_TRY(need_model(ctx));
-  CMX_TRY(check_kind(ctx, kind));
-  const bool with_null = d_null_stat != nullptr;
-  if (!d_counts || n == 0 || ldc < n || !d_norm || (capacity && !d_out) || n > 0x7fffffffull || row_begin > row_end || row_end > n ||
-      (with_null && (!d_null_nmin || nclasses < 1 || nclasses > 64)) || nnull > 0xfffffff0ull)
-    return fail(ctx, CMX_ERR_INVALID, "cmx_intra_compact_range: bad arguments");
-  const HostModel& h = ctx->hm;
-  if (h.B < 2) return fail(ctx, CMX_ERR_INVALID, "cmx_intra_compact_range: need at least two branches");
-  if (kind == CMX_STAT_EUCLIDIAN_DISTANCE) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_intra_compact_range: EuclidianDistance is a distance, not a statistic");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the pass after each Gram block writes the records at their arithmetic position (no filters: no counting pass, no scan);
+  // the Gram blocks may be there already (cmx_intra_gram_prefetch_dev with these arguments): then only the record pass runs
+  RowRange r{kind, params, d_counts, n, ldc, d_norm, d_null_stat, d_null_nmin, nnull, nclasses, row_begin, row_end};
+  CMX_TRY(row_range_check(ctx, "cmx_intra_compact_range", r, !(capacity && !d_out)));
   hipStream_t st = (hipStream_t)stream;
   if (row_begin == row_end) return CMX_OK;
-  // the same operand, null index and row blocks as cmx_intra_rows_range_dev; the pass after each Gram block writes the
-  // records at their arithmetic position (no filters: no counting pass, no scan)
-  // the Gram blocks may be there already (cmx_intra_gram_prefetch_dev with these arguments): then only the record pass runs
   const cmx_ctx::GramKept gk0 = ctx->gram_kept;
   ctx->gram_kept.valid = false;
   const double* kept = gk0.valid && gk0.kind == kind && gk0.counts == d_counts && gk0.n == n && gk0.ldc == ldc && gk0.row_begin == row_begin &&
                                gk0.row_end == row_end ? gk0.stat : nullptr;
-  Stat sk;
-  PairOperand x;
-  CMX_TRY(resolve_stat(ctx, kind, params, stream, &sk));
-  if (!kept) CMX_TRY(pair_operand(ctx, sk, d_counts, n, ldc, "1", st, &x));
-  NullTable nt{};
-  if (with_null) CMX_TRY(prepare_null(ctx, d_norm, n, nclasses, d_null_stat, d_null_nmin, nnull, st, &nt));
-  const size_t RB = pair_row_block(n, row_end - row_begin);
+  CMX_TRY(row_range_prepare(ctx, r, kept, st));
   double* blk_stat = nullptr;
-  if (!kept) CMX_TRY(scratch(ctx, "blk_stat", RB * n, &blk_stat));
-  for (size_t i0 = row_begin; i0 < row_end; i0 += RB) {
-    const size_t rb = std::min(RB, row_end - i0);
-    if (!kept) CMX_TRY(pair_block(ctx, sk, x, i0, rb, x, 2, blk_stat, n, st));
-    HIP_TRY(ctx, launch_pair_compact(kept ? kept + (i0 - row_begin) * n : blk_stat, n, n, d_norm, with_null ? &nt : nullptr, d_out, capacity, st, i0, rb,
+  if (!kept) CMX_TRY(scratch(ctx, "blk_stat", r.RB * n, &blk_stat));
+  for (size_t i0 = row_begin; i0 < row_end; i0 += r.RB) {
+    const size_t rb = std::min(r.RB, row_end - i0);
+    if (!kept) CMX_TRY(pair_block(ctx, r.sk, r.x, i0, rb, r.x, kPairUpperRows, blk_stat, n, st));
+    HIP_TRY(ctx, launch_pair_compact(kept ? kept + (i0 - row_begin) * n : blk_stat, n, n, d_norm, &r.nt, d_out, capacity, st, i0, rb,
                                      row_begin));
   }
   return CMX_OK;
@@ -491,13 +504,13 @@ cmx_status cmx_inter_rows_dev(cmx_ctx* ctx, int kind, const double* params, cons
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
-  // the compaction of a block of statistics, in two phases: without a temporary it only reports the size of the scan's
-  unsigned long long *rowcount, *count = reinterpret_cast<unsigned long long*>(d_count);
-  size_t tmp_bytes = 0;
-  void* tmp = nullptr;
-  auto rows = [&](const double* stat, size_t ldo, size_t i0, size_t nrows, const unsigned long long* base) {
-    return launch_inter_rows(stat, ldo, n2, d_rc1, d_pr1, d_nm1, d_rc2, d_pr2, d_nm2, f, rowcount, tmp, tmp_bytes, d_rows, capacity, count, st, i0,
-                             nrows, base);
+  // the compaction of a block of statistics: [nrows][ldo], every block's rows behind those at *base
+  unsigned long long* count = reinterpret_cast<unsigned long long*>(d_count);
+  const SiteCols cols1{d_rc1, d_pr1, d_nm1}, cols2{d_rc2, d_pr2, d_nm2};
+  auto inter_pass = [&](const double* stat, size_t ldo, const unsigned long long* base) {
+    return row_pass([=, &f](RowScan& scan, size_t i0, size_t nrows) {
+      return launch_inter_rows(stat, ldo, n2, cols1, cols2, f, scan, d_rows, capacity, count, i0, nrows, scan.tmp ? base : nullptr, st);
+    });
   };
   double* dstat = nullptr;
   if (f.independent_comparisons) CMX_TRY(scratch(ctx, "inter_diag", n1, &dstat));
@@ -509,15 +522,14 @@ cmx_status cmx_inter_rows_dev(cmx_ctx* ctx, int kind, const double* params, cons
     if (sk.mi()) {
       CMX_TRY(pair_operand(ctx, sk, d_counts1, n1, ld1, "1", st, &a));
       CMX_TRY(pair_operand(ctx, sk, d_counts2, n2, ld2, "2", st, &b));
-      HIP_TRY(ctx, launch_mi_pairs_diag(h.B, a.cls, a.bad, a.ldx, b.cls, b.bad, b.ldx, n1, dstat, st));
+      HIP_TRY(ctx, launch_mi_pairs_diag(h.B, a, b, n1, dstat, st));
     } else {
-      HIP_TRY(ctx, launch_pair_diag(kind, sk.param, h.B, h.K, d_counts1, ld1, d_counts2, ld2, n1, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                    nullptr, dstat, nullptr, nullptr, nullptr, sk.d_mean, st, sk.d_w));
+      const PairOut diag{dstat};   // the statistic alone: no columns, no minima
+      HIP_TRY(ctx, launch_pair_diag(sk, d_counts1, ld1, SiteCols{}, d_counts2, ld2, SiteCols{}, n1, diag, st));
     }
-    CMX_TRY(scratch(ctx, "rows_count", n1 + 1, &rowcount));
-    HIP_TRY(ctx, rows(dstat, 1, 0, n1, nullptr));
-    CMX_TRY(scratch(ctx, "rows_scan", tmp_bytes ? tmp_bytes : 16, &tmp));
-    HIP_TRY(ctx, rows(dstat, 1, 0, n1, nullptr));
+    auto rows = inter_pass(dstat, 1, nullptr);
+    CMX_TRY(rows.open(ctx, n1 + 1, n1));
+    HIP_TRY(ctx, rows(0, n1));
     return CMX_OK;
   }
   // operands of both data sets once, then row blocks of data set 1 (dense scratch <= 256 MiB)
@@ -526,13 +538,12 @@ cmx_status cmx_inter_rows_dev(cmx_ctx* ctx, int kind, const double* params, cons
   const size_t RB = pair_row_block(n2, n1);
   double* blk;
   CMX_TRY(scratch(ctx, "blk_stat", RB * n2, &blk));
-  CMX_TRY(scratch(ctx, "rows_count", RB + 1, &rowcount));
-  HIP_TRY(ctx, rows(blk, n2, 0, RB, nullptr));
-  CMX_TRY(scratch(ctx, "rows_scan", tmp_bytes ? tmp_bytes : 16, &tmp));
+  auto rows = inter_pass(blk, n2, count);
+  CMX_TRY(rows.open(ctx, RB + 1, RB));
   for (size_t i0 = 0; i0 < n1; i0 += RB) {
     const size_t rb = std::min(RB, n1 - i0);
-    CMX_TRY(pair_block(ctx, sk, a, i0, rb, b, 0, blk, n2, st));
-    HIP_TRY(ctx, rows(blk, n2, i0, rb, count));
+    CMX_TRY(pair_block(ctx, sk, a, i0, rb, b, kPairRectangle, blk, n2, st));
+    HIP_TRY(ctx, rows(i0, rb));
   }
   return CMX_OK;
 }
@@ -585,11 +596,10 @@ cmx_status cmx_group_stats_dev(cmx_ctx* ctx, int kind, const double* params, con
   if (sk.mi()) {
     PairOperand g;
     CMX_TRY(pair_operand(ctx, sk, d_counts, n, ldc, "g", (hipStream_t)stream, &g));
-    HIP_TRY(ctx, launch_mi_group(sk.B, g.cls, g.bad, g.ldx, d_offsets, d_sites, ngroups, d_out, (hipStream_t)stream));
+    HIP_TRY(ctx, launch_mi_group(sk.B, g, d_offsets, d_sites, ngroups, d_out, (hipStream_t)stream));
     return CMX_OK;
   }
-  HIP_TRY(ctx, launch_group_stats(kind, sk.param, sk.B, sk.K, d_counts, ldc, d_offsets, d_sites, ngroups, d_out, sk.d_mean, (hipStream_t)stream,
-                                  sk.d_w));
+  HIP_TRY(ctx, launch_group_stats(sk, d_counts, ldc, d_offsets, d_sites, ngroups, d_out, (hipStream_t)stream));
   return CMX_OK;
 }
 

@@ -1,6 +1,6 @@
 // What every stage of the C-ABI's host orchestration (cmx_api_*.cpp) shares: the context, error handling, the named scratch
-// buffers and their guard, the device temporaries of the host-pointer entry points, and the few shapes the stages have in
-// common -- a statistic resolved for one call, a data set as the pair kernels read it, the four result buffers of a null.
+// buffers and their guard, the device temporaries of the host-pointer entry points, and what fills the pair stage's shapes of
+// cmx_device.h -- a statistic resolved for one call, a data set as the pair kernels read it, the four result buffers of a null.
 // Internal: nothing here is exported (the library's ABI is include/comap_mi355x.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -166,25 +166,19 @@ cmx_status download(cmx_ctx* ctx, T* host, const T* dev, size_t count) {
   return CMX_OK;
 }
 
-// the four results of a null, one entry per pair: the statistic and the pair's smaller rate class, posterior rate and norm
-struct NullOut {
-  double* stat = nullptr;
-  int32_t* rcmin = nullptr;
-  double *prmin = nullptr, *nmin = nullptr;
-  NullOut at(size_t o) const { return {stat + o, rcmin ? rcmin + o : nullptr, prmin ? prmin + o : nullptr, nmin ? nmin + o : nullptr}; }
-  cmx_status alloc(cmx_ctx* ctx, TmpDev& tmp, size_t n) {
-    CMX_TRY(tmp.alloc(ctx, &stat, n));
-    CMX_TRY(tmp.alloc(ctx, &prmin, n));
-    CMX_TRY(tmp.alloc(ctx, &nmin, n));
-    return tmp.alloc(ctx, &rcmin, n);
-  }
-  cmx_status fetch(cmx_ctx* ctx, size_t n, const NullOut& host) const {   // host.stat is never null
-    CMX_TRY(download(ctx, host.stat, stat, n));
-    CMX_TRY(download(ctx, host.rcmin, rcmin, n));
-    CMX_TRY(download(ctx, host.prmin, prmin, n));
-    return download(ctx, host.nmin, nmin, n);
-  }
-};
+// the four results of a null (PairOut, n pairs) as device temporaries, and their way back to the host
+inline cmx_status alloc_out(cmx_ctx* ctx, TmpDev& tmp, size_t n, PairOut* d) {
+  CMX_TRY(tmp.alloc(ctx, &d->stat, n));
+  CMX_TRY(tmp.alloc(ctx, &d->prmin, n));
+  CMX_TRY(tmp.alloc(ctx, &d->nmin, n));
+  return tmp.alloc(ctx, &d->rcmin, n);
+}
+inline cmx_status fetch_out(cmx_ctx* ctx, size_t n, const PairOut& d, const PairOut& host) {   // host.stat is never null
+  CMX_TRY(download(ctx, host.stat, d.stat, n));
+  CMX_TRY(download(ctx, host.rcmin, d.rcmin, n));
+  CMX_TRY(download(ctx, host.prmin, d.prmin, n));
+  return download(ctx, host.nmin, d.nmin, n);
+}
 
 inline cmx_status check_kind(cmx_ctx* ctx, int kind) {
   if (kind < CMX_STAT_CORRELATION || kind > CMX_STAT_SCALAR_PRODUCT) return fail(ctx, CMX_ERR_INVALID, "unknown statistic kind");
@@ -202,13 +196,6 @@ inline const double* stat_weights(const cmx_ctx* ctx, int kind) {
   }
   return nullptr;
 }
-// the epilogue of pair_gram_kernel for `kind` (after CorrectedCorrelation -> Correlation): a weighted operand
-// (pair_prep_kernel with w) carries the weights already, so weighted correlation is g / sqrt(s_i s_j) -- the Cosinus
-// epilogue -- and weighted covariance is g -- the scalar product's: no (B-1) factors
-inline int gram_kind(int gk, const double* d_w) {
-  if (!d_w) return gk;
-  return gk == CMX_STAT_CORRELATION ? CMX_STAT_COSINUS : gk == CMX_STAT_COVARIANCE ? CMX_STAT_SCALAR_PRODUCT : gk;
-}
 
 // the simulator's counter layout (cmx_simulate.hip philox_uniform): 47 bits of simulated-site index, 17 bits of draw index
 inline cmx_status rng_range(cmx_ctx* ctx, uint64_t g_end, const char* who) {
@@ -224,40 +211,18 @@ cmx_status map_sites_impl(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, siz
                           size_t ldc, double* d_logL, double* d_post_rate, int32_t* d_rate_class, double* d_norm, void* stream,
                           bool full_grid);
 
-// ---- the pair stage's shapes (cmx_api_pairs.cpp)
-// A statistic with its parameters resolved for one call: the DiscreteMI threshold, CorrectedCorrelation's mean vectors or
-// the MI bounds uploaded on the caller's stream (one turn of the context's rotating parameter buffers), the branch weights.
-struct Stat {
-  int kind = 0;                      // as the caller named it
-  int gk = 0;                        // CorrectedCorrelation -> Correlation: the same Gram and epilogue
-  int B = 0, K = 0;
-  double param = 0.0;                // DiscreteMI: the threshold
-  const double* d_mean = nullptr;    // CorrectedCorrelation: [2][B]
-  const double* d_w = nullptr;       // the context's weights where the kind uses them
-  int nb = 0;                        // DiscreteMI with bounds
-  const double* d_bounds = nullptr;
-  bool mi() const { return kind == CMX_STAT_DISCRETE_MI_BOUNDS; }
-};
+// ---- the pair stage's shapes (Stat, PairOperand: cmx_device.h) as cmx_api_pairs.cpp fills them
+// params: the DiscreteMI threshold, or CorrectedCorrelation's mean vectors or the MI bounds, uploaded on the caller's stream (one
+// turn of the context's rotating parameter buffers); the branch weights are the context's
 cmx_status resolve_stat(cmx_ctx* ctx, int kind, const double* params, void* stream, Stat* out);
-
-// One data set as the pair kernels read it: the Gram operand X [Bp][ldx] with the per-site vectors s and r, or (MI with
-// bounds) the class words [B][ldx] with the per-site out-of-range flags.
-struct PairOperand {
-  double *X = nullptr, *s = nullptr, *r = nullptr;
-  uint32_t* cls = nullptr;
-  uint8_t* bad = nullptr;
-  size_t n = 0, ldx = 0;
-};
-inline int pair_Bp(int B) { return (B + 3) / 4 * 4; }
 // prepared on `st` into the scratch buffers of `slot`: "1" / "2" (pair_X1 .., mi_cls_1 ..), "gram" (gram_X1 ..), or a tag of
 // the MI classes alone ("n1", "n2", "g").  The second data set ("2") takes the second mean vector.  block: the n sites are
 // replicates of `block` sites each, an operand block per replicate (clustering); 0: one block.
 cmx_status pair_operand(cmx_ctx* ctx, const Stat& sk, const double* d_counts, size_t n, size_t ldc, const char* slot, hipStream_t st,
                         PairOperand* out, size_t block = 0);
-// rows [i0, i0 + rb) of `a` against all of `b` -> out[rb][ldo].  mode as the kernels take it: 0 rectangle, 1 one data set,
-// 2 upper triangle of one data set (the block's global row i0 then places the diagonal)
-cmx_status pair_block(cmx_ctx* ctx, const Stat& sk, const PairOperand& a, size_t i0, size_t rb, const PairOperand& b, int mode, double* out,
-                      size_t ldo, hipStream_t st);
+// rows [i0, i0 + rb) of `a` against all of `b` -> out[rb][ldo] (kPairUpperRows: the block's global row i0 places the diagonal)
+cmx_status pair_block(cmx_ctx* ctx, const Stat& sk, const PairOperand& a, size_t i0, size_t rb, const PairOperand& b, PairMode mode,
+                      double* out, size_t ldo, hipStream_t st);
 // the row blocks of the pair loop: <= 256 MiB of statistics of n columns, whole 64-row tiles
 inline size_t pair_row_block(size_t n, size_t rows) {
   size_t RB = ((size_t)256 << 20) / (8 * n) / 64 * 64;

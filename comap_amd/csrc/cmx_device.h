@@ -129,18 +129,60 @@ struct MapArgs {
 static_assert(sizeof(DevModel) == 256 && sizeof(Workspace) == 56 && sizeof(MapArgs) == 512 && offsetof(MapArgs, rep_site) == 496,
               "kernel-argument layout of the mapping kernels");
 
+// ---- the pair stage's shapes: host structures (the kernels keep taking their pointers one by one, as with MicaSide)
+// how a block of pairs lies in the matrix of all pairs (the kernels' `int intra`): two data sets, every pair; one data set, pairs
+// j <= i are NaN; a row block of one data set's upper triangle, pairs j <= i are left to the caller, who never reads them
+enum PairMode : int { kPairRectangle = 0, kPairOneSet = 1, kPairUpperRows = 2 };
+// A statistic with its parameters resolved for one call (resolve_stat, cmx_ctx.h): the DiscreteMI threshold,
+// CorrectedCorrelation's mean vectors or the MI bounds on the device, the branch weights.
+struct Stat {
+  int kind = 0;                      // as the caller named it
+  int gk = 0;                        // CorrectedCorrelation -> Correlation: the same Gram and epilogue
+  int B = 0, K = 0;
+  double param = 0.0;                // DiscreteMI: the threshold
+  const double* d_mean = nullptr;    // CorrectedCorrelation: [2][B]
+  const double* d_w = nullptr;       // the context's weights where the kind uses them
+  int nb = 0;                        // DiscreteMI with bounds
+  const double* d_bounds = nullptr;
+  bool mi() const { return kind == CMX_STAT_DISCRETE_MI_BOUNDS; }
+};
+// One data set as the pair kernels read it: the Gram operand X [Bp][ldx] with the per-site vectors s and r, or (MI with
+// bounds) the class words [B][ldx] with the per-site out-of-range flags.
+struct PairOperand {
+  double *X = nullptr, *s = nullptr, *r = nullptr;
+  uint32_t* cls = nullptr;
+  uint8_t* bad = nullptr;
+  size_t n = 0, ldx = 0;
+  PairOperand rows(size_t i0, size_t nrows) const {   // the sites [i0, i0 + nrows) as an operand of their own (a row block's rows)
+    return {X ? X + i0 : X, s ? s + i0 : s, r ? r + i0 : r, cls ? cls + i0 : cls, bad ? bad + i0 : bad, nrows, ldx};
+  }
+};
+inline int pair_Bp(int B) { return (B + 3) / 4 * 4; }
+// one data set's per-site columns: rate class, posterior rate, norm
+struct SiteCols { const int32_t* rc = nullptr; const double *pr = nullptr, *nm = nullptr; };
+// the four results of a pair (a null: an entry per pair): statistic, smaller rate class, posterior rate and norm; null: not asked for
+struct PairOut {
+  double* stat = nullptr;
+  int32_t* rcmin = nullptr;
+  double *prmin = nullptr, *nmin = nullptr;
+  PairOut at(size_t o) const { return {stat + o, rcmin ? rcmin + o : nullptr, prmin ? prmin + o : nullptr, nmin ? nmin + o : nullptr}; }
+};
+// the clustering null's Gram: nblk independent site blocks (grid.z) of the operands' n sites each, block z at site offset
+// z * zsite of s / r, its operand at z * zx, its output at z * zout
+struct GramBatch { size_t nblk, zsite, zout, zx; };
+// what a row pass keeps between its calls: the runs' counts (then offsets) and the scan's temporary (null: the call only sizes it)
+struct RowScan { unsigned long long* rowcount = nullptr; void* tmp = nullptr; size_t tmp_bytes = 0; };
+
 // launchers by source file (cmx_map.hip; pair_diag and group_stats are there for map_kernel's sake)
 hipError_t launch_map(const MapArgs& a, int mode, int grid_blocks, hipStream_t stream);
 hipError_t launch_map_finalize(const MapArgs& a, hipStream_t stream);
 // fills rows S.. of every leaf operator from d_masks[S .. S+max_ambig(S)) (null: every state compatible)
 hipError_t launch_extend_leaf_rows(const DevModel& m, const uint32_t* d_masks, hipStream_t stream);
-hipError_t launch_pair_diag(int kind, double param, int B, int K, const double* c1, size_t ld1, const double* c2, size_t ld2,
-                            size_t n, const int32_t* rc1, const int32_t* rc2, const double* pr1, const double* pr2,
-                            const double* nm1, const double* nm2, double* stat, int32_t* rcmin, double* prmin, double* nmin,
-                            const double* d_mean, hipStream_t stream, const double* d_w = nullptr);
-hipError_t launch_group_stats(int kind, double param, int B, int K, const double* d_counts, size_t ld, const int64_t* d_offsets,
-                              const int32_t* d_sites, size_t ngroups, double* d_out, const double* d_mean, hipStream_t stream,
-                              const double* d_w = nullptr);
+// pairs (j of data set 1, j of data set 2), j < n: the members of `out` that are set
+hipError_t launch_pair_diag(const Stat& st, const double* c1, size_t ld1, const SiteCols& s1, const double* c2, size_t ld2,
+                            const SiteCols& s2, size_t n, const PairOut& out, hipStream_t stream);
+hipError_t launch_group_stats(const Stat& st, const double* d_counts, size_t ld, const int64_t* d_offsets, const int32_t* d_sites,
+                              size_t ngroups, double* d_out, hipStream_t stream);
 // (cmx_simulate.hip)
 hipError_t launch_simulate(const DevModel& m, uint64_t seed, uint64_t g0, size_t n, uint8_t* d_aln, size_t ld,
                            int32_t* d_classes, uint8_t* d_states, hipStream_t stream, size_t rep_ram = 0, uint64_t gstep = 0);
@@ -148,25 +190,20 @@ hipError_t launch_simulate_continuous(const DevModel& m, uint64_t seed, uint64_t
                                       uint8_t* d_aln, size_t ld, double* d_rates, uint8_t* d_states, hipStream_t stream);
 hipError_t launch_simulate_blocked(const DevModel& m, uint64_t seed, uint64_t g0, size_t nsites, size_t blk, uint8_t* d_aln,
                                    uint8_t* d_states, size_t chunk, hipStream_t stream);
-// (cmx_pairs.hip)
-hipError_t launch_pair_prep(int kind, double param, const double* d_counts, size_t n, size_t ldc, int B, int K,
-                            double* d_X, size_t ldx, int Bp, double* d_s, double* d_r, const double* d_mvec,
-                            hipStream_t stream, size_t blk = 0, const double* d_w = nullptr);
-hipError_t launch_pair_gram(int kind, int B, int Bp, const double* d_X1, const double* d_s1, const double* d_r1,
-                            size_t n1, size_t ldx1, const double* d_X2, const double* d_s2, const double* d_r2,
-                            size_t n2, size_t ldx2, int intra, double* d_out, size_t ldo, hipStream_t stream,
-                            size_t nblk = 1, size_t zsite = 0, size_t zout = 0, size_t zx = 0, size_t irow0 = 0);
+// (cmx_pairs.hip) the operand of st.gk into o (d_mvec: this data set's mean vector or null; blk: an operand block per `blk` sites,
+// 0: one block); the statistic of all pairs of a's and b's sites, rows irow0 .. of the full matrix
+hipError_t launch_pair_prep(const Stat& st, const double* d_counts, size_t n, size_t ldc, const double* d_mvec, size_t blk,
+                            const PairOperand& o, hipStream_t stream);
+hipError_t launch_pair_gram(const Stat& st, const PairOperand& a, const PairOperand& b, PairMode mode, double* d_out, size_t ldo,
+                            const GramBatch& z, size_t irow0, hipStream_t stream);
 // (cmx_stat_mi.hip) DiscreteMI with a bounds vector: class words [B][ldx] (class | marginal count << 16) + per-site
 // out-of-range flags; all-pairs block, diagonal pairs, groups
-hipError_t launch_mi_classify(const double* d_counts, size_t n, size_t ldc, int B, int K, const double* d_bounds, int nb,
-                              uint32_t* d_cls, size_t ldx, uint8_t* d_bad, hipStream_t stream);
-hipError_t launch_mi_pairs_block(int B, const uint32_t* d_cls1, const uint8_t* d_bad1, size_t nrows, size_t ld1, const uint32_t* d_cls2,
-                                 const uint8_t* d_bad2, size_t n2, size_t ld2, int intra, double* d_out, size_t ldo, size_t irow0,
-                                 hipStream_t stream);
-hipError_t launch_mi_pairs_diag(int B, const uint32_t* d_cls1, const uint8_t* d_bad1, size_t ld1, const uint32_t* d_cls2,
-                                const uint8_t* d_bad2, size_t ld2, size_t n, double* d_out, hipStream_t stream);
-hipError_t launch_mi_group(int B, const uint32_t* d_cls, const uint8_t* d_bad, size_t ld, const int64_t* d_offsets,
-                           const int32_t* d_sites, size_t ngroups, double* d_out, hipStream_t stream);
+hipError_t launch_mi_classify(const Stat& st, const double* d_counts, size_t n, size_t ldc, const PairOperand& o, hipStream_t stream);
+hipError_t launch_mi_pairs_block(int B, const PairOperand& a, const PairOperand& b, PairMode mode, double* d_out, size_t ldo,
+                                 size_t irow0, hipStream_t stream);
+hipError_t launch_mi_pairs_diag(int B, const PairOperand& a, const PairOperand& b, size_t n, double* d_out, hipStream_t stream);
+hipError_t launch_mi_group(int B, const PairOperand& g, const int64_t* d_offsets, const int32_t* d_sites, size_t ngroups,
+                           double* d_out, hipStream_t stream);
 // (cmx_variants.hip) nijt.average = no: the no-averaging mapping as plain kernels over a global scratch
 // mode: which LegacySubstitutionMappingTools function (CoETools.cpp:395-405)
 // kVariantJoint: the default mapping (computeSubstitutionVectors: averaged, joint) for the alphabets the matrix-core walk
@@ -250,12 +287,11 @@ hipError_t launch_null_patterns(const uint8_t* d_sup, int T, size_t rep_ram, siz
 hipError_t launch_null_pattern_moments(int B, int K, const double* counts, int tile_sites, int tile_row, const uint32_t* npat,
                                        size_t cap, double* pat_mean, double* pat_ss, hipStream_t stream);
 // statistic and minima of pair q = (rep, j) from the patterns of sites (rep, 0, j) and (rep, 1, j); counts in tiles of
-// [B*K][tile_row] doubles, tile_sites patterns each (MapArgs); pat_mean / pat_ss for kinds 0 and 4
-hipError_t launch_null_pattern_pairs(int kind, double param, int B, int K, const double* counts, int tile_sites, int tile_row,
-                                     const double* pat_mean, const double* pat_ss, const double* post_rate,
-                                     const int32_t* rate_class, const double* norm, const uint32_t* pat_of, size_t rep_ram,
-                                     size_t npairs, const double* d_mean, double* stat, int32_t* rcmin, double* prmin, double* nmin,
-                                     hipStream_t stream);
+// [B*K][tile_row] doubles, tile_sites patterns each (MapArgs); pat_mean / pat_ss for Correlation and Covariance; pat: the
+// patterns' columns
+hipError_t launch_null_pattern_pairs(const Stat& st, const double* counts, int tile_sites, int tile_row, const double* pat_mean,
+                                     const double* pat_ss, const SiteCols& pat, const uint32_t* pat_of, size_t rep_ram, size_t npairs,
+                                     const PairOut& out, hipStream_t stream);
 // (cmx_rows.hip)
 hipError_t launch_max_reduce(const double* d_x, size_t n, double* d_out, hipStream_t stream);
 hipError_t launch_null_classify(const double* d_stat, const double* d_nmin, size_t nnull, const double* d_maxnorm,
@@ -279,22 +315,20 @@ struct NullTable {
 };
 hipError_t launch_null_index(const double* d_sorted, const uint32_t* d_hist, int nclasses, size_t nnull, NullClass* d_cls,
                              uint32_t* d_bins, hipStream_t stream);
+// nrows rows irow0 .. of the full matrix
 hipError_t launch_pvalues(const double* d_stat, size_t ldo, const double* d_norms, size_t n, const NullTable& nt, double* d_pvalue,
-                          int32_t* d_nsim, hipStream_t stream, size_t irow0 = 0, size_t nrows = 0);
+                          int32_t* d_nsim, size_t irow0, size_t nrows, hipStream_t stream);
 hipError_t sort_null_by_class(void* d_tmp, size_t& tmp_bytes, double* d_stat_in, double* d_stat_tmp, uint32_t* d_cls_in,
                               uint32_t* d_cls_tmp, size_t n, hipStream_t stream);
-hipError_t launch_pair_rows(const double* d_stat, size_t ldo, const double* d_pvalue, const int32_t* d_nsim, size_t n,
-                            const int32_t* d_rc, const double* d_pr, const double* d_norm, const cmx_pair_filters& f,
-                            unsigned long long* d_rowcount /*[n + 1]*/, void* d_tmp, size_t& tmp_bytes, cmx_pair_row* d_rows,
-                            size_t capacity, unsigned long long* d_count, hipStream_t stream, size_t irow0 = 0, size_t nrows = 0,
-                            const unsigned long long* d_base = nullptr, const NullTable* d_inline_null = nullptr);
+hipError_t launch_pair_rows(const double* d_stat, size_t ldo, const double* d_pvalue, const int32_t* d_nsim, size_t n, const SiteCols& s,
+                            const cmx_pair_filters& f, RowScan& scan /* rowcount [nrows * kPairRowSegs + 1] */, cmx_pair_row* d_rows,
+                            size_t capacity, unsigned long long* d_count, size_t irow0, size_t nrows, const unsigned long long* d_base,
+                            const NullTable* d_inline_null, hipStream_t stream);
 hipError_t launch_pair_compact(const double* d_stat, size_t ldo, size_t n, const double* d_norm, const NullTable* nt, cmx_pair_compact* d_out,
                                size_t capacity, hipStream_t stream, size_t irow0, size_t nrows, size_t row_begin);
-hipError_t launch_inter_rows(const double* d_stat, size_t ldo, size_t n2, const int32_t* d_rc1, const double* d_pr1, const double* d_nm1,
-                             const int32_t* d_rc2, const double* d_pr2, const double* d_nm2, const cmx_inter_filters& f,
-                             unsigned long long* d_rowcount, void* d_tmp, size_t& tmp_bytes, cmx_pair_row* d_rows, size_t capacity,
-                             unsigned long long* d_count, hipStream_t stream, size_t irow0, size_t nrows,
-                             const unsigned long long* d_base);
+hipError_t launch_inter_rows(const double* d_stat, size_t ldo, size_t n2, const SiteCols& s1, const SiteCols& s2, const cmx_inter_filters& f,
+                             RowScan& scan /* rowcount [nrows + 1] */, cmx_pair_row* d_rows, size_t capacity, unsigned long long* d_count,
+                             size_t irow0, size_t nrows, const unsigned long long* d_base, hipStream_t stream);
 // (cmx_mica.hip)
 hipError_t launch_mi_pairs(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t ld1, const uint8_t* d_aln2,
                            size_t ld2, const int64_t* d_idx1, const int64_t* d_idx2, size_t npairs, double* d_mi,

@@ -1044,12 +1044,10 @@ __global__ void pair_diag_kernel(int kind, double param, int B, int K, const dou
   if (nmin) nmin[j] = nm1[j] < nm2[j] ? nm1[j] : nm2[j];
 }
 
-hipError_t launch_pair_diag(int kind, double param, int B, int K, const double* c1, size_t ld1, const double* c2, size_t ld2,
-                            size_t n, const int32_t* rc1, const int32_t* rc2, const double* pr1, const double* pr2,
-                            const double* nm1, const double* nm2, double* stat, int32_t* rcmin, double* prmin, double* nmin,
-                            const double* d_mean, hipStream_t stream, const double* d_w) {
-  hipLaunchKernelGGL(pair_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, kind, param, B, K, c1, ld1,
-                     c2, ld2, n, rc1, rc2, pr1, pr2, nm1, nm2, stat, rcmin, prmin, nmin, d_mean, d_w);
+hipError_t launch_pair_diag(const Stat& st, const double* c1, size_t ld1, const SiteCols& s1, const double* c2, size_t ld2,
+                            const SiteCols& s2, size_t n, const PairOut& out, hipStream_t stream) {
+  hipLaunchKernelGGL(pair_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, st.kind, st.param, st.B, st.K, c1, ld1,
+                     c2, ld2, n, s1.rc, s2.rc, s1.pr, s2.pr, s1.nm, s2.nm, out.stat, out.rcmin, out.prmin, out.nmin, st.d_mean, st.d_w);
   return hipGetLastError();
 }
 
@@ -1109,12 +1107,11 @@ __global__ __launch_bounds__(kWave) void group_stat_kernel(int kind, double para
   if (lane == 0) out[g] = best;
 }
 
-hipError_t launch_group_stats(int kind, double param, int B, int K, const double* d_counts, size_t ld, const int64_t* d_offsets,
-                              const int32_t* d_sites, size_t ngroups, double* d_out, const double* d_mean, hipStream_t stream,
-                              const double* d_w) {
+hipError_t launch_group_stats(const Stat& st, const double* d_counts, size_t ld, const int64_t* d_offsets, const int32_t* d_sites,
+                              size_t ngroups, double* d_out, hipStream_t stream) {
   if (ngroups == 0) return hipSuccess;
-  hipLaunchKernelGGL(group_stat_kernel, dim3((unsigned)ngroups), dim3(kWave), 0, stream, kind, param, B, K, d_counts, ld,
-                     d_offsets, d_sites, d_out, d_mean, d_w);
+  hipLaunchKernelGGL(group_stat_kernel, dim3((unsigned)ngroups), dim3(kWave), 0, stream, st.kind, st.param, st.B, st.K, d_counts, ld,
+                     d_offsets, d_sites, d_out, st.d_mean, st.d_w);
   return hipGetLastError();
 }
 

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(kPatThreads) void null_pattern_pairs_kernel(int kin
   const size_t tile = (size_t)B * K * tile_row;
   const double* ca = counts + (pa / tile_sites) * tile + pa % tile_sites;
   const double* cb = counts + (pb / tile_sites) * tile + pb % tile_sites;
-  if (pat_mean)   // kinds 0 and 4: every count is read once
+  if (pat_mean)   // Correlation / Covariance: every count is read once
     stat[q] = pair_stat_moments(kind, B, K, ca, (size_t)tile_row, pat_mean[pa], pat_ss[pa], cb, (size_t)tile_row, pat_mean[pb], pat_ss[pb]);
   else
     stat[q] = pair_stat_strided(kind, param, B, K, ca, (size_t)tile_row, cb, (size_t)tile_row, mean);
@@ -264,16 +264,14 @@ hipError_t launch_null_pattern_moments(int B, int K, const double* counts, int t
   return hipGetLastError();
 }
 
-hipError_t launch_null_pattern_pairs(int kind, double param, int B, int K, const double* counts, int tile_sites, int tile_row,
-                                     const double* pat_mean, const double* pat_ss, const double* post_rate,
-                                     const int32_t* rate_class, const double* norm, const uint32_t* pat_of, size_t rep_ram,
-                                     size_t npairs, const double* d_mean, double* stat, int32_t* rcmin, double* prmin, double* nmin,
-                                     hipStream_t stream) {
+hipError_t launch_null_pattern_pairs(const Stat& st, const double* counts, int tile_sites, int tile_row, const double* pat_mean,
+                                     const double* pat_ss, const SiteCols& pat, const uint32_t* pat_of, size_t rep_ram, size_t npairs,
+                                     const PairOut& out, hipStream_t stream) {
   if (tile_sites < 1 || tile_row < tile_sites || (pat_mean != nullptr) != (pat_ss != nullptr)) return hipErrorInvalidValue;
-  if (pat_mean && kind != 0 && kind != 4) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(null_pattern_pairs_kernel, dim3(pat_grid(npairs)), dim3(kPatThreads), 0, stream, kind, param, B, K, counts,
-                     (uint32_t)tile_sites, (uint32_t)tile_row, pat_mean, pat_ss, post_rate, rate_class, norm, pat_of, rep_ram, npairs,
-                     d_mean, stat, rcmin, prmin, nmin);
+  if (pat_mean && st.kind != CMX_STAT_CORRELATION && st.kind != CMX_STAT_COVARIANCE) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(null_pattern_pairs_kernel, dim3(pat_grid(npairs)), dim3(kPatThreads), 0, stream, st.kind, st.param, st.B, st.K, counts,
+                     (uint32_t)tile_sites, (uint32_t)tile_row, pat_mean, pat_ss, pat.pr, pat.rc, pat.nm, pat_of, rep_ram, npairs,
+                     st.d_mean, out.stat, out.rcmin, out.prmin, out.nmin);
   return hipGetLastError();
 }
 

@@ -11,11 +11,11 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------ pair statistics
 // prep: X[b][i] (Bp rows, zero padded) and per-site scalars s (sum of squares) and r (row sum of indicators)
-//   kind 0/4: X = type-0 count - mean;  3: X = type-0 count;  1: X = per-branch total;
-//   2: X = [total >= 1];  5: X = [total >= threshold], r = sum X, s = NaN flag when a total leaves [0, 10000)
-// w (normalised branch weights, or null; kinds 0, 1, 3, 4, 7 only): X_b = weight_factor(kind, w_b) * (the value above),
-// the mean of kind 0/4 is sum w x; the caller then scores kind 0 with the Cosinus epilogue and kind 4 with the scalar
-// product's (no (B-1) factors: DESIGN A.7, weighted)
+//   Correlation / Covariance: X = type-0 count - mean;  Cosinus: X = type-0 count;  Compensation: X = per-branch total;
+//   Cosubstitution: X = [total >= 1];  DiscreteMI: X = [total >= threshold], r = sum X, s = NaN flag when a total leaves [0, 10000)
+// w (normalised branch weights, or null; Correlation, Compensation, Cosinus, Covariance, EuclidianDistance only):
+// X_b = weight_factor(kind, w_b) * (the value above), the mean of Correlation / Covariance is sum w x; the launcher then
+// scores Correlation with the Cosinus epilogue and Covariance with the scalar product's (no (B-1) factors: DESIGN A.7, weighted)
 __global__ void pair_prep_kernel(int kind, double param, const double* __restrict__ counts, size_t n, size_t ldc, int B,
                                  int K, double* __restrict__ X, size_t ldx, int Bp, double* __restrict__ sv,
                                  double* __restrict__ rv, const double* __restrict__ mvec /* [B] or null */, size_t blk,
@@ -27,7 +27,7 @@ __global__ void pair_prep_kernel(int kind, double param, const double* __restric
   // 4 MB apart thrash the TLB and land on one L2 channel)
   if (blk) X += (i / blk) * ((size_t)Bp * ldx) - (i / blk) * blk;
   if (w) {
-    const bool centred = kind == 0 || kind == 4;
+    const bool centred = kind == CMX_STAT_CORRELATION || kind == CMX_STAT_COVARIANCE;
     double mean = 0.0;
     if (centred)
       for (int b = 0; b < B; ++b) mean += w[b] * (counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0));
@@ -35,7 +35,7 @@ __global__ void pair_prep_kernel(int kind, double param, const double* __restric
     for (int b = 0; b < B; ++b) {
       double v;
       if (centred) v = counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0) - mean;
-      else if (kind == 3) v = counts[(size_t)b * K * ldc + i];
+      else if (kind == CMX_STAT_COSINUS) v = counts[(size_t)b * K * ldc + i];
       else {
         v = 0.0;
         for (int k = 0; k < K; ++k) v += counts[((size_t)b * K + k) * ldc + i];
@@ -51,7 +51,7 @@ __global__ void pair_prep_kernel(int kind, double param, const double* __restric
     return;
   }
   double mean = 0.0;
-  if (kind == 0 || kind == 4) {   // (CorrectedCorrelation arrives as kind 0 with its mean vector in mvec)
+  if (kind == CMX_STAT_CORRELATION || kind == CMX_STAT_COVARIANCE) {   // (CorrectedCorrelation arrives as Correlation with its mean vector in mvec)
     for (int b = 0; b < B; ++b) mean += counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0);
     mean /= B;
   }
@@ -59,13 +59,13 @@ __global__ void pair_prep_kernel(int kind, double param, const double* __restric
   bool bad = false;
   for (int b = 0; b < B; ++b) {
     double v;
-    if (kind == 0 || kind == 4) v = counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0) - mean;
-    else if (kind == 3 || kind == 9) v = counts[(size_t)b * K * ldc + i];
+    if (kind == CMX_STAT_CORRELATION || kind == CMX_STAT_COVARIANCE) v = counts[(size_t)b * K * ldc + i] - (mvec ? mvec[b] : 0.0) - mean;
+    else if (kind == CMX_STAT_COSINUS || kind == CMX_STAT_SCALAR_PRODUCT) v = counts[(size_t)b * K * ldc + i];
     else {
       double t = 0.0;
       for (int k = 0; k < K; ++k) t += counts[((size_t)b * K + k) * ldc + i];
-      if (kind == 1 || kind == 7) v = t;
-      else if (kind == 2) v = t >= 1.0 ? 1.0 : 0.0;
+      if (kind == CMX_STAT_COMPENSATION || kind == CMX_STAT_EUCLIDIAN_DISTANCE) v = t;
+      else if (kind == CMX_STAT_COSUBSTITUTION) v = t >= 1.0 ? 1.0 : 0.0;
       else {
         v = t >= param ? 1.0 : 0.0;
         if (!(t >= 0.0 && t < 10000.0)) bad = true;
@@ -80,38 +80,37 @@ __global__ void pair_prep_kernel(int kind, double param, const double* __restric
   rv[i] = r;
 }
 
-hipError_t launch_pair_prep(int kind, double param, const double* d_counts, size_t n, size_t ldc, int B, int K,
-                            double* d_X, size_t ldx, int Bp, double* d_s, double* d_r, const double* d_mvec,
-                            hipStream_t stream, size_t blk, const double* d_w) {
+hipError_t launch_pair_prep(const Stat& st, const double* d_counts, size_t n, size_t ldc, const double* d_mvec, size_t blk,
+                            const PairOperand& o, hipStream_t stream) {
   const int block = 256;
-  hipLaunchKernelGGL(pair_prep_kernel, dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, stream, kind, param,
-                     d_counts, n, ldc, B, K, d_X, ldx, Bp, d_s, d_r, d_mvec, blk, d_w);
+  hipLaunchKernelGGL(pair_prep_kernel, dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, stream, st.gk, st.param,
+                     d_counts, n, ldc, st.B, st.K, o.X, o.ldx, pair_Bp(st.B), o.s, o.r, d_mvec, blk, st.d_w);
   return hipGetLastError();
 }
 
 // the factor of a statistic that depends on one site only (fi, fj of pair_epilogue)
 __device__ __forceinline__ double pair_site_factor(int kind, int B, double s) {
-  if (kind == 0) return sqrt(s / (B - 1));
-  if (kind == 3 || kind == 1) return sqrt(s);
+  if (kind == CMX_STAT_CORRELATION) return sqrt(s / (B - 1));
+  if (kind == CMX_STAT_COSINUS || kind == CMX_STAT_COMPENSATION) return sqrt(s);
   return 0.0;
 }
 __device__ __forceinline__ double pair_epilogue(int kind, int B, double g, double si, double sj, double ri, double rj, double fi,
                                                 double fj) {
   switch (kind) {
-    case 0: {
+    case CMX_STAT_CORRELATION: {
       const double cov = g / (B - 1);
       return cov / (fi * fj);
     }
-    case 4: return g / (B - 1);
-    case 9: return g;
-    case 3: return g / (fi * fj);
-    case 1: {
+    case CMX_STAT_COVARIANCE: return g / (B - 1);
+    case CMX_STAT_SCALAR_PRODUCT: return g;
+    case CMX_STAT_COSINUS: return g / (fi * fj);
+    case CMX_STAT_COMPENSATION: {
       double s3 = si + sj + 2.0 * g;
       if (s3 < 0.0) s3 = 0.0;
       return 1.0 - sqrt(s3) / (fi + fj);
     }
-    case 2: return g;
-    case 5: {
+    case CMX_STAT_COSUBSTITUTION: return g;
+    case CMX_STAT_DISCRETE_MI: {
       if (si != si || sj != sj) return __builtin_nan("");
       const double np = B;
       const double cell[4] = {g, ri - g, rj - g, np - ri - rj + g};
@@ -148,9 +147,9 @@ __global__ __launch_bounds__(4 * kWave) void pair_gram_kernel(int kind, int B, i
   if (j0 >= n2) return;
   const double nanv = __builtin_nan("");
   // irow0: the rows are rows irow0 .. of the full matrix (row-block / multi-GPU processing); "below the diagonal" is
-  // then j <= irow0 + i.  A tile wholly below it is skipped (intra == 2: the caller never reads it) or NaN-filled.
-  if (intra == 2 && j0 + 63 < irow0 + i0) return;   // (clustering: mirrored distances; row blocks: only j > i is read)
-  if (intra && irow0 == 0 && tj < ti) {  // strictly below the diagonal: NaN fill (reference loop is j > i, CoETools.cpp:680)
+  // then j <= irow0 + i.  A tile wholly below it is skipped (kPairUpperRows: the caller never reads it) or NaN-filled.
+  if (intra == kPairUpperRows && j0 + 63 < irow0 + i0) return;   // (clustering: mirrored distances; row blocks: only j > i is read)
+  if (intra != kPairRectangle && irow0 == 0 && tj < ti) {  // strictly below the diagonal: NaN fill (reference loop is j > i, CoETools.cpp:680)
     for (int r = 0; r < 64; ++r) {
       const size_t i = i0 + r, j = j0 + lane;
       if (i < n1 && j < n2) out[i * ldo + j] = nanv;
@@ -214,7 +213,7 @@ __global__ __launch_bounds__(4 * kWave) void pair_gram_kernel(int kind, int B, i
         const size_t j = j0 + 16 * q + li;
         if (j < n2) {
           double v = pair_epilogue(kind, B, acc[p][q][r], si, sjv[q], ri, rjv[q], fi, fj[q]);
-          if (intra && j <= irow0 + i) v = nanv;
+          if (intra != kPairRectangle && j <= irow0 + i) v = nanv;
           out[i * ldo + j] = v;
         }
       }
@@ -224,7 +223,7 @@ __global__ __launch_bounds__(4 * kWave) void pair_gram_kernel(int kind, int B, i
 constexpr int kEuclidRows = 8;
 // EuclidianDistance (CoMap/Distance.h:157-171): sqrt(sum_b (tot2_b - tot1_b)^2) over the per-branch totals.  Computed from
 // the differences themselves, not from the Gram matrix: ||a||^2 + ||b||^2 - 2 a.b loses all digits for near-identical
-// vectors.  X = the totals operand of pair_prep_kernel (kind 1), [Bp][ldx]; one thread per pair, row i broadcast.
+// vectors.  X = the totals operand of pair_prep_kernel (as Compensation's), [Bp][ldx]; one thread per pair, row i broadcast.
 __global__ __launch_bounds__(256) void pair_euclid_kernel(int B, const double* __restrict__ X1, size_t n1, size_t ldx1,
                                                          const double* __restrict__ X2, size_t n2, size_t ldx2, int intra,
                                                          double* __restrict__ out, size_t ldo, size_t zx,
@@ -235,7 +234,7 @@ __global__ __launch_bounds__(256) void pair_euclid_kernel(int B, const double* _
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const size_t i0 = ((size_t)blockIdx.y * 4 + wave) * kEuclidRows, j = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
   if (i0 >= n1) return;
-  if (intra == 2 && (size_t)blockIdx.x * 64 + 63 <= i0) return;   // whole tile in the lower triangle: left to the caller
+  if (intra == kPairUpperRows && (size_t)blockIdx.x * 64 + 63 <= i0) return;   // whole tile in the lower triangle: left to the caller
   const size_t jc = j < n2 ? j : n2 - 1;
   double d[kEuclidRows];
 #pragma unroll
@@ -253,27 +252,33 @@ __global__ __launch_bounds__(256) void pair_euclid_kernel(int B, const double* _
 #pragma unroll
   for (int r = 0; r < kEuclidRows; ++r) {
     const size_t i = i0 + r;
-    if (i >= n1 || (intra == 2 && j <= i)) continue;
-    out[i * ldo + j] = (!intra || j > i) ? sqrt(d[r]) : __builtin_nan("");
+    if (i >= n1 || (intra == kPairUpperRows && j <= i)) continue;
+    out[i * ldo + j] = (intra == kPairRectangle || j > i) ? sqrt(d[r]) : __builtin_nan("");
   }
 }
 
-// nblk > 1: nblk independent site blocks of n1 (= n2) sites, block z at site offset z * zsite, output at z * zout
-hipError_t launch_pair_gram(int kind, int B, int Bp, const double* d_X1, const double* d_s1, const double* d_r1,
-                            size_t n1, size_t ldx1, const double* d_X2, const double* d_s2, const double* d_r2,
-                            size_t n2, size_t ldx2, int intra, double* d_out, size_t ldo, hipStream_t stream,
-                            size_t nblk, size_t zsite, size_t zout, size_t zx, size_t irow0) {
-  for (size_t z0 = 0; z0 < nblk; z0 += 65535) {     // grid.z limit
-    const unsigned gz = (unsigned)std::min<size_t>(65535, nblk - z0);
-    const size_t so = z0 * zsite, xo = z0 * zx;
-    double* out = d_out + z0 * zout;
+// the epilogue of pair_gram_kernel for st.gk: a weighted operand (pair_prep_kernel with w) carries the weights already, so
+// weighted correlation is g / sqrt(s_i s_j) -- the Cosinus epilogue -- and weighted covariance is g -- the scalar
+// product's: no (B-1) factors
+static int gram_kind(const Stat& st) {
+  if (!st.d_w) return st.gk;
+  return st.gk == CMX_STAT_CORRELATION ? CMX_STAT_COSINUS : st.gk == CMX_STAT_COVARIANCE ? CMX_STAT_SCALAR_PRODUCT : st.gk;
+}
+
+hipError_t launch_pair_gram(const Stat& st, const PairOperand& a, const PairOperand& b, PairMode mode, double* d_out, size_t ldo,
+                            const GramBatch& z, size_t irow0, hipStream_t stream) {
+  const int kind = gram_kind(st);
+  for (size_t z0 = 0; z0 < z.nblk; z0 += 65535) {     // grid.z limit
+    const unsigned gz = (unsigned)std::min<size_t>(65535, z.nblk - z0);
+    const size_t so = z0 * z.zsite, xo = z0 * z.zx;
+    double* out = d_out + z0 * z.zout;
     if (kind == CMX_STAT_EUCLIDIAN_DISTANCE) {
-      hipLaunchKernelGGL(pair_euclid_kernel, dim3((unsigned)((n2 + 63) / 64), (unsigned)((n1 + 4 * kEuclidRows - 1) / (4 * kEuclidRows)), gz), dim3(256), 0, stream, B,
-                         d_X1 + xo, n1, ldx1, d_X2 + xo, n2, ldx2, intra, out, ldo, zx, zout);
+      hipLaunchKernelGGL(pair_euclid_kernel, dim3((unsigned)((b.n + 63) / 64), (unsigned)((a.n + 4 * kEuclidRows - 1) / (4 * kEuclidRows)), gz), dim3(256), 0, stream,
+                         st.B, a.X + xo, a.n, a.ldx, b.X + xo, b.n, b.ldx, mode, out, ldo, z.zx, z.zout);
     } else {
-      dim3 grid((unsigned)((n2 + 255) / 256), (unsigned)((n1 + 63) / 64), gz);
-      hipLaunchKernelGGL(pair_gram_kernel, grid, dim3(4 * kWave), 0, stream, kind, B, Bp, d_X1 + xo, d_s1 + so, d_r1 + so, n1,
-                         ldx1, d_X2 + xo, d_s2 + so, d_r2 + so, n2, ldx2, intra, out, ldo, zsite, zout, zx, irow0);
+      dim3 grid((unsigned)((b.n + 255) / 256), (unsigned)((a.n + 63) / 64), gz);
+      hipLaunchKernelGGL(pair_gram_kernel, grid, dim3(4 * kWave), 0, stream, kind, st.B, pair_Bp(st.B), a.X + xo, a.s + so, a.r + so, a.n,
+                         a.ldx, b.X + xo, b.s + so, b.r + so, b.n, b.ldx, mode, out, ldo, z.zsite, z.zout, z.zx, irow0);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

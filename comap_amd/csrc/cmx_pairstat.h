@@ -10,12 +10,12 @@ namespace cmx {
 // per-lane statistic between two count columns (row strides ld1 / ld2), CoMap/Statistics.h
 __device__ __forceinline__ double pair_stat_strided(int kind, double param, int B, int K, const double* __restrict__ c1,
                                                     size_t ld1, const double* __restrict__ c2, size_t ld2,
-                                                    const double* __restrict__ mv = nullptr /* [2][B], kind 6 */) {
+                                                    const double* __restrict__ mv = nullptr /* [2][B], CorrectedCorrelation */) {
   switch (kind) {
-    case 0: case 4: case 6: {  // Correlation / Covariance / CorrectedCorrelation: VectorTools::cor, two-pass on type 0
+    case CMX_STAT_CORRELATION: case CMX_STAT_COVARIANCE: case CMX_STAT_CORRECTED_CORRELATION: {  // VectorTools::cor, two-pass on type 0
       // CorrectedCorrelation (Statistics.h:176-204) first subtracts a per-branch mean vector from either operand
-      const double* u1 = kind == 6 ? mv : nullptr;
-      const double* u2 = kind == 6 ? mv + B : nullptr;
+      const double* u1 = kind == CMX_STAT_CORRECTED_CORRELATION ? mv : nullptr;
+      const double* u2 = kind == CMX_STAT_CORRECTED_CORRELATION ? mv + B : nullptr;
       double m1 = 0, m2 = 0;
 #pragma unroll 8
       for (int b = 0; b < B; ++b) {
@@ -30,15 +30,15 @@ __device__ __forceinline__ double pair_stat_strided(int kind, double param, int 
         sxy += dx * dy; sxx += dx * dx; syy += dy * dy;
       }
       const double cov = sxy / (B - 1);
-      if (kind == 4) return cov;
+      if (kind == CMX_STAT_COVARIANCE) return cov;
       return cov / (sqrt(sxx / (B - 1)) * sqrt(syy / (B - 1)));
     }
-    case 9: {  // scalar product (VectorTools::scalar)
+    case CMX_STAT_SCALAR_PRODUCT: {  // VectorTools::scalar
       double sxy = 0;
       for (int b = 0; b < B; ++b) sxy += c1[(size_t)b * K * ld1] * c2[(size_t)b * K * ld2];
       return sxy;
     }
-    case 3: {  // Cosinus
+    case CMX_STAT_COSINUS: {
       double sxy = 0, sxx = 0, syy = 0;
       for (int b = 0; b < B; ++b) {
         const double x = c1[(size_t)b * K * ld1], y = c2[(size_t)b * K * ld2];
@@ -46,7 +46,7 @@ __device__ __forceinline__ double pair_stat_strided(int kind, double param, int 
       }
       return sxy / (sqrt(sxx) * sqrt(syy));
     }
-    case 7: {  // EuclidianDistance
+    case CMX_STAT_EUCLIDIAN_DISTANCE: {
       double d = 0;
       for (int b = 0; b < B; ++b) {
         double t1 = 0, t2 = 0;
@@ -55,7 +55,7 @@ __device__ __forceinline__ double pair_stat_strided(int kind, double param, int 
       }
       return sqrt(d);
     }
-    case 1: case 2: case 5: {
+    case CMX_STAT_COMPENSATION: case CMX_STAT_COSUBSTITUTION: case CMX_STAT_DISCRETE_MI: {
       double s1 = 0, s2 = 0, s3 = 0, cc = 0, n11 = 0, r1 = 0, r2 = 0;
       bool bad = false;
       for (int b = 0; b < B; ++b) {
@@ -67,8 +67,8 @@ __device__ __forceinline__ double pair_stat_strided(int kind, double param, int 
         const double i1 = t1 >= param ? 1.0 : 0.0, i2 = t2 >= param ? 1.0 : 0.0;
         n11 += i1 * i2; r1 += i1; r2 += i2;
       }
-      if (kind == 1) return 1.0 - sqrt(s3) / (sqrt(s1) + sqrt(s2));
-      if (kind == 2) return cc;
+      if (kind == CMX_STAT_COMPENSATION) return 1.0 - sqrt(s3) / (sqrt(s1) + sqrt(s2));
+      if (kind == CMX_STAT_COSUBSTITUTION) return cc;
       if (bad) return __builtin_nan("");
       const double np = B;
       const double cell[4] = {n11, r1 - n11, r2 - n11, np - r1 - r2 + n11};
@@ -83,7 +83,7 @@ __device__ __forceinline__ double pair_stat_strided(int kind, double param, int 
   return __builtin_nan("");
 }
 
-// ---- Correlation / Covariance (kinds 0 and 4) in one pass over the pair (the fused null's pattern table).
+// ---- Correlation / Covariance in one pass over the pair (the fused null's pattern table).
 // pair_stat_strided's first pass and two of its three second-pass sums depend on one operand alone, so they are taken once
 // per pattern (null_pattern_moments_kernel) -- in its order, with its expressions, the squares contracted into v_fma_f64 as the compiler contracts them
 // there -- and a pair adds the cross products.  The statistic is the same bytes as pair_stat_strided's.  That rests on the
@@ -114,7 +114,7 @@ __device__ __forceinline__ double pair_stat_moments(int kind, int B, int K, cons
     sxy = __builtin_fma(dx, dy, sxy);
   }
   const double cov = sxy / (B - 1);
-  if (kind == 4) return cov;
+  if (kind == CMX_STAT_COVARIANCE) return cov;
   return cov / (sqrt(sxx / (B - 1)) * sqrt(syy / (B - 1)));
 }
 
@@ -123,22 +123,22 @@ __device__ __forceinline__ double pair_stat_moments(int kind, int B, int K, cons
 // on the lanes here and in the Gram operand of pair_prep_kernel alike, so a corrected reading of bpp-core's
 // VectorTools changes this one line: Cosinus squares the weights (scalar(x, y, w) = sum w^2 x y and norm(x, w)),
 // Correlation / Covariance / Compensation / EuclidianDistance take them once.
-__device__ __forceinline__ double weight_factor(int kind, double w) { return kind == 3 ? w : sqrt(w); }
+__device__ __forceinline__ double weight_factor(int kind, double w) { return kind == CMX_STAT_COSINUS ? w : sqrt(w); }
 
-// weighted per-lane statistic (kinds 0, 1, 3, 4, 6, 7; the others ignore weights as the reference does).  A function of
+// weighted per-lane statistic (the kinds below; the others ignore weights as the reference does).  A function of
 // its own: pair_stat_strided is inlined into map_kernel's null mode and stays as it is.
-//   0 / 6: VectorTools::cor(x, y, w, false) = sum w dx dy / sqrt(sum w dx^2 sum w dy^2), m = sum w x (no (B-1) factors)
-//   4:     VectorTools::cov(x, y, w, false, false) = sum w dx dy
-//   3:     sum w^2 x y / (sqrt(sum w^2 x^2) sqrt(sum w^2 y^2))
-//   1:     1 - sqrt(sum w (t1 + t2)^2) / (sqrt(sum w t1^2) + sqrt(sum w t2^2))   (Statistics.h:255-264)
-//   7:     sqrt(sum w (t2 - t1)^2)                                                   (Distance.h:160-168)
+//   (Corrected)Correlation: VectorTools::cor(x, y, w, false) = sum w dx dy / sqrt(sum w dx^2 sum w dy^2), m = sum w x (no (B-1) factors)
+//   Covariance:        VectorTools::cov(x, y, w, false, false) = sum w dx dy
+//   Cosinus:           sum w^2 x y / (sqrt(sum w^2 x^2) sqrt(sum w^2 y^2))
+//   Compensation:      1 - sqrt(sum w (t1 + t2)^2) / (sqrt(sum w t1^2) + sqrt(sum w t2^2))   (Statistics.h:255-264)
+//   EuclidianDistance: sqrt(sum w (t2 - t1)^2)                                               (Distance.h:160-168)
 __device__ inline double pair_stat_weighted(int kind, double param, int B, int K, const double* __restrict__ c1,
                                                   size_t ld1, const double* __restrict__ c2, size_t ld2,
                                                   const double* __restrict__ mv, const double* __restrict__ w) {
   switch (kind) {
-    case 0: case 4: case 6: {
-      const double* u1 = kind == 6 ? mv : nullptr;
-      const double* u2 = kind == 6 ? mv + B : nullptr;
+    case CMX_STAT_CORRELATION: case CMX_STAT_COVARIANCE: case CMX_STAT_CORRECTED_CORRELATION: {
+      const double* u1 = kind == CMX_STAT_CORRECTED_CORRELATION ? mv : nullptr;
+      const double* u2 = kind == CMX_STAT_CORRECTED_CORRELATION ? mv + B : nullptr;
       double m1 = 0, m2 = 0;
       for (int b = 0; b < B; ++b) {
         m1 += w[b] * (c1[(size_t)b * K * ld1] - (u1 ? u1[b] : 0.0));
@@ -150,10 +150,10 @@ __device__ inline double pair_stat_weighted(int kind, double param, int B, int K
         const double dx = f * (c1[(size_t)b * K * ld1] - (u1 ? u1[b] : 0.0) - m1), dy = f * (c2[(size_t)b * K * ld2] - (u2 ? u2[b] : 0.0) - m2);
         sxy += dx * dy; sxx += dx * dx; syy += dy * dy;
       }
-      if (kind == 4) return sxy;
+      if (kind == CMX_STAT_COVARIANCE) return sxy;
       return sxy / (sqrt(sxx) * sqrt(syy));
     }
-    case 3: {
+    case CMX_STAT_COSINUS: {
       double sxy = 0, sxx = 0, syy = 0;
       for (int b = 0; b < B; ++b) {
         const double f = weight_factor(kind, w[b]);
@@ -162,7 +162,7 @@ __device__ inline double pair_stat_weighted(int kind, double param, int B, int K
       }
       return sxy / (sqrt(sxx) * sqrt(syy));
     }
-    case 1: case 7: {
+    case CMX_STAT_COMPENSATION: case CMX_STAT_EUCLIDIAN_DISTANCE: {
       double s1 = 0, s2 = 0, s3 = 0, d = 0;
       for (int b = 0; b < B; ++b) {
         double t1 = 0, t2 = 0;
@@ -172,7 +172,7 @@ __device__ inline double pair_stat_weighted(int kind, double param, int B, int K
         s1 += t1 * t1; s2 += t2 * t2; s3 += (t1 + t2) * (t1 + t2);
         d = __builtin_fma(t2 - t1, t2 - t1, d);
       }
-      if (kind == 7) return sqrt(d);
+      if (kind == CMX_STAT_EUCLIDIAN_DISTANCE) return sqrt(d);
       return 1.0 - sqrt(s3) / (sqrt(s1) + sqrt(s2));
     }
   }

@@ -125,8 +125,7 @@ __global__ void pvalue_kernel(const double* __restrict__ stat, size_t ldo, const
 }
 
 hipError_t launch_pvalues(const double* d_stat, size_t ldo, const double* d_norms, size_t n, const NullTable& nt, double* d_pvalue,
-                          int32_t* d_nsim, hipStream_t stream, size_t irow0, size_t nrows) {
-  if (nrows == 0) nrows = n;
+                          int32_t* d_nsim, size_t irow0, size_t nrows, hipStream_t stream) {
   dim3 grid((unsigned)((n + 255) / 256), (unsigned)nrows);
   hipLaunchKernelGGL(pvalue_kernel, grid, dim3(256), 0, stream, d_stat, ldo, d_norms, n, nt, d_pvalue, d_nsim, irow0);
   return hipGetLastError();
@@ -283,23 +282,21 @@ static hipError_t two_pass_rows(size_t nruns, unsigned long long* d_rowcount, vo
   return hipGetLastError();
 }
 
-// nrows rows irow0 .. irow0 + nrows - 1 of an n-column matrix (nrows == 0: the whole matrix).  d_base (device, may be
-// null): number of rows already in d_rows -- this block's rows are appended behind them and *d_count becomes the new
-// total, so that consecutive row blocks fill one array in the reference's (i, j) order.
-hipError_t launch_pair_rows(const double* d_stat, size_t ldo, const double* d_pvalue, const int32_t* d_nsim, size_t n,
-                            const int32_t* d_rc, const double* d_pr, const double* d_norm, const cmx_pair_filters& f,
-                            unsigned long long* d_rowcount /*[nrows * kPairRowSegs + 1]*/, void* d_tmp, size_t& tmp_bytes, cmx_pair_row* d_rows,
-                            size_t capacity, unsigned long long* d_count, hipStream_t stream, size_t irow0, size_t nrows,
-                            const unsigned long long* d_base, const NullTable* d_inline_null) {
+// nrows rows irow0 .. irow0 + nrows - 1 of an n-column matrix.  d_base (device, may be null): number of rows already in
+// d_rows -- this block's rows are appended behind them and *d_count becomes the new total, so that consecutive row blocks
+// fill one array in the reference's (i, j) order.
+hipError_t launch_pair_rows(const double* d_stat, size_t ldo, const double* d_pvalue, const int32_t* d_nsim, size_t n, const SiteCols& s,
+                            const cmx_pair_filters& f, RowScan& scan, cmx_pair_row* d_rows, size_t capacity, unsigned long long* d_count,
+                            size_t irow0, size_t nrows, const unsigned long long* d_base, const NullTable* d_inline_null,
+                            hipStream_t stream) {
   // d_inline_null: the write pass looks the p-values up itself (no dense p-value / Nsim block, no pvalue_kernel)
   const NullTable nt = d_inline_null ? *d_inline_null : NullTable{nullptr, nullptr, nullptr, nullptr, 0};
-  if (nrows == 0) nrows = n;
   const size_t nruns = nrows * kPairRowSegs;
   auto pass = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nruns), dim3(64), 0, stream, d_stat, ldo, d_pvalue, d_nsim, n, d_rc, d_pr, d_norm, f,
-                       d_rowcount, d_rows, capacity, irow0, d_base, nt);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nruns), dim3(64), 0, stream, d_stat, ldo, d_pvalue, d_nsim, n, s.rc, s.pr, s.nm, f,
+                       scan.rowcount, d_rows, capacity, irow0, d_base, nt);
   };
-  return two_pass_rows(nruns, d_rowcount, d_tmp, tmp_bytes, d_count, d_base, stream, [&] { pass(pair_rows_kernel<false>); },
+  return two_pass_rows(nruns, scan.rowcount, scan.tmp, scan.tmp_bytes, d_count, d_base, stream, [&] { pass(pair_rows_kernel<false>); },
                        [&] { pass(pair_rows_kernel<true>); });
 }
 
@@ -392,16 +389,14 @@ __global__ __launch_bounds__(64) void inter_rows_kernel(const double* __restrict
 
 // rows irow0 .. irow0 + nrows - 1 of data set 1; d_stat: [nrows][ldo] (or [nrows] for independant comparisons); d_base
 // / d_count as in launch_pair_rows
-hipError_t launch_inter_rows(const double* d_stat, size_t ldo, size_t n2, const int32_t* d_rc1, const double* d_pr1, const double* d_nm1,
-                             const int32_t* d_rc2, const double* d_pr2, const double* d_nm2, const cmx_inter_filters& f,
-                             unsigned long long* d_rowcount, void* d_tmp, size_t& tmp_bytes, cmx_pair_row* d_rows, size_t capacity,
-                             unsigned long long* d_count, hipStream_t stream, size_t irow0, size_t nrows,
-                             const unsigned long long* d_base) {
+hipError_t launch_inter_rows(const double* d_stat, size_t ldo, size_t n2, const SiteCols& s1, const SiteCols& s2, const cmx_inter_filters& f,
+                             RowScan& scan, cmx_pair_row* d_rows, size_t capacity, unsigned long long* d_count, size_t irow0, size_t nrows,
+                             const unsigned long long* d_base, hipStream_t stream) {
   auto pass = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nrows), dim3(64), 0, stream, d_stat, ldo, n2, d_rc1, d_pr1, d_nm1, d_rc2, d_pr2, d_nm2, f,
-                       d_rowcount, d_rows, capacity, irow0, d_base);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nrows), dim3(64), 0, stream, d_stat, ldo, n2, s1.rc, s1.pr, s1.nm, s2.rc, s2.pr, s2.nm, f,
+                       scan.rowcount, d_rows, capacity, irow0, d_base);
   };
-  return two_pass_rows(nrows, d_rowcount, d_tmp, tmp_bytes, d_count, d_base, stream, [&] { pass(inter_rows_kernel<false>); },
+  return two_pass_rows(nrows, scan.rowcount, scan.tmp, scan.tmp_bytes, d_count, d_base, stream, [&] { pass(inter_rows_kernel<false>); },
                        [&] { pass(inter_rows_kernel<true>); });
 }
 

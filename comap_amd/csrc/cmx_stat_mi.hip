@@ -132,8 +132,8 @@ __device__ __forceinline__ double mi_pair_wave(const MiTable& t, int lane, int B
 
 constexpr int kMiTile = 32;   // columns per workgroup
 
-// rows irow0 .. of the full matrix against all columns: out[il * ldo + j].  intra: 0 two data sets, 1 NaN for j <= i,
-// 2 pairs j <= i are left untouched (row blocks: the caller only reads j > i)
+// rows irow0 .. of the full matrix against all columns: out[il * ldo + j].  intra: a PairMode -- kPairRectangle two data sets,
+// kPairOneSet NaN for j <= i, kPairUpperRows pairs j <= i are left untouched (row blocks: the caller only reads j > i)
 __global__ __launch_bounds__(kWave) void mi_pairs_block_kernel(int B, const uint32_t* __restrict__ cls1, const uint8_t* __restrict__ bad1,
                                                                size_t ld1, const uint32_t* __restrict__ cls2,
                                                                const uint8_t* __restrict__ bad2, size_t n2, size_t ld2, int intra,
@@ -142,8 +142,8 @@ __global__ __launch_bounds__(kWave) void mi_pairs_block_kernel(int B, const uint
   const int lane = threadIdx.x;
   const size_t il = blockIdx.y, i = irow0 + il, j0 = (size_t)blockIdx.x * kMiTile;
   const size_t jend = std::min(n2, j0 + kMiTile);
-  if (intra && jend <= i + 1) {
-    if (intra == 1)
+  if (intra != kPairRectangle && jend <= i + 1) {
+    if (intra == kPairOneSet)
       for (size_t j = j0 + lane; j < jend; j += kWave) out[il * ldo + j] = __builtin_nan("");
     return;
   }
@@ -154,8 +154,8 @@ __global__ __launch_bounds__(kWave) void mi_pairs_block_kernel(int B, const uint
   const bool badi = bad1[il] != 0;
   for (size_t j = j0; j < jend; ++j) {
     double v;
-    if (intra && j <= i) {
-      if (intra == 2) continue;
+    if (intra != kPairRectangle && j <= i) {
+      if (intra == kPairUpperRows) continue;
       v = __builtin_nan("");
     } else if (badi || bad2[j]) {
       v = __builtin_nan("");
@@ -208,10 +208,9 @@ __global__ __launch_bounds__(kWave) void mi_group_kernel(int B, const uint32_t* 
   if (lane == 0) out[g] = best;
 }
 
-hipError_t launch_mi_classify(const double* d_counts, size_t n, size_t ldc, int B, int K, const double* d_bounds, int nb,
-                              uint32_t* d_cls, size_t ldx, uint8_t* d_bad, hipStream_t stream) {
-  hipLaunchKernelGGL(mi_classify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_counts, n, ldc, B, K, d_bounds, nb,
-                     d_cls, ldx, d_bad);
+hipError_t launch_mi_classify(const Stat& st, const double* d_counts, size_t n, size_t ldc, const PairOperand& o, hipStream_t stream) {
+  hipLaunchKernelGGL(mi_classify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_counts, n, ldc, st.B, st.K, st.d_bounds,
+                     st.nb, o.cls, o.ldx, o.bad);
   return hipGetLastError();
 }
 
@@ -220,37 +219,35 @@ static hipError_t mi_lds_attr(const void* fn, size_t lds) {
   return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
-hipError_t launch_mi_pairs_block(int B, const uint32_t* d_cls1, const uint8_t* d_bad1, size_t nrows, size_t ld1, const uint32_t* d_cls2,
-                                 const uint8_t* d_bad2, size_t n2, size_t ld2, int intra, double* d_out, size_t ldo, size_t irow0,
-                                 hipStream_t stream) {
+hipError_t launch_mi_pairs_block(int B, const PairOperand& a, const PairOperand& b, PairMode mode, double* d_out, size_t ldo,
+                                 size_t irow0, hipStream_t stream) {
   const size_t lds = mi_lds_bytes(B);
   hipError_t e = mi_lds_attr(reinterpret_cast<const void*>(&mi_pairs_block_kernel), lds);
   if (e != hipSuccess) return e;
-  for (size_t r0 = 0; r0 < nrows; r0 += 65535) {   // grid.y limit
-    const size_t rb = std::min<size_t>(65535, nrows - r0);
-    hipLaunchKernelGGL(mi_pairs_block_kernel, dim3((unsigned)((n2 + kMiTile - 1) / kMiTile), (unsigned)rb), dim3(kWave), lds, stream, B,
-                       d_cls1 + r0, d_bad1 + r0, ld1, d_cls2, d_bad2, n2, ld2, intra, d_out + r0 * ldo, ldo, irow0 + r0);
+  for (size_t r0 = 0; r0 < a.n; r0 += 65535) {   // grid.y limit
+    const size_t rb = std::min<size_t>(65535, a.n - r0);
+    hipLaunchKernelGGL(mi_pairs_block_kernel, dim3((unsigned)((b.n + kMiTile - 1) / kMiTile), (unsigned)rb), dim3(kWave), lds, stream, B,
+                       a.cls + r0, a.bad + r0, a.ldx, b.cls, b.bad, b.n, b.ldx, mode, d_out + r0 * ldo, ldo, irow0 + r0);
   }
   return hipGetLastError();
 }
 
-hipError_t launch_mi_pairs_diag(int B, const uint32_t* d_cls1, const uint8_t* d_bad1, size_t ld1, const uint32_t* d_cls2,
-                                const uint8_t* d_bad2, size_t ld2, size_t n, double* d_out, hipStream_t stream) {
+hipError_t launch_mi_pairs_diag(int B, const PairOperand& a, const PairOperand& b, size_t n, double* d_out, hipStream_t stream) {
   const size_t lds = mi_lds_bytes(B);
   hipError_t e = mi_lds_attr(reinterpret_cast<const void*>(&mi_pairs_diag_kernel), lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(mi_pairs_diag_kernel, dim3((unsigned)((n + kMiTile - 1) / kMiTile)), dim3(kWave), lds, stream, B, d_cls1, d_bad1, ld1,
-                     d_cls2, d_bad2, ld2, n, d_out);
+  hipLaunchKernelGGL(mi_pairs_diag_kernel, dim3((unsigned)((n + kMiTile - 1) / kMiTile)), dim3(kWave), lds, stream, B, a.cls, a.bad, a.ldx,
+                     b.cls, b.bad, b.ldx, n, d_out);
   return hipGetLastError();
 }
 
-hipError_t launch_mi_group(int B, const uint32_t* d_cls, const uint8_t* d_bad, size_t ld, const int64_t* d_offsets,
-                           const int32_t* d_sites, size_t ngroups, double* d_out, hipStream_t stream) {
+hipError_t launch_mi_group(int B, const PairOperand& g, const int64_t* d_offsets, const int32_t* d_sites, size_t ngroups,
+                           double* d_out, hipStream_t stream) {
   if (ngroups == 0) return hipSuccess;
   const size_t lds = mi_lds_bytes(B);
   hipError_t e = mi_lds_attr(reinterpret_cast<const void*>(&mi_group_kernel), lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(mi_group_kernel, dim3((unsigned)ngroups), dim3(kWave), lds, stream, B, d_cls, d_bad, ld, d_offsets, d_sites, d_out);
+  hipLaunchKernelGGL(mi_group_kernel, dim3((unsigned)ngroups), dim3(kWave), lds, stream, B, g.cls, g.bad, g.ldx, d_offsets, d_sites, d_out);
   return hipGetLastError();
 }
 

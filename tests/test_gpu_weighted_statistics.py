@@ -169,6 +169,32 @@ def test_kept_gram_blocks_follow_new_weights(setup):
     eng.set_statistic_weights(None)
 
 
+@pytest.mark.parametrize("kind", [engine.STAT_CORRELATION, engine.STAT_COMPENSATION, engine.STAT_COSINUS])
+def test_inter_rows_carry_the_weighted_statistic(setup, kind):
+    """cmx_inter_rows with weights set, both of its ways to the statistic: the row blocks of the Gram (70 x 33 sites: one
+    full 64-column step and a tail) and, for independant comparisons, the diagonal pairs scored lane by lane.  No filter
+    drops a pair, so the rows are every pair in (i, j) order with the restatement's value."""
+    eng, m, wn = setup["eng"], setup["m"], setup["wn"]
+
+    def part(lo, hi):
+        return {k: m[k][lo:hi] for k in ("counts", "rate_class", "post_rate", "norm")}
+
+    eng.set_statistic_weights(setup["w"])
+    a, b = part(0, 70), part(57, 90)
+    rows, count = eng.inter_rows(kind, a, b)
+    d1, d2 = part(0, 45), part(45, 90)
+    diag, ndiag = eng.inter_rows(kind, d1, d2, engine.InterFilters(independent_comparisons=True))
+    eng.set_statistic_weights(None)
+    assert count == len(rows) == 70 * 33
+    assert np.array_equal(rows["i"], np.repeat(np.arange(70), 33)) and np.array_equal(rows["j"], np.tile(np.arange(33), 70))
+    _close(rows["stat"].reshape(70, 33), wr.matrix_gram(kind, a["counts"], wn, b["counts"]))
+    assert np.array_equal(rows["n_min"], np.minimum.outer(a["norm"], b["norm"]).ravel())
+    assert ndiag == len(diag) == 45
+    assert np.array_equal(diag["i"], np.arange(45)) and np.array_equal(diag["j"], np.arange(45))
+    _close(diag["stat"], np.diag(wr.matrix_gram(kind, d1["counts"], wn, d2["counts"])))
+    assert np.array_equal(diag["rc_min"], np.minimum(d1["rate_class"], d2["rate_class"]))
+
+
 # ------------------------------------------------------------------------------------------------ groups, clustering
 @pytest.mark.parametrize("kind", [engine.STAT_CORRELATION, engine.STAT_COMPENSATION, engine.STAT_COSINUS, engine.STAT_COVARIANCE])
 def test_group_stats_match_the_restatement(setup, kind):
