@@ -13,8 +13,9 @@
 //   a layout where lane = (state inside a 4-state tile, site of a group of 16).
 //   Matrices are packed host-side in 4x4 blocks so that one copy serves both P.d (inside) and P^T.u (outside).
 //   Inside vectors / outside messages that must survive go to a per-wave HBM workspace as [S/2][lane][2]: every
-//   access is one fully coalesced 1 KiB row; they come back by plain global loads into registers the walk has declared
-//   dead long before (DevWalk::load).  LDS holds, per wave, two operator stage buffers and four symbol slots; the 64-site
+//   access is one fully coalesced 1 KiB row; they come back by compiler-visible global loads into registers the walk has
+//   declared dead long before (DevWalk::load), under the cache policy StatePolicy names (`nt` both ways for proteins).
+//   LDS holds, per wave, two operator stage buffers and four symbol slots; the 64-site
 //   protein walk adds one workspace vector (DevWalk::kLdsSlot) for the short-lived vectors the host's plan names.
 //   DESIGN.md 4.1 has the full description and the measurements.
 //   MODE == kModeNull: map (x2 batches) -> per-pair statistic of AnalysisTools::getNullDistributionIntraDR
@@ -295,18 +296,62 @@ __device__ __forceinline__ double cherry_apply(const uint8_t* buf, const uint8_t
 // loads at 3 of the 5 load sites of map_kernel<20, null> -- the loaded quads do not match the registers the vector's phi
 // with the other arms of the child switch got -- and 64-bit loads remove copies and early waits alike.  Twice the VMEM
 // instructions cost what that saved: target launch 445 -> 450 ms, same box, profiles/r04_ab_workspace_64bit.log.)
-template <int S>
+//
+// ---- Cache policy of the per-wave state.  Every global access of state a wave keeps for itself goes through
+// state_load / state_store (store_vec / load_vec for whole vectors) with a compile-time policy; StatePolicy names the
+// policy of each class of state per instantiation (DESIGN.md 4.1 has the table with every reader):
+//   V  workspace vectors (DevWalk::store / load)          P  per-class counts `part` (dot3 / ldot / cdot, the epilogue's loads)
+//   T  final counts and per-site scalars (the epilogue's tile / cnt0 / cnt1 stores, observed mode's copy loop)
+//   S  class-split mode's split_part / split_lc
+// Operators (LDS-DMA, plain) and symbols (sc0 sc1) are not state and keep their own forms.
+// RULE: a location stored with a form that may bypass the CU's L1 (anything but kPolPlain) is loaded ONLY with a form
+// that bypasses the L1 too (kPolNt), by every reader in every kernel.  A slot is rewritten in every class pass and
+// read back by the same wave: a store that does not update the L1 followed by a plain load could be served the
+// previous pass's line.  The walk's other traffic evicts that line almost always, so no test can show a violation:
+// the rule holds by construction (StatePolicy's static_asserts) or not at all.
+// Loads stay compiler-visible (plain or __builtin_nontemporal_load: hipcc counts them, os.vs / wait_vm keep their exact
+// counts); a vector is kVecInstrs VMEM instructions under every policy.
+enum { kPolPlain = 0, kPolNt = 1 };   // kPolNt: `nt` -- streaming in the L2, past the L1 (DESIGN.md 8.8 has the forms that lost)
+template <int POL, class T>
+__device__ __forceinline__ T state_load(const T* p) {
+  static_assert(POL == kPolPlain || POL == kPolNt, "load forms");
+  if constexpr (POL == kPolNt) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <int POL, class T>
+__device__ __forceinline__ void state_store(const T v, T* p) {   // (value first: evaluated in an assignment's order)
+  static_assert(POL == kPolPlain || POL == kPolNt, "store forms");
+  if constexpr (POL == kPolNt) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+template <int S, int MODE, int FUSE, int NG>
+struct StatePolicy {
+  // V streams through the L2 in the 64-site and 16-site protein walks (each byte written once and read once, 10 KiB per
+  // vector and wave); the class-fused and 4-state instantiations keep plain accesses (not measured: their device code is
+  // the parent's).  P, T and S stay plain everywhere: `nt` stores of P or of the pattern tiles gained nothing (DESIGN.md
+  // 8.8), cnt0 / cnt1 are read back by pair_stat_strided and split_part / split_lc by map_finalize_kernel with plain loads.
+  static constexpr bool kOn = S == 20 && FUSE == 1;
+  static constexpr int v_store = kOn ? kPolNt : kPolPlain, v_load = v_store;
+  static constexpr int p_store = kPolPlain, p_load = kPolPlain;
+  static constexpr int t_store = kPolPlain, t_load = kPolPlain;
+  static constexpr int split_store = kPolPlain;
+  static_assert(v_store == kPolPlain || v_load != kPolPlain, "RULE: V");
+  static_assert(p_store == kPolPlain || p_load != kPolPlain, "RULE: P");
+  static_assert(t_store == kPolPlain && split_store == kPolPlain, "RULE: T and S have readers outside this file with plain loads");
+};
+
+template <int S, int POL>
 __device__ __forceinline__ void load_vec(const double* p /* slice base */, double (&v)[S], int lane) {
   p += 2 * lane;
 #pragma unroll
   for (int i = 0; i < S / 2; ++i) {
-    const d2 t = *reinterpret_cast<const d2*>(p + (size_t)i * 2 * kWave);
+    const d2 t = state_load<POL>(reinterpret_cast<const d2*>(p + (size_t)i * 2 * kWave));
     v[2 * i] = t[0];
     v[2 * i + 1] = t[1];
   }
-  if constexpr (S % 2) v[S - 1] = p[(size_t)(S / 2) * 2 * kWave - lane];
+  if constexpr (S % 2) v[S - 1] = state_load<POL>(p + (size_t)(S / 2) * 2 * kWave - lane);
 }
-template <int S>
+template <int S, int POL>
 __device__ __forceinline__ void store_vec(double* p, const double (&v)[S], int lane) {
   p += 2 * lane;
 #pragma unroll
@@ -314,9 +359,9 @@ __device__ __forceinline__ void store_vec(double* p, const double (&v)[S], int l
     d2 t;
     t[0] = v[2 * i];
     t[1] = v[2 * i + 1];
-    *reinterpret_cast<d2*>(p + (size_t)i * 2 * kWave) = t;
+    state_store<POL>(t, reinterpret_cast<d2*>(p + (size_t)i * 2 * kWave));
   }
-  if constexpr (S % 2) p[(size_t)(S / 2) * 2 * kWave - lane] = v[S - 1];
+  if constexpr (S % 2) state_store<POL>(v[S - 1], p + (size_t)(S / 2) * 2 * kWave - lane);
 }
 
 // ------------------------------------------------------------------------------------------------ mapping core
@@ -352,7 +397,7 @@ struct OpState {
 // same walk on the host and checked numerically there -- says where the operators are.
 // RESOLVED: every symbol of the alignment is a state (the null's simulated or supplied alignments): leaf ops then stage the
 // S0 state rows of the transposed operator only, not its ambiguity rows
-template <int S, int FUSE, int NG, bool RESOLVED>
+template <int S, int FUSE, int NG, bool RESOLVED, class POL>
 struct DevWalk {
   static constexpr int VL = S / 4 * NG, kSites = 16 * NG;
   static constexpr bool DIAG = FUSE > 1 && S / FUSE == 4;
@@ -507,18 +552,20 @@ struct DevWalk {
     op_end(nseq);
     return tot;
   }
+  // per-class count of row `row` of this lane's site (P; class-split mode: S)
+  __device__ __forceinline__ void part_store(int row, double v) { state_store<POL::p_store>(v, pcnt + ((size_t)row * kSites + vsidx())); }
   template <int D> __device__ __forceinline__ void lset(int, int) { (void)row_op<false, LEAF_SET, D, D>(); }
   template <int SRC, int D> __device__ __forceinline__ void lmul(int, int) { (void)row_op<false, LEAF_MUL, SRC, D>(); }
   template <int SRC> __device__ __forceinline__ void ldot(int, int, int row) {
     const double tot = row_op<false, LEAF_DOT, SRC, SRC>();
-    pcnt[(size_t)row * kSites + vsidx()] = pc * tot;
+    part_store(row, pc * tot);
   }
   template <int D> __device__ __forceinline__ void cset(int, int, int) { (void)row_op<true, LEAF_SET, D, D>(); }
   template <int SRC> __device__ __forceinline__ void cdot(int, int, int, int, int row) {
     const double tot = row_op<true, LEAF_DOT, SRC, SRC>();
-    pcnt[(size_t)row * kSites + vsidx()] = pc * tot;
+    part_store(row, pc * tot);
   }
-  // workspace vector -> register: plain global loads straight into the destination register, which the walk has
+  // workspace vector -> register: global loads (POL::v_load) straight into the destination register, which the walk has
   // declared dead (kill) long before -- in the outside pass the two sibling messages of a node are requested before the
   // first product and first read after it, so their latency hides behind ~100 MFMAs without a landing buffer.  The
   // loads are compiler-visible (hipcc waits for them before the first use); they are counted in vs like every VMEM
@@ -527,7 +574,7 @@ struct DevWalk {
   __device__ __forceinline__ void load(int arr, int slot) {
     {
       const int vl = vlane();
-      load_vec<VL>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<D>(), vl);
+      load_vec<VL, POL::v_load>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<D>(), vl);
     }
     os.vs += kVecInstrs;
   }
@@ -535,7 +582,7 @@ struct DevWalk {
   __device__ __forceinline__ void store(int arr, int slot) {
     {
       const int vl = vlane();
-      store_vec<VL>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<SRC>(), vl);
+      store_vec<VL, POL::v_store>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<SRC>(), vl);
     }
     os.vs += kVecInstrs;
   }
@@ -622,7 +669,7 @@ struct DevWalk {
     for (int sb = 0; sb < S / 4; ++sb)
 #pragma unroll
       for (int g = 0; g < NG; ++g) p_[g] = __builtin_fma(R3[sb * NG + g] * R1[sb * NG + g], R2[sb * NG + g], p_[g]);
-    pcnt[(size_t)row * kSites + vsidx()] = pc * reduce_sites<NG>(p_);
+    part_store(row, pc * reduce_sites<NG>(p_));
   }
 };
 
@@ -632,14 +679,14 @@ struct DevWalk {
 // cnt[(b*K+k)*64 + lane] holds the final counts n(b, site, k) and the scalars are per lane; without (class-split
 // observed mode) only part[] and L_out = sum of p_c L_c over the processed classes are produced.
 // part: [C][B*K][64] per-class joint counts (written once each, summed at the end: no read-modify-write in the loop).
-template <int S, int FUSE, int NG, bool RESOLVED>
+template <int S, int FUSE, int NG, bool RESOLVED, class POL>
 __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restrict__ wsM, double* __restrict__ wsU,
                                                double* __restrict__ part, double* __restrict__ cnt, int lds_off,
                                                const uint8_t* __restrict__ gcodes, size_t gstride, int lane,
                                                OpState& os, double& L_out, double& pr_out, int& rc_out,
                                                double& norm_out, int c_begin, int c_end, int c_after, bool finalize) {
   const DevModel& m = a.m;
-  constexpr bool kTables = DevWalk<S, FUSE, NG, RESOLVED>::kCherryTables;   // (the launcher guarantees m.msched_r then)
+  constexpr bool kTables = DevWalk<S, FUSE, NG, RESOLVED, POL>::kCherryTables;   // (the launcher guarantees m.msched_r then)
   const ConstModel cm(m, kTables);
   constexpr int kSites = 16 * NG;      // sites per wave (NG site groups of 16; an S-vector is S / 4 * NG doubles per lane)
   // site of this lane inside the wave's block for per-site scalars and arrays: NG = 4: the lane itself; NG = 1: lanes
@@ -648,7 +695,7 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
   const int C = m.C, K = m.K;
   double Lsum = 0.0, prsum = 0.0, best = -1.0;
   int bestc = 0;
-  DevWalk<S, FUSE, NG, RESOLVED> be(os, cm);
+  DevWalk<S, FUSE, NG, RESOLVED, POL> be(os, cm);
   be.pi = m.pi;
   be.nmv = kTables ? m.nmv_r : m.nmv;
   be.wsM = wsM;
@@ -731,7 +778,7 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
       for (int q = 0; q < 4; ++q) {
         const double* pp = part + ((size_t)(c + q) * BK + r0) * kSites + sidx;
 #pragma unroll
-        for (int u = 0; u < RC; ++u) t[q][u] = pp[(size_t)(r0 + u < BK ? u : 0) * kSites];
+        for (int u = 0; u < RC; ++u) t[q][u] = state_load<POL::p_load>(pp + (size_t)(r0 + u < BK ? u : 0) * kSites);
       }
 #pragma unroll
       for (int u = 0; u < RC; ++u) v[u] = (((v[u] + t[0][u]) + t[1][u]) + t[2][u]) + t[3][u];
@@ -739,13 +786,13 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
     for (; c < C; ++c) {
       const double* pp = part + ((size_t)c * BK + r0) * kSites + sidx;
 #pragma unroll
-      for (int u = 0; u < RC; ++u) v[u] += pp[(size_t)(r0 + u < BK ? u : 0) * kSites];
+      for (int u = 0; u < RC; ++u) v[u] += state_load<POL::p_load>(pp + (size_t)(r0 + u < BK ? u : 0) * kSites);
     }
 #pragma unroll
     for (int u = 0; u < RC; ++u) {
       if (r0 + u < BK) {
         const double q = v[u] / Lsum;
-        cnt[(size_t)(r0 + u) * kSites + sidx] = q;
+        state_store<POL::t_store>(q, cnt + ((size_t)(r0 + u) * kSites + sidx));
         tot += q;
         if (++kk == K) {
           nrm = __builtin_fma(tot, tot, nrm);
@@ -775,9 +822,10 @@ static_assert(kWavesPerBlock * map_lds_fixed<20>(1, 4) <= 160 * 1024 / map_waves
 template <int S, int MODE, int FUSE, int NG = map_ng(S)>
 __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void map_kernel(const MapArgs a) {
   constexpr int VL = S / 4 * NG, kSites = 16 * NG;
+  using POL = StatePolicy<S, MODE, FUSE, NG>;
   const DevModel& m = a.m;
   // the null's alignments are fully resolved: class-fused nucleotide models walk them with the cherry tables' stream
-  constexpr bool kTables = (MODE == kModeNull || MODE == kModeNullPatterns) && DevWalk<S, FUSE, NG, true>::kCherryTables;
+  constexpr bool kTables = (MODE == kModeNull || MODE == kModeNullPatterns) && DevWalk<S, FUSE, NG, true, POL>::kCherryTables;
   const ConstModel cm(m, kTables);
   const int lane = threadIdx.x & (kWave - 1);
   const int sidx = NG == 4 ? lane : (lane & 15);   // site of this lane in the wave's block
@@ -814,12 +862,12 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
       const size_t s = site < a.nsites ? site : a.nsites - 1;
       double L, pr, nrm;
       int rc;
-      map_sites_wave<S, FUSE, NG, false>(a, wsD, wsU, a.split_part + sb * m.C * BK * kSites, nullptr, lds_off, a.aln + s, a.ld, lane, os, L, pr,
+      map_sites_wave<S, FUSE, NG, false, POL>(a, wsD, wsU, a.split_part + sb * m.C * BK * kSites, nullptr, lds_off, a.aln + s, a.ld, lane, os, L, pr,
                         rc, nrm, c, c + 1, (int)((task + nwaves) % m.C), false);
-      a.split_lc[task * kSites + sidx] = L;
-      a.split_lc[(ntasks + task) * kSites + sidx] = pr;
-      a.split_lc[(2 * ntasks + task) * kSites + sidx] = nrm;          // weight of the pass's best class
-      a.split_lc[(3 * ntasks + task) * kSites + sidx] = (double)rc;   // ... and its index
+      state_store<POL::split_store>(L, a.split_lc + (task * kSites + sidx));
+      state_store<POL::split_store>(pr, a.split_lc + ((ntasks + task) * kSites + sidx));
+      state_store<POL::split_store>(nrm, a.split_lc + ((2 * ntasks + task) * kSites + sidx));          // weight of the pass's best class
+      state_store<POL::split_store>((double)rc, a.split_lc + ((3 * ntasks + task) * kSites + sidx));   // ... and its index
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     return;
@@ -839,7 +887,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
       // tile sb of the pattern table is this wave's count block: the class-sum epilogue writes the final counts there,
       // once, with its own row stride (lanes past npat write their clamped copy into the last tile's spare columns)
       double* tile = a.counts + sb * ((size_t)m.B * m.K * kSites);
-      map_sites_wave<S, FUSE, NG, true>(a, wsD, wsU, part, tile, lds_off, a.supplied + rh * (size_t)m.T * a.rep_ram + j, a.rep_ram,
+      map_sites_wave<S, FUSE, NG, true, POL>(a, wsD, wsU, part, tile, lds_off, a.supplied + rh * (size_t)m.T * a.rep_ram + j, a.rep_ram,
                                         lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
       if (active) {
         a.post_rate[p] = pr;
@@ -857,14 +905,17 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
     if (MODE == kModeObserved) {
       double L, pr, nrm;
       int rc;
-      map_sites_wave<S, FUSE, NG, false>(a, wsD, wsU, part, cnt0, lds_off, a.aln + s, a.ld, lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
+      map_sites_wave<S, FUSE, NG, false, POL>(a, wsD, wsU, part, cnt0, lds_off, a.aln + s, a.ld, lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
       if (active) {
         if (a.logL) a.logL[s] = log(L);
         if (a.post_rate) a.post_rate[s] = pr;
         if (a.rate_class) a.rate_class[s] = rc;
         if (a.norm) a.norm[s] = nrm;
         if (a.counts)
-          for (int r = 0; r < m.B * m.K; ++r) a.counts[(size_t)r * a.ldc + s] = cnt0[(size_t)r * kSites + sidx];
+          for (int r = 0; r < m.B * m.K; ++r) {
+            const double q = state_load<POL::t_load>(&cnt0[(size_t)r * kSites + sidx]);
+            a.counts[(size_t)r * a.ldc + s] = q;
+          }
       }
     } else {
       // null pair q = s: replicate rep, column j; simulated-site index g_h = ((rep*2 + h)*rep_ram + j).
@@ -881,7 +932,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
         gstride = a.rep_ram;
         double L, pr, nrm;
         int rc;
-        map_sites_wave<S, FUSE, NG, true>(a, wsD, wsU, part, h ? cnt1 : cnt0, lds_off, gbase, gstride, lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
+        map_sites_wave<S, FUSE, NG, true, POL>(a, wsD, wsU, part, h ? cnt1 : cnt0, lds_off, gbase, gstride, lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
         if (h == 0) { prmin = pr; nmin = nrm; rcmin = rc; }
         else { prmin = pr < prmin ? pr : prmin; nmin = nrm < nmin ? nrm : nmin; rcmin = rc < rcmin ? rc : rcmin; }
       }
