@@ -1,11 +1,13 @@
 // C-ABI, mapping stage: substitution mapping of observed alignments and its variants, ancestral states, the simulators.
 #include "cmx_ctx.h"
 
-// nijt.average = no (cmx_set_mapping_options): counts and norms of the sites just mapped are replaced by those of
-// computeSubstitutionVectorsNoAveraging (cmx_variants.hip); likelihood, posterior rate and rate class stay.
-// full_grid names the caller as in map_sites_impl: the engine's own null / clustering / candidate pipelines (true) and the
-// public observed-alignment mapping (false) may run on two streams at once, so each has its own scratch -- the averaged
-// path keeps ws and ws_obs apart for the same reason.
+// What a mapping reads ([T][ld] codes; masks null: every code >= nstates is an unknown) and writes (counts [B*K][ldc], the rest
+// per site, each optional), as map_sites_impl is given it: the walk's MapArgs and the plain stage's PlainArgs are filled from these.
+struct MapIn { const uint8_t* aln; size_t nsites, ld; const uint32_t* masks; };
+struct MapOut { double* counts; size_t ldc; double *norm, *logL, *post_rate; int32_t* rate_class; };
+// pass budgets of the plain stage's per-node vectors (plain_sites_per_pass): the mapping fills its passes, ancestral states balance theirs
+constexpr size_t kPlainMapScratchBytes = (size_t)1 << 30, kAsrScratchBytes = (size_t)2 << 30;
+
 // S x S matrices padded with zeros to SP x SP (the plain path's kernels run at kPlainStates states)
 static std::vector<double> pad_mats(const std::vector<double>& m, int S, int SP) {
   if (S == SP) return m;
@@ -40,80 +42,67 @@ static cmx_status upload_variant_operators(cmx_ctx* ctx) {
 
 // the model and alignment fields of the plain kernels' arguments (operators uploaded); the caller sets the mode, the
 // outputs and the sites per pass
-static NoAvgArgs variant_args(cmx_ctx* ctx, const uint8_t* d_aln, size_t ld, const uint32_t* d_masks) {
+static PlainArgs plain_args(cmx_ctx* ctx, const MapIn& in) {
   const HostModel& h = ctx->hm;
-  NoAvgArgs a{};
+  PlainArgs a{};
   a.S = h.plain ? kPlainStates : h.S; a.Sreal = h.S; a.C = h.C; a.K = h.K; a.nn = h.nn; a.B = h.B; a.root = h.root;
   a.first_child = ctx->va_first; a.next_sib = ctx->va_next; a.taxon_of = ctx->dm.taxon_of; a.parent = ctx->dm.parent;
   a.P = ctx->va_P; a.N1 = ctx->va_N1; a.NC = ctx->va_NC; a.PN = ctx->va_PN; a.pi = h.plain ? ctx->va_pi : ctx->dm.pi; a.probs = ctx->dm.probs;
   a.rates = ctx->dm.rates;
-  a.masks = d_masks; a.aln = d_aln; a.ld = ld;
+  a.masks = in.masks; a.aln = in.aln; a.ld = in.ld;
   return a;
 }
 
-// plain: the caller is map_plain (alphabets other than 4 / 20 states): every mapping option, the default one included, and
-// the site scalars come from these kernels
-static cmx_status map_variant(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks,
-                              double* d_counts, size_t ldc, double* d_norm, void* stream, bool full_grid,
-                              double* d_logL = nullptr, double* d_post_rate = nullptr, int32_t* d_rate_class = nullptr) {
+// Does a mapping go through the plain stage (cmx_variants.hip)?  Other alphabets than 4 / 20 states: for any output.
+// 4 / 20 states: for the counts or the norms under a non-default option (cmx_set_mapping_options); the scalars stay the walk's.
+static bool plain_stage_wanted(const cmx_ctx* ctx, const MapOut& out) {
+  const bool counts = out.counts || out.norm;
+  if (ctx->hm.plain) return counts || out.logL || out.post_rate || out.rate_class;
+  return counts && !(ctx->map_average && ctx->map_joint);
+}
+
+// The plain stage of a mapping.  full_grid names the caller as in map_sites_impl: the engine's own null / clustering /
+// candidate pipelines (true) and the public observed-alignment mapping (false) may run on two streams at once, so each has
+// its own scratch -- the averaged path keeps ws and ws_obs apart for the same reason.
+static cmx_status map_plain(cmx_ctx* ctx, const MapIn& in, MapOut out, void* stream, bool full_grid) {
   const HostModel& h = ctx->hm;
-  const bool scalars = h.plain && (d_logL || d_post_rate || d_rate_class);
-  if (!h.plain && ((ctx->map_average && ctx->map_joint) || (!d_counts && !d_norm))) return CMX_OK;
-  if (h.plain && !d_counts && !d_norm && !scalars) return CMX_OK;
-  const int SD = h.plain ? kPlainStates : h.S;   // device states
   CMX_TRY(upload_variant_operators(ctx));
-  const bool want_counts = d_counts || d_norm;
-  if (!d_counts && want_counts) {   // only the norms were asked for: they still need the counts
-    CMX_TRY(scratch(ctx, full_grid ? "va_counts_null" : "va_counts_obs", (size_t)h.B * h.K * nsites, &d_counts));
-    ldc = nsites;
+  if (!out.counts && out.norm) {   // only the norms were asked for: they still need the counts
+    CMX_TRY(scratch(ctx, full_grid ? "va_counts_null" : "va_counts_obs", (size_t)h.B * h.K * in.nsites, &out.counts));
+    out.ldc = in.nsites;
   }
-  NoAvgArgs a = variant_args(ctx, d_aln, ld, d_masks);
-  a.mode = ctx->map_joint ? (ctx->map_average ? kVariantJoint : kVariantNoAvg) : (ctx->map_average ? kVariantMarginal : kVariantNoAvgMarginal);
-  a.logL = d_logL; a.post_rate = d_post_rate; a.rate_class = d_rate_class;
-  // sites per pass: per-node vectors of a pass stay under 1 GiB
-  const size_t per_site = sizeof(double) * noavg_scratch_doubles(SD, h.C, h.nn, 1);
-  a.chunk = std::max<size_t>(256, std::min<size_t>(nsites, ((size_t)1 << 30) / per_site / 256 * 256));
-  a.counts = d_counts; a.ldc = ldc;
+  PlainArgs a = plain_args(ctx, in);
+  using M = PlainMode;
+  a.mode = ctx->map_joint ? (ctx->map_average ? M::Joint : M::NoAvg) : (ctx->map_average ? M::Marginal : M::NoAvgMarginal);
+  if (h.plain) { a.logL = out.logL; a.post_rate = out.post_rate; a.rate_class = out.rate_class; }   // 4 / 20 states: the walk wrote them
+  a.chunk = plain_sites_per_pass(a.S, h.C, h.nn, in.nsites, kPlainMapScratchBytes, false);
+  a.counts = out.counts; a.ldc = out.ldc;
   double* buf;
-  CMX_TRY(scratch(ctx, full_grid ? "va_nodes_null" : "va_nodes_obs", noavg_scratch_doubles(SD, h.C, h.nn, a.chunk), &buf));
-  HIP_TRY(ctx, launch_map_noavg(a, nsites, buf, d_norm, (hipStream_t)stream));
+  CMX_TRY(scratch(ctx, full_grid ? "va_nodes_null" : "va_nodes_obs", plain_node_doubles(a.S, h.C, h.nn, a.chunk), &buf));
+  HIP_TRY(ctx, launch_plain_map(a, in.nsites, buf, out.norm, (hipStream_t)stream));
   return CMX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ mapping
-// full_grid: use the whole-chip workspace of the null launches instead of the quarter-chip slice reserved for
-// observed alignments (which exists so that a caller can overlap the observed mapping with cmx_null_intra_dev on a
-// second stream).  Only the engine's own simulate -> map pipelines (inter null, clustering null, candidate groups)
-// ask for it: they are blocking calls on the null stream and map hundreds of thousands of simulated sites.
-cmx_status map_sites_impl(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks, double* d_counts,
-                          size_t ldc, double* d_logL, double* d_post_rate, int32_t* d_rate_class, double* d_norm, void* stream,
-                          bool full_grid) {
-  CMX_TRY(need_model(ctx));
-  if (!d_aln || nsites == 0 || ld < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_map_sites: bad alignment arguments");
-  if (d_counts && ldc < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_map_sites: ldc < nsites");
-  if (d_counts && d_counts == ctx->gram_kept.counts) ctx->gram_kept.valid = false;   // the vectors the kept Gram blocks were made from are rewritten
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (ctx->hm.plain) {
-    // alphabets other than 4 / 20 states (codon models): likelihood, rates and every mapping option from the plain kernels.
-    // No mask table: every code >= nstates is an unknown.
-    if (d_masks) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_map_sites: no ambiguity table for alphabets other than 4 / 20 states (codes >= nstates are unknowns)");
-    return map_variant(ctx, d_aln, nsites, ld, d_masks, d_counts, ldc, d_norm, stream, full_grid, d_logL, d_post_rate, d_rate_class);
-  }
+// The matrix-core walk of a 4- or 20-state mapping (cmx_map.hip).  full_grid: use the whole-chip workspace of the null launches
+// instead of the quarter-chip slice reserved for observed alignments (which exists so that a caller can overlap the observed
+// mapping with cmx_null_intra_dev on a second stream).  Only the engine's own simulate -> map pipelines (inter null, clustering
+// null, candidate groups) ask for it: they are blocking calls on the null stream and map hundreds of thousands of simulated sites.
+static cmx_status map_walk(cmx_ctx* ctx, const MapIn& in, const MapOut& out, void* stream, bool full_grid) {
+  const size_t nsites = in.nsites;
   const int max_blocks = full_grid ? ctx->grid_blocks : ctx->obs_blocks;
   MapArgs a{};
-  a.m = ctx->dm; a.ws = full_grid ? ctx->ws : ctx->ws_obs;
-  a.aln = d_aln; a.ld = ld; a.nsites = nsites;
+  a.m = ctx->dm; a.ws = full_grid ? ctx->ws : ctx->ws_obs; a.aln = in.aln; a.ld = in.ld; a.nsites = nsites;
   // ambiguity ids S .. S+max_ambig(S)-1: rebuild the extra rows of the leaf operators when the table changes.
   // Not for the engine's own pipelines (full_grid): their simulated alignments are fully resolved and never read those
   // rows, and rebuilding them on the null's stream would race with an observed mapping of ambiguous codes that a caller
   // has in flight on a second stream.  leaf_rows_custom stays as it is, so the next public call without a table still
   // restores the default rows.
-  if (!full_grid && (d_masks || ctx->leaf_rows_custom)) {
-    HIP_TRY(ctx, launch_extend_leaf_rows(ctx->dm, d_masks, (hipStream_t)stream));
-    ctx->leaf_rows_custom = d_masks != nullptr;
+  if (!full_grid && (in.masks || ctx->leaf_rows_custom)) {
+    HIP_TRY(ctx, launch_extend_leaf_rows(ctx->dm, in.masks, (hipStream_t)stream));
+    ctx->leaf_rows_custom = in.masks != nullptr;
   }
-  a.counts = d_counts; a.ldc = ldc; a.logL = d_logL; a.post_rate = d_post_rate; a.rate_class = d_rate_class;
-  a.norm = d_norm;
+  a.counts = out.counts; a.ldc = out.ldc; a.logL = out.logL; a.post_rate = out.post_rate; a.rate_class = out.rate_class; a.norm = out.norm;
   size_t ks = (size_t)map_sites_per_wave(ctx->hm.dS);
   size_t nblocks = (nsites + ks - 1) / ks;
   const size_t obs_waves = (size_t)max_blocks * kWavesPerBlock;
@@ -134,12 +123,29 @@ cmx_status map_sites_impl(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, siz
     const int grid = (int)((ntasks + kWavesPerBlock - 1) / kWavesPerBlock);
     HIP_TRY(ctx, launch_map(a, kModeObservedSplit, grid, (hipStream_t)stream));
     HIP_TRY(ctx, launch_map_finalize(a, (hipStream_t)stream));
-    return map_variant(ctx, d_aln, nsites, ld, d_masks, d_counts, ldc, d_norm, stream, full_grid);
+    return CMX_OK;
   }
   const size_t blocks_needed = (nblocks + kWavesPerBlock - 1) / kWavesPerBlock;
   const int grid = (int)std::min<size_t>(blocks_needed, (size_t)max_blocks);
   HIP_TRY(ctx, launch_map(a, kModeObserved, grid, (hipStream_t)stream));
-  return map_variant(ctx, d_aln, nsites, ld, d_masks, d_counts, ldc, d_norm, stream, full_grid);
+  return CMX_OK;
+}
+
+// a mapping: the walk at 4 / 20 states, then (or instead) the plain stage where it is wanted
+cmx_status map_sites_impl(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks, double* d_counts,
+                          size_t ldc, double* d_logL, double* d_post_rate, int32_t* d_rate_class, double* d_norm, void* stream,
+                          bool full_grid) {
+  CMX_TRY(need_model(ctx));
+  if (!d_aln || nsites == 0 || ld < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_map_sites: bad alignment arguments");
+  if (d_counts && ldc < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_map_sites: ldc < nsites");
+  if (d_counts && d_counts == ctx->gram_kept.counts) ctx->gram_kept.valid = false;   // the vectors the kept Gram blocks were made from are rewritten
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (ctx->hm.plain && d_masks)   // (codon models)
+    return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_map_sites: no ambiguity table for alphabets other than 4 / 20 states (codes >= nstates are unknowns)");
+  const MapIn in{d_aln, nsites, ld, d_masks};
+  const MapOut out{d_counts, ldc, d_norm, d_logL, d_post_rate, d_rate_class};
+  if (!ctx->hm.plain) CMX_TRY(map_walk(ctx, in, out, stream, full_grid));
+  return plain_stage_wanted(ctx, out) ? map_plain(ctx, in, out, stream, full_grid) : CMX_OK;
 }
 
 cmx_status cmx_map_sites_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks,
@@ -220,8 +226,16 @@ cmx_status cmx_map_sites(cmx_ctx* ctx, const uint8_t* aln, size_t nsites, size_t
 // ancestral_kernel (cmx_variants.hip).  Scratch of its own ("asr_nodes", not the mapping's "va_nodes_*"), so it may run on
 // a stream beside a mapping or a null; it reads the caller's mask table directly and leaves the leaf operators' ambiguity
 // rows and the kept Gram blocks alone.  Sites per pass: the four per-node vectors of a pass stay under kAsrScratchBytes,
-// the passes balanced and rounded up to whole workgroups.
-constexpr size_t kAsrScratchBytes = (size_t)2 << 30;
+// the passes balanced and rounded up to whole workgroups.  need_inner_nodes: the rows of the result, uploaded at the first use.
+static cmx_status need_inner_nodes(cmx_ctx* ctx) {
+  if (ctx->asr_inner) return CMX_OK;
+  std::vector<int> inner;
+  for (int n = 0; n < ctx->hm.nn; ++n)
+    if (ctx->hm.first_child[n] >= 0) inner.push_back(n);
+  CMX_TRY(upload(ctx, inner, &ctx->asr_inner));
+  ctx->asr_n_inner = (int)inner.size();
+  return CMX_OK;
+}
 
 cmx_status cmx_ancestral_states_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks,
                                     uint8_t* d_states, size_t lds, double* d_post, size_t ldp, void* stream) {
@@ -235,20 +249,11 @@ cmx_status cmx_ancestral_states_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t n
   if (d_post && ldp < nsites) return fail(ctx, CMX_ERR_INVALID, "cmx_ancestral_states: ldp < nsites");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   CMX_TRY(upload_variant_operators(ctx));
-  if (!ctx->asr_inner) {
-    std::vector<int> inner;
-    for (int n = 0; n < h.nn; ++n)
-      if (h.first_child[n] >= 0) inner.push_back(n);
-    CMX_TRY(upload(ctx, inner, &ctx->asr_inner));
-    ctx->asr_n_inner = (int)inner.size();
-  }
-  NoAvgArgs a = variant_args(ctx, d_aln, ld, d_masks);
-  const size_t per_site = sizeof(double) * noavg_scratch_doubles(a.S, h.C, h.nn, 1);
-  const size_t max_chunk = std::max<size_t>(256, kAsrScratchBytes / per_site / 256 * 256);
-  const size_t passes = (nsites + max_chunk - 1) / max_chunk;
-  a.chunk = std::min(nsites, ((nsites + passes - 1) / passes + 255) / 256 * 256);
+  CMX_TRY(need_inner_nodes(ctx));
+  PlainArgs a = plain_args(ctx, MapIn{d_aln, nsites, ld, d_masks});
+  a.chunk = plain_sites_per_pass(a.S, h.C, h.nn, nsites, kAsrScratchBytes, true);
   double* buf;
-  CMX_TRY(scratch(ctx, "asr_nodes", noavg_scratch_doubles(a.S, h.C, h.nn, a.chunk), &buf));
+  CMX_TRY(scratch(ctx, "asr_nodes", plain_node_doubles(a.S, h.C, h.nn, a.chunk), &buf));
   HIP_TRY(ctx, launch_ancestral(a, nsites, buf, ctx->asr_inner, ctx->asr_n_inner, d_states, lds, d_post, ldp, (hipStream_t)stream));
   return CMX_OK;
 }
@@ -265,8 +270,8 @@ cmx_status cmx_ancestral_states(cmx_ctx* ctx, const uint8_t* aln, size_t nsites,
   uint8_t* d_states = nullptr;
   double* d_post = nullptr;
   CMX_TRY(upload_host_alignment(ctx, tmp, aln, nsites, ld, masks, nmasks, &d_aln, &d_masks));
-  int n_inner = 0;
-  for (int n = 0; n < h.nn; ++n) n_inner += h.first_child[n] >= 0;
+  CMX_TRY(need_inner_nodes(ctx));
+  const int n_inner = ctx->asr_n_inner;
   CMX_TRY(tmp.alloc(ctx, &d_states, (size_t)n_inner * nsites));
   if (post) CMX_TRY(tmp.alloc(ctx, &d_post, (size_t)n_inner * h.S * nsites));
   CMX_TRY(cmx_ancestral_states_dev(ctx, d_aln, nsites, nsites, d_masks, d_states, nsites, d_post, nsites, nullptr));

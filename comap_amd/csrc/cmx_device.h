@@ -204,35 +204,44 @@ hipError_t launch_mi_pairs_block(int B, const PairOperand& a, const PairOperand&
 hipError_t launch_mi_pairs_diag(int B, const PairOperand& a, const PairOperand& b, size_t n, double* d_out, hipStream_t stream);
 hipError_t launch_mi_group(int B, const PairOperand& g, const int64_t* d_offsets, const int32_t* d_sites, size_t ngroups,
                            double* d_out, hipStream_t stream);
-// (cmx_variants.hip) nijt.average = no: the no-averaging mapping as plain kernels over a global scratch
-// mode: which LegacySubstitutionMappingTools function (CoETools.cpp:395-405)
-// kVariantJoint: the default mapping (computeSubstitutionVectors: averaged, joint) for the alphabets the matrix-core walk
-// does not serve
-enum { kVariantNoAvg = 0 /* NoAveraging */, kVariantMarginal = 1 /* Marginal */, kVariantNoAvgMarginal = 2 /* NoAveragingMarginal */,
-       kVariantJoint = 3 };
-struct NoAvgArgs {
-  int S, C, K, nn, B, root, mode;
+// (cmx_variants.hip) the plain kernels: one thread per (site, class), (site, branch) or (site, internal node) over per-node
+// vectors in a global scratch.  Four uses: nijt.average = no; nijt.joint = no (the two marginal mappings); the default
+// mapping, likelihood and site scalars of the alphabets the matrix-core walk does not serve (states padded to
+// kPlainStates); marginal ancestral states.
+// PlainMode: which LegacySubstitutionMappingTools function (CoETools.cpp:395-405); Joint is the default mapping
+// (computeSubstitutionVectors: averaged, joint), built for kPlainStates only
+enum class PlainMode : int { NoAvg = 0 /* NoAveraging */, Marginal = 1, NoAvgMarginal = 2 /* NoAveragingMarginal */, Joint = 3 };
+struct PlainArgs {
+  int S, C, K, nn, B, root;
+  PlainMode mode;
   int Sreal;              // states of the alphabet; < S on the plain path, whose operators are padded with zeros to S = 64
-  const double* PN;       // [C][B][K][S*S] joint counts P o N^k (kVariantJoint)
+  const double* PN;       // [C][B][K][S*S] joint counts P o N^k (PlainMode::Joint)
   const double* rates;    // [C] (site scalars)
   double *logL, *post_rate;   // [ld...] per site, optional: likelihood, posterior rate, rate class (plain path)
   int32_t* rate_class;
   const int *first_child, *next_sib, *taxon_of, *parent;
   const double* P;        // [C][B][S*S] row-major transition matrices
   const double* N1;       // [B][K][S*S] conditional counts at the branch length itself
-  const double* NC;       // [C][B][K][S*S] conditional counts at r_c t_b (kVariantMarginal)
+  const double* NC;       // [C][B][K][S*S] conditional counts at r_c t_b (PlainMode::Marginal)
   const double *pi, *probs;
   const uint32_t* masks;  // compatibility masks of the codes >= S (NULL: every state)
   const uint8_t* aln;
-  size_t ld, site0, nsites, chunk;
-  double *D, *M, *U, *Up;  // [C][nn][S][chunk]
+  size_t ld, site0, nsites, chunk;   // chunk: sites per pass (plain_sites_per_pass)
+  double *D, *M, *U, *Up;  // [C][nn][S][chunk], carved from the scratch by the launchers
   double* counts;          // [B*K][ldc]
   size_t ldc;
 };
-size_t noavg_scratch_doubles(int S, int C, int nn, size_t chunk);
-hipError_t launch_map_noavg(NoAvgArgs a, size_t nsites_total, double* scratch, double* d_norm, hipStream_t stream);
+static_assert(sizeof(PlainArgs) == 240 && offsetof(PlainArgs, mode) == 24 && offsetof(PlainArgs, counts) == 224,
+              "kernel-argument layout of the plain kernels");
+// doubles of the four per-node vectors of `chunk` sites, and the sites of a pass that keeps them under budget_bytes: whole
+// workgroups of 256 sites, at least one.  balanced: passes of equal size rounded up to 256 (ancestral states); otherwise full
+// passes and a remainder (the mapping)
+size_t plain_node_doubles(int S, int C, int nn, size_t chunk);
+size_t plain_sites_per_pass(int S, int C, int nn, size_t nsites, size_t budget_bytes, bool balanced);
+// scratch: plain_node_doubles(a.S, a.C, a.nn, a.chunk) doubles; d_norm (or null) over all nsites_total sites after the last pass
+hipError_t launch_plain_map(PlainArgs a, size_t nsites_total, double* scratch, double* d_norm, hipStream_t stream);
 // asr.method = marginal (cmx_ancestral_states*): states [n_inner][lds], optional posterior [n_inner][Sreal][ldp]
-hipError_t launch_ancestral(NoAvgArgs a, size_t nsites_total, double* scratch, const int* d_inner, int n_inner, uint8_t* d_states,
+hipError_t launch_ancestral(PlainArgs a, size_t nsites_total, double* scratch, const int* d_inner, int n_inner, uint8_t* d_states,
                             size_t lds, double* d_post, size_t ldp, hipStream_t stream);
 // (cmx_mica_post.hip) Mica post-processing
 hipError_t launch_mica_average(const double* d_mi, size_t n, size_t ld, double* d_avg, double* d_full, hipStream_t stream);
