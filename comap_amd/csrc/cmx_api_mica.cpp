@@ -36,14 +36,34 @@ static cmx_status mica_side_scratch(cmx_ctx* ctx, MicaPath path, int Tp, int k, 
   return scratch(ctx, ("mica_Ss" + t).c_str(), n, &s->Ss);
 }
 
+// Alphabets other than 4 / 20 states (2 .. 64, cmx_mica_wide.hip): every code >= nalpha is an unknown, a mask table is refused
+static bool mica_wide(int nalpha) { return nalpha != 4 && nalpha != 20; }
+static cmx_status mica_alphabet(cmx_ctx* ctx, const char* who, int nalpha, const void* masks) {
+  if (nalpha < 2 || nalpha > 64) return fail(ctx, CMX_ERR_INVALID, std::string(who) + ": 2 <= alphabet size <= 64");
+  if (mica_wide(nalpha) && masks)
+    return fail(ctx, CMX_ERR_UNSUPPORTED, std::string(who) + ": no ambiguity table for alphabets other than 4 / 20 states (codes >= nstates are unknowns)");
+  return CMX_OK;
+}
+// their scratch, under names of its own: the symbol bytes and column sums of the matrix-core kernel, the counts of both kernels
+static cmx_status mica_wide_side_scratch(cmx_ctx* ctx, MicaPath path, int nalpha, int Tp, int k, MicaSide* s) {
+  const std::string t = std::to_string(k);
+  const size_t n = s->n;
+  CMX_TRY(scratch(ctx, ("micaw_cnt" + t).c_str(), n * (size_t)nalpha, &s->cnt));
+  CMX_TRY(scratch(ctx, ("micaw_unk" + t).c_str(), n, &s->unk));
+  if (path != kMicaWide) return CMX_OK;
+  CMX_TRY(scratch(ctx, ("micaw_C" + t).c_str(), n * (size_t)Tp, &s->C));
+  CMX_TRY(scratch(ctx, ("micaw_g" + t).c_str(), n, &s->gap));
+  return scratch(ctx, ("micaw_S" + t).c_str(), n, &s->S);
+}
+
 cmx_status cmx_mi_columns_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* d_masks, const uint8_t* d_aln1,
                               size_t n1, size_t ld1, const uint8_t* d_aln2, size_t n2, size_t ld2, double* d_mi,
                               double* d_hjoint, size_t ldo, double* d_h1, double* d_h2, void* stream) {
   if (!ctx) return CMX_ERR_INVALID;
-  if (nalpha != 4 && nalpha != 20) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mi_columns: alphabet size must be 4 or 20");
+  CMX_TRY(mica_alphabet(ctx, "cmx_mi_columns", nalpha, d_masks));
   const bool intra = d_aln2 == nullptr;
   if (intra) { d_aln2 = d_aln1; n2 = n1; ld2 = ld1; }
-  CMX_TRY(default_mi_masks(ctx, nalpha, &d_masks));
+  if (!mica_wide(nalpha)) CMX_TRY(default_mi_masks(ctx, nalpha, &d_masks));
   if (!d_aln1 || !d_mi || !d_hjoint || ntaxa < 1 || n1 == 0 || n2 == 0 || ld1 < n1 || ld2 < n2 || ldo < n2)
     return fail(ctx, CMX_ERR_INVALID, "cmx_mi_columns: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -52,7 +72,14 @@ cmx_status cmx_mi_columns_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_
   MicaWork w{{{n1}, {n2}}};   // the column counts; every pointer null
   w.Tp = mica_padded_taxa(ntaxa);
   const MicaPath path = mica_path(nalpha, ntaxa, n1, n2);
-  if (path != kMicaTables && path != kMicaRefused) {
+  if (mica_wide(nalpha) && path == kMicaRefused)
+    return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mi_columns: more column tiles than one launch of the matrix-core kernel takes (2^31 - 1); split the call");
+  if (path == kMicaWide || path == kMicaWidePlain) {
+    CMX_TRY(mica_wide_side_scratch(ctx, path, nalpha, w.Tp, 1, &w.s[0]));
+    if (intra) w.s[1] = w.s[0];
+    else CMX_TRY(mica_wide_side_scratch(ctx, path, nalpha, w.Tp, 2, &w.s[1]));
+    if (path == kMicaWide) CMX_TRY(scratch(ctx, "micaw_ftab", micaw_ftab_entries(nalpha, ntaxa), &w.ftab));
+  } else if (path != kMicaTables && path != kMicaRefused) {
     CMX_TRY(mica_side_scratch(ctx, path, w.Tp, 1, &w.s[0]));
     if (intra) w.s[1] = w.s[0];
     else CMX_TRY(mica_side_scratch(ctx, path, w.Tp, 2, &w.s[1]));
@@ -68,14 +95,15 @@ cmx_status cmx_mi_columns_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_
 cmx_status cmx_mi_columns(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* masks, size_t nmasks, const uint8_t* aln1,
                           size_t n1, const uint8_t* aln2, size_t n2, double* mi, double* hjoint, double* h1, double* h2) {
   if (!ctx) return CMX_ERR_INVALID;
-  if (!aln1 || !mi || !hjoint || n1 == 0 || ntaxa < 1 || nalpha < 2 || nalpha > 31) return fail(ctx, CMX_ERR_INVALID, "cmx_mi_columns: bad arguments");
+  if (!aln1 || !mi || !hjoint || n1 == 0 || ntaxa < 1 || nalpha < 2 || nalpha > 64) return fail(ctx, CMX_ERR_INVALID, "cmx_mi_columns: bad arguments");
+  CMX_TRY(mica_alphabet(ctx, "cmx_mi_columns", nalpha, masks));
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!aln2) n2 = n1;
   TmpDev tmp;
-  uint32_t* d_masks;
+  uint32_t* d_masks = nullptr;
   uint8_t *d1, *d2 = nullptr;
   double *d_mi, *d_hj, *d_h1, *d_h2 = nullptr;
-  CMX_TRY(tmp.upload(ctx, &d_masks, mi_mask_table(nalpha, masks, nmasks).data(), 256));
+  if (!mica_wide(nalpha)) CMX_TRY(tmp.upload(ctx, &d_masks, mi_mask_table(nalpha, masks, nmasks).data(), 256));
   CMX_TRY(tmp.upload(ctx, &d1, aln1, (size_t)ntaxa * n1));
   if (aln2) {
     CMX_TRY(tmp.upload(ctx, &d2, aln2, (size_t)ntaxa * n2));
@@ -98,12 +126,12 @@ cmx_status cmx_mi_pairs_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t*
                             const uint8_t* d_aln2, size_t n2, size_t ld2, const int64_t* d_idx1, const int64_t* d_idx2, size_t npairs,
                             double* d_mi, double* d_hjoint, void* stream) {
   if (!ctx) return CMX_ERR_INVALID;
-  if (nalpha != 4 && nalpha != 20) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mi_pairs: alphabet size must be 4 or 20");
+  CMX_TRY(mica_alphabet(ctx, "cmx_mi_pairs", nalpha, d_masks));
   if (!d_aln2) { d_aln2 = d_aln1; n2 = n1; ld2 = ld1; }
   if (!d_aln1 || !d_idx1 || !d_idx2 || !d_mi || !d_hjoint || n1 == 0 || n2 == 0 || ld1 < n1 || ld2 < n2 || ntaxa < 1 || npairs == 0)
     return fail(ctx, CMX_ERR_INVALID, "cmx_mi_pairs: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  CMX_TRY(default_mi_masks(ctx, nalpha, &d_masks));
+  if (!mica_wide(nalpha)) CMX_TRY(default_mi_masks(ctx, nalpha, &d_masks));
   HIP_TRY(ctx, launch_mi_pairs(nalpha, ntaxa, d_masks, d_aln1, ld1, d_aln2, ld2, d_idx1, d_idx2, npairs, d_mi, d_hjoint, (hipStream_t)stream));
   return CMX_OK;
 }
@@ -112,7 +140,7 @@ cmx_status cmx_mi_pairs(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* mas
                         size_t n1, const uint8_t* aln2, size_t n2, const int64_t* idx1, const int64_t* idx2, size_t npairs,
                         double* mi, double* hjoint) {
   if (!ctx) return CMX_ERR_INVALID;
-  if (nalpha != 4 && nalpha != 20) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mi_pairs: alphabet size must be 4 or 20");
+  CMX_TRY(mica_alphabet(ctx, "cmx_mi_pairs", nalpha, masks));
   if (!aln1 || !idx1 || !idx2 || !mi || !hjoint || n1 == 0 || ntaxa < 1 || npairs == 0)
     return fail(ctx, CMX_ERR_INVALID, "cmx_mi_pairs: bad arguments");
   if (!aln2) n2 = n1;
@@ -121,11 +149,11 @@ cmx_status cmx_mi_pairs(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* mas
       return fail(ctx, CMX_ERR_INVALID, "cmx_mi_pairs: column index out of range");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   TmpDev tmp;
-  uint32_t* d_masks;
+  uint32_t* d_masks = nullptr;
   uint8_t *d1, *d2 = nullptr;
   int64_t *di1, *di2;
   double *d_mi, *d_hj;
-  CMX_TRY(tmp.upload(ctx, &d_masks, mi_mask_table(nalpha, masks, nmasks).data(), 256));
+  if (!mica_wide(nalpha)) CMX_TRY(tmp.upload(ctx, &d_masks, mi_mask_table(nalpha, masks, nmasks).data(), 256));
   CMX_TRY(tmp.upload(ctx, &d1, aln1, (size_t)ntaxa * n1));
   if (aln2) CMX_TRY(tmp.upload(ctx, &d2, aln2, (size_t)ntaxa * n2));
   CMX_TRY(tmp.upload(ctx, &di1, idx1, npairs));
@@ -213,6 +241,8 @@ cmx_status cmx_mica_parametric_null(cmx_ctx* ctx, int nalpha, uint64_t seed, siz
   }
   return CMX_OK;
 }
+
+int cmx_debug_mica_wide_plain(int on) { return mica_wide_plain(on); }
 
 // ------------------------------------------------------------------------------------------------ Mica post-processing
 cmx_status cmx_mica_average_mi_dev(cmx_ctx* ctx, const double* d_mi, size_t n, size_t ldo, double* d_average,

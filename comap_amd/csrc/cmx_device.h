@@ -346,7 +346,9 @@ hipError_t launch_mi_pairs(int A, int T, const uint32_t* d_masks, const uint8_t*
 // or the eight-wave protein kernel, the four-wave or the one-column-per-tile nucleotide kernel; or none (hipErrorInvalidValue):
 // cmx_mi_columns_dev requests scratch from it, launch_mi_columns dispatches on it.  Every size the host shares with a Mica
 // kernel is a function beside that kernel (mica_ftab_entries, mica4_info_words, mica4_image_bytes, the *_lds_bytes).
-enum MicaPath { kMicaTables, kMicaProtein4, kMicaProtein8, kMicaDna4, kMicaDna1, kMicaRefused };
+// Alphabets other than 4 / 20 states (cmx_mica_wide.hip): the matrix-core kernel of that file, or its plain kernel alone (above
+// 2 047 taxa, or under cmx_debug_mica_wide_plain).
+enum MicaPath { kMicaTables, kMicaProtein4, kMicaProtein8, kMicaDna4, kMicaDna1, kMicaWide, kMicaWidePlain, kMicaRefused };
 MicaPath mica_path(int A, int T, size_t n1, size_t n2);
 constexpr int mica_padded_taxa(int T) { return (T + 31) / 32 * 32; }   // whole MFMA steps of 32 taxa
 constexpr int kMicaLdsF2 = 4096;   // entries of f2 the weighted four-wave kernel keeps in LDS (m < 4096: cells of up to ten taxa)
@@ -355,7 +357,7 @@ constexpr int kMicaCodePad = 64;   // columns of "no row" symbols behind the las
 struct MicaSide {
   size_t n;          // columns
   int8_t* H;         // [n][32][Tp] one-hot int8 (kMicaDna1)
-  uint8_t* C;        // [n + kMicaCodePad][Tp] one-hot row of each taxon (state, A = unknown, 63 = none)
+  uint8_t* C;        // [n + kMicaCodePad][Tp] one-hot row of each taxon (state, A = unknown, 63 = none); kMicaWide: [n][Tp], state or 255 = none
   uint8_t* flag;     // [n] column has ambiguous symbols other than "unknown" (-> LDS-table kernel)
   uint8_t* gap;      // [n] column has unknowns (gap / X / N: compatible with every state; handled on the matrix cores)
   double* S;         // [n] sum_a f(count_a)
@@ -363,6 +365,8 @@ struct MicaSide {
   unsigned* order;   // [n] original column of a sorted position (columns without unknowns first, stable)
   uint8_t* Cs;       // [n + kMicaCodePad][Tp] symbol bytes in sorted order
   double* Ss;        // [n] column sums in sorted order
+  int* cnt;          // [n][A] integer state counts (kMicaWide, kMicaWidePlain, as the next)
+  int* unk;          // [n] unknowns of the column
 };
 struct MicaWork {
   MicaSide s[2];     // the two alignments (n always set, the rest as mica_path(A, T, s[0].n, s[1].n) needs it); intra layout: s[1] == s[0]
@@ -381,6 +385,16 @@ hipError_t mica_allow_lds(K* kernel, size_t bytes) {
 hipError_t launch_mi_columns(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t ld1, const uint8_t* d_aln2,
                              size_t ld2, int intra, double* d_mi, double* d_hj, size_t ldo, double* d_h1, double* d_h2,
                              const MicaWork& work, hipStream_t stream);
+// (cmx_mica_wide.hip) alphabets other than 4 / 20 states, up to 64: codes >= A are unknowns, there is no mask table
+int mica_wide_plain(int on);                          // cmx_debug_mica_wide_plain: set (on >= 0) / query, returns the previous state
+size_t micaw_ftab_entries(int A, int T);               // doubles of its two tables (micaw_ftable_kernel)
+size_t micaw_tiles(int A, size_t n1, size_t n2);      // workgroups of the matrix-core kernel (a 32-bit grid)
+hipError_t launch_mi_pairs_wide(int A, int T, const uint8_t* d_aln1, size_t ld1, const uint8_t* d_aln2, size_t ld2,
+                                const int64_t* d_idx1, const int64_t* d_idx2, size_t npairs, double* d_mi, double* d_hj,
+                                hipStream_t stream);
+hipError_t launch_mi_columns_wide(int A, int T, const uint8_t* d_aln1, size_t ld1, const uint8_t* d_aln2, size_t ld2, int intra,
+                                  double* d_mi, double* d_hj, size_t ldo, double* d_h1, double* d_h2, const MicaWork& work,
+                                  hipStream_t stream);
 // (cmx_mica4.hip) the four-wave kernels (unknowns included; partial ambiguity codes are not served): proteins, nucleotides
 size_t mica4_info_words(size_t n);
 size_t mica4_image_bytes(int Tp, size_t n2);

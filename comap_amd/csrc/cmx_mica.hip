@@ -149,7 +149,7 @@ __global__ __launch_bounds__(64) void mi_pairs_kernel(int T, const uint32_t* __r
 hipError_t launch_mi_pairs(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t ld1, const uint8_t* d_aln2,
                            size_t ld2, const int64_t* d_idx1, const int64_t* d_idx2, size_t npairs, double* d_mi,
                            double* d_hj, hipStream_t stream) {
-  if (A != 20 && A != 4) return hipErrorInvalidValue;
+  if (A != 20 && A != 4) return launch_mi_pairs_wide(A, T, d_aln1, ld1, d_aln2, ld2, d_idx1, d_idx2, npairs, d_mi, d_hj, stream);
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)((npairs + 15) / 16)), dim3(64), sizeof(double) * A * A * 16, stream, T, d_masks, d_aln1, ld1,
                        d_aln2, ld2, d_idx1, d_idx2, npairs, d_mi, d_hj);
@@ -760,7 +760,13 @@ __global__ __launch_bounds__(64) void column_entropy_kernel(int T, const uint32_
 // taxa of operands in registers and addresses the symbol arrays and one operand image with 31-bit byte offsets; the
 // eight-wave kernel takes the rest.  Nucleotides: the four-wave kernel up to eight k-steps = 256 taxa (its whole weighted
 // table in LDS), the same 31-bit offsets -- past them nothing serves the call; the one-column-per-tile kernel above 256 taxa.
+// Other alphabets (cmx_mica_wide.hip): the matrix-core kernel up to 2 047 taxa unless the debug switch asks for the plain one; its
+// grid is one 32-bit dimension.
 MicaPath mica_path(int A, int T, size_t n1, size_t n2) {
+  if (A != 4 && A != 20) {
+    if (T > 2047 || mica_wide_plain(-1)) return kMicaWidePlain;
+    return micaw_tiles(A, n1, n2) <= 0x7fffffffull ? kMicaWide : kMicaRefused;
+  }
   if (T > 2047) return kMicaTables;
   const int Tp = mica_padded_taxa(T);
   const bool off31 = (std::max(n1, n2) + kMicaCodePad) * (size_t)Tp < 0x7fffffffull;
@@ -772,7 +778,8 @@ MicaPath mica_path(int A, int T, size_t n1, size_t n2) {
 hipError_t launch_mi_columns(int A, int T, const uint32_t* d_masks, const uint8_t* d_aln1, size_t ld1, const uint8_t* d_aln2,
                              size_t ld2, int intra, double* d_mi, double* d_hj, size_t ldo, double* d_h1, double* d_h2,
                              const MicaWork& work, hipStream_t stream) {
-  if (A != 20 && A != 4) return hipErrorInvalidValue;
+  if (A != 20 && A != 4)
+    return launch_mi_columns_wide(A, T, d_aln1, ld1, d_aln2, ld2, intra, d_mi, d_hj, ldo, d_h1, d_h2, work, stream);
   const MicaSide &s1 = work.s[0], &s2 = work.s[1];
   const size_t n1 = s1.n, n2 = s2.n;
   const int Tp = work.Tp;
@@ -796,7 +803,7 @@ hipError_t launch_mi_columns(int A, int T, const uint32_t* d_masks, const uint8_
   hipError_t e = hipSuccess;
   switch (path) {
     case kMicaTables: break;
-    case kMicaRefused: return hipErrorInvalidValue;
+    case kMicaWide: case kMicaWidePlain: case kMicaRefused: return hipErrorInvalidValue;
     case kMicaProtein4: e = launch_mica4(T, work, intra, d_mi, d_hj, ldo, stream); break;
     case kMicaDna4: e = launch_mica_dna4(T, work, intra, d_mi, d_hj, ldo, stream); break;
     case kMicaProtein8: {

@@ -417,10 +417,12 @@ cmx_status cmx_inter_rows(cmx_ctx* ctx, int kind, const double* params, const do
 
 /* ---- Mica: mutual information between alignment columns over taxa (Mica.cpp:93-95, 349-361, 646-660).
  * aln2 == NULL: intra (filled for j > i, NaN elsewhere).  Outputs dense [n1][n2] (mi, hjoint) and per-column entropies;
- * nalpha = alphabet size.  Alignment codes >= nalpha index `masks` (bit a set = compatible with state a; masks == NULL:
- * every such code is an unknown): SiteTools::*(.., resolveUnknowns = true) spreads such a symbol evenly over its
- * compatible states.  Unknowns (gap, X, N: all states) cost nothing extra; a column with a partial ambiguity code sends
- * its pairs through a slower kernel. */
+ * nalpha = alphabet size, 2 .. 64 (anything else: CMX_ERR_INVALID).  With 4 or 20 states, alignment codes >= nalpha index
+ * `masks` (bit a set = compatible with state a; masks == NULL: every such code is an unknown): SiteTools::*(..,
+ * resolveUnknowns = true) spreads such a symbol evenly over its compatible states.  Unknowns (gap, X, N: all states) cost
+ * nothing extra; a column with a partial ambiguity code sends its pairs through a slower kernel.  Every other alphabet
+ * (codon models) has no ambiguity table: a code < nalpha is that state (63 included), every code >= nalpha is an unknown
+ * (1/nalpha per state), and a non-NULL masks / d_masks is refused with CMX_ERR_UNSUPPORTED.  Same outputs and conventions. */
 cmx_status cmx_mi_columns(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* masks, size_t nmasks,
                           const uint8_t* aln1, size_t n1, const uint8_t* aln2, size_t n2, double* mi,
                           double* hjoint, double* h1, double* h2);
@@ -437,6 +439,11 @@ cmx_status cmx_mi_pairs(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* mas
 cmx_status cmx_mi_pairs_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* d_masks, const uint8_t* d_aln1, size_t n1, size_t ld1,
                             const uint8_t* d_aln2, size_t n2, size_t ld2, const int64_t* d_idx1, const int64_t* d_idx2, size_t npairs,
                             double* d_mi, double* d_hjoint, void* stream);
+/* Alphabets other than 4 / 20 states: cmx_mi_columns(_dev) runs a matrix-core kernel up to 2 047 taxa and a plain kernel (one
+ * wave per pair, an integer table in LDS; also what cmx_mi_pairs runs) above.  cmx_debug_mica_wide_plain(1) makes the column
+ * stage run the plain kernel at every size (A/B runs, a cross-check for tests); 0 restores; on < 0: query only.  Returns the
+ * previous state.  Process-wide, host only. */
+int cmx_debug_mica_wide_plain(int on);
 
 /* Mica's bootstrap nulls.
  * cmx_mica_bootstrap_indices (host-side only, no GPU): the site indices of null.method = nonparametric-bootstrap

@@ -906,7 +906,9 @@ class ClusterTools {
 // CoMap/Mica.cpp on top of the C-ABI: all-pairs MI / joint entropy / entropies (one-hot Gram on the matrix cores),
 // averageMI -> APC / RCW (:346-363, :656-657), the four null methods (:399-632) and the p-value rule of :671-683.
 // The alignment is [taxon][site] state codes; codes >= alphabetSize index `masks` (bit a = compatible with state a),
-// as SiteTools::*(.., resolveUnknowns = true) resolves them.  An Engine WITH a model is Mica's `use_model` case: the
+// as SiteTools::*(.., resolveUnknowns = true) resolves them.  alphabetSize: 2 .. 64; other than 4 / 20 states (codon
+// alphabets) `masks` must be null -- every code >= alphabetSize is an unknown -- and nullMethod "permutations" is refused.
+// An Engine WITH a model is Mica's `use_model` case: the
 // parametric bootstrap needs it, and norms (from CoETools::getVectors on the same engine) then bin the p-values
 // (:383-386) and add the Nmin column.
 class Mica {
