@@ -82,6 +82,7 @@ cmx_status scratch(cmx_ctx* ctx, const char* name, size_t bytes, void** out) {
       HIP_TRY(ctx, hipMalloc(&b.p, (bytes ? bytes : 16) + kGuardBytes));
       b.bytes = bytes;
       b.guarded = true;
+      ++b.allocs;
     }
     b.logical = logical;
     HIP_TRY(ctx, guard_arm(b.p, b.logical));
@@ -95,6 +96,7 @@ cmx_status scratch(cmx_ctx* ctx, const char* name, size_t bytes, void** out) {
     HIP_TRY(ctx, hipMalloc(&b.p, bytes ? bytes : 16));
     b.bytes = bytes;
     b.guarded = false;
+    ++b.allocs;
   }
   *out = b.p;
   return CMX_OK;

@@ -348,7 +348,7 @@ cmx_status cmx_mica_permutation_test_masks_dev(cmx_ctx* ctx, int nalpha, int nta
                                                const uint8_t* d_aln, size_t n, size_t ld, uint32_t max_perm, uint64_t seed,
                                                size_t pair_begin, size_t pair_end, double* d_pvalue, int32_t* d_nperm, void* stream) {
   if (!ctx) return CMX_ERR_INVALID;
-  if (nalpha != 4 && nalpha != 20) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: alphabet size must be 4 or 20");
+  if (nalpha != 4 && nalpha != 20) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: alphabet size must be 4 or 20 (other alphabets: cmx_mica_permutation_test_states)");
   if (ntaxa < 2 || ntaxa > mica_perm_max_taxa())
     return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: 2 <= ntaxa <= " + std::to_string(mica_perm_max_taxa()));
   if (!d_aln || n < 2 || ld < n || max_perm == 0 || pair_end <= pair_begin || pair_end > n * (n - 1) / 2 || !d_pvalue || !d_nperm)
@@ -464,3 +464,102 @@ cmx_status cmx_mica_permutation_test(cmx_ctx* ctx, int nalpha, int ntaxa, const 
   return cmx_mica_permutation_test_masks(ctx, nalpha, ntaxa, nullptr, 0, aln, n, max_perm, seed, pvalue, nperm);
 }
 
+// ---- the same test for every alphabet of 2 .. 64 states, without a mask table (cmx_mica_perm_wide.hip); 4 / 20 states are
+// the entry above with masks = NULL.  The entries above keep refusing the other alphabets: folding the two families into one
+// entry is a later change.
+static cmx_status permw_shape(cmx_ctx* ctx, int nalpha, int ntaxa) {
+  if (nalpha < 2 || nalpha > 64) return fail(ctx, CMX_ERR_INVALID, "cmx_mica_permutation_test_states: 2 <= alphabet size <= 64");
+  if (ntaxa < 2 || ntaxa > mica_permw_max_taxa())
+    return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test_states: 2 <= ntaxa <= " + std::to_string(mica_permw_max_taxa()));
+  return CMX_OK;
+}
+
+cmx_status cmx_mica_permutation_test_states_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint8_t* d_aln, size_t n, size_t ld,
+                                                uint32_t max_perm, uint64_t seed, size_t pair_begin, size_t pair_end,
+                                                double* d_pvalue, int32_t* d_nperm, void* stream) {
+  if (!ctx) return CMX_ERR_INVALID;
+  CMX_TRY(permw_shape(ctx, nalpha, ntaxa));
+  if (!mica_wide(nalpha))
+    return cmx_mica_permutation_test_masks_dev(ctx, nalpha, ntaxa, nullptr, 0, d_aln, n, ld, max_perm, seed, pair_begin, pair_end,
+                                               d_pvalue, d_nperm, stream);
+  if (!d_aln || n < 2 || ld < n || max_perm == 0 || pair_end <= pair_begin || pair_end > n * (n - 1) / 2 || !d_pvalue || !d_nperm)
+    return fail(ctx, CMX_ERR_INVALID, "cmx_mica_permutation_test_states: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int A = nalpha, T = ntaxa;
+  uint16_t *d_end, *d_unk, *d_order;
+  uint8_t* d_flag;
+  int* d_any;
+  long long *d_dF, *d_F = nullptr;
+  CMX_TRY(scratch(ctx, "permw_end", n * (size_t)A, &d_end));
+  CMX_TRY(scratch(ctx, "permw_unk", n, &d_unk));
+  CMX_TRY(scratch(ctx, "permw_flag", n, &d_flag));
+  CMX_TRY(scratch(ctx, "permw_order", n * (size_t)T, &d_order));
+  CMX_TRY(scratch(ctx, "permw_any", 1, &d_any));
+  CMX_TRY(scratch(ctx, "permw_dF", (size_t)T, &d_dF));
+  // resolved pairs: F[c] = round(c ln c * 2^40), kept as the increments F[c+1] - F[c] (host logarithm: the restatement's)
+  std::vector<long long>& dF = ctx->permw_dF_host;
+  dF.assign(T, 0);
+  long long prev = 0;
+  for (int c = 1; c <= T; ++c) {
+    const long long f = std::llround((double)c * std::log((double)c) * 1099511627776.0);
+    dF[c - 1] = f - prev;
+    prev = f;
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(d_dF, dF.data(), sizeof(long long) * T, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemsetAsync(d_any, 0, sizeof(int), st));
+  HIP_TRY(ctx, launch_mica_permw_classify(A, T, d_aln, ld, n, d_end, d_unk, d_flag, d_order, d_any, st));
+  int any = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&any, d_any, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));   // the one host decision of this call: are there columns with unknowns at all
+  if (any) {
+    // F_g[m] = round(m ln m 2^sh) for m <= M = A^2 T (8.4 M entries at 64 states x 2 047 taxa): built once per (states,
+    // taxa, shift) and kept on the device
+    const size_t M = (size_t)A * A * (size_t)T;
+    const int sh = std::min(40, 62 - (int)std::ceil(std::log2((double)M * std::log((double)M))));
+    CMX_TRY(scratch(ctx, "permw_F", M + 1, &d_F));
+    std::vector<long long>& F = ctx->permw_F_host;
+    const bool built = ctx->permw_F_A == A && ctx->permw_F_T == T && ctx->permw_F_sh == sh && F.size() == M + 1;
+    if (!built) {
+      ctx->permw_F_sh = -1;
+      ctx->permw_F_allocs = 0;
+      F.assign(M + 1, 0);
+      const double scale = std::ldexp(1.0, sh);
+      for (size_t m = 1; m <= M; ++m) F[m] = std::llround((double)m * std::log((double)m) * scale);
+      ctx->permw_F_A = A; ctx->permw_F_T = T; ctx->permw_F_sh = sh;
+    }
+    // (the device copy is keyed by the buffer's allocation too: scratch starts over when it grows, and when the scratch
+    // guard is switched on after the context was created)
+    const size_t allocs = ctx->scratch["permw_F"].allocs;
+    if (ctx->permw_F_allocs != allocs) {
+      HIP_TRY(ctx, hipMemcpyAsync(d_F, F.data(), sizeof(long long) * (M + 1), hipMemcpyHostToDevice, st));
+      ctx->permw_F_allocs = allocs;
+    }
+  }
+  int cus = 0;
+  HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  HIP_TRY(ctx, launch_mica_permw(A, T, d_aln, ld, n, d_end, d_unk, d_flag, d_order, d_dF, d_F, max_perm, seed, pair_begin, pair_end,
+                                 d_pvalue, d_nperm, cus, st));
+  return CMX_OK;
+}
+
+cmx_status cmx_mica_permutation_test_states(cmx_ctx* ctx, int nalpha, int ntaxa, const uint8_t* aln, size_t n, uint32_t max_perm,
+                                            uint64_t seed, size_t pair_begin, size_t pair_end, double* pvalue, int32_t* nperm) {
+  if (!ctx) return CMX_ERR_INVALID;
+  CMX_TRY(permw_shape(ctx, nalpha, ntaxa));
+  if (!aln || n < 2 || max_perm == 0 || pair_end <= pair_begin || pair_end > n * (n - 1) / 2 || !pvalue || !nperm)
+    return fail(ctx, CMX_ERR_INVALID, "cmx_mica_permutation_test_states: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t np = pair_end - pair_begin;
+  TmpDev tmp;
+  uint8_t* d_aln;
+  double* d_pv;
+  int32_t* d_np;
+  CMX_TRY(tmp.upload(ctx, &d_aln, aln, (size_t)ntaxa * n));
+  CMX_TRY(tmp.alloc(ctx, &d_pv, np));
+  CMX_TRY(tmp.alloc(ctx, &d_np, np));
+  CMX_TRY(cmx_mica_permutation_test_states_dev(ctx, nalpha, ntaxa, d_aln, n, n, max_perm, seed, pair_begin, pair_end, d_pv, d_np, nullptr));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  CMX_TRY(download(ctx, pvalue, d_pv, np));
+  return download(ctx, nperm, d_np, np);
+}

@@ -28,6 +28,7 @@ struct DevBuf {
   size_t bytes = 0;     // capacity the callers may use (the allocation is kGuardBytes longer under the guard)
   size_t logical = 0;   // guard only: what the last caller asked for; the canary sits at [logical, logical + kGuardBytes)
   bool guarded = false; // allocated with room for the canary (a buffer from before the guard was switched on is not)
+  size_t allocs = 0;    // how often it was allocated: what a caller that keeps content across calls keys that content on
 };
 
 struct cmx_ctx {
@@ -62,6 +63,10 @@ struct cmx_ctx {
   std::vector<uint8_t> perm_tab_host;
   unsigned long long perm_F_L = 0;
   int perm_F_T = 0, perm_F_sh = -1;
+  // the same for alphabets other than 4 / 20 states (cmx_mica_perm_wide.hip), under a key of their own: (states, taxa, shift) + the allocation of the device buffer
+  std::vector<long long> permw_dF_host, permw_F_host;
+  int permw_F_A = 0, permw_F_T = 0, permw_F_sh = -1;
+  size_t permw_F_allocs = 0;   // the allocation of scratch "permw_F" that holds the table of that key (0: none)
   // cmx_intra_gram_prefetch_dev: the Gram blocks kept for the next cmx_intra_compact_range_dev with the same arguments
   struct GramKept { bool valid = false; int kind = 0; const double* counts = nullptr; size_t n = 0, ldc = 0, row_begin = 0, row_end = 0; const double* stat = nullptr; } gram_kept;
   const double *va_P = nullptr, *va_N1 = nullptr, *va_NC = nullptr;   // their operators, uploaded at first use

@@ -262,6 +262,16 @@ hipError_t launch_mica_perm_general(const uint8_t* d_aln, int T, size_t n, size_
 hipError_t launch_mica_perm(const uint8_t* d_aln, int T, size_t n, size_t ld, int A, const uint16_t* d_colcnt,
                             const uint8_t* d_hasamb, const long long* d_dF, bool nperm_preset, uint32_t max_perm, uint64_t seed,
                             size_t pair_begin, size_t pair_end, double* d_pvalue, int32_t* d_nperm, int cu_count, hipStream_t stream);
+// (cmx_mica_perm_wide.hip) the permutation test for alphabets other than 4 / 20 states: no mask table, codes >= A are unknowns
+int mica_permw_max_taxa();
+bool mica_permw_opening_fits(int T, int A);
+hipError_t launch_mica_permw_classify(int A, int T, const uint8_t* d_aln, size_t ld, size_t n, uint16_t* d_end, uint16_t* d_unk,
+                                      uint8_t* d_flag, uint16_t* d_order, int* d_any, hipStream_t stream);
+// d_F: the fixed-point table of the unknowns' path (A^2 T + 1 entries), or null when no column has unknowns
+hipError_t launch_mica_permw(int A, int T, const uint8_t* d_aln, size_t ld, size_t n, const uint16_t* d_end, const uint16_t* d_unk,
+                             const uint8_t* d_flag, const uint16_t* d_order, const long long* d_dF, const long long* d_F,
+                             uint32_t max_perm, uint64_t seed, size_t pair_begin, size_t pair_end, double* d_pvalue, int32_t* d_nperm,
+                             int cu_count, hipStream_t stream);
 // (cmx_cluster.hip)
 size_t hclust_lds_bytes(int n);
 size_t cluster_props_lds_bytes(int n);

@@ -54,7 +54,7 @@ EXPORTS = [
     "cmx_pair_stats", "cmx_pair_stats_dev", "cmx_null_intra", "cmx_null_simulate_dev", "cmx_null_intra_dev", "cmx_null_inter",
     "cmx_null_inter_dev", "cmx_intra_pvalues", "cmx_intra_rows", "cmx_intra_rows_dev", "cmx_intra_rows_range_dev",
     "cmx_intra_pvalues_dev", "cmx_inter_rows", "cmx_inter_rows_dev", "cmx_mica_bootstrap_indices", "cmx_mica_parametric_null", "cmx_mi_columns", "cmx_mi_columns_dev", "cmx_mi_pairs", "cmx_debug_mica_wide_plain",
-    "cmx_mica_permutation_test", "cmx_mica_permutation_test_dev", "cmx_mica_permutation_test_masks", "cmx_mica_permutation_test_masks_dev", "cmx_mica_average_mi", "cmx_mica_average_mi_dev", "cmx_mica_zscore_null", "cmx_mica_zscore_null_dev",
+    "cmx_mica_permutation_test", "cmx_mica_permutation_test_dev", "cmx_mica_permutation_test_masks", "cmx_mica_permutation_test_masks_dev", "cmx_mica_permutation_test_states", "cmx_mica_permutation_test_states_dev", "cmx_mica_average_mi", "cmx_mica_average_mi_dev", "cmx_mica_zscore_null", "cmx_mica_zscore_null_dev",
     "cmx_group_stats", "cmx_group_stats_dev", "cmx_candidate_groups", "cmx_debug_candidate_cursor",
     "cmx_hclust", "cmx_hclust_dev", "cmx_cluster_sites", "cmx_cluster_sites_dev", "cmx_cluster_null",
     "cmx_intra_compact_range_dev", "cmx_intra_gram_prefetch_dev", "cmx_expand_compact_rows", "cmx_vector_matrix",
@@ -685,6 +685,18 @@ class Engine:
         self._check(self._lib.cmx_mica_permutation_test_masks(self._ctx, int(nalpha), int(T), _vp(mk) if mk is not None else None,
                                                               _sz(0 if mk is None else len(mk)), _vp(a), _sz(n),
                                                               ctypes.c_uint32(max_perm), ctypes.c_uint64(seed), _vp(pv), _vp(npm)))
+        return pv, npm
+
+    def mica_permutation_test_states(self, aln, max_perm, seed, nalpha, pair_begin=0, pair_end=None):
+        """miTest for any alphabet of 2 .. 64 states without a mask table (codes >= nalpha are unknowns; 4 / 20 states run
+        mica_permutation_test's kernels) -> (pvalue, nperm) of the pairs [pair_begin, pair_end) of the (i < j) row order"""
+        a = np.ascontiguousarray(aln, dtype=np.uint8)
+        T, n = a.shape
+        pair_end = n * (n - 1) // 2 if pair_end is None else int(pair_end)
+        npairs = max(pair_end - int(pair_begin), 0)
+        pv, npm = np.zeros(npairs), np.zeros(npairs, dtype=np.int32)
+        self._check(self._lib.cmx_mica_permutation_test_states(self._ctx, int(nalpha), int(T), _vp(a), _sz(n), ctypes.c_uint32(max_perm),
+                                                               ctypes.c_uint64(seed), _sz(pair_begin), _sz(pair_end), _vp(pv), _vp(npm)))
         return pv, npm
 
     def mica_zscore_null(self, which, mi, key):

@@ -9,7 +9,8 @@
 Site indices come from the engine's counter-based generator scheme (Philox keyed by seed), not from Bio++'s global
 generator: null distributions agree with the reference in distribution, not draw for draw.
   zscore_null / analysis  <- null.method = z-score, CoMap/Mica.cpp:549-607, and the output table of :634-690
-  permutation_test        <- null.method = permutations, miTest CoMap/Mica.cpp:93-118 (fully resolved columns only)"""
+  permutation_test        <- null.method = permutations, miTest CoMap/Mica.cpp:93-118 (4 / 20 states with an ambiguity
+                             table; every alphabet of 2 .. 64 states without one)"""
 import numpy as np
 
 
@@ -74,7 +75,10 @@ def parametric_null_via_host(engine, seed, nrep_cpu=10, nrep_ram=100, nalpha=20,
 def permutation_test(engine, aln, max_perm=1000, seed=0, nalpha=20, masks=None):
     """-> dense (pvalue [n, n], nperm [n, n]) filled for j > i: Perm.p.value / Perm.nb of Mica.cpp:667-668"""
     n = aln.shape[1]
-    pv, npm = engine.mica_permutation_test(aln, max_perm, seed, nalpha, masks=masks)
+    if nalpha not in (4, 20) and masks is None:
+        pv, npm = engine.mica_permutation_test_states(aln, max_perm, seed, nalpha)
+    else:
+        pv, npm = engine.mica_permutation_test(aln, max_perm, seed, nalpha, masks=masks)
     iu = np.triu_indices(n, 1)
     P, N = np.full((n, n), np.nan), np.zeros((n, n), dtype=np.int32)
     P[iu], N[iu] = pv, npm

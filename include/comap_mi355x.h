@@ -537,6 +537,25 @@ cmx_status cmx_mica_permutation_test_dev(cmx_ctx* ctx, int nalpha, int ntaxa, co
                                          double* d_pvalue, int32_t* d_nperm, void* stream);
 cmx_status cmx_mica_permutation_test(cmx_ctx* ctx, int nalpha, int ntaxa, const uint8_t* aln, size_t n, uint32_t max_perm,
                                      uint64_t seed, double* pvalue /*[n(n-1)/2]*/, int32_t* nperm);
+/* The same test for every alphabet of 2 <= nalpha <= 64 states (codon models), without a mask table: a code < nalpha is
+ * that state -- at 64 states code 63 too, nothing is reserved -- and every code >= nalpha is an unknown, the rule of
+ * cmx_mi_columns for these alphabets.  nalpha outside 2 .. 64: CMX_ERR_INVALID.  nalpha = 4 / 20 forwards to
+ * cmx_mica_permutation_test_masks_dev with masks = NULL (the same kernels, the same bytes); the four entries above keep
+ * refusing every other alphabet.  Pair order, p-value, stopping rule, constant columns (an all-unknown column is one) and
+ * the shuffles are those described above.  A resolved pair is decided on sum_xy F[c_xy], F[c] = round(c ln c 2^40); a pair
+ * with an unknown in either column on sum_ab F_g[m_ab] over all nalpha^2 cells of the integer table m_ab = A^2 N_ab +
+ * A (N_aU + N_Ub) + N_UU, F_g[m] = round(m ln m 2^sh), sh = min(40, 62 - ceil(log2(M ln M))), M = A^2 ntaxa; both tables
+ * are built on the host (libm's log) and kept by the context per (nalpha, ntaxa, sh) -- F_g (up to 8.4 M entries, 67 MB on
+ * the device) only when a call has a column with unknowns.  2 <= ntaxa <= 2047, else CMX_ERR_UNSUPPORTED; both paths hold
+ * 2 047 taxa at 64 states in the 160 KB of LDS (158 592 and 150 912 bytes, one wave per workgroup), so neither has a smaller
+ * limit of its own.  The host entry takes the pair range too; outputs are indexed by pair - pair_begin.  The call blocks
+ * the host once, as above. */
+cmx_status cmx_mica_permutation_test_states_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint8_t* d_aln, size_t n, size_t ld,
+                                                uint32_t max_perm, uint64_t seed, size_t pair_begin, size_t pair_end,
+                                                double* d_pvalue, int32_t* d_nperm, void* stream);
+cmx_status cmx_mica_permutation_test_states(cmx_ctx* ctx, int nalpha, int ntaxa, const uint8_t* aln, size_t n,
+                                            uint32_t max_perm, uint64_t seed, size_t pair_begin, size_t pair_end,
+                                            double* pvalue /*[pair_end - pair_begin]*/, int32_t* nperm);
 
 /* ---- clustering analysis (CoMap/CoMap.cpp:395-560; null: ClusterTools::computeGlobalDistanceDistribution,
  * CoMap/ClusterTools.cpp:200-294).  Distances of CoMap.cpp:402-428: 1 - correlation (StatisticBasedDistance(cor, 1.),

@@ -907,7 +907,7 @@ class ClusterTools {
 // averageMI -> APC / RCW (:346-363, :656-657), the four null methods (:399-632) and the p-value rule of :671-683.
 // The alignment is [taxon][site] state codes; codes >= alphabetSize index `masks` (bit a = compatible with state a),
 // as SiteTools::*(.., resolveUnknowns = true) resolves them.  alphabetSize: 2 .. 64; other than 4 / 20 states (codon
-// alphabets) `masks` must be null -- every code >= alphabetSize is an unknown -- and nullMethod "permutations" is refused.
+// alphabets) `masks` must be null -- every code >= alphabetSize is an unknown.
 // An Engine WITH a model is Mica's `use_model` case: the
 // parametric bootstrap needs it, and norms (from CoETools::getVectors on the same engine) then bin the p-values
 // (:383-386) and add the Nmin column.
@@ -946,8 +946,12 @@ class Mica {
     const size_t np = nbSites * (nbSites - 1) / 2;
     pvalue.assign(np, 0.);
     nbPermutations.assign(np, 0);
-    eng.check(cmx_mica_permutation_test_masks(eng.ctx(), alphabetSize, (int)nbTaxa, masks, nbMasks, aln, nbSites,
-                                              (uint32_t)maxNbPermutations, seed, pvalue.data(), nbPermutations.data()));
+    if (alphabetSize != 4 && alphabetSize != 20 && !masks)   // 2 .. 64 states without a table: the entry of its own
+      eng.check(cmx_mica_permutation_test_states(eng.ctx(), alphabetSize, (int)nbTaxa, aln, nbSites, (uint32_t)maxNbPermutations, seed,
+                                                 0, np, pvalue.data(), nbPermutations.data()));
+    else
+      eng.check(cmx_mica_permutation_test_masks(eng.ctx(), alphabetSize, (int)nbTaxa, masks, nbMasks, aln, nbSites,
+                                                (uint32_t)maxNbPermutations, seed, pvalue.data(), nbPermutations.data()));
   }
 
   static Result analyse(const Engine& eng, const uint8_t* aln, size_t nbTaxa, size_t nbSites, int alphabetSize,
