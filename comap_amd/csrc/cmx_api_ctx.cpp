@@ -20,6 +20,8 @@ std::map<std::string, size_t> g_guard_shrink;
 
 std::atomic<int> g_lds_slot{1};         // cmx_debug_lds_slot: 0 = the mapping walk's LDS slot is planned empty (A/B runs, tests)
 std::atomic<int> g_pat_hash_bits{64};   // (tests force collisions with it)
+std::atomic<int> g_map_queue{1};        // cmx_debug_map_queue: 0 = strided block assignment in every mapping launch (A/B runs, tests)
+std::atomic<int> g_map_grid{0};         // cmx_debug_map_grid: cap of a new context's grid_blocks / obs_blocks (tests: many rounds of blocks on few waves)
 
 bool guard_on() {
   int g = g_guard.load();
@@ -258,6 +260,11 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
     ctx->grid_blocks = ctx->cu_count * map_waves_per_simd(h.dS);   // 4-wave workgroups, that many per CU
     ctx->waves = ctx->grid_blocks * kWavesPerBlock;
     ctx->obs_blocks = std::max(1, ctx->grid_blocks / 4);
+    if (const int cap = g_map_grid.load()) {
+      ctx->grid_blocks = std::min(ctx->grid_blocks, cap);
+      ctx->waves = ctx->grid_blocks * kWavesPerBlock;
+      ctx->obs_blocks = std::min(ctx->obs_blocks, cap);
+    }
     auto alloc_ws = [&](Workspace* ws, size_t w, size_t* bytes) -> cmx_status {
       const size_t ks = (size_t)map_sites_per_wave(h.dS);   // sites per mapping wave
       const size_t bD = w * h.NIW * h.dS * ks * sizeof(double);
@@ -283,6 +290,7 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
     ctx->ws_bytes = 0;
     CMX_TRY(alloc_ws(&ctx->ws, (size_t)ctx->waves, &ctx->ws_bytes));
     CMX_TRY(alloc_ws(&ctx->ws_obs, (size_t)ctx->obs_blocks * kWavesPerBlock, &ctx->ws_bytes));
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->map_queue, sizeof(unsigned long long) * kMapQueueRing));   // map_queue_take
     return CMX_OK;
   };
   cmx_status s = dev_init();
@@ -297,6 +305,7 @@ void cmx_ctx_destroy(cmx_ctx* ctx) {
     (void)guard_verify_all(ctx);   // destroy cannot fail: findings go to stderr and to cmx_debug_scratch_guard_failures
   for (void* p : ctx->model_allocs) (void)hipFree(p);
   if (ctx->d_stat_w) (void)hipFree(ctx->d_stat_w);
+  if (ctx->map_queue) (void)hipFree(ctx->map_queue);
   for (auto& kv : ctx->scratch) if (kv.second.p) (void)hipFree(kv.second.p);
   for (Workspace* ws : {&ctx->ws, &ctx->ws_obs}) {
     if (ws->D) (void)hipFree(ws->D);
@@ -305,6 +314,19 @@ void cmx_ctx_destroy(cmx_ctx* ctx) {
     if (ws->part) (void)hipFree(ws->part);
   }
   delete ctx;
+}
+
+cmx_status map_queue_take(cmx_ctx* ctx, size_t nblocks, int grid, hipStream_t stream, unsigned long long** queue) {
+  *queue = nullptr;
+  const size_t nwaves = (size_t)grid * kWavesPerBlock;
+  if (nblocks <= nwaves || g_map_queue.load() == 0) return CMX_OK;
+  // A word is reused kMapQueueRing queued launches later: the ring assumes fewer than kMapQueueRing queued mapping launches
+  // of one context in flight at a time, over all streams (a launch is done with its word when its kernel ends).  Two
+  // launches in flight on two streams -- the observed mapping beside the null -- therefore never share a counter.
+  unsigned long long* q = ctx->map_queue + ctx->map_queue_turn++ % kMapQueueRing;
+  HIP_TRY(ctx, launch_map_queue_init(q, (unsigned long long)nwaves, stream));
+  *queue = q;
+  return CMX_OK;
 }
 
 cmx_status cmx_get_info(const cmx_ctx* ctx, cmx_info* info) {
@@ -380,6 +402,18 @@ int cmx_debug_scratch_guard(int on) {
 int cmx_debug_lds_slot(int on) {
   const int was = g_lds_slot.load();
   if (on >= 0) g_lds_slot.store(on ? 1 : 0);
+  return was;
+}
+
+int cmx_debug_map_queue(int on) {
+  const int was = g_map_queue.load();
+  if (on >= 0) g_map_queue.store(on ? 1 : 0);
+  return was;
+}
+
+int cmx_debug_map_grid(int workgroups) {
+  const int was = g_map_grid.load();
+  if (workgroups >= 0) g_map_grid.store(workgroups);
   return was;
 }
 

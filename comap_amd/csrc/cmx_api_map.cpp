@@ -127,6 +127,7 @@ static cmx_status map_walk(cmx_ctx* ctx, const MapIn& in, const MapOut& out, voi
   }
   const size_t blocks_needed = (nblocks + kWavesPerBlock - 1) / kWavesPerBlock;
   const int grid = (int)std::min<size_t>(blocks_needed, (size_t)max_blocks);
+  CMX_TRY(map_queue_take(ctx, nblocks, grid, (hipStream_t)stream, &a.queue));
   HIP_TRY(ctx, launch_map(a, kModeObserved, grid, (hipStream_t)stream));
   return CMX_OK;
 }

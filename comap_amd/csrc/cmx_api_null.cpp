@@ -173,7 +173,9 @@ static cmx_status null_patterns_dev(cmx_ctx* ctx, const Stat& sk, MapArgs a, siz
     a.nsites = n;
     a.npat = b.incl + (n - 1);
     const size_t blocks_needed = ((n + ks - 1) / ks + kWavesPerBlock - 1) / kWavesPerBlock;
-    HIP_TRY(ctx, launch_map(a, kModeNullPatterns, (int)std::min<size_t>(blocks_needed, (size_t)ctx->grid_blocks), (hipStream_t)stream));
+    const int grid = (int)std::min<size_t>(blocks_needed, (size_t)ctx->grid_blocks);
+    CMX_TRY(map_queue_take(ctx, (n + ks - 1) / ks, grid, (hipStream_t)stream, &a.queue));
+    HIP_TRY(ctx, launch_map(a, kModeNullPatterns, grid, (hipStream_t)stream));
     if (moments)
       HIP_TRY(ctx, launch_null_pattern_moments(h.B, h.K, cnt, (int)ks, (int)ks, a.npat, n, pmean, pss, (hipStream_t)stream));
     HIP_TRY(ctx, launch_null_pattern_pairs(sk, cnt, (int)ks, (int)ks, pmean, pss, SiteCols{rc, pr, nm}, b.pat_of, rep_ram, n / 2, out.at(r0 * rep_ram),
@@ -235,6 +237,7 @@ cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint
   const size_t ks = (size_t)map_sites_per_wave(ctx->hm.dS);
   const size_t blocks_needed = ((a.nsites + ks - 1) / ks + kWavesPerBlock - 1) / kWavesPerBlock;
   const int grid = (int)std::min<size_t>(blocks_needed, (size_t)ctx->grid_blocks);
+  CMX_TRY(map_queue_take(ctx, (a.nsites + ks - 1) / ks, grid, (hipStream_t)stream, &a.queue));
   HIP_TRY(ctx, launch_map(a, kModeNull, grid, (hipStream_t)stream));
   ctx->null_mapped_host += 2 * a.nsites;
   return CMX_OK;

@@ -41,6 +41,10 @@ struct cmx_ctx {
   int obs_blocks = 0;
   int cu_count = 0, waves = 0, grid_blocks = 0;
   size_t ws_bytes = 0;
+  // block counters of the queued mapping launches (MapArgs::queue, map_queue_take): a ring of kMapQueueRing 64-bit words,
+  // allocated with the workspace; the next launch takes word map_queue_turn % kMapQueueRing
+  unsigned long long* map_queue = nullptr;
+  unsigned map_queue_turn = 0;
   std::vector<void*> model_allocs;
   std::map<std::string, DevBuf> scratch;
   struct GuardedFixed { std::string name; void* p; size_t bytes; };
@@ -104,6 +108,8 @@ extern std::mutex g_guard_mu;
 extern std::vector<std::string> g_guard_failures;      // buffers found trampled, in the order found
 extern std::map<std::string, size_t> g_guard_shrink;   // test hook: logical size override per buffer name
 extern std::atomic<int> g_pat_hash_bits;               // cmx_debug_null_hash_bits: the fused null's column hash keeps only its low bits
+extern std::atomic<int> g_map_queue;                   // cmx_debug_map_queue: 0 = every mapping launch keeps the strided block assignment
+extern std::atomic<int> g_map_grid;                    // cmx_debug_map_grid: workgroups a new context's mapping launches may use (0: no cap)
 
 inline cmx_status fail(cmx_ctx* ctx, cmx_status s, const std::string& msg) {
   if (ctx) ctx->err = msg;
@@ -209,6 +215,13 @@ inline cmx_status rng_range(cmx_ctx* ctx, uint64_t g_end, const char* who) {
   return CMX_OK;
 }
 
+
+// cmx_api_ctx.cpp.  The block counter of a mapping launch of `grid` workgroups over at most nblocks site blocks (pattern mode:
+// the blocks of the pass's sites, the waves read the pattern count), for MapArgs::queue: null when there is nothing to balance
+// (nblocks <= waves: every wave holds at most one block) or under cmx_debug_map_queue(0); otherwise the context's next ring
+// word, set to the launch's wave count on `stream` -- call it right before launch_map on that stream.
+constexpr unsigned kMapQueueRing = 256;
+cmx_status map_queue_take(cmx_ctx* ctx, size_t nblocks, int grid, hipStream_t stream, unsigned long long** queue);
 
 // cmx_api_map.cpp.  full_grid: the whole-chip workspace of the null launches (the engine's own simulate -> map pipelines)
 // instead of the quarter-chip slice of the observed alignments

@@ -123,10 +123,15 @@ struct MapArgs {
   const uint32_t* npat;
   // ... counts is then the tile-major pattern table: tile p / kSites is [B*K][kSites] doubles, pattern p its column p % kSites
   // (kSites patterns per wave: the block map_sites_wave's epilogue writes)
+  // how blocks reach the waves (appended as well).  Null: wave w maps blocks w, w + nwaves, ...  Otherwise a
+  // device counter the launch's stream has set to nwaves: a wave maps block w first, then the blocks it draws from the counter
+  // (next_block, cmx_map.hip).  kModeObservedSplit ignores it.
+  unsigned long long* queue;
 };
 // The code hipcc emits for the mapping kernels depends on where these structures' fields sit in the kernel argument
 // (DESIGN.md 4.5.4): an unused field keeps its slot.
-static_assert(sizeof(DevModel) == 256 && sizeof(Workspace) == 56 && sizeof(MapArgs) == 512 && offsetof(MapArgs, rep_site) == 496,
+static_assert(sizeof(DevModel) == 256 && sizeof(Workspace) == 56 && sizeof(MapArgs) == 520 && offsetof(MapArgs, rep_site) == 496 &&
+                  offsetof(MapArgs, queue) == 512,
               "kernel-argument layout of the mapping kernels");
 
 // ---- the pair stage's shapes: host structures (the kernels keep taking their pointers one by one, as with MicaSide)
@@ -175,6 +180,8 @@ struct RowScan { unsigned long long* rowcount = nullptr; void* tmp = nullptr; si
 
 // launchers by source file (cmx_map.hip; pair_diag and group_stats are there for map_kernel's sake)
 hipError_t launch_map(const MapArgs& a, int mode, int grid_blocks, hipStream_t stream);
+// sets a block counter (MapArgs::queue) to `first` on the stream of the launch that will draw from it
+hipError_t launch_map_queue_init(unsigned long long* queue, unsigned long long first, hipStream_t stream);
 hipError_t launch_map_finalize(const MapArgs& a, hipStream_t stream);
 // fills rows S.. of every leaf operator from d_masks[S .. S+max_ambig(S)) (null: every state compatible)
 hipError_t launch_extend_leaf_rows(const DevModel& m, const uint32_t* d_masks, hipStream_t stream);

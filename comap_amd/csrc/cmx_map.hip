@@ -819,6 +819,22 @@ static int map_lds_per_wave(int S, int fuse, int ng) {
 }
 static_assert(kWavesPerBlock * map_lds_fixed<20>(1, 4) <= 160 * 1024 / map_waves_per_simd(20), "the protein walk's workgroup fits its share of a CU's LDS");
 
+// How blocks reach the waves: the block a wave maps after block sb.  Without a queue the fixed share, block
+// sb + nwaves.  With one, the next block nobody has taken: the counter starts at nwaves (every wave's first block is its own
+// index, no atomic), lane 0 draws with one vector atomic and the index is made wave-uniform; a wave leaves at the first index
+// past the last block.  One wave-uniform branch between two blocks, outside the walk: the atomic is issued after the block's
+// epilogue, OpState::vs does not count it (an uncounted VMEM instruction only makes wait_vm stricter), and the wait for its
+// result drains it with the operator DMA the block's last op left in flight -- (class 0, entry 0), right for any next block.
+// Which wave maps a block changes no output: workspace, part and cnt0 / cnt1 are keyed by wave, tiles and per-site results by block.
+__device__ __forceinline__ size_t next_block(unsigned long long* queue, size_t sb, int nwaves, int lane) {
+  if (queue == nullptr) return sb + nwaves;
+  unsigned long long t = 0;
+  if (lane == 0) t = atomicAdd(queue, 1ull);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)t);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(t >> 32));
+  return (size_t)(((unsigned long long)hi << 32) | lo);
+}
+
 template <int S, int MODE, int FUSE, int NG = map_ng(S)>
 __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void map_kernel(const MapArgs a) {
   constexpr int VL = S / 4 * NG, kSites = 16 * NG;
@@ -877,7 +893,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
     // the null mode walks a site of a pair; per pattern what observed mode writes per site
     const size_t npat = *a.npat;
     const size_t nb = (npat + kSites - 1) / kSites;
-    for (size_t sb = wave; sb < nb; sb += nwaves) {
+    for (size_t sb = wave; sb < nb; sb = next_block(a.queue, sb, nwaves, lane)) {
       const size_t p = sb * kSites + sidx;
       const bool active = p < npat;
       const size_t g = a.rep_site[active ? p : npat - 1];
@@ -898,7 +914,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     return;
   }
-  for (size_t sb = wave; sb < nblocks; sb += nwaves) {
+  for (size_t sb = wave; sb < nblocks; sb = next_block(a.queue, sb, nwaves, lane)) {
     const size_t site = sb * kSites + sidx;
     const bool active = site < a.nsites;
     const size_t s = active ? site : a.nsites - 1;
@@ -986,6 +1002,14 @@ hipError_t launch_map(const MapArgs& a_in, int mode, int grid_blocks, hipStream_
   if (a.m.S == 16 && a.m.fuse == 4) return launch_map_mode<16, 4>(mode, a, grid, block, lds, lim, stream);
   if (a.m.S == 4 && a.m.fuse == 1) return launch_map_mode<4, 1>(mode, a, grid, block, lds, lim, stream);
   return hipErrorInvalidValue;
+}
+
+// a launch's block counter, set on the launch's own stream right before it (next_block): one thread, one store
+__global__ void map_queue_init_kernel(unsigned long long* queue, unsigned long long first) { *queue = first; }
+
+hipError_t launch_map_queue_init(unsigned long long* queue, unsigned long long first, hipStream_t stream) {
+  hipLaunchKernelGGL(map_queue_init_kernel, dim3(1), dim3(1), 0, stream, queue, first);
+  return hipGetLastError();
 }
 
 // class-split observed mode: sums the per-class results in class order exactly as map_sites_wave's own epilogue does.

@@ -58,7 +58,7 @@ EXPORTS = [
     "cmx_group_stats", "cmx_group_stats_dev", "cmx_candidate_groups", "cmx_debug_candidate_cursor",
     "cmx_hclust", "cmx_hclust_dev", "cmx_cluster_sites", "cmx_cluster_sites_dev", "cmx_cluster_null",
     "cmx_intra_compact_range_dev", "cmx_intra_gram_prefetch_dev", "cmx_expand_compact_rows", "cmx_vector_matrix",
-    "cmx_scratch_check", "cmx_debug_lds_slot", "cmx_debug_scratch_guard", "cmx_debug_scratch_guard_failures", "cmx_debug_scratch_shrink",
+    "cmx_scratch_check", "cmx_debug_lds_slot", "cmx_debug_map_queue", "cmx_debug_map_grid", "cmx_debug_scratch_guard", "cmx_debug_scratch_guard_failures", "cmx_debug_scratch_shrink",
     "cmx_set_null_patterns", "cmx_null_pattern_count", "cmx_debug_null_hash_bits",
 ]
 # clustering.distance / clustering.method options of the reference (CoMap/CoMap.cpp:402-428, :460-472)
@@ -83,6 +83,20 @@ def lds_slot(on=None):
     walk's LDS slot (None = query); returns the previous state.  Off = every workspace vector goes through HBM."""
     lib = load_library()
     return bool(lib.cmx_debug_lds_slot(ctypes.c_int(-1 if on is None else int(bool(on)))))
+
+
+def map_queue(on=None):
+    """cmx_debug_map_queue (include/comap_mi355x.h): whether the 64-site mapping launches issued from now on hand their site
+    blocks to the waves through a queue (None = query); returns the previous state.  Off = the fixed strided assignment."""
+    lib = load_library()
+    return bool(lib.cmx_debug_map_queue(ctypes.c_int(-1 if on is None else int(bool(on)))))
+
+
+def map_grid(workgroups=None):
+    """cmx_debug_map_grid: cap on the workgroups of the mapping launches of engines created from now on (0 = no cap, None =
+    query); returns the previous value."""
+    lib = load_library()
+    return int(lib.cmx_debug_map_grid(ctypes.c_int(-1 if workgroups is None else int(workgroups))))
 
 
 def mica_wide_plain(on=None):

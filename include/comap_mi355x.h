@@ -158,6 +158,15 @@ cmx_status cmx_debug_walk(const cmx_model* model, const cmx_tree* tree, int32_t*
  * results are the same bits either way).  cmx_debug_lds_slot(0) makes contexts created from now on plan the slot empty, i.e.
  * every vector goes through HBM (A/B runs, tests).  on < 0: query only; returns the previous state.  Process-wide, host only. */
 int cmx_debug_lds_slot(int on);
+/* How the 64-site mapping launches hand their site blocks to the waves (same bits either way): a wave maps the block of its
+ * own index first and then draws further blocks from a device counter, one per launch, taken from a ring of 256 in the
+ * context (so: fewer than 256 such launches of one context in flight at a time); launches with at most one block per wave
+ * and the class-split launch of small alignments keep the fixed assignment, block w, w + waves, ...
+ * cmx_debug_map_queue(0) gives every launch from now on the fixed assignment (A/B runs, tests).  cmx_debug_map_grid(n) caps the
+ * workgroups of the mapping launches of contexts created from now on, observed and null alike (0: no cap; tests: many
+ * rounds of blocks on a few waves).  Negative argument: query only; both return the previous value.  Process-wide, host only. */
+int cmx_debug_map_queue(int on);
+int cmx_debug_map_grid(int workgroups);
 
 /* ---- substitution mapping: replaces DRHomogeneousTreeLikelihood::initialize + getLogLikelihoodPerSite /
  * getPosteriorRatePerSite / getRateClassWithMaxPostProbPerSite + computeSubstitutionVectors + computeNormForSite
