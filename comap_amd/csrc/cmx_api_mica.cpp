@@ -1,5 +1,6 @@
 // C-ABI, Mica stage: mutual information of alignment columns, the bootstrap nulls, averages / z-scores, the permutation test.
 #include "cmx_ctx.h"
+#include "cmx_mica_perm.h"
 
 // the 256 compatibility masks of an alphabet: a state is itself, every other code "unknown" (compatible with all states)
 // unless the caller's table says otherwise (an empty mask there is an unknown too)
@@ -310,7 +311,6 @@ struct PermCodes {
   uint8_t emap[256];
   uint32_t emask[32], ewgt[32];
   uint32_t L;
-  int sh;
 };
 cmx_status perm_codes(cmx_ctx* ctx, int A, const uint32_t* masks, size_t nmasks, int T, PermCodes* pc) {
   const uint32_t all = (1u << A) - 1u;
@@ -339,8 +339,77 @@ cmx_status perm_codes(cmx_ctx* ctx, int A, const uint32_t* masks, size_t nmasks,
     return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: lcm of the ambiguity codes' state counts too large for the fixed-point table");
   pc->L = (uint32_t)L;
   for (int e = 0; e < 32; ++e) pc->ewgt[e] = (uint32_t)(L / (unsigned long long)k[e]);
-  pc->sh = std::min(40, 62 - (int)std::ceil(std::log2(M * std::log(M))));
   return CMX_OK;
+}
+
+// ---- what the entries of both alphabet families share (who: the entry's name in its messages)
+cmx_status perm_taxa(cmx_ctx* ctx, const char* who, int ntaxa) {
+  if (ntaxa < 2 || ntaxa > mica_perm_max_taxa())
+    return fail(ctx, CMX_ERR_UNSUPPORTED, std::string(who) + ": 2 <= ntaxa <= " + std::to_string(mica_perm_max_taxa()));
+  return CMX_OK;
+}
+cmx_status perm_args(cmx_ctx* ctx, const char* who, const uint8_t* aln, size_t n, size_t ld, uint32_t max_perm, size_t pair_begin,
+                     size_t pair_end, const double* pvalue, const int32_t* nperm) {
+  if (!aln || n < 2 || ld < n || max_perm == 0 || pair_end <= pair_begin || pair_end > n * (n - 1) / 2 || !pvalue || !nperm)
+    return fail(ctx, CMX_ERR_INVALID, std::string(who) + ": bad arguments");
+  return CMX_OK;
+}
+
+// resolved pairs: F[c] = round(c ln c * 2^40); the kernels accumulate F[c+1] - F[c] per increment of a joint count.  Into
+// scratch `name` on `st` (the source is owned by the context: a failing call further down must not free memory an upload
+// still reads; every caller synchronises `st` before it returns)
+cmx_status perm_increments(cmx_ctx* ctx, const char* name, int T, hipStream_t st, long long** d_dF) {
+  CMX_TRY(scratch(ctx, name, (size_t)T, d_dF));
+  std::vector<long long>& dF = ctx->perm_dF_host;
+  dF.assign(T, 0);
+  long long prev = 0;
+  for (int c = 1; c <= T; ++c) {
+    const long long f = std::llround((double)c * std::log((double)c) * 1099511627776.0);
+    dF[c - 1] = f - prev;
+    prev = f;
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(*d_dF, dF.data(), sizeof(long long) * T, hipMemcpyHostToDevice, st));
+  return CMX_OK;
+}
+
+// pairs with non-states: F[m] = round(m ln m 2^sh) for m <= M, resident in scratch `name` on `st`.  Built on the host, with the
+// oracle's logarithm, so that the fixed-point sums, and with them every tie, are the oracle's; once per (M, sh) -- a caller that
+// shards the pairs over several calls pays for it once.  The device copy is keyed by the buffer's allocation too: scratch
+// starts over when it grows, and when the scratch guard is switched on after the context was created.
+cmx_status perm_table(cmx_ctx* ctx, PermTable& t, const char* name, size_t M, hipStream_t st, long long** d_F) {
+  const int sh = std::min(40, 62 - (int)std::ceil(std::log2((double)M * std::log((double)M))));
+  CMX_TRY(scratch(ctx, name, M + 1, d_F));
+  if (t.M != M || t.sh != sh || t.host.size() != M + 1) {
+    t.sh = -1;
+    t.allocs = 0;
+    t.host.assign(M + 1, 0);
+    const double scale = std::ldexp(1.0, sh);
+    for (size_t m = 1; m <= M; ++m) t.host[m] = std::llround((double)m * std::log((double)m) * scale);
+    t.M = M; t.sh = sh;
+  }
+  const size_t allocs = ctx->scratch[name].allocs;
+  if (t.allocs != allocs) {
+    HIP_TRY(ctx, hipMemcpyAsync(*d_F, t.host.data(), sizeof(long long) * (M + 1), hipMemcpyHostToDevice, st));
+    t.allocs = allocs;
+  }
+  return CMX_OK;
+}
+
+// the host-pointer entries: the alignment up, run(d_aln, d_pvalue, d_nperm) for np pairs, both results down
+template <class Run>
+cmx_status perm_host_call(cmx_ctx* ctx, int ntaxa, const uint8_t* aln, size_t n, size_t np, double* pvalue, int32_t* nperm, Run run) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  TmpDev tmp;
+  uint8_t* d_aln;
+  double* d_pv;
+  int32_t* d_np;
+  CMX_TRY(tmp.upload(ctx, &d_aln, aln, (size_t)ntaxa * n));
+  CMX_TRY(tmp.alloc(ctx, &d_pv, np));
+  CMX_TRY(tmp.alloc(ctx, &d_np, np));
+  CMX_TRY(run(d_aln, d_pv, d_np));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  CMX_TRY(download(ctx, pvalue, d_pv, np));
+  return download(ctx, nperm, d_np, np);
 }
 }  // namespace
 
@@ -349,41 +418,28 @@ cmx_status cmx_mica_permutation_test_masks_dev(cmx_ctx* ctx, int nalpha, int nta
                                                size_t pair_begin, size_t pair_end, double* d_pvalue, int32_t* d_nperm, void* stream) {
   if (!ctx) return CMX_ERR_INVALID;
   if (nalpha != 4 && nalpha != 20) return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: alphabet size must be 4 or 20 (other alphabets: cmx_mica_permutation_test_states)");
-  if (ntaxa < 2 || ntaxa > mica_perm_max_taxa())
-    return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: 2 <= ntaxa <= " + std::to_string(mica_perm_max_taxa()));
-  if (!d_aln || n < 2 || ld < n || max_perm == 0 || pair_end <= pair_begin || pair_end > n * (n - 1) / 2 || !d_pvalue || !d_nperm)
-    return fail(ctx, CMX_ERR_INVALID, "cmx_mica_permutation_test: bad arguments");
+  CMX_TRY(perm_taxa(ctx, "cmx_mica_permutation_test", ntaxa));
+  CMX_TRY(perm_args(ctx, "cmx_mica_permutation_test", d_aln, n, ld, max_perm, pair_begin, pair_end, d_pvalue, d_nperm));
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   PermCodes pc;
   CMX_TRY(perm_codes(ctx, nalpha, masks, nmasks, ntaxa, &pc));
-  uint16_t *d_cnt, *d_ext;
+  uint16_t *d_cnt, *d_ext, *d_order = nullptr;
   uint8_t *d_emap, *d_hasamb;
   uint32_t* d_tab;   // emask[32] | ewgt[32]
   int* d_bad;
-  long long* d_dF;
+  long long *d_dF, *d_F = nullptr;
   CMX_TRY(scratch(ctx, "perm_cnt", n * nalpha, &d_cnt));
   CMX_TRY(scratch(ctx, "perm_ext", n * 32, &d_ext));
   CMX_TRY(scratch(ctx, "perm_emap", 256, &d_emap));
   CMX_TRY(scratch(ctx, "perm_hasamb", n, &d_hasamb));
   CMX_TRY(scratch(ctx, "perm_tab", 64, &d_tab));
   CMX_TRY(scratch(ctx, "perm_bad", 2, &d_bad));
-  CMX_TRY(scratch(ctx, "perm_dF", ntaxa, &d_dF));
-  // resolved pairs: F[c] = round(c ln c * 2^40); the kernel accumulates F[c+1] - F[c] per increment of a joint count
-  // (sources owned by the context: a failing call further down must not free memory an upload still reads)
-  std::vector<long long>& dF = ctx->perm_dF_host;
-  dF.assign(ntaxa, 0);
-  long long prev = 0;
-  for (int c = 1; c <= ntaxa; ++c) {
-    const long long f = std::llround((double)c * std::log((double)c) * 1099511627776.0);
-    dF[c - 1] = f - prev;
-    prev = f;
-  }
+  CMX_TRY(perm_increments(ctx, "perm_dF", ntaxa, st, &d_dF));
   ctx->perm_tab_host.assign(256 + 64 * sizeof(uint32_t), 0);
   std::memcpy(ctx->perm_tab_host.data(), pc.emap, 256);
   std::memcpy(ctx->perm_tab_host.data() + 256, pc.emask, 32 * sizeof(uint32_t));
   std::memcpy(ctx->perm_tab_host.data() + 256 + 32 * sizeof(uint32_t), pc.ewgt, 32 * sizeof(uint32_t));
-  HIP_TRY(ctx, hipMemcpyAsync(d_dF, dF.data(), sizeof(long long) * ntaxa, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d_emap, ctx->perm_tab_host.data(), 256, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d_tab, ctx->perm_tab_host.data() + 256, sizeof(uint32_t) * 64, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemsetAsync(d_bad, 0, 2 * sizeof(int), st));
@@ -393,40 +449,18 @@ cmx_status cmx_mica_permutation_test_masks_dev(cmx_ctx* ctx, int nalpha, int nta
   HIP_TRY(ctx, hipStreamSynchronize(st));   // the one host decision of this call: are there pairs with unknowns at all
   int cus = 0;
   HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  const size_t npairs = pair_end - pair_begin;
-  bool preset = false;
   if (bad[0]) {
-    // pairs with gaps / unknowns / ambiguity codes (SiteTools::*(.., resolveUnknowns = true)): their own kernel, first
+    // pairs with gaps / unknowns / ambiguity codes (SiteTools::*(.., resolveUnknowns = true)): a kernel of their own, with
+    // the fixed-point table for m <= L^2 T and column i's visiting order
     if (mica_perm_general_lds(ntaxa, nalpha, bad[1]) == 0)
       return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test: " + std::to_string(ntaxa) + " taxa with " + std::to_string(bad[1]) +
                                             " distinct ambiguity codes in one column do not fit the LDS");
-    const size_t M = (size_t)pc.L * pc.L * (size_t)ntaxa;
-    long long* d_F;
-    uint16_t* d_order;
-    CMX_TRY(scratch(ctx, "perm_F", (M + 1), &d_F));
+    CMX_TRY(perm_table(ctx, ctx->perm_F, "perm_F", (size_t)pc.L * pc.L * (size_t)ntaxa, st, &d_F));
     CMX_TRY(scratch(ctx, "perm_order", n * (size_t)ntaxa, &d_order));
-    // F[m] = round(m ln m 2^sh), up to 2^26 entries with a logarithm each: built once per (L, taxa, shift) and kept on the
-    // device -- a caller that shards the pairs over several calls pays for it once.  (Built on the host with the oracle's
-    // logarithm so that the fixed-point sums, and with them every tie, are the oracle's.)
-    if (ctx->perm_F_L != pc.L || ctx->perm_F_T != ntaxa || ctx->perm_F_sh != pc.sh || ctx->perm_F_host.size() != M + 1) {
-      ctx->perm_F_sh = -1;
-      std::vector<long long>& F = ctx->perm_F_host;
-      F.assign(M + 1, 0);
-      const double scale = std::ldexp(1.0, pc.sh);
-      for (size_t m = 1; m <= M; ++m) F[m] = std::llround((double)m * std::log((double)m) * scale);
-      HIP_TRY(ctx, hipMemcpyAsync(d_F, F.data(), sizeof(long long) * (M + 1), hipMemcpyHostToDevice, st));
-      ctx->perm_F_L = pc.L; ctx->perm_F_T = ntaxa; ctx->perm_F_sh = pc.sh;
-    }
     HIP_TRY(ctx, launch_mica_colorder(d_aln, ntaxa, n, ld, nalpha, d_emap, d_ext, d_order, st));
-    if (!mica_perm_opening_fits(ntaxa, nalpha)) {
-      HIP_TRY(ctx, hipMemsetAsync(d_nperm, 0xFF, sizeof(int32_t) * npairs, st));   // -1: undecided, no hits (resolved pairs)
-      preset = true;
-    }
-    HIP_TRY(ctx, launch_mica_perm_general(d_aln, ntaxa, n, ld, nalpha, d_emap, d_ext, d_order, d_hasamb, d_tab, d_tab + 32, d_F, pc.L,
-                                          bad[1], max_perm, seed, pair_begin, pair_end, d_pvalue, d_nperm, cus, st));
   }
-  HIP_TRY(ctx, launch_mica_perm(d_aln, ntaxa, n, ld, nalpha, d_cnt, d_hasamb, d_dF, preset, max_perm, seed, pair_begin, pair_end,
-                                d_pvalue, d_nperm, cus, st));
+  HIP_TRY(ctx, launch_mica_perm(nalpha, ntaxa, d_aln, ld, n, d_cnt, d_hasamb, d_emap, d_ext, d_order, d_tab, d_tab + 32, d_dF, d_F, pc.L,
+                                bad[1], max_perm, seed, pair_begin, pair_end, d_pvalue, d_nperm, cus, st));
   return CMX_OK;
 }
 
@@ -442,21 +476,10 @@ cmx_status cmx_mica_permutation_test_masks(cmx_ctx* ctx, int nalpha, int ntaxa, 
                                            int32_t* nperm) {
   if (!ctx) return CMX_ERR_INVALID;
   if (!aln || n < 2 || ntaxa < 2 || !pvalue || !nperm) return fail(ctx, CMX_ERR_INVALID, "cmx_mica_permutation_test: bad arguments");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t np = n * (n - 1) / 2;
-  TmpDev tmp;
-  uint8_t* d_aln;
-  double* d_pv;
-  int32_t* d_np;
-  CMX_TRY(tmp.upload(ctx, &d_aln, aln, (size_t)ntaxa * n));
-  CMX_TRY(tmp.alloc(ctx, &d_pv, np));
-  CMX_TRY(tmp.alloc(ctx, &d_np, np));
-  cmx_status s = cmx_mica_permutation_test_masks_dev(ctx, nalpha, ntaxa, masks, nmasks, d_aln, n, n, max_perm, seed, 0, np, d_pv, d_np,
-                                                     nullptr);
-  if (s != CMX_OK) return s;
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  CMX_TRY(download(ctx, pvalue, d_pv, np));
-  return download(ctx, nperm, d_np, np);
+  return perm_host_call(ctx, ntaxa, aln, n, np, pvalue, nperm, [&](const uint8_t* d_aln, double* d_pv, int32_t* d_np) {
+    return cmx_mica_permutation_test_masks_dev(ctx, nalpha, ntaxa, masks, nmasks, d_aln, n, n, max_perm, seed, 0, np, d_pv, d_np, nullptr);
+  });
 }
 
 cmx_status cmx_mica_permutation_test(cmx_ctx* ctx, int nalpha, int ntaxa, const uint8_t* aln, size_t n, uint32_t max_perm,
@@ -469,9 +492,7 @@ cmx_status cmx_mica_permutation_test(cmx_ctx* ctx, int nalpha, int ntaxa, const 
 // entry is a later change.
 static cmx_status permw_shape(cmx_ctx* ctx, int nalpha, int ntaxa) {
   if (nalpha < 2 || nalpha > 64) return fail(ctx, CMX_ERR_INVALID, "cmx_mica_permutation_test_states: 2 <= alphabet size <= 64");
-  if (ntaxa < 2 || ntaxa > mica_permw_max_taxa())
-    return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_mica_permutation_test_states: 2 <= ntaxa <= " + std::to_string(mica_permw_max_taxa()));
-  return CMX_OK;
+  return perm_taxa(ctx, "cmx_mica_permutation_test_states", ntaxa);
 }
 
 cmx_status cmx_mica_permutation_test_states_dev(cmx_ctx* ctx, int nalpha, int ntaxa, const uint8_t* d_aln, size_t n, size_t ld,
@@ -482,8 +503,7 @@ cmx_status cmx_mica_permutation_test_states_dev(cmx_ctx* ctx, int nalpha, int nt
   if (!mica_wide(nalpha))
     return cmx_mica_permutation_test_masks_dev(ctx, nalpha, ntaxa, nullptr, 0, d_aln, n, ld, max_perm, seed, pair_begin, pair_end,
                                                d_pvalue, d_nperm, stream);
-  if (!d_aln || n < 2 || ld < n || max_perm == 0 || pair_end <= pair_begin || pair_end > n * (n - 1) / 2 || !d_pvalue || !d_nperm)
-    return fail(ctx, CMX_ERR_INVALID, "cmx_mica_permutation_test_states: bad arguments");
+  CMX_TRY(perm_args(ctx, "cmx_mica_permutation_test_states", d_aln, n, ld, max_perm, pair_begin, pair_end, d_pvalue, d_nperm));
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   const int A = nalpha, T = ntaxa;
@@ -496,46 +516,14 @@ cmx_status cmx_mica_permutation_test_states_dev(cmx_ctx* ctx, int nalpha, int nt
   CMX_TRY(scratch(ctx, "permw_flag", n, &d_flag));
   CMX_TRY(scratch(ctx, "permw_order", n * (size_t)T, &d_order));
   CMX_TRY(scratch(ctx, "permw_any", 1, &d_any));
-  CMX_TRY(scratch(ctx, "permw_dF", (size_t)T, &d_dF));
-  // resolved pairs: F[c] = round(c ln c * 2^40), kept as the increments F[c+1] - F[c] (host logarithm: the restatement's)
-  std::vector<long long>& dF = ctx->permw_dF_host;
-  dF.assign(T, 0);
-  long long prev = 0;
-  for (int c = 1; c <= T; ++c) {
-    const long long f = std::llround((double)c * std::log((double)c) * 1099511627776.0);
-    dF[c - 1] = f - prev;
-    prev = f;
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(d_dF, dF.data(), sizeof(long long) * T, hipMemcpyHostToDevice, st));
+  CMX_TRY(perm_increments(ctx, "permw_dF", T, st, &d_dF));
   HIP_TRY(ctx, hipMemsetAsync(d_any, 0, sizeof(int), st));
   HIP_TRY(ctx, launch_mica_permw_classify(A, T, d_aln, ld, n, d_end, d_unk, d_flag, d_order, d_any, st));
   int any = 0;
   HIP_TRY(ctx, hipMemcpyAsync(&any, d_any, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));   // the one host decision of this call: are there columns with unknowns at all
-  if (any) {
-    // F_g[m] = round(m ln m 2^sh) for m <= M = A^2 T (8.4 M entries at 64 states x 2 047 taxa): built once per (states,
-    // taxa, shift) and kept on the device
-    const size_t M = (size_t)A * A * (size_t)T;
-    const int sh = std::min(40, 62 - (int)std::ceil(std::log2((double)M * std::log((double)M))));
-    CMX_TRY(scratch(ctx, "permw_F", M + 1, &d_F));
-    std::vector<long long>& F = ctx->permw_F_host;
-    const bool built = ctx->permw_F_A == A && ctx->permw_F_T == T && ctx->permw_F_sh == sh && F.size() == M + 1;
-    if (!built) {
-      ctx->permw_F_sh = -1;
-      ctx->permw_F_allocs = 0;
-      F.assign(M + 1, 0);
-      const double scale = std::ldexp(1.0, sh);
-      for (size_t m = 1; m <= M; ++m) F[m] = std::llround((double)m * std::log((double)m) * scale);
-      ctx->permw_F_A = A; ctx->permw_F_T = T; ctx->permw_F_sh = sh;
-    }
-    // (the device copy is keyed by the buffer's allocation too: scratch starts over when it grows, and when the scratch
-    // guard is switched on after the context was created)
-    const size_t allocs = ctx->scratch["permw_F"].allocs;
-    if (ctx->permw_F_allocs != allocs) {
-      HIP_TRY(ctx, hipMemcpyAsync(d_F, F.data(), sizeof(long long) * (M + 1), hipMemcpyHostToDevice, st));
-      ctx->permw_F_allocs = allocs;
-    }
-  }
+  // the unknowns' table: m <= A^2 T (8.4 M entries at 64 states x 2 047 taxa)
+  if (any) CMX_TRY(perm_table(ctx, ctx->permw_F, "permw_F", (size_t)A * A * (size_t)T, st, &d_F));
   int cus = 0;
   HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
   HIP_TRY(ctx, launch_mica_permw(A, T, d_aln, ld, n, d_end, d_unk, d_flag, d_order, d_dF, d_F, max_perm, seed, pair_begin, pair_end,
@@ -547,19 +535,8 @@ cmx_status cmx_mica_permutation_test_states(cmx_ctx* ctx, int nalpha, int ntaxa,
                                             uint64_t seed, size_t pair_begin, size_t pair_end, double* pvalue, int32_t* nperm) {
   if (!ctx) return CMX_ERR_INVALID;
   CMX_TRY(permw_shape(ctx, nalpha, ntaxa));
-  if (!aln || n < 2 || max_perm == 0 || pair_end <= pair_begin || pair_end > n * (n - 1) / 2 || !pvalue || !nperm)
-    return fail(ctx, CMX_ERR_INVALID, "cmx_mica_permutation_test_states: bad arguments");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t np = pair_end - pair_begin;
-  TmpDev tmp;
-  uint8_t* d_aln;
-  double* d_pv;
-  int32_t* d_np;
-  CMX_TRY(tmp.upload(ctx, &d_aln, aln, (size_t)ntaxa * n));
-  CMX_TRY(tmp.alloc(ctx, &d_pv, np));
-  CMX_TRY(tmp.alloc(ctx, &d_np, np));
-  CMX_TRY(cmx_mica_permutation_test_states_dev(ctx, nalpha, ntaxa, d_aln, n, n, max_perm, seed, pair_begin, pair_end, d_pv, d_np, nullptr));
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  CMX_TRY(download(ctx, pvalue, d_pv, np));
-  return download(ctx, nperm, d_np, np);
+  CMX_TRY(perm_args(ctx, "cmx_mica_permutation_test_states", aln, n, n, max_perm, pair_begin, pair_end, pvalue, nperm));
+  return perm_host_call(ctx, ntaxa, aln, n, pair_end - pair_begin, pvalue, nperm, [&](const uint8_t* d_aln, double* d_pv, int32_t* d_np) {
+    return cmx_mica_permutation_test_states_dev(ctx, nalpha, ntaxa, d_aln, n, n, max_perm, seed, pair_begin, pair_end, d_pv, d_np, nullptr);
+  });
 }

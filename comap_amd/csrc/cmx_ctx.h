@@ -31,6 +31,15 @@ struct DevBuf {
   size_t allocs = 0;    // how often it was allocated: what a caller that keeps content across calls keys that content on
 };
 
+// F[m] = round(m ln m 2^sh), m <= M, of Mica's permutation test (perm_table, cmx_api_mica.cpp): up to 2^26 entries with a
+// logarithm each, so the host copy is kept per (M, sh) and the device copy per allocation of the scratch buffer that holds it
+struct PermTable {
+  std::vector<long long> host;
+  size_t M = 0;
+  int sh = -1;
+  size_t allocs = 0;    // DevBuf::allocs of the buffer `host` was uploaded to (0: none)
+};
+
 struct cmx_ctx {
   int device = 0;
   bool has_model = false;
@@ -62,15 +71,11 @@ struct cmx_ctx {
   std::vector<double> stat_w;
   double* d_stat_w = nullptr;
   // Mica's permutation test: host-side sources of its asynchronous table uploads (they must outlive the copies, also
-  // when a later call fails), and which (L, taxa, shift) the fixed-point table F on the device was built for
-  std::vector<long long> perm_dF_host, perm_F_host;
+  // when a later call fails), and the fixed-point table of each family's pairs with non-states (scratch "perm_F": 4 / 20
+  // states, "permw_F": the other alphabets -- a caller that alternates keeps both)
+  std::vector<long long> perm_dF_host;
   std::vector<uint8_t> perm_tab_host;
-  unsigned long long perm_F_L = 0;
-  int perm_F_T = 0, perm_F_sh = -1;
-  // the same for alphabets other than 4 / 20 states (cmx_mica_perm_wide.hip), under a key of their own: (states, taxa, shift) + the allocation of the device buffer
-  std::vector<long long> permw_dF_host, permw_F_host;
-  int permw_F_A = 0, permw_F_T = 0, permw_F_sh = -1;
-  size_t permw_F_allocs = 0;   // the allocation of scratch "permw_F" that holds the table of that key (0: none)
+  PermTable perm_F, permw_F;
   // cmx_intra_gram_prefetch_dev: the Gram blocks kept for the next cmx_intra_compact_range_dev with the same arguments
   struct GramKept { bool valid = false; int kind = 0; const double* counts = nullptr; size_t n = 0, ldc = 0, row_begin = 0, row_end = 0; const double* stat = nullptr; } gram_kept;
   const double *va_P = nullptr, *va_N1 = nullptr, *va_NC = nullptr;   // their operators, uploaded at first use

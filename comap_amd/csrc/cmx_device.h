@@ -254,24 +254,22 @@ hipError_t launch_ancestral(PlainArgs a, size_t nsites_total, double* scratch, c
 hipError_t launch_mica_average(const double* d_mi, size_t n, size_t ld, double* d_avg, double* d_full, hipStream_t stream);
 hipError_t launch_mica_zscore(int which, const double* d_mi, size_t n, size_t ld, const double* d_avg, const double* d_full,
                               const double* d_key, double* d_stat, double* d_outkey, hipStream_t stream);
-int mica_perm_max_taxa();
+// (cmx_mica_perm.hip) the permutation test for 4 / 20 states; the taxon limit of both families is mica_perm_max_taxa(),
+// cmx_mica_perm.h
 hipError_t launch_mica_colcount(const uint8_t* d_aln, int T, size_t n, size_t ld, int A, const uint8_t* d_emap, uint16_t* d_cnt,
                                 uint16_t* d_ext, uint8_t* d_hasamb, int* d_bad, hipStream_t stream);
 hipError_t launch_mica_colorder(const uint8_t* d_aln, int T, size_t n, size_t ld, int A, const uint8_t* d_emap, const uint16_t* d_ext,
                                 uint16_t* d_order, hipStream_t stream);
-bool mica_perm_opening_fits(int T, int A);   // the four-pairs-per-wave opening pass fits the LDS (else nperm must be preset to -1)
+// LDS of one wave of the kernel for pairs with non-states, `namb` distinct ones at most in a column (0: it does not fit one workgroup)
 size_t mica_perm_general_lds(int T, int A, int namb);
-hipError_t launch_mica_perm_general(const uint8_t* d_aln, int T, size_t n, size_t ld, int A, const uint8_t* d_emap,
-                                    const uint16_t* d_ext, const uint16_t* d_order, const uint8_t* d_hasamb, const uint32_t* d_emask,
-                                    const uint32_t* d_ewgt, const long long* d_F, uint32_t L, int namb, uint32_t max_perm, uint64_t seed,
-                                    size_t pair_begin, size_t pair_end, double* d_pvalue, int32_t* d_nperm, int cu_count,
-                                    hipStream_t stream);
-hipError_t launch_mica_perm(const uint8_t* d_aln, int T, size_t n, size_t ld, int A, const uint16_t* d_colcnt,
-                            const uint8_t* d_hasamb, const long long* d_dF, bool nperm_preset, uint32_t max_perm, uint64_t seed,
-                            size_t pair_begin, size_t pair_end, double* d_pvalue, int32_t* d_nperm, int cu_count, hipStream_t stream);
+// d_F: the fixed-point table of the pairs with non-states (L^2 T + 1 entries), or null when every column is resolved
+// (d_order, d_emask, d_ewgt, L, namb are not read then)
+hipError_t launch_mica_perm(int A, int T, const uint8_t* d_aln, size_t ld, size_t n, const uint16_t* d_colcnt, const uint8_t* d_hasamb,
+                            const uint8_t* d_emap, const uint16_t* d_ext, const uint16_t* d_order, const uint32_t* d_emask,
+                            const uint32_t* d_ewgt, const long long* d_dF, const long long* d_F, uint32_t L, int namb, uint32_t max_perm,
+                            uint64_t seed, size_t pair_begin, size_t pair_end, double* d_pvalue, int32_t* d_nperm, int cu_count,
+                            hipStream_t stream);
 // (cmx_mica_perm_wide.hip) the permutation test for alphabets other than 4 / 20 states: no mask table, codes >= A are unknowns
-int mica_permw_max_taxa();
-bool mica_permw_opening_fits(int T, int A);
 hipError_t launch_mica_permw_classify(int A, int T, const uint8_t* d_aln, size_t ld, size_t n, uint16_t* d_end, uint16_t* d_unk,
                                       uint8_t* d_flag, uint16_t* d_order, int* d_any, hipStream_t stream);
 // d_F: the fixed-point table of the unknowns' path (A^2 T + 1 entries), or null when no column has unknowns

@@ -1,9 +1,7 @@
 // Mica's permutation test (miTest, CoMap/Mica.cpp:93-118) for alphabets other than 4 / 20 states (2 .. 64: codon models).
-// The scheme is the one of cmx_mica_post.hip -- only column j is shuffled, by a forward Fisher-Yates from the counter RNG
-// (Philox4x32-10, key = seed, counter = (pair, pair >> 32, shuffle, 'P' << 24 | position / 4)); "MI of the shuffle >= MI" is
-// decided on a fixed-point sum over the joint table; one lane per shuffle, the stopping rule by ballot + popcount; an
-// opening pass of 16 shuffles for four pairs per wave -- specialised to the alphabet rule of cmx_mica_wide.hip: a code < A is
-// that state (63 included), every code >= A is THE unknown, there is no mask table.  What differs from the 4 / 20 kernels:
+// The scheme and its shared pieces are in cmx_mica_perm.h, here specialised to the alphabet rule of cmx_mica_wide.hip: a code
+// < A is that state (63 included), every code >= A is THE unknown, there is no mask table.  What differs from the 4 / 20
+// kernels (cmx_mica_perm.hip):
 //  * classification is a wave per column (64 counters do not fit a thread's registers) and leaves, per column, the end of
 //    every state's run in the visiting order (unknowns first, then the states ascending, stable), the unknowns, two flags and
 //    the visiting order itself;
@@ -19,37 +17,13 @@
 #include <algorithm>
 
 #include "cmx_device.h"
+#include "cmx_mica_perm.h"
 
 namespace cmx {
 
 namespace {
 
-constexpr int kPermwMaxTaxa = 2047;   // 16-bit positions and counts; the private column copies of 64 lanes in LDS
-constexpr int kPermwFirst = 16;       // shuffles of the opening pass
 constexpr int kPermwSeg = 128;        // bytes of a pair's run ends in LDS (64 states x 16 bits)
-
-// (the generator of cmx_mica_post.hip, restated: that file's device code stays as it is)
-__device__ __forceinline__ void permw_philox4(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t (&out)[4]) {
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// (i, j) of pair p in row-major (i < j) order: p = i n - i (i + 1) / 2 + (j - i - 1)
-__device__ __forceinline__ void permw_pair(size_t p, size_t n, size_t* pi, size_t* pj) {
-  size_t i = (size_t)((2.0 * n - 1.0 - sqrt((2.0 * n - 1.0) * (2.0 * n - 1.0) - 8.0 * (double)p)) / 2.0);
-  while (i > 0 && i * n - i * (i + 1) / 2 > p) --i;
-  while ((i + 1) * n - (i + 1) * (i + 2) / 2 <= p) ++i;
-  *pi = i;
-  *pj = p - (i * n - i * (i + 1) / 2) + i + 1;
-}
 
 constexpr unsigned kPermwUnknown = 1, kPermwConstant = 2;   // flag bits of a column
 
@@ -114,9 +88,8 @@ __global__ __launch_bounds__(64) void permw_classify_kernel(int A, int T, const 
   }
 }
 
-// bytes per lane of the private column copy (an odd number of words) and of 16-bit counters cleared with 64-bit stores
-// (an odd number of 8-byte chunks: the 16 lanes of a ds_write_b64 group fall on 16 different bank pairs)
-inline int permw_qstride(int T) { int sd = (T + 3) / 4; if (sd % 2 == 0) ++sd; return 4 * sd; }
+// bytes per lane of 16-bit counters cleared with 64-bit stores (an odd number of 8-byte chunks: the 16 lanes of a
+// ds_write_b64 group fall on 16 different bank pairs)
 inline int permw_cstride(int counters) { int c8 = (counters * 2 + 7) / 8; if (c8 % 2 == 0) ++c8; return 8 * c8; }
 
 __device__ __forceinline__ void permw_clear(uint16_t* cnt, int chunks) {
@@ -137,22 +110,6 @@ struct PermwArgs {
   int qstride, cstride, wave_bytes;
   uint32_t first;            // shuffles already done by the opening pass (0 if it was skipped)
 };
-
-// the sequential stopping rule on the results of `avail` shuffles done side by side (bit l of m: shuffle done + l reached the
-// observed value): the (5 - count)-th hit ends the test
-__device__ __forceinline__ bool permw_stop(unsigned long long m, uint32_t avail, uint32_t& done, uint32_t& count) {
-  const int need = 5 - (int)count;
-  if (__popcll(m) >= need) {
-    unsigned long long mm = m;
-    for (int z = 1; z < need; ++z) mm &= mm - 1;
-    done += (uint32_t)(__ffsll((long long)mm) - 1) + 1;
-    count = 5;
-    return true;
-  }
-  count += (uint32_t)__popcll(m);
-  done += avail;
-  return false;
-}
 
 // ---- resolved pairs.  G = 4: the opening pass (four pairs per wave, 16 shuffles each; an undecided pair leaves nperm =
 // -1 - hits); G = 1: one pair per wave, 64 shuffles per round, from shuffle a.first on.  Per pair in LDS: the run ends of
@@ -188,7 +145,7 @@ __global__ void permw_kernel(PermwArgs a) {
       done = a.first;
     }
     size_t i, j;
-    permw_pair(p, n, &i, &j);
+    perm_pair_of(p, n, &i, &j);
     const unsigned fl = (unsigned)a.flag[i] | (unsigned)a.flag[j];
     if (fl & kPermwUnknown) {          // decided by permw_general_kernel: nothing is written for it here
       open = false;
@@ -236,7 +193,7 @@ __global__ void permw_kernel(PermwArgs a) {
           if (t >= end) continue;
           permw_clear(cnt, clr);
           for (; t < end; ++t) {
-            if ((t & 3) == 0) permw_philox4(a.seed, (uint32_t)p, (uint32_t)((uint64_t)p >> 32), k, 0x50000000u | (uint32_t)(t >> 2), r);
+            if ((t & 3) == 0) perm_philox4(a.seed, (uint32_t)p, (uint32_t)((uint64_t)p >> 32), k, 0x50000000u | (uint32_t)(t >> 2), r);
             const int jj = t + (int)__umulhi(r[t & 3], (uint32_t)(T - t));
             const uint8_t vj = q[jj], vt = q[t];
             q[jj] = vt;                  // q[t] itself is not read again
@@ -249,16 +206,9 @@ __global__ void permw_kernel(PermwArgs a) {
       }
       const unsigned long long mw = __ballot(hit);
       const unsigned long long m = G == 1 ? mw : (mw >> (grp * LPG)) & ((1ull << LPG) - 1ull);
-      stop = permw_stop(m, min((uint32_t)LPG, a.max_perm - done), done, count);
+      stop = perm_stop(m, min((uint32_t)LPG, a.max_perm - done), done, count);
     } while (G == 1 && !stop && done < a.max_perm);
-    if (open && gl == 0) {
-      if (stop || done >= a.max_perm) {
-        a.pvalue[p - a.pair_begin] = (double)(count + 1) / (double)(done + 1);
-        a.nperm[p - a.pair_begin] = (int32_t)done;
-      } else {
-        a.nperm[p - a.pair_begin] = -1 - (int32_t)count;   // undecided after kPermwFirst shuffles
-      }
-    }
+    if (open && gl == 0) perm_write(a, p, stop, done, count);
   }
 }
 
@@ -278,7 +228,7 @@ __device__ __forceinline__ long long permw_general_eval(const PermwArgs& a, cons
     for (; t < end; ++t) {
       uint8_t vj;
       if (SHUF) {
-        if ((t & 3) == 0) permw_philox4(a.seed, (uint32_t)p, (uint32_t)((uint64_t)p >> 32), k, 0x50000000u | (uint32_t)(t >> 2), r);
+        if ((t & 3) == 0) perm_philox4(a.seed, (uint32_t)p, (uint32_t)((uint64_t)p >> 32), k, 0x50000000u | (uint32_t)(t >> 2), r);
         const int jj = t + (int)__umulhi(r[t & 3], (uint32_t)(T - t));
         vj = q[jj];
         q[jj] = q[t];
@@ -334,7 +284,7 @@ __global__ void permw_general_kernel(PermwArgs a) {
   const size_t n = a.n;
   for (size_t p = a.pair_begin + (size_t)blockIdx.x * nwaves + wave; p < a.pair_end; p += (size_t)gridDim.x * nwaves) {
     size_t i, j;
-    permw_pair(p, n, &i, &j);
+    perm_pair_of(p, n, &i, &j);
     const unsigned fl = (unsigned)a.flag[i] | (unsigned)a.flag[j];
     if (!(fl & kPermwUnknown)) continue;             // fully resolved pair: permw_kernel
     if (fl & kPermwConstant) {                       // Mica.cpp:100-104
@@ -354,37 +304,29 @@ __global__ void permw_general_kernel(PermwArgs a) {
       const uint32_t k = done + (uint32_t)lane;
       const long long s = permw_general_eval<true>(a, qbase, q, cnt, nu, seg, unk_i, p, k);
       const bool hit = k < a.max_perm && s >= sobs;
-      stop = permw_stop(__ballot(hit), min(64u, a.max_perm - done), done, count);
+      stop = perm_stop(__ballot(hit), min(64u, a.max_perm - done), done, count);
     } while (!stop && done < a.max_perm);
-    if (lane == 0) {
-      a.pvalue[p - a.pair_begin] = (double)(count + 1) / (double)(done + 1);
-      a.nperm[p - a.pair_begin] = (int32_t)done;
-    }
+    if (lane == 0) perm_write(a, p, stop, done, count);
   }
 }
 
-constexpr size_t kPermwLds = 160 * 1024;
-// LDS of one wave: the resolved kernel with G pairs per wave, the unknowns' kernel
+// LDS of one wave: the resolved kernel with G pairs per wave, the unknowns' kernel.  2 047 taxa x 64 states, the largest
+// shape, in bytes -- resolved, one pair per wave: 16 384 (dF) + 128 + 2 048 + 64 x 2 052 + 64 x 136 = 158 592; with unknowns:
+// 128 + 2 048 + 64 x 2 052 + 2 x 64 x 136 = 150 912; both below 163 840, so there is no smaller limit for either path.  The
+// opening pass (G = 4) adds three more columns and run ends: it fits up to 2 028 taxa.
 size_t permw_wave_bytes(int T, int A, int G) {
-  return ((size_t)G * (kPermwSeg + ((T + 7) & ~7)) + 64 * (size_t)permw_qstride(T) + 64 * (size_t)permw_cstride(A) + 15) & ~(size_t)15;
+  return ((size_t)G * (kPermwSeg + ((T + 7) & ~7)) + 64 * (size_t)perm_qstride(T) + 64 * (size_t)permw_cstride(A) + 15) & ~(size_t)15;
 }
 size_t permw_general_wave_bytes(int T, int A) {
-  return ((size_t)kPermwSeg + ((T + 7) & ~7) + 64 * (size_t)permw_qstride(T) + 2 * 64 * (size_t)permw_cstride(A + 1) + 15) & ~(size_t)15;
+  return ((size_t)kPermwSeg + ((T + 7) & ~7) + 64 * (size_t)perm_qstride(T) + 2 * 64 * (size_t)permw_cstride(A + 1) + 15) & ~(size_t)15;
 }
 size_t permw_dF_bytes(int T) { return ((size_t)T * 8 + 15) & ~(size_t)15; }
 
 }  // namespace
 
-int mica_permw_max_taxa() { return kPermwMaxTaxa; }
-
-// 2 047 taxa x 64 states, the largest shape, in bytes -- resolved, one pair per wave: 16 384 (dF) + 128 + 2 048 + 64 x 2 052
-// + 64 x 136 = 158 592; with unknowns: 128 + 2 048 + 64 x 2 052 + 2 x 64 x 136 = 150 912; both below 163 840, so there is no
-// smaller limit for either path.  The opening pass (G = 4) adds three more columns and run ends: it fits up to 2 028 taxa.
-bool mica_permw_opening_fits(int T, int A) { return permw_dF_bytes(T) + permw_wave_bytes(T, A, 4) <= kPermwLds; }
-
 hipError_t launch_mica_permw_classify(int A, int T, const uint8_t* d_aln, size_t ld, size_t n, uint16_t* d_end, uint16_t* d_unk,
                                       uint8_t* d_flag, uint16_t* d_order, int* d_any, hipStream_t stream) {
-  if (A < 2 || A > 64 || T < 2 || T > kPermwMaxTaxa) return hipErrorInvalidValue;
+  if (A < 2 || A > 64 || T < 2 || T > kPermMaxTaxa) return hipErrorInvalidValue;
   hipLaunchKernelGGL(permw_classify_kernel, dim3((unsigned)std::min<size_t>(n, (size_t)1 << 20)), dim3(64), 0, stream, A, T, d_aln, ld, n,
                      d_end, d_unk, d_flag, d_order, d_any);
   return hipGetLastError();
@@ -396,38 +338,24 @@ hipError_t launch_mica_permw(int A, int T, const uint8_t* d_aln, size_t ld, size
                              const uint8_t* d_flag, const uint16_t* d_order, const long long* d_dF, const long long* d_F,
                              uint32_t max_perm, uint64_t seed, size_t pair_begin, size_t pair_end, double* d_pvalue, int32_t* d_nperm,
                              int cu_count, hipStream_t stream) {
-  if (A < 2 || A > 64 || T < 2 || T > kPermwMaxTaxa || pair_end <= pair_begin) return hipErrorInvalidValue;
+  if (A < 2 || A > 64 || T < 2 || T > kPermMaxTaxa || pair_end <= pair_begin) return hipErrorInvalidValue;
   PermwArgs a{};
   a.aln = d_aln; a.T = T; a.n = n; a.ld = ld; a.A = A; a.end = d_end; a.unk = d_unk; a.order = d_order; a.flag = d_flag;
   a.dF = d_dF; a.F = d_F; a.max_perm = max_perm; a.seed = seed; a.pair_begin = pair_begin; a.pair_end = pair_end;
   a.pvalue = d_pvalue; a.nperm = d_nperm;
-  a.qstride = permw_qstride(T);
+  a.qstride = perm_qstride(T);
   const size_t npairs = pair_end - pair_begin;
-  // waves per workgroup: up to four within 150 KB; workgroups per CU by what is left of the 160 KB
-  auto go = [&](auto kern, size_t shared, size_t wave_bytes, int G) -> hipError_t {
-    if (shared + wave_bytes > kPermwLds) return hipErrorInvalidValue;
-    a.wave_bytes = (int)wave_bytes;
-    const int waves = (int)std::max<size_t>(1, std::min<size_t>(4, (150 * 1024 - shared) / wave_bytes));
-    const size_t lds = shared + (size_t)waves * wave_bytes;
-    const hipError_t e = mica_allow_lds(kern, lds);
-    if (e != hipSuccess) return e;
-    const size_t per_cu = std::max<size_t>(1, kPermwLds / lds);
-    const size_t units = (npairs + G - 1) / G;
-    const unsigned grid = (unsigned)std::min<size_t>((units + waves - 1) / waves, (size_t)cu_count * per_cu);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * waves), lds, stream, a);
-    return hipGetLastError();
-  };
-  const bool opening = mica_permw_opening_fits(T, A);
+  const bool opening = permw_dF_bytes(T) + permw_wave_bytes(T, A, 4) <= kPermLdsLimit;
   hipError_t e;
   if (!opening && (e = hipMemsetAsync(d_nperm, 0xFF, sizeof(int32_t) * npairs, stream)) != hipSuccess) return e;   // -1: undecided, no hits
   if (d_F) {
     a.cstride = permw_cstride(A + 1);
-    if ((e = go(&permw_general_kernel, 0, permw_general_wave_bytes(T, A), 1)) != hipSuccess) return e;
+    if ((e = perm_launch(&permw_general_kernel, a, 0, permw_general_wave_bytes(T, A), 1, npairs, cu_count, stream)) != hipSuccess) return e;
   }
   a.cstride = permw_cstride(A);
-  a.first = opening ? kPermwFirst : 0;
-  if (opening && (e = go(&permw_kernel<4>, permw_dF_bytes(T), permw_wave_bytes(T, A, 4), 4)) != hipSuccess) return e;
-  return go(&permw_kernel<1>, permw_dF_bytes(T), permw_wave_bytes(T, A, 1), 1);
+  a.first = opening ? kPermFirst : 0;
+  if (opening && (e = perm_launch(&permw_kernel<4>, a, permw_dF_bytes(T), permw_wave_bytes(T, A, 4), 4, npairs, cu_count, stream)) != hipSuccess) return e;
+  return perm_launch(&permw_kernel<1>, a, permw_dF_bytes(T), permw_wave_bytes(T, A, 1), 1, npairs, cu_count, stream);
 }
 
 }  // namespace cmx
