@@ -23,6 +23,20 @@ constexpr int mat_unit(int S) { return (S + max_ambig(S)) * leaf_row_stride(S); 
 // lane of the matrix-core layout needs from a row are contiguous.
 constexpr int leaf_col(int X, int dS) { return (X % 4) * (dS / 4) + X / 4; }
 
+// A packed SxS product operator is S/4 x S/4 tiles of 4x4 doubles, tile (bi, bj) at position bi * (S/4) + bj, element
+// (r, c) of a tile at 4 r + c (cmx_host_model.cpp: pack_blocks).  The two matrix instructions of the mapping walk read it
+// one double per lane:
+//   v_mfma_f64_4x4x4_4b    A slot of lane l = (row l & 3, column l >> 4) of one tile
+//   v_mfma_f64_16x16x4     A slot of lane l = (row l & 15, column l >> 4) of a 16x4 panel = four tiles of one tile column
+// The byte offset of lane l's A element for input tile i (columns 4 i .. 4 i + 3 of the operator, or of its transpose
+// with tr) of the panel of output rows 0 .. 15: a per-lane base plus a compile-time step.
+constexpr int mfma_a_tile_offset(int lane, bool tr) {   // inside a tile, both instructions
+  return (tr ? 4 * (lane >> 4) + (lane & 3) : 4 * (lane & 3) + (lane >> 4)) * 8;
+}
+constexpr int mfma16_a_offset(int lane, int i, bool tr, int S) {
+  return ((tr ? i * (S / 4) + ((lane & 15) >> 2) : ((lane & 15) >> 2) * (S / 4) + i) * 16) * 8 + mfma_a_tile_offset(lane, tr);
+}
+
 // A class block of HostModel::MAT / DevModel::MAT: per device class one run of count() matrices of mat_unit doubles.
 // `which` names an operator of a branch as in cmx_walk.h: OPER_P (< 0) = transition matrix, k >= 0 = count operator k.
 //   [0, NI)                        P of internal edges, 4x4-block packed (matrix-vector products), by operator slot

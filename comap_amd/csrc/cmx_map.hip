@@ -9,7 +9,8 @@
 //   (call sites CoMap/CoETools.cpp:397, CoMap/AnalysisTools.cpp:592-612; algorithm SURVEY.md A.2/A.3/A.6).
 //   The SxS operator of an edge is the same for all 64 lanes: every operator use of a class pass (products on
 //   internal edges, row gathers by observed symbol on leaf edges) is listed by the host in one op stream and staged
-//   in LDS by LDS-DMA one op ahead; products run on the matrix cores (v_mfma_f64_4x4x4_4b, 100 per 20x20 product) in
+//   in LDS by LDS-DMA one op ahead; products run on the matrix cores (v_mfma_f64_4x4x4_4b, 100 per 20x20 product; the
+//   64-site protein walk: 20 v_mfma_f64_16x16x4_f64 for states 0..15 and 20 v_mfma_f64_4x4x4_4b for states 16..19) in
 //   a layout where lane = (state inside a 4-state tile, site of a group of 16).
 //   Matrices are packed host-side in 4x4 blocks so that one copy serves both P.d (inside) and P^T.u (outside).
 //   Inside vectors / outside messages that must survive go to a per-wave HBM workspace as [S/2][lane][2]: every
@@ -197,6 +198,50 @@ template <int S, bool TR, bool DIAG>
 __device__ __forceinline__ constexpr int mfma_tile(int q) {
   return DIAG ? q : (TR ? (q % (S / 4)) * (S / 4) + q / (S / 4) : q);   // (DIAG: the host stores tile (q, q) at position q)
 }
+// ---- The 64-site protein walk (kMfma16) runs output states 0 .. 15 of a product on v_mfma_f64_16x16x4_f64.  Measured on
+// gfx950 (scripts/probe_mfma_f64_16x16x4.hip): A lane = (row l & 15, k l >> 4), B lane = (k l >> 4, column l & 15), D (lane,
+// register q) = (column l & 15, row (l >> 4) + 4 q).  With column = site of a group and k / row = state, B is the register
+// x of input tile i as it stands and the four D registers are states 4 q + (l >> 4), q = 0 .. 3, of the group: the walk's
+// layout with q = sb.  Per site group a product is a chain of five 16x16x4 over the input tiles (A = the 16x4 panel of the
+// operator, cmx_layout.h: mfma16_a_offset) and, for states 16 .. 19, the five 4x4x4_4b of output tile 4 as before: 20 + 20
+// matrix instructions and 10 operator reads instead of 100 and 25.  Both instructions have K = 4 and the chain over the input
+// tiles keeps its order: the same bits as 25 tile steps (the probe compares them).
+// The instruction wants a group's four results in consecutive registers and the 16-byte workspace accesses want pairs, so
+// an S-vector of this walk is named [g][sb 0 .. 3] followed by [sb 4][g]; every other instantiation keeps [sb][g].
+template <int S, int NG, bool DIAG>
+constexpr bool kMfma16 = S == 20 && NG == 4 && !DIAG;
+template <int S, int NG, bool DIAG>
+__device__ __forceinline__ constexpr int vreg(int sb, int g) {
+  return kMfma16<S, NG, DIAG> ? (sb < 4 ? g * 4 + sb : 16 + g) : sb * NG + g;
+}
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+// step i of such a product: input tile i into all five output tiles of the four site groups.  The operator elements of
+// step i + 1 are read before the eight matrix instructions of step i (4 x 64 + 4 x 16 cycles) that cover the read; a
+// group's next 16x16x4 comes eight matrix instructions after its previous one, so no accumulator is waited for.
+template <int S, bool TR, int I>
+__device__ __forceinline__ void mfma16_steps(const uint8_t* pan0, const uint8_t* tile0, double p0, double t0, const double (&x)[S],
+                                             d4 (&acc)[4], double (&y)[S]) {
+  constexpr int NB = S / 4;
+  if constexpr (I < NB) {
+    double p1 = 0.0, t1 = 0.0;
+    if constexpr (I + 1 < NB) {
+      p1 = *reinterpret_cast<const double*>(pan0 + mfma16_a_offset(0, I + 1, TR, S));
+      t1 = *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, false>((NB - 1) * NB + I + 1) * 128);
+      // (the reads stay in front of the statement, and this step's operands are its outputs: hipcc otherwise moves the
+      // step's matrix instructions in front of the reads and waits for them right behind)
+      asm volatile("" : "+v"(p0), "+v"(t0) :: "memory");
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const double xi = x[vreg<S, 4, false>(I, g)];
+      acc[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(p0, xi, I == 0 ? (d4){0.0, 0.0, 0.0, 0.0} : acc[g], 0, 0, 0);
+      y[vreg<S, 4, false>(NB - 1, g)] = __builtin_amdgcn_mfma_f64_4x4x4f64(t0, xi, I == 0 ? 0.0 : y[vreg<S, 4, false>(NB - 1, g)], 0, 0, 0);
+    }
+    mfma16_steps<S, TR, I + 1>(pan0, tile0, p1, t1, x, acc, y);
+  }
+}
+
 template <int S, bool TR, int NG, bool DIAG, int Q>
 __device__ __forceinline__ void mfma_steps(const uint8_t* tile0, double m0, double m1, double m2, const double (&x)[S / 4 * NG],
                                            double (&y)[S / 4 * NG]) {
@@ -224,9 +269,20 @@ __device__ __forceinline__ void matvec_stage(const uint8_t* buf, int lane, const
   // element (row r, column c) of a packed tile sits at (4 r + c) * 8; the A slot of lane l is row l & 3, column l >> 4
   // (transposed product: the transposed tile, i.e. row l >> 4, column l & 3)
   const uint8_t* tile0 = buf + (TR ? (4 * (lane >> 4) + (lane & 3)) : (4 * (lane & 3) + (lane >> 4))) * 8;
-  mfma_steps<S, TR, NG, DIAG, 0>(tile0, *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, DIAG>(0) * 128),
-                       NT > 1 ? *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, DIAG>(1) * 128) : 0.0,
-                       NT > 2 ? *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, DIAG>(2) * 128) : 0.0, x, y);
+  if constexpr (kMfma16<S, NG, DIAG>) {
+    const uint8_t* pan0 = buf + mfma16_a_offset(lane, 0, TR, S);
+    d4 acc[4];
+    mfma16_steps<S, TR, 0>(pan0, tile0, *reinterpret_cast<const double*>(pan0),
+                           *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, false>((S / 4 - 1) * (S / 4)) * 128), x, acc, y);
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int sb = 0; sb < 4; ++sb) y[vreg<S, NG, DIAG>(sb, g)] = acc[g][sb];
+  } else {
+    mfma_steps<S, TR, NG, DIAG, 0>(tile0, *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, DIAG>(0) * 128),
+                         NT > 1 ? *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, DIAG>(1) * 128) : 0.0,
+                         NT > 2 ? *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, DIAG>(2) * 128) : 0.0, x, y);
+  }
 }
 
 // Message of a leaf edge from the transposed operator staged in buf ([z][x] = M[x][z], rows >= S: ambiguity ids):
@@ -236,7 +292,7 @@ enum { LEAF_SET = 0, LEAF_MUL = 1, LEAF_DOT = 2 };
 // r[g]: the lane's values of site group g's row (rows are stored state-in-tile major: state 4 sb + s4 at position
 // s4 * NB + sb, cmx_layout.h: leaf_col).  Per site group the row values and their use: the reads of the next group do not
 // depend on anything computed for the previous one.
-template <int S, int MODE, int NG>
+template <int S, int MODE, int NG, bool DIAG>
 __device__ __forceinline__ double rows_apply(const double* const (&r)[NG], const double (&in)[S / 4 * NG], double (&out)[S / 4 * NG]) {
   constexpr int NB = S / 4;
   double part[NG];
@@ -248,9 +304,10 @@ __device__ __forceinline__ double rows_apply(const double* const (&r)[NG], const
     for (int sb = 0; sb < NB; ++sb) v[sb] = r[g][sb];
 #pragma unroll
     for (int sb = 0; sb < NB; ++sb) {
-      if (MODE == LEAF_SET) out[sb * NG + g] = v[sb];
-      else if (MODE == LEAF_MUL) out[sb * NG + g] = v[sb] * in[sb * NG + g];
-      else part[g] = __builtin_fma(in[sb * NG + g], v[sb], part[g]);
+      const int X = vreg<S, NG, DIAG>(sb, g);
+      if (MODE == LEAF_SET) out[X] = v[sb];
+      else if (MODE == LEAF_MUL) out[X] = v[sb] * in[X];
+      else part[g] = __builtin_fma(in[X], v[sb], part[g]);
     }
   }
   if (MODE != LEAF_DOT) return 0.0;
@@ -261,7 +318,7 @@ template <int S>
 __device__ __forceinline__ const double* stage_row(const uint8_t* buf, unsigned row, int lane) {
   return reinterpret_cast<const double*>(buf + row * (leaf_row_stride(S) * 8)) + (lane >> 4) * (S / 4);
 }
-template <int S, int MODE, int NG>
+template <int S, int MODE, int NG, bool DIAG>
 __device__ __forceinline__ double leaf_apply(const uint8_t* buf, const uint8_t* codes /* slot + 4 * (lane & 15) */, int lane,
                                              const double (&in)[S / 4 * NG], double (&out)[S / 4 * NG]) {
   // all symbols first (one LDS round trip): one dword per LANE in the slot, group g at 64 / NG * g
@@ -272,12 +329,12 @@ __device__ __forceinline__ double leaf_apply(const uint8_t* buf, const uint8_t* 
 #pragma unroll
   for (int g = 0; g < NG; ++g)
     r[g] = stage_row<S>(buf, code[g] < (unsigned)MatStage<S>::NROW ? code[g] : (unsigned)(MatStage<S>::NROW - 1), lane);
-  return rows_apply<S, MODE, NG>(r, in, out);
+  return rows_apply<S, MODE, NG, DIAG>(r, in, out);
 }
 
 // Row of a cherry table (cmx_walk.h): the row is named by the symbols of the cherry's two leaves, 4 * symbol(l1) + symbol(l2)
 // (fully resolved alignments only: both symbols are states of the 4-letter alphabet), the columns are a leaf row's.
-template <int S, int MODE, int NG>
+template <int S, int MODE, int NG, bool DIAG>
 __device__ __forceinline__ double cherry_apply(const uint8_t* buf, const uint8_t* codes1, const uint8_t* codes2, int lane,
                                                const double (&in)[S / 4 * NG], double (&out)[S / 4 * NG]) {
   unsigned c1[NG], c2[NG];
@@ -286,7 +343,7 @@ __device__ __forceinline__ double cherry_apply(const uint8_t* buf, const uint8_t
   const double* r[NG];
 #pragma unroll
   for (int g = 0; g < NG; ++g) r[g] = stage_row<S>(buf, ((c1[g] & 3u) << 2) | (c2[g] & 3u), lane);
-  return rows_apply<S, MODE, NG>(r, in, out);
+  return rows_apply<S, MODE, NG, DIAG>(r, in, out);
 }
 
 // ------------------------------------------------------------------------------------------------ small helpers
@@ -443,6 +500,8 @@ struct DevWalk {
     const int l = vlane();
     return NG == 4 ? l : (l & 15);
   }
+  // where an S-vector keeps state tile sb of site group g (vreg)
+  static constexpr int vr(int sb, int g) { return vreg<S, NG, DIAG>(sb, g); }
   template <int I>
   __device__ __forceinline__ double (&reg())[VL] {
     if constexpr (I == 0) return R0;
@@ -546,8 +605,8 @@ struct DevWalk {
     const int vl = vlane();
     const uint8_t* codes = cslot + os.par * kCodeSlotBytes + 4 * (vl & 15);
     double tot;
-    if constexpr (CHERRY) tot = cherry_apply<S, MODE, NG>(buf, codes, cslot2 + os.par * kCodeSlotBytes + 4 * (vl & 15), vl, reg<SRC>(), reg<DST>());
-    else tot = leaf_apply<S, MODE, NG>(buf, codes, vl, reg<SRC>(), reg<DST>());
+    if constexpr (CHERRY) tot = cherry_apply<S, MODE, NG, DIAG>(buf, codes, cslot2 + os.par * kCodeSlotBytes + 4 * (vl & 15), vl, reg<SRC>(), reg<DST>());
+    else tot = leaf_apply<S, MODE, NG, DIAG>(buf, codes, vl, reg<SRC>(), reg<DST>());
     asm volatile("" :: "v"(tot), "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
     op_end(nseq);
     return tot;
@@ -634,7 +693,7 @@ struct DevWalk {
     for (int sb = 0; sb < S / 4; ++sb) {
       const double pv = pi[(4 * sb + (vlane() >> 4)) % (S / FUSE)];
 #pragma unroll
-      for (int g = 0; g < NG; ++g) reg<D>()[sb * NG + g] = pv;
+      for (int g = 0; g < NG; ++g) reg<D>()[vr(sb, g)] = pv;
     }
   }
   template <int SRC> __device__ __forceinline__ void rootl() {
@@ -647,7 +706,7 @@ struct DevWalk {
       for (int sb = 0; sb < S / 4; ++sb) {
         const double pv = pi[4 * sb + (vlane() >> 4)];
 #pragma unroll
-        for (int g = 0; g < NG; ++g) p_[g] = __builtin_fma(pv, reg<SRC>()[sb * NG + g], p_[g]);
+        for (int g = 0; g < NG; ++g) p_[g] = __builtin_fma(pv, reg<SRC>()[vr(sb, g)], p_[g]);
       }
       Lg[0] = reduce_sites<NG>(p_);
     } else {   // one 4-state tile per fused class
@@ -656,7 +715,7 @@ struct DevWalk {
       for (int sb = 0; sb < FUSE; ++sb) {
         double p_[NG];
 #pragma unroll
-        for (int g = 0; g < NG; ++g) p_[g] = pv * reg<SRC>()[sb * NG + g];
+        for (int g = 0; g < NG; ++g) p_[g] = pv * reg<SRC>()[vr(sb, g)];
         Lg[sb] = reduce_sites<NG>(p_);
       }
     }
@@ -668,7 +727,7 @@ struct DevWalk {
 #pragma unroll
     for (int sb = 0; sb < S / 4; ++sb)
 #pragma unroll
-      for (int g = 0; g < NG; ++g) p_[g] = __builtin_fma(R3[sb * NG + g] * R1[sb * NG + g], R2[sb * NG + g], p_[g]);
+      for (int g = 0; g < NG; ++g) p_[g] = __builtin_fma(R3[vr(sb, g)] * R1[vr(sb, g)], R2[vr(sb, g)], p_[g]);
     part_store(row, pc * reduce_sites<NG>(p_));
   }
 };
