@@ -9,7 +9,9 @@
 //   (call sites CoMap/CoETools.cpp:397, CoMap/AnalysisTools.cpp:592-612; algorithm SURVEY.md A.2/A.3/A.6).
 //   The SxS operator of an edge is the same for all 64 lanes: every operator use of a class pass (products on
 //   internal edges, row gathers by observed symbol on leaf edges) is listed by the host in one op stream and staged
-//   in LDS by LDS-DMA one op ahead; products run on the matrix cores (v_mfma_f64_4x4x4_4b, 100 per 20x20 product; the
+//   in LDS by LDS-DMA one op ahead (an op requests the next op's operator and waits for its own; a product of the 64-site
+//   protein walk requests from the gaps between its first matrix instructions); products run on the matrix cores
+//   (v_mfma_f64_4x4x4_4b, 100 per 20x20 product; the
 //   64-site protein walk: 20 v_mfma_f64_16x16x4_f64 for states 0..15 and 20 v_mfma_f64_4x4x4_4b for states 16..19) in
 //   a layout where lane = (state inside a 4-state tile, site of a group of 16).
 //   Matrices are packed host-side in 4x4 blocks so that one copy serves both P.d (inside) and P^T.u (outside).
@@ -219,9 +221,26 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // step i of such a product: input tile i into all five output tiles of the four site groups.  The operator elements of
 // step i + 1 are read before the eight matrix instructions of step i (4 x 64 + 4 x 16 cycles) that cover the read; a
 // group's next 16x16x4 comes eight matrix instructions after its previous one, so no accumulator is waited for.
-template <int S, bool TR, int I>
+// REQ: the request of the NEXT op's operator, issued in the product's gaps (DevWalk::ProductRequest).  Slot 4 I + g lies
+// between the 16x16x4 of site group g in step I -- 64 cycles during which the matrix pipe takes nothing else from this
+// wave -- and the group's 4x4x4_4b; req.slot gets the accumulator the former wrote and the operand the latter reads.
+struct NoRequest {
+  template <int SLOT> __device__ __forceinline__ void slot(d4&, double&) {}
+};
+template <int S, int I, int G, class REQ>   // site groups G .. 3 of step I (a recursion: the slot is a template argument)
+__device__ __forceinline__ void mfma16_groups(double& p0, double& t0, const double (&x)[S], d4 (&acc)[4], double (&y)[S], REQ& req) {
+  if constexpr (G < 4) {
+    const double xi = x[vreg<S, 4, false>(I, G)];
+    double& y4 = y[vreg<S, 4, false>(S / 4 - 1, G)];
+    acc[G] = __builtin_amdgcn_mfma_f64_16x16x4f64(p0, xi, I == 0 ? (d4){0.0, 0.0, 0.0, 0.0} : acc[G], 0, 0, 0);
+    req.template slot<4 * I + G>(acc[G], t0);
+    y4 = __builtin_amdgcn_mfma_f64_4x4x4f64(t0, xi, I == 0 ? 0.0 : y4, 0, 0, 0);
+    mfma16_groups<S, I, G + 1>(p0, t0, x, acc, y, req);
+  }
+}
+template <int S, bool TR, int I, class REQ>
 __device__ __forceinline__ void mfma16_steps(const uint8_t* pan0, const uint8_t* tile0, double p0, double t0, const double (&x)[S],
-                                             d4 (&acc)[4], double (&y)[S]) {
+                                             d4 (&acc)[4], double (&y)[S], REQ& req) {
   constexpr int NB = S / 4;
   if constexpr (I < NB) {
     double p1 = 0.0, t1 = 0.0;
@@ -232,13 +251,8 @@ __device__ __forceinline__ void mfma16_steps(const uint8_t* pan0, const uint8_t*
       // step's matrix instructions in front of the reads and waits for them right behind)
       asm volatile("" : "+v"(p0), "+v"(t0) :: "memory");
     }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const double xi = x[vreg<S, 4, false>(I, g)];
-      acc[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(p0, xi, I == 0 ? (d4){0.0, 0.0, 0.0, 0.0} : acc[g], 0, 0, 0);
-      y[vreg<S, 4, false>(NB - 1, g)] = __builtin_amdgcn_mfma_f64_4x4x4f64(t0, xi, I == 0 ? 0.0 : y[vreg<S, 4, false>(NB - 1, g)], 0, 0, 0);
-    }
-    mfma16_steps<S, TR, I + 1>(pan0, tile0, p1, t1, x, acc, y);
+    mfma16_groups<S, I, 0>(p0, t0, x, acc, y, req);
+    mfma16_steps<S, TR, I + 1>(pan0, tile0, p1, t1, x, acc, y, req);
   }
 }
 
@@ -261,9 +275,9 @@ __device__ __forceinline__ void mfma_steps(const uint8_t* tile0, double m0, doub
 }
 
 // y = M x (TR = false) or y = M^T x (TR = true) with M = the packed matrix staged in buf (already landed)
-template <int S, bool TR, int NG, bool DIAG>
+template <int S, bool TR, int NG, bool DIAG, class REQ>
 __device__ __forceinline__ void matvec_stage(const uint8_t* buf, int lane, const double (&x)[S / 4 * NG],
-                                             double (&y)[S / 4 * NG]) {
+                                             double (&y)[S / 4 * NG], REQ& req) {
   static_assert(S % 4 == 0, "state count must be a multiple of 4");
   constexpr int NT = DIAG ? S / 4 : (S / 4) * (S / 4);
   // element (row r, column c) of a packed tile sits at (4 r + c) * 8; the A slot of lane l is row l & 3, column l >> 4
@@ -273,7 +287,7 @@ __device__ __forceinline__ void matvec_stage(const uint8_t* buf, int lane, const
     const uint8_t* pan0 = buf + mfma16_a_offset(lane, 0, TR, S);
     d4 acc[4];
     mfma16_steps<S, TR, 0>(pan0, tile0, *reinterpret_cast<const double*>(pan0),
-                           *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, false>((S / 4 - 1) * (S / 4)) * 128), x, acc, y);
+                           *reinterpret_cast<const double*>(tile0 + mfma_tile<S, TR, false>((S / 4 - 1) * (S / 4)) * 128), x, acc, y, req);
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -539,8 +553,15 @@ struct DevWalk {
                         "=v"(r[9]), "=v"(r[10]), "=v"(r[11]), "=v"(r[12]), "=v"(r[13]), "=v"(r[14]), "=v"(r[15]), "=v"(r[16]),
                         "=v"(r[17]), "=v"(r[18]), "=v"(r[19]));
   }
-  // One operator op: request the operator (and symbols) of the NEXT op of the stream -- entry mi + 1, or entry 0 of the
-  // next class / next site block -- into the other buffer, then wait for this op's operator.  Returns its buffer.
+  // One operator op has two halves.  The request: the operator (and symbols) of the NEXT op of the stream -- entry mi + 1,
+  // or entry 0 of the next class / next site block -- into the other buffer, and the stream entry two ops ahead.  The
+  // wait: for this op's operator; it returns its buffer.  op_begin requests, then waits: a leaf op has no matrix
+  // instructions to hide the request behind, and every product but those of the 64-site protein walk keeps this order.
+  // (One function on purpose: as two, op_request and op_wait, hipcc orders a few instructions of the request otherwise in
+  // thirteen kernels that are to keep their text.)  A product of the 64-site protein walk waits (op_wait), then requests
+  // from inside the product (ProductRequest).
+  // The request overwrites the other stage buffer and code slot, whose last readers are the LDS reads of the op before:
+  // op_begin waits for them (lgkmcnt(0)) first.
   __device__ __forceinline__ const uint8_t* op_begin(unsigned& nseq) {
     const bool more = (mi + 1 < nmv);
     const int emat = os.pre_mat, etx = os.pre_tx;
@@ -549,7 +570,16 @@ struct DevWalk {
     {
       const double* src = (more ? mat_c : mat_after) + emat;   // element offset, premultiplied on the host
       const uint32_t dst = lds_stage + (os.par ^ 1u) * MatStage<S>::BYTES;
-      if constexpr (kProductBytes == MatStage<S>::BYTES && kLeafBytes == MatStage<S>::BYTES) {
+      if constexpr (kMfma16<S, NG, DIAG>) {
+        // the 64-site protein walk addresses the rows as (wave-uniform base in SGPRs) + (16 x lane), here and in
+        // ProductRequest: no 64-bit address per lane.  Three full rows and a partial one, whatever the next op is.
+        static_assert(MatStage<S>::FULL == 3 && MatPart<kLeafBytes>::FULL == 3 && kProductBytes == MatStage<S>::BYTES, "rows of a request");
+        const int l = vlane();
+        const int tl = etx >= 0 ? MatPart<kLeafBytes>::TAIL : MatStage<S>::TAIL;
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
+        if (l < tl) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
+        issued = MatStage<S>::ROWS;
+      } else if constexpr (kProductBytes == MatStage<S>::BYTES && kLeafBytes == MatStage<S>::BYTES) {
         mat_dma_l<S>(src, dst, vlane());
         issued = MatStage<S>::ROWS;
       } else if (etx >= 0) {   // (wave-uniform: the next op is a leaf op -- or a cherry-table op)
@@ -585,17 +615,108 @@ struct DevWalk {
     nseq = os.vs;
     return stage + os.par * MatStage<S>::BYTES;
   }
+  // wait for this op's operator with nothing newly issued: what os.vs has counted since its request may stay in flight
+  __device__ __forceinline__ const uint8_t* op_wait() {
+    wait_vm<S, VL>((int)(os.vs - os.cur_seq));
+    return stage + os.par * MatStage<S>::BYTES;
+  }
   __device__ __forceinline__ void op_end(unsigned nseq) {
     os.par ^= 1u;
     os.cur_seq = nseq;
     ++mi;
   }
+  // ---- The request of a product of the 64-site protein walk (kMfma16), cut into six pieces that mfma16_steps places in
+  // its slots: behind a 16x16x4 the matrix pipe is busy for 64 cycles and the wave has nothing else to issue.  The pieces:
+  // the operator's three full DMA rows (0 .. 2), its last row under the exec mask (3), the symbols (4), the stream entry
+  // two ops ahead (5); req_slot says where each goes.  All of them sit in step 0: there the accumulators of the site
+  // groups behind the slot are not live yet, so the pieces' temporaries -- a lane offset, the symbols' 64-bit address --
+  // take registers nobody holds; from step 1 on they would come on top of the kernel's peak (DESIGN.md 4.1 has the counts).
+  // The rows are addressed as (wave-uniform base in SGPRs) + (16 x lane): no 64-bit address per lane.
+  // What op_begin requests, transfer for transfer, in another place; why each point holds there:
+  //  * DMA overwrite.  The pieces write the other stage buffer and code slot; their last readers are LDS reads of earlier
+  //    ops, all of them in front of op_wait's asm in program order (a "memory" clobber: no access moves across it), hence
+  //    issued before the product's first operand read.  Slot 0 lies behind the product's first matrix instruction, which
+  //    reads that operand: the wave has executed an lgkmcnt wait that covers it (lgkmcnt(0) if a scalar load is in
+  //    flight), and LDS reads return in order, so every earlier LDS read has returned.  No lgkmcnt(0) of our own is needed.
+  //  * Workspace loads in front of the product are counted in os.vs and stay in flight across op_wait as before.
+  //  * Scheduling.  A slot begins with an empty asm that names the accumulator the 16x16x4 in front of it wrote ("+v": it
+  //    cannot rise above that instruction) and the operand of the 4x4x4_4b behind it, as every DMA asm does (the 4x4x4_4b
+  //    cannot rise above them); volatile asm statements keep their order, and the lane index the address arithmetic
+  //    starts from is an output of the slot's first asm.  No asm reads the two registers.  The stream entry is a pair of
+  //    compiler-visible scalar loads, which hipcc places where it likes.
+  //  * M0.  Every piece that issues a DMA writes M0 itself.  Nothing else in a product reads or writes it: matrix
+  //    instructions, ds_read_b64 and VALU arithmetic do not use M0 on gfx950.
+  static constexpr int kReqPieces = 6;
+  static constexpr int req_slot(int piece) { return piece < 2 ? 0 : (piece < 4 ? 1 : piece - 2); }
+  static_assert(req_slot(kReqPieces - 1) < 4, "step 0");
+  struct ProductRequest {
+    DevWalk& w;
+    bool more;
+    int etx, tail;       // the next op's stream entry; lanes of its operator's last DMA row
+    unsigned issued;     // VMEM instructions of the request
+    const double* src;   // wave-uniform
+    uint32_t dst;
+    __device__ __forceinline__ explicit ProductRequest(DevWalk& w_) : w(w_) {
+      static_assert(kMfma16<S, NG, DIAG> && !kCherryTables && kProductBytes == MatStage<S>::BYTES, "the 64-site protein walk");
+      static_assert(MatStage<S>::FULL == 3 && MatPart<kLeafBytes>::FULL == 3 && MatStage<S>::TAIL > 0 && MatPart<kLeafBytes>::TAIL > 0,
+                    "three full rows and a partial one, whatever the next op is");
+      more = (w.mi + 1 < w.nmv);
+      etx = w.os.pre_tx;
+      src = (more ? w.mat_c : w.mat_after) + w.os.pre_mat;
+      dst = w.lds_stage + (w.os.par ^ 1u) * MatStage<S>::BYTES;
+      tail = etx >= 0 ? MatPart<kLeafBytes>::TAIL : MatStage<S>::TAIL;   // (a leaf op's operator may be shorter: kLeafBytes)
+      issued = MatStage<S>::ROWS;
+    }
+    template <int P, int SLOT>
+    __device__ __forceinline__ void piece(int l, d4& acc, double& t) {
+      if constexpr (req_slot(P) == SLOT) {
+        if constexpr (P < 3) {
+          asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %4 offset:%5"
+                       : "+v"(acc), "+v"(t) : "s"(dst), "v"(16 * l), "s"(src), "i"(P * 1024) : "memory");
+        } else if constexpr (P == 3) {
+          if (l < tail)
+            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
+        } else if constexpr (P == 4) {
+          if (etx >= 0 && (more || w.c + 1 < w.c_end)) {
+            code_dma_l(w.gcodes + (size_t)etx * w.gstride, w.lds_codes + (w.os.par ^ 1u) * kCodeSlotBytes);
+            issued += 1;
+          }
+        } else {
+          const int i2 = more ? w.mi + 2 : 1;   // as op_begin
+          w.os.pre_mat = w.cm.msched[2 * i2];
+          w.os.pre_tx = w.cm.msched[2 * i2 + 1];
+          w.os.vs += issued;
+        }
+      }
+    }
+    template <int SLOT>
+    __device__ __forceinline__ void slot(d4& acc, double& t) {
+      if constexpr (SLOT <= req_slot(kReqPieces - 1)) {
+        int l = w.lane;
+        if constexpr (SLOT <= req_slot(kReqPieces - 2)) asm volatile("" : "+v"(l), "+v"(acc), "+v"(t));   // (the stream entry alone: nothing to pin)
+        piece<0, SLOT>(l, acc, t);
+        piece<1, SLOT>(l, acc, t);
+        piece<2, SLOT>(l, acc, t);
+        piece<3, SLOT>(l, acc, t);
+        piece<4, SLOT>(l, acc, t);
+        piece<5, SLOT>(l, acc, t);
+      }
+    }
+  };
   template <int SRC, int DST, bool TR>
   __device__ __forceinline__ void mv(int, int) {
-    unsigned nseq;
-    const uint8_t* buf = op_begin(nseq);
-    matvec_stage<S, TR, NG, DIAG>(buf, vlane(), reg<SRC>(), reg<DST>()); asm volatile("" :: "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
-    op_end(nseq);
+    if constexpr (kMfma16<S, NG, DIAG>) {
+      const uint8_t* buf = op_wait();
+      ProductRequest req(*this);
+      matvec_stage<S, TR, NG, DIAG>(buf, vlane(), reg<SRC>(), reg<DST>(), req); asm volatile("" :: "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
+      op_end(os.vs);
+    } else {
+      unsigned nseq;
+      const uint8_t* buf = op_begin(nseq);
+      NoRequest req;
+      matvec_stage<S, TR, NG, DIAG>(buf, vlane(), reg<SRC>(), reg<DST>(), req); asm volatile("" :: "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
+      op_end(nseq);
+    }
   }
   // a leaf op, or a cherry-table op (cmx_walk.h): the table is staged like a leaf operator, its row named by two symbols
   template <bool CHERRY, int MODE, int SRC, int DST>
