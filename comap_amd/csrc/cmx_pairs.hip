@@ -125,6 +125,30 @@ __device__ __forceinline__ double pair_epilogue(int kind, int B, double g, doubl
   return __builtin_nan("");
 }
 
+// Compensation's sum (t1 + t2)^2 of one pair taken over the operand columns themselves, by a whole wave: lane = branch
+// mod 64, eight of a lane's branches per trip with their loads in flight together (a branch past B adds (0 + 0)^2),
+// then a butterfly sum.  Every lane returns the sum.  The value depends on the two columns only.
+__device__ __forceinline__ double comp_direct_wave(int lane, int B, const double* __restrict__ c1, size_t ldx1,
+                                                   const double* __restrict__ c2, size_t ldx2) {
+  double s3 = 0.0;
+  for (int b0 = lane; b0 < B; b0 += 8 * kWave) {
+    double x[8], y[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int b = b0 + u * kWave;
+      x[u] = c1[(size_t)(b < B ? b : 0) * ldx1];
+      y[u] = c2[(size_t)(b < B ? b : 0) * ldx2];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const double t = b0 + u * kWave < B ? x[u] + y[u] : 0.0;
+      s3 += t * t;
+    }
+  }
+  for (int off = 32; off; off >>= 1) s3 += __shfl_xor(s3, off);
+  return s3;
+}
+
 // One wave computes a 64x64 tile of G = X1^T-rows . X2-rows on v_mfma_f64_16x16x4_f64 (A[i][k]: lane = i + 16k,
 // C[row = (lane>>4) + 4r][col = lane & 15]); operands come straight from L2 (X is a few MB), prefetched one k-step
 // ahead; 16 MFMAs per 8 operand loads.
@@ -193,6 +217,7 @@ __global__ __launch_bounds__(4 * kWave) void pair_gram_kernel(int kind, int B, i
   // and column of the tile, not once per pair -- the same operations on the same operands, so the values do not
   // change, but 64 pairs per lane no longer repeat them (they were three quarters of the kernel's instructions).
   double sjv[4], rjv[4], fj[4];
+  unsigned long long redo = 0;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const size_t j = j0 + 16 * q + li;
@@ -213,11 +238,31 @@ __global__ __launch_bounds__(4 * kWave) void pair_gram_kernel(int kind, int B, i
         const size_t j = j0 + 16 * q + li;
         if (j < n2) {
           double v = pair_epilogue(kind, B, acc[p][q][r], si, sjv[q], ri, rjv[q], fi, fj[q]);
+          // (Compensation, signed totals: pairs whose s3 = si + sj + 2g cancels are redone below; bit = this pair)
+          if (kind == CMX_STAT_COMPENSATION && 2.0 * acc[p][q][r] < -0.5 * (si + sjv[q]) && !(intra != kPairRectangle && j <= irow0 + i))
+            redo |= 1ull << (16 * p + 4 * r + q);
           if (intra != kPairRectangle && j <= irow0 + i) v = nanv;
           out[i * ldo + j] = v;
         }
       }
     }
+  // Compensation forms sum (t1 + t2)^2 as si + sj + 2g.  With signed totals (g < 0) that cancels: near anti-parallel
+  // vectors lost every digit of it (1.0 for 1 - 4.9e-10; up to 7e-12 at 10 000 sites of configuration 4, enough to
+  // move the count of null values below the statistic for 0.07 % of its pairs).  Where the Gram form keeps less than half of
+  // si + sj the sum is taken over the operand columns themselves (comp_direct_wave).  A pair of non-negative totals has
+  // g >= 0 and never comes here.  Not in the epilogue above: a loop over b there keeps it from unrolling, and the
+  // accumulators then live in scratch.  The wave takes the marked pairs one at a time -- a lane alone would walk its B
+  // branches while 63 wait -- so the value depends on the pair only, not on its place in a tile, a row block or a rank.
+  // (Every lane of the wave is here: the returns above are per wave.)
+  for (unsigned long long live = __ballot(redo != 0); live; live &= live - 1) {
+    const int src = __builtin_ctzll(live);
+    for (unsigned long long m = __shfl(redo, src); m; m &= m - 1) {
+      const int bit = __builtin_ctzll(m);
+      const size_t i = i0 + 16 * (bit >> 4) + (src >> 4) + 4 * ((bit >> 2) & 3), j = j0 + 16 * (bit & 3) + (src & 15);   // i < n1, j < n2: marked there only
+      const double s3 = comp_direct_wave(lane, B, X1 + i, ldx1, X2 + j, ldx2);
+      if (lane == src) out[i * ldo + j] = 1.0 - sqrt(s3) / (pair_site_factor(kind, B, s1[i]) + pair_site_factor(kind, B, s2[j]));
+    }
+  }
 }
 
 constexpr int kEuclidRows = 8;

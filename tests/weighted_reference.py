@@ -149,6 +149,8 @@ def matrix_gram(kind, c1, w, c2=None, mv=None):
                 out = g
             elif kind == COMPENSATION:
                 s3 = np.maximum(s1[:, None] + s2[None, :] + 2 * g, 0.0)
+                direct = ((X1[:, None, :] + X2[None, :, :]) ** 2).sum(2)      # signed totals: where the identity cancels
+                s3 = np.where(2 * g < -0.5 * (s1[:, None] + s2[None, :]), direct, s3)
                 out = 1.0 - np.sqrt(s3) / (np.sqrt(s1)[:, None] + np.sqrt(s2)[None, :])
             else:     # correlation (centred operand) and cosinus: g / sqrt(s_i s_j)
                 out = g / (np.sqrt(s1)[:, None] * np.sqrt(s2)[None, :])
