@@ -456,6 +456,19 @@ cmx_status cmx_set_mapping_options(cmx_ctx* ctx, int average, int joint) {
   return CMX_OK;
 }
 
+// per-site likelihood scaling: host state only, read by the next mapping, null or ancestral-state call
+cmx_status cmx_set_likelihood_scaling(cmx_ctx* ctx, int on) {
+  CMX_TRY(need_model(ctx));
+  ctx->scaling = on != 0;
+  return CMX_OK;
+}
+
+cmx_status cmx_get_likelihood_scaling(const cmx_ctx* ctx, int32_t* on) {
+  if (!ctx || !on) return CMX_ERR_INVALID;
+  *on = ctx->scaling ? 1 : 0;
+  return CMX_OK;
+}
+
 // Statistic::setWeights / deleteWeights (CoMap/Statistics.h:83-104, 135-140): stored divided by their sum, in the
 // reference's summation order.  Validated before any device work; the device copy is written once here, after the
 // device has drained (a kernel of an earlier call on any stream may still read the previous weights).

@@ -37,6 +37,8 @@ static cmx_status upload_variant_operators(cmx_ctx* ctx) {
       CMX_TRY(upload(ctx, pi, &ctx->va_pi));
     }
   }
+  // the scaled default mapping at 4 / 20 states reads the joint counts too: at its first use, whatever was uploaded before
+  if (ctx->scaling && !ctx->va_PN) CMX_TRY(upload(ctx, h.PN, &ctx->va_PN));
   return CMX_OK;
 }
 
@@ -55,9 +57,10 @@ static PlainArgs plain_args(cmx_ctx* ctx, const MapIn& in) {
 
 // Does a mapping go through the plain stage (cmx_variants.hip)?  Other alphabets than 4 / 20 states: for any output.
 // 4 / 20 states: for the counts or the norms under a non-default option (cmx_set_mapping_options); the scalars stay the walk's.
+// With likelihood scaling (cmx_set_likelihood_scaling) the walk is not used: every alphabet, any output.
 static bool plain_stage_wanted(const cmx_ctx* ctx, const MapOut& out) {
   const bool counts = out.counts || out.norm;
-  if (ctx->hm.plain) return counts || out.logL || out.post_rate || out.rate_class;
+  if (ctx->hm.plain || ctx->scaling) return counts || out.logL || out.post_rate || out.rate_class;
   return counts && !(ctx->map_average && ctx->map_joint);
 }
 
@@ -74,11 +77,17 @@ static cmx_status map_plain(cmx_ctx* ctx, const MapIn& in, MapOut out, void* str
   PlainArgs a = plain_args(ctx, in);
   using M = PlainMode;
   a.mode = ctx->map_joint ? (ctx->map_average ? M::Joint : M::NoAvg) : (ctx->map_average ? M::Marginal : M::NoAvgMarginal);
-  if (h.plain) { a.logL = out.logL; a.post_rate = out.post_rate; a.rate_class = out.rate_class; }   // 4 / 20 states: the walk wrote them
+  if (h.plain || ctx->scaling) { a.logL = out.logL; a.post_rate = out.post_rate; a.rate_class = out.rate_class; }   // else (4 / 20 states) the walk wrote them
   a.chunk = plain_sites_per_pass(a.S, h.C, h.nn, in.nsites, kPlainMapScratchBytes, false);
   a.counts = out.counts; a.ldc = out.ldc;
   double* buf;
   CMX_TRY(scratch(ctx, full_grid ? "va_nodes_null" : "va_nodes_obs", plain_node_doubles(a.S, h.C, h.nn, a.chunk), &buf));
+  if (ctx->scaling) {   // the exponents beside the vectors, per caller like them
+    int32_t* exps;
+    CMX_TRY(scratch(ctx, full_grid ? "va_exps_null" : "va_exps_obs", plain_exponent_ints(h.C, h.nn, a.chunk), &exps));
+    HIP_TRY(ctx, launch_scaled_map(a, in.nsites, buf, exps, out.norm, (hipStream_t)stream));
+    return CMX_OK;
+  }
   HIP_TRY(ctx, launch_plain_map(a, in.nsites, buf, out.norm, (hipStream_t)stream));
   return CMX_OK;
 }
@@ -132,7 +141,8 @@ static cmx_status map_walk(cmx_ctx* ctx, const MapIn& in, const MapOut& out, voi
   return CMX_OK;
 }
 
-// a mapping: the walk at 4 / 20 states, then (or instead) the plain stage where it is wanted
+// a mapping: the walk at 4 / 20 states (unless the context scales its likelihoods), then (or instead) the plain stage where
+// it is wanted
 cmx_status map_sites_impl(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks, double* d_counts,
                           size_t ldc, double* d_logL, double* d_post_rate, int32_t* d_rate_class, double* d_norm, void* stream,
                           bool full_grid) {
@@ -145,7 +155,7 @@ cmx_status map_sites_impl(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, siz
     return fail(ctx, CMX_ERR_UNSUPPORTED, "cmx_map_sites: no ambiguity table for alphabets other than 4 / 20 states (codes >= nstates are unknowns)");
   const MapIn in{d_aln, nsites, ld, d_masks};
   const MapOut out{d_counts, ldc, d_norm, d_logL, d_post_rate, d_rate_class};
-  if (!ctx->hm.plain) CMX_TRY(map_walk(ctx, in, out, stream, full_grid));
+  if (!ctx->hm.plain && !ctx->scaling) CMX_TRY(map_walk(ctx, in, out, stream, full_grid));
   return plain_stage_wanted(ctx, out) ? map_plain(ctx, in, out, stream, full_grid) : CMX_OK;
 }
 
@@ -255,6 +265,12 @@ cmx_status cmx_ancestral_states_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t n
   a.chunk = plain_sites_per_pass(a.S, h.C, h.nn, nsites, kAsrScratchBytes, true);
   double* buf;
   CMX_TRY(scratch(ctx, "asr_nodes", plain_node_doubles(a.S, h.C, h.nn, a.chunk), &buf));
+  if (ctx->scaling) {
+    int32_t* exps;
+    CMX_TRY(scratch(ctx, "asr_exps", plain_exponent_ints(h.C, h.nn, a.chunk), &exps));
+    HIP_TRY(ctx, launch_scaled_ancestral(a, nsites, buf, exps, ctx->asr_inner, ctx->asr_n_inner, d_states, lds, d_post, ldp, (hipStream_t)stream));
+    return CMX_OK;
+  }
   HIP_TRY(ctx, launch_ancestral(a, nsites, buf, ctx->asr_inner, ctx->asr_n_inner, d_states, lds, d_post, ldp, (hipStream_t)stream));
   return CMX_OK;
 }

@@ -191,11 +191,12 @@ cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint
   CMX_TRY(check_kind(ctx, kind));
   if (rep_end <= rep_begin || rep_ram == 0 || !d_stat) return fail(ctx, CMX_ERR_INVALID, "cmx_null_intra: bad arguments");
   CMX_TRY(rng_range(ctx, (uint64_t)rep_end * 2 * rep_ram, "cmx_null_intra"));
-  if (!ctx->map_average || !ctx->map_joint || kind == CMX_STAT_DISCRETE_MI_BOUNDS || ctx->hm.plain || stat_weights(ctx, kind)) {
+  if (!ctx->map_average || !ctx->map_joint || kind == CMX_STAT_DISCRETE_MI_BOUNDS || ctx->hm.plain || stat_weights(ctx, kind) || ctx->scaling) {
     // nijt.average = no (AnalysisTools.cpp:598-610): the fused kernel only knows the averaged mapping; and a statistic that
     // needs a joint table per pair cannot be evaluated per lane inside the mapping wave.  The same simulate -> map ->
     // score sequence then runs unfused, which is what the two-data-set null does with both sides equal.  So does a
-    // statistic with branch weights (map_kernel's lanes score unweighted only).
+    // statistic with branch weights (map_kernel's lanes score unweighted only), and a context with likelihood scaling (the
+    // fused kernel is the unscaled walk).
     if (ctx->null_depth == 0) { ctx->null_mapped_host = 2 * (rep_end - rep_begin) * rep_ram; ctx->null_mapped_dev = false; }
     return null_unfused_dev(ctx, ctx, kind, params, seed, rep_begin, rep_end, rep_ram, d_supplied, d_stat, d_rcmin, d_prmin, d_nmin, stream);
   }

@@ -66,6 +66,9 @@ struct cmx_ctx {
   bool leaf_rows_custom = false;   // the leaf operators' ambiguity rows were built from a caller's mask table
   bool map_average = true;         // nijt.average (cmx_set_mapping_options); false: the no-averaging mapping of cmx_variants.hip
   bool map_joint = true;           // nijt.joint; false: the ...Marginal variants of cmx_variants.hip
+  // cmx_set_likelihood_scaling: every mapping, null and ancestral-state call goes through the scaled plain kernels
+  // (cmx_scaled.hip), the walk and the fused null are not used
+  bool scaling = false;
   // Statistic::setWeights (cmx_set_statistic_weights): the normalised branch weights, host copy + device copy (B doubles,
   // allocated at the first set); empty = unweighted
   std::vector<double> stat_w;
@@ -79,7 +82,7 @@ struct cmx_ctx {
   // cmx_intra_gram_prefetch_dev: the Gram blocks kept for the next cmx_intra_compact_range_dev with the same arguments
   struct GramKept { bool valid = false; int kind = 0; const double* counts = nullptr; size_t n = 0, ldc = 0, row_begin = 0, row_end = 0; const double* stat = nullptr; } gram_kept;
   const double *va_P = nullptr, *va_N1 = nullptr, *va_NC = nullptr;   // their operators, uploaded at first use
-  const double *va_PN = nullptr, *va_pi = nullptr;                     // plain path: joint counts and frequencies, padded
+  const double *va_PN = nullptr, *va_pi = nullptr;                     // plain path: joint counts and frequencies, padded (va_PN also: scaled mapping at 4 / 20 states)
   const int *va_first = nullptr, *va_next = nullptr;
   const int* asr_inner = nullptr;   // cmx_ancestral_states*: the internal nodes, ascending (uploaded at first use)
   int asr_n_inner = 0;

@@ -250,6 +250,15 @@ hipError_t launch_plain_map(PlainArgs a, size_t nsites_total, double* scratch, d
 // asr.method = marginal (cmx_ancestral_states*): states [n_inner][lds], optional posterior [n_inner][Sreal][ldp]
 hipError_t launch_ancestral(PlainArgs a, size_t nsites_total, double* scratch, const int* d_inner, int n_inner, uint8_t* d_states,
                             size_t lds, double* d_post, size_t ldp, hipStream_t stream);
+// computeNormForSite over branch-major counts [B*K][ldc] of n sites (what launch_plain_map ends with)
+hipError_t launch_counts_norm(const double* d_counts, size_t ldc, int B, int K, size_t n, double* d_norm, hipStream_t stream);
+// (cmx_scaled.hip) the same stage with per-site likelihood scaling (cmx_set_likelihood_scaling): `scratch` as above, and
+// plain_exponent_ints(a.C, a.nn, a.chunk) int32 exponents of the inside and outside vectors in `exps`.  Every mode and the
+// site scalars at 4, 20 and kPlainStates states.
+size_t plain_exponent_ints(int C, int nn, size_t chunk);
+hipError_t launch_scaled_map(PlainArgs a, size_t nsites_total, double* scratch, int32_t* exps, double* d_norm, hipStream_t stream);
+hipError_t launch_scaled_ancestral(PlainArgs a, size_t nsites_total, double* scratch, int32_t* exps, const int* d_inner, int n_inner,
+                                   uint8_t* d_states, size_t lds, double* d_post, size_t ldp, hipStream_t stream);
 // (cmx_mica_post.hip) Mica post-processing
 hipError_t launch_mica_average(const double* d_mi, size_t n, size_t ld, double* d_avg, double* d_full, hipStream_t stream);
 hipError_t launch_mica_zscore(int which, const double* d_mi, size_t n, size_t ld, const double* d_avg, const double* d_full,

@@ -359,11 +359,14 @@ hipError_t launch_plain_map(PlainArgs a, size_t nsites_total, double* scratch, d
     plain_passes<S>(a, nsites_total, scratch, a.counts != nullptr, stream, [&](const PlainArgs& pass, unsigned gx) {
       hipLaunchKernelGGL(mode_kernel, dim3(gx, pass.B), dim3(256), 0, stream, pass);
     });
-    if (d_norm && a.counts)
-      hipLaunchKernelGGL(counts_norm_kernel, dim3((unsigned)((nsites_total + 255) / 256)), dim3(256), 0, stream, a.counts, a.ldc,
-                         a.B, a.K, nsites_total, d_norm);
+    if (d_norm && a.counts) return launch_counts_norm(a.counts, a.ldc, a.B, a.K, nsites_total, d_norm, stream);
     return hipGetLastError();
   });
+}
+
+hipError_t launch_counts_norm(const double* d_counts, size_t ldc, int B, int K, size_t n, double* d_norm, hipStream_t stream) {
+  hipLaunchKernelGGL(counts_norm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_counts, ldc, B, K, n, d_norm);
+  return hipGetLastError();
 }
 
 // asr.method = marginal: the inside and outside kernels of the mapping, unchanged, then ancestral_kernel per pass (a's model

@@ -49,7 +49,7 @@ COUNT_EXPECTED, COUNT_NAIVE = 0, 1
 
 EXPORTS = [
     "cmx_version", "cmx_ctx_create", "cmx_ctx_destroy", "cmx_last_error", "cmx_get_info",
-    "cmx_get_transition_matrices", "cmx_synchronize", "cmx_debug_walk", "cmx_map_sites", "cmx_set_mapping_options", "cmx_set_statistic_weights", "cmx_get_statistic_weights", "cmx_map_sites_dev", "cmx_ancestral_states", "cmx_ancestral_states_dev", "cmx_simulate", "cmx_simulate_dev", "cmx_simulate_continuous",
+    "cmx_get_transition_matrices", "cmx_synchronize", "cmx_debug_walk", "cmx_map_sites", "cmx_set_mapping_options", "cmx_set_likelihood_scaling", "cmx_get_likelihood_scaling", "cmx_set_statistic_weights", "cmx_get_statistic_weights", "cmx_map_sites_dev", "cmx_ancestral_states", "cmx_ancestral_states_dev", "cmx_simulate", "cmx_simulate_dev", "cmx_simulate_continuous",
     "cmx_simulate_continuous_dev", "cmx_null_intra_continuous", "cmx_null_intra_continuous_dev", "cmx_mi_pairs_dev",
     "cmx_pair_stats", "cmx_pair_stats_dev", "cmx_null_intra", "cmx_null_simulate_dev", "cmx_null_intra_dev", "cmx_null_inter",
     "cmx_null_inter_dev", "cmx_intra_pvalues", "cmx_intra_rows", "cmx_intra_rows_dev", "cmx_intra_rows_range_dev",
@@ -436,6 +436,19 @@ class Engine:
         """nijt.average / nijt.joint (CoETools.cpp:393-406): which of computeSubstitutionVectors{, NoAveraging, Marginal,
         NoAveragingMarginal} every later mapping of this engine (observed data and nulls) uses; default (True, True)."""
         self._check(self._lib.cmx_set_mapping_options(self._ctx, int(bool(average)), int(bool(joint))))
+
+    def set_likelihood_scaling(self, on=True):
+        """cmx_set_likelihood_scaling: per-site power-of-two scaling of the conditional likelihoods in every later mapping,
+        null and ancestral-state call of this engine, for trees whose site likelihoods leave fp64's range (several
+        hundred taxa: logL = -inf and NaN counts without it).  Default off; on, the mapping runs through the plain
+        kernels and the null unfused."""
+        self._check(self._lib.cmx_set_likelihood_scaling(self._ctx, int(bool(on))))
+
+    def likelihood_scaling(self):
+        """whether this engine scales its likelihoods (cmx_get_likelihood_scaling)"""
+        on = ctypes.c_int32(0)
+        self._check(self._lib.cmx_get_likelihood_scaling(self._ctx, ctypes.byref(on)))
+        return bool(on.value)
 
     def set_null_patterns(self, on=None):
         """cmx_set_null_patterns: the fused null maps each distinct simulated column once (True), every site of every pair

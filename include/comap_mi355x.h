@@ -187,6 +187,22 @@ cmx_status cmx_map_sites_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, 
  * ancestral states -- through plain (slow) kernels; the null then runs unfused.  Likelihood, posterior rate and rate
  * class do not depend on the variant.  Parity unpinned: bpp-phyl is not in the reference tree. */
 cmx_status cmx_set_mapping_options(cmx_ctx* ctx, int average, int joint);
+/* Per-site likelihood scaling, for trees beyond fp64's range.  The conditional likelihoods are plain fp64 without
+ * rescaling, as in the reference's legacy DR classes, so a site likelihood underflows to 0 somewhere between 300 and 600
+ * taxa (the reference only warns: "saturated" likelihoods, CoMap/CoETools.cpp:235-262); then logL = -inf and the counts,
+ * the posterior rate and everything built on them are NaN.  on != 0: every later cmx_map_sites* (all four mapping options,
+ * any alphabet), cmx_ancestral_states* and every pipeline of this context that maps simulated sites (cmx_null_intra* also
+ * continuous, cmx_null_inter*, cmx_cluster_null, cmx_candidate_groups, the norms of cmx_mica_parametric_null) keeps a
+ * power-of-two exponent per (rate class, node, site) beside its conditional vectors, and is defined wherever the true
+ * likelihood is positive, however small: logL = ln(mantissa) + exponent ln 2 is finite.  Only powers of two are applied,
+ * so where the unscaled computation meets no underflow or subnormal the results are the same up to rounding of the class
+ * sums.  A site whose likelihood is exactly 0 (data impossible under the model) keeps logL = -inf, NaN counts, state 0.
+ * Price: the mapping runs through plain kernels instead of the matrix-core walk and the null runs unfused (DESIGN.md
+ * 4.5.5).  Per context, default 0, may be flipped between calls like the mapping options; host state only.  A tree whose
+ * walk workspaces do not fit at cmx_ctx_create stays out of reach either way.  ctx == NULL (or on == NULL):
+ * CMX_ERR_INVALID. */
+cmx_status cmx_set_likelihood_scaling(cmx_ctx* ctx, int on);
+cmx_status cmx_get_likelihood_scaling(const cmx_ctx* ctx, int32_t* on);
 
 /* ---- marginal ancestral state reconstruction (asr.method = marginal, CoMap/CoMap.cpp:169-197:
  * LegacyMarginalAncestralStateReconstruction::getAncestralSequences / getAncestralStatesForNode).  For every internal node

@@ -166,6 +166,15 @@ class Engine {
   // computeSubstitutionVectorsNoAveraging from here on (observed data and nulls; what nijt = Label with the MI statistic
   // needs, CoETools.cpp:577-588); joint = no selects the two ...Marginal variants (CoETools.cpp:399-405).
   void setMappingOptions(bool average, bool joint) { check(cmx_set_mapping_options(ctx_, average ? 1 : 0, joint ? 1 : 0)); }
+  // Per-site likelihood scaling (cmx_set_likelihood_scaling): switch it on where CoETools.cpp:235-262 would report saturated
+  // likelihoods (several hundred sequences); every later mapping, null and ancestral-state call is then range-safe, through
+  // plain kernels.  Default off.
+  void setLikelihoodScaling(bool on) { check(cmx_set_likelihood_scaling(ctx_, on ? 1 : 0)); }
+  bool getLikelihoodScaling() const {
+    int32_t on = 0;
+    check(cmx_get_likelihood_scaling(ctx_, &on));
+    return on != 0;
+  }
   // simulations.continuous = yes (CoMap.cpp:146, 213: seqSim->enableContinuousRates(true)): n simulated sites [taxon][site]
   // with global site indices g0 .. g0 + n - 1, every site with its own rate from the continuous Gamma(alpha, alpha)
   // (+ invariant mass pInvariant); the drawn rates are returned in *rates when given
