@@ -19,6 +19,17 @@ static std::vector<double> pad_mats(const std::vector<double>& m, int S, int SP)
   return o;
 }
 
+// 64 x 64 row-major matrices packed for the wide mapping (wide_op_offset, cmx_layout.h), or their transposes
+static std::vector<double> pack_wide(const std::vector<double>& m, bool transpose) {
+  constexpr int SP = kPlainStates;
+  std::vector<double> o(m.size());
+  for (size_t q = 0; q < m.size() / ((size_t)SP * SP); ++q)
+    for (int x = 0; x < SP; ++x)
+      for (int y = 0; y < SP; ++y)
+        o[q * SP * SP + (transpose ? wide_op_offset(y, x) : wide_op_offset(x, y))] = m[(q * SP + x) * SP + y];
+  return o;
+}
+
 // the operators of the plain kernels (cmx_variants.hip), uploaded at the first use by the mapping variants or by the
 // ancestral states (padded with zeros to kPlainStates on the plain path)
 static cmx_status upload_variant_operators(cmx_ctx* ctx) {
@@ -33,8 +44,12 @@ static cmx_status upload_variant_operators(cmx_ctx* ctx) {
     if (h.plain) {
       std::vector<double> pi(SD, 0.0);
       std::copy(h.pi.begin(), h.pi.end(), pi.begin());
-      CMX_TRY(upload(ctx, pad_mats(h.PN, h.S, SD), &ctx->va_PN));
+      const std::vector<double> P = pad_mats(h.P, h.S, SD), PN = pad_mats(h.PN, h.S, SD);
+      CMX_TRY(upload(ctx, PN, &ctx->va_PN));
       CMX_TRY(upload(ctx, pi, &ctx->va_pi));
+      CMX_TRY(upload(ctx, pack_wide(P, false), &ctx->va_wide.P));
+      CMX_TRY(upload(ctx, pack_wide(P, true), &ctx->va_wide.PT));
+      CMX_TRY(upload(ctx, pack_wide(PN, false), &ctx->va_wide.PN));
     }
   }
   // the scaled default mapping at 4 / 20 states reads the joint counts too: at its first use, whatever was uploaded before
@@ -88,9 +103,19 @@ static cmx_status map_plain(cmx_ctx* ctx, const MapIn& in, MapOut out, void* str
     HIP_TRY(ctx, launch_scaled_map(a, in.nsites, buf, exps, out.norm, (hipStream_t)stream));
     return CMX_OK;
   }
+  // the default mapping of the plain path's alphabets: the matrix-core kernels of cmx_map_wide.hip, unless
+  // cmx_debug_map_wide_plain forces the plain ones (read at each call)
+  if (h.plain && a.mode == M::Joint && !map_wide_plain(-1)) {
+    double* part;
+    CMX_TRY(scratch(ctx, full_grid ? "va_part_null" : "va_part_obs", wide_part_doubles(h.C, h.B, h.K, a.chunk), &part));
+    HIP_TRY(ctx, launch_wide_map(a, ctx->va_wide, in.nsites, buf, part, out.norm, (hipStream_t)stream));
+    return CMX_OK;
+  }
   HIP_TRY(ctx, launch_plain_map(a, in.nsites, buf, out.norm, (hipStream_t)stream));
   return CMX_OK;
 }
+
+int cmx_debug_map_wide_plain(int on) { return map_wide_plain(on); }
 
 // ------------------------------------------------------------------------------------------------ mapping
 // The matrix-core walk of a 4- or 20-state mapping (cmx_map.hip).  full_grid: use the whole-chip workspace of the null launches

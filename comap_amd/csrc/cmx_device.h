@@ -252,6 +252,21 @@ hipError_t launch_ancestral(PlainArgs a, size_t nsites_total, double* scratch, c
                             size_t lds, double* d_post, size_t ldp, hipStream_t stream);
 // computeNormForSite over branch-major counts [B*K][ldc] of n sites (what launch_plain_map ends with)
 hipError_t launch_counts_norm(const double* d_counts, size_t ldc, int B, int K, size_t n, double* d_norm, hipStream_t stream);
+// the site scalars of one pass of the plain path (site_scalars_kernel on the root's a.D; a.S == kPlainStates), for the wide mapping
+hipError_t launch_plain_site_scalars(const PlainArgs& pass, hipStream_t stream);
+// (cmx_map_wide.hip) PlainMode::Joint and the site scalars at kPlainStates states on the f64 matrix instruction: the pass
+// structure, the scratch and the arithmetic of launch_plain_map, which it replaces by default for contexts without likelihood
+// scaling.  Operators packed by wide_op_offset (cmx_layout.h), uploaded beside the plain ones.
+struct WideOps {
+  const double* P;    // [C][B][S*S] transition matrices
+  const double* PT;   // [C][B][S*S] their transposes
+  const double* PN;   // [C][B][K][S*S] joint counts P o N^k
+};
+int map_wide_plain(int on);   // cmx_debug_map_wide_plain: set (on >= 0) / query, returns the previous state
+// part: wide_part_doubles(a.C, a.B, a.K, a.chunk) doubles, the per-class partial counts [C][B*K][chunk] and the likelihoods [chunk]
+size_t wide_part_doubles(int C, int B, int K, size_t chunk);
+hipError_t launch_wide_map(PlainArgs a, const WideOps& o, size_t nsites_total, double* scratch, double* part, double* d_norm,
+                           hipStream_t stream);
 // (cmx_scaled.hip) the same stage with per-site likelihood scaling (cmx_set_likelihood_scaling): `scratch` as above, and
 // plain_exponent_ints(a.C, a.nn, a.chunk) int32 exponents of the inside and outside vectors in `exps`.  Every mode and the
 // site scalars at 4, 20 and kPlainStates states.

@@ -37,6 +37,36 @@ constexpr int mfma16_a_offset(int lane, int i, bool tr, int S) {
   return ((tr ? i * (S / 4) + ((lane & 15) >> 2) : ((lane & 15) >> 2) * (S / 4) + i) * 16) * 8 + mfma_a_tile_offset(lane, tr);
 }
 
+// The operators of the wide mapping (cmx_map_wide.hip: the default mapping of the plain path's alphabets, kPlainStates x
+// kPlainStates, on v_mfma_f64_16x16x4).  With column = site and k = row = state, the A operand of output panel p (rows 16 p ..
+// 16 p + 15) and k-step i (columns 4 i .. 4 i + 3) is (row 16 p + (l & 15), column 4 i + (l >> 4)) in lane l.  Packed, that is
+// double l of the 64 consecutive doubles of (p, i): one coalesced 512-byte read per wave and step.  The host packer
+// (cmx_api_map.cpp: pack_wide) and the kernels both place an element with this one function.
+constexpr int wide_op_offset(int row, int col) {
+  return ((row >> 4) * (kPlainStates / 4) + (col >> 2)) * 64 + (col & 3) * 16 + (row & 15);
+}
+constexpr bool wide_op_offset_is_bijection() {
+  bool seen[kPlainStates * kPlainStates] = {};
+  for (int r = 0; r < kPlainStates; ++r)
+    for (int c = 0; c < kPlainStates; ++c) {
+      const int o = wide_op_offset(r, c);
+      if (o < 0 || o >= kPlainStates * kPlainStates || seen[o]) return false;
+      seen[o] = true;
+    }
+  return true;
+}
+// what the kernels rely on: lane l's element of step (p, i) lies at (step's first double) + l
+constexpr bool wide_op_offset_is_lane_major() {
+  for (int p = 0; p < kPlainStates / 16; ++p)
+    for (int i = 0; i < kPlainStates / 4; ++i)
+      for (int l = 0; l < 64; ++l)
+        if (wide_op_offset(16 * p + (l & 15), 4 * i + (l >> 4)) != wide_op_offset(16 * p, 4 * i) + l) return false;
+  return true;
+}
+static_assert(kPlainStates == 64, "wide_op_offset: four panels of sixteen k-steps");
+static_assert(wide_op_offset_is_bijection(), "wide_op_offset must be a bijection onto 64 x 64");
+static_assert(wide_op_offset_is_lane_major() && wide_op_offset(0, 0) == 0, "a step's A operand is 64 consecutive doubles, lane-major");
+
 // A class block of HostModel::MAT / DevModel::MAT: per device class one run of count() matrices of mat_unit doubles.
 // `which` names an operator of a branch as in cmx_walk.h: OPER_P (< 0) = transition matrix, k >= 0 = count operator k.
 //   [0, NI)                        P of internal edges, 4x4-block packed (matrix-vector products), by operator slot

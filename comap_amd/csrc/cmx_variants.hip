@@ -13,6 +13,9 @@
 //   2. nijt.joint = no (PlainMode::Marginal, PlainMode::NoAvgMarginal): marginal_kernel.
 //   3. alphabets other than 4 / 20 states, padded to kPlainStates: the default mapping (PlainMode::Joint, joint_kernel) and the
 //      site scalars (site_scalars_kernel).  At 4 / 20 states the scalars do not depend on the option and stay the walk's.
+//      By default cmx_map_wide.hip serves this use on the matrix cores, inside the same passes and with site_scalars_kernel
+//      itself (launch_plain_site_scalars); joint_kernel and the inside / outside kernels at 64 states run for it under
+//      cmx_debug_map_wide_plain(1) only.
 //   4. marginal ancestral states (asr.method = marginal): ancestral_kernel.
 // One dispatch on the state count (with_plain_states), one pass loop (plain_passes); what a change must keep: DESIGN.md 4.5.4.
 #include <hip/hip_runtime.h>
@@ -362,6 +365,12 @@ hipError_t launch_plain_map(PlainArgs a, size_t nsites_total, double* scratch, d
     if (d_norm && a.counts) return launch_counts_norm(a.counts, a.ldc, a.B, a.K, nsites_total, d_norm, stream);
     return hipGetLastError();
   });
+}
+
+hipError_t launch_plain_site_scalars(const PlainArgs& pass, hipStream_t stream) {
+  if (pass.S != kPlainStates) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(site_scalars_kernel<kPlainStates>, dim3((unsigned)((pass.nsites + 255) / 256)), dim3(256), 0, stream, pass);
+  return hipGetLastError();
 }
 
 hipError_t launch_counts_norm(const double* d_counts, size_t ldc, int B, int K, size_t n, double* d_norm, hipStream_t stream) {

@@ -170,13 +170,23 @@ int cmx_debug_map_grid(int workgroups);
 
 /* ---- substitution mapping: replaces DRHomogeneousTreeLikelihood::initialize + getLogLikelihoodPerSite /
  * getPosteriorRatePerSite / getRateClassWithMaxPostProbPerSite + computeSubstitutionVectors + computeNormForSite
- * as reached from CoETools::getVectors (CoETools.cpp:397) and AnalysisTools.cpp:592-612.  Any output may be NULL. */
+ * as reached from CoETools::getVectors (CoETools.cpp:397) and AnalysisTools.cpp:592-612.  Any output may be NULL.
+ * Which kernels serve a call: 4 / 20 states, the matrix-core walk; every other alphabet (2 .. 64 states, codon models: no
+ * ambiguity table, every code >= nstates is an unknown), the default mapping and the site scalars on matrix-core kernels of
+ * their own, 16 sites per wave on v_mfma_f64_16x16x4_f64 with the states padded to 64; the mapping variants
+ * (cmx_set_mapping_options), every mapping under cmx_set_likelihood_scaling and the ancestral states, plain kernels. */
 cmx_status cmx_map_sites(cmx_ctx* ctx, const uint8_t* aln, size_t nsites, size_t ld, const uint32_t* masks,
                          size_t nmasks, double* counts /*[N][B][K]*/, double* logL, double* post_rate,
                          int32_t* rate_class, double* norm);
 cmx_status cmx_map_sites_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, size_t ld, const uint32_t* d_masks,
                              double* d_counts /*[B*K][ldc]*/, size_t ldc, double* d_logL, double* d_post_rate,
                              int32_t* d_rate_class, double* d_norm, void* stream);
+/* Alphabets other than 4 / 20 states: cmx_debug_map_wide_plain(1) makes the default mapping and its site scalars -- observed
+ * alignments and every pipeline that maps simulated sites -- run the plain kernels the variants use, one thread per (site,
+ * class), instead of the matrix-core ones (A/B runs, a cross-check for tests; the two agree to rounding, not as bits); 0
+ * restores; on < 0: query only.  Returns the previous state; the default is 0.  Read at each call, no context keeps it.
+ * Process-wide, host only. */
+int cmx_debug_map_wide_plain(int on);
 /* nijt.average / nijt.joint (CoMap/CoETools.cpp:393-406, CoMap/AnalysisTools.cpp:598-633: which of
  * LegacySubstitutionMappingTools::computeSubstitutionVectors{, NoAveraging, Marginal, NoAveragingMarginal} maps the
  * sites; "for benchmarking only" in the reference, but nijt = Label with the MI statistic requires average = no,
