@@ -21,6 +21,7 @@ std::map<std::string, size_t> g_guard_shrink;
 std::atomic<int> g_lds_slot{1};         // cmx_debug_lds_slot: 0 = the mapping walk's LDS slot is planned empty (A/B runs, tests)
 std::atomic<int> g_pat_hash_bits{64};   // (tests force collisions with it)
 std::atomic<int> g_map_queue{1};        // cmx_debug_map_queue: 0 = strided block assignment in every mapping launch (A/B runs, tests)
+std::atomic<int> g_map_small_blocks{1};      // cmx_debug_map_small_blocks: 0 = the class-split launch of a protein alignment keeps 64-site blocks (tests)
 std::atomic<int> g_map_grid{0};         // cmx_debug_map_grid: cap of a new context's grid_blocks / obs_blocks (tests: many rounds of blocks on few waves)
 
 bool guard_on() {
@@ -241,6 +242,8 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
       d.msched_r = nullptr;
       d.nmv_r = 0;
       if (!h.msched_r.empty()) CMX_TRY(up_stream(h.msched_r, &d.msched_r, &d.nmv_r));   // the cherry-table walk's stream
+      d.plan = nullptr;
+      if (!h.wait_imm.empty()) CMX_TRY(upload(ctx, planned_stream(h), &d.plan));   // the 64-site protein walk reads this one
       UP(nrec);
     }
     UP(simg); UP(simord);
@@ -378,6 +381,27 @@ cmx_status cmx_debug_walk(const cmx_model* model, const cmx_tree* tree, int32_t*
   return CMX_OK;
 }
 
+cmx_status cmx_debug_wait_plan(const cmx_model* model, const cmx_tree* tree, int32_t* distance, int32_t* immediate, size_t cap, size_t* n) {
+  HostModel hm;
+  int code = CMX_OK;
+  hm.lds_slot = g_lds_slot.load() != 0;
+  const std::string msg = build_host_model(model, tree, &hm, &code);
+  if (!msg.empty()) {
+    g_create_error = msg;
+    return (cmx_status)code;
+  }
+  if (hm.wait_imm.size() > cap) {
+    g_create_error = "cmx_debug_wait_plan: buffers too small";
+    return CMX_ERR_INVALID;
+  }
+  std::memcpy(distance, hm.wait_dist.data(), hm.wait_dist.size() * sizeof(int32_t));
+  std::memcpy(immediate, hm.wait_imm.data(), hm.wait_imm.size() * sizeof(int32_t));
+  *n = hm.wait_imm.size();
+  return CMX_OK;
+}
+
+int cmx_debug_wait_skew(int entry) { return wait_plan_skew(entry); }
+
 cmx_status cmx_synchronize(cmx_ctx* ctx) {
   if (!ctx) return CMX_ERR_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -408,6 +432,12 @@ int cmx_debug_lds_slot(int on) {
 int cmx_debug_map_queue(int on) {
   const int was = g_map_queue.load();
   if (on >= 0) g_map_queue.store(on ? 1 : 0);
+  return was;
+}
+
+int cmx_debug_map_small_blocks(int on) {
+  const int was = g_map_small_blocks.load();
+  if (on >= 0) g_map_small_blocks.store(on ? 1 : 0);
   return was;
 }
 

@@ -145,7 +145,8 @@ static cmx_status map_walk(cmx_ctx* ctx, const MapIn& in, const MapOut& out, voi
     // Proteins, when even that leaves most of the chip idle: 16-site blocks (one site group per wave) -- four times the
     // tasks, a quarter of the matrix work per operator op, and a wave's slices of the workspaces are a quarter as large,
     // so 4 * obs_waves of them fit the same allocation
-    if (ctx->hm.dS == 20 && ctx->hm.fuse == 1 && ((nsites + 15) / 16) * (size_t)ctx->hm.dC <= 4 * obs_waves) {
+    // (cmx_debug_map_small_blocks(0) keeps the 64-site blocks: the only road to map_kernel<20, split, 1, NG = 4>, for tests)
+    if (ctx->hm.dS == 20 && ctx->hm.fuse == 1 && g_map_small_blocks.load() != 0 && ((nsites + 15) / 16) * (size_t)ctx->hm.dC <= 4 * obs_waves) {
       ks = 16;
       nblocks = (nsites + ks - 1) / ks;
     }

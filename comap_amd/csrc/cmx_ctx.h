@@ -118,6 +118,7 @@ extern std::vector<std::string> g_guard_failures;      // buffers found trampled
 extern std::map<std::string, size_t> g_guard_shrink;   // test hook: logical size override per buffer name
 extern std::atomic<int> g_pat_hash_bits;               // cmx_debug_null_hash_bits: the fused null's column hash keeps only its low bits
 extern std::atomic<int> g_map_queue;                   // cmx_debug_map_queue: 0 = every mapping launch keeps the strided block assignment
+extern std::atomic<int> g_map_small_blocks;                 // cmx_debug_map_small_blocks: 0 = no 16-site blocks in the class-split launch
 extern std::atomic<int> g_map_grid;                    // cmx_debug_map_grid: workgroups a new context's mapping launches may use (0: no cap)
 
 inline cmx_status fail(cmx_ctx* ctx, cmx_status s, const std::string& msg) {

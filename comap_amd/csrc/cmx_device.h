@@ -46,7 +46,10 @@ struct DevModel {
   int nmv;                 // number of pairs
   const int* msched_r;     // the cherry-table walk's stream (class-fused nucleotide models, resolved alignments: the null), or null
   int nmv_r;
-  const int* ldsched;      // unused (null): the load schedule stays on the host; the slot keeps the kernel-argument layout
+  // the planned stream of the 64-site protein walk (cmx_layout.h: PlanEntry): planned_stream_copies(C) copies of nmv + 2
+  // entries; null for every other model.  (In the slot of the load schedule the device once read: the kernel-argument
+  // layout is the parent's, and with it the text of the kernels that do not read the plan.)
+  const PlanEntry* plan;
   // simulator: running sums of the rows of P, [C][nn][S(x)][S], and a 32-entry guide table per row (see draw_guided)
   const double* CP;
   const uint8_t* CPG;      // [C][nn][S(x)][32]

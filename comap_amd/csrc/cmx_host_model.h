@@ -42,6 +42,10 @@ struct HostModel {
   std::vector<int> nrec;    // [NV][16] per-visited-node records (cmx_walk.h)
   std::vector<int> msched;  // operator uses of one class pass in program order: (matrix index, taxon or -1) pairs
   std::vector<int> ldsched; // workspace loads of one class pass: load_word(array, slot, prefetchable)
+  // Wait plan (cmx_layout.h; 20-state unfused models, else empty): per op of msched the counted VMEM distance at its wait --
+  // the smallest over the op's dynamic instances (a pass inside a site block, a block's first and last pass) -- and the
+  // vmcnt immediate taken from it.
+  std::vector<int> wait_dist, wait_imm;
   // Cherry tables (cmx_walk.h; class-fused nucleotide models only): an inlined cherry's message and outside visit as rows
   // of 1 + 3 K tables indexed by its two leaves' symbols, for fully resolved alignments (the null's).  The tables follow
   // the leaf operators in a class block (matrix index cherry_base + cherry_of[node] * (1 + 3 K) + table); the walk that
@@ -64,8 +68,13 @@ struct HostModel {
 // computation (empty string when they agree).
 void build_records(HostModel* hm);
 void plan_lds_slot(HostModel* hm);   // after build_records, before record_walk: sets the FLAG_LDS_* bits of the records
-void record_walk(HostModel* hm);
+void record_walk(HostModel* hm);   // ... and the wait plan of the 20-state unfused walk
 std::string verify_walk(const HostModel& hm);
+// the device stream of a model with a wait plan (cmx_layout.h: PlanEntry), every copy: [planned_stream_copies(dC)][nmv + 2]
+std::vector<PlanEntry> planned_stream(const HostModel& hm);
+// test hook (host only, process-wide): the NEXT wait plan built gets the immediate of entry `entry` raised by one -- a wait
+// that is too lax, which verify_walk has to refuse before a context exists.  entry < 0 clears; returns the previous value.
+int wait_plan_skew(int entry);
 
 // (cmx_host_model.cpp) returns empty string on success, otherwise the error message (status in *code)
 std::string build_host_model(const cmx_model* model, const cmx_tree* tree, HostModel* out, int* code);

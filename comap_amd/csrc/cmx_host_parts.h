@@ -15,6 +15,18 @@ inline std::vector<int> children(const HostModel& hm, int n) {
   return v;
 }
 
+// the members of the backend concept that apply no operator and move no workspace vector: nothing to list for them
+struct RegisterOpsIgnored {
+  template <int D, int S> void mov() {}
+  template <int D, int S> void mul() {}
+  template <int D, int A, int B> void prod() {}
+  void mulup() {}
+  template <int D> void setpi() {}
+  template <int S> void rootl() {}
+  void dot3(int) {}
+  template <int R> void kill() {}
+};
+
 // Stages of build_host_model (cmx_host_tree.cpp).  build_tree: the tree's checks in their order, then parent -> first_child /
 // next_sib / taxon_of / slot / int_post; error message or empty string.  The other two cannot fail.
 std::string build_tree(const cmx_tree* tree, HostModel* hm);

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cmath>
 
 namespace cmx {
@@ -159,18 +160,6 @@ void build_records(HostModel* hm) {
 }
 
 namespace {
-// the members of the backend concept that apply no operator and move no workspace vector: nothing to list for them
-struct RegisterOpsIgnored {
-  template <int D, int S> void mov() {}
-  template <int D, int S> void mul() {}
-  template <int D, int A, int B> void prod() {}
-  void mulup() {}
-  template <int D> void setpi() {}
-  template <int S> void rootl() {}
-  void dot3(int) {}
-  template <int R> void kill() {}
-};
-
 // ---- Recorder: the operator stream (matrix index in a class block, taxon or -1) and the workspace loads of a pass
 template <bool CT, bool CR>
 struct Recorder : RegisterOpsIgnored {
@@ -182,9 +171,13 @@ struct Recorder : RegisterOpsIgnored {
   std::vector<long> store_time[2];
   struct Ld { int arr, slot; long t, src; };
   std::vector<Ld> loads;
+  // what the wait plan counts (plan_waits): the pass's ops by stream index and, as -1, every workspace vector that moves
+  // through HBM -- the device's OpState bookkeeping of the run-time count (vs += kVecInstrs), nothing for LDS-slot transfers
+  std::vector<int> vm_events;
   explicit Recorder(HostModel* h) : hm(h), blk(h->block()) { store_time[0].assign(h->NIW, -1); store_time[1].assign(h->NIW, -1); }
   void op(int mat, int tx) {
     std::vector<int>& ms = CT ? hm->msched_r : hm->msched;
+    vm_events.push_back((int)(ms.size() / 2));
     ms.push_back(mat); ms.push_back(tx); ++t;
   }
   void leaf_use(int leaf, int which) {
@@ -204,13 +197,53 @@ struct Recorder : RegisterOpsIgnored {
   template <int D> void cset(int node, int l1, int l2) { cherry_use(node, l1, l2, 0); }
   template <int S> void cdot(int node, int l1, int l2, int table, int) { cherry_use(node, l1, l2, table); }
   template <int S, int D, bool TR> void mv(int node, int which) { op(blk.internal(hm->slot[node], which), -1); (CT ? hm->n_products_r : hm->n_products)++; }
-  template <int D> void load(int arr, int slot) { loads.push_back({arr, slot, t++, store_time[arr][slot]}); if (!CT) hm->n_loads++; }
-  template <int S> void store(int arr, int slot) { store_time[arr][slot] = t++; if (!CT) hm->n_stores++; }
+  void note_load(int arr, int slot) { loads.push_back({arr, slot, t++, store_time[arr][slot]}); if (!CT) hm->n_loads++; }
+  void note_store(int arr, int slot) { store_time[arr][slot] = t++; if (!CT) hm->n_stores++; }
+  template <int D> void load(int arr, int slot) { note_load(arr, slot); vm_events.push_back(-1); }
+  template <int S> void store(int arr, int slot) { note_store(arr, slot); vm_events.push_back(-1); }
   // transfers the LDS slot serves: still loads and stores of the walk (n_loads, n_stores, ldsched), counted beside them
-  template <int D> void lload(int arr, int slot) { load<D>(arr, slot); hm->n_lds_loads++; }
-  template <int S> void lstore(int arr, int slot) { store<S>(arr, slot); hm->n_lds_stores++; }
+  template <int D> void lload(int arr, int slot) { note_load(arr, slot); hm->n_lds_loads++; }
+  template <int S> void lstore(int arr, int slot) { note_store(arr, slot); hm->n_lds_stores++; }
   template <int S> void lcopy(int, int) { ++t; hm->n_lds_copies++; }
 };
+
+std::atomic<int> g_wait_skew{-1};   // wait_plan_skew
+
+// The wait plan (cmx_layout.h) of the 64-site protein walk, from the events of one recorded pass.  The count is the
+// device's run-time one (cmx_map.hip: OpState::vs / cur_seq in the kernels that keep it), replayed over two site blocks of
+// all classes: a leaf op requests the next op's operator before it waits, a product after; the symbols of the next op come
+// with its operator unless it is op 0 of the next site block.  An op's instances differ only there (the last op of a pass),
+// and the smallest distance is kept: a smaller immediate only waits for more.  Op 0 of a block's first pass finds its
+// operator behind the block prologue's drain and is served by any immediate.  Uncounted VMEM -- the epilogue between two
+// blocks, compiler spills -- only adds instructions in flight behind the one waited for.
+void plan_waits(HostModel* hm, const std::vector<int>& events) {
+  hm->wait_dist.clear();
+  hm->wait_imm.clear();
+  if (hm->S != 20 || hm->fuse != 1) return;
+  const int n = (int)(hm->msched.size() / 2), C = hm->C;   // (unfused: the device's classes are the model's)
+  auto leaf = [&](int i) { return hm->msched[2 * (size_t)i + 1] >= 0; };
+  std::vector<long> dist(n, -1);
+  long vs = kPlanRows, cur = vs;   // the kernel's first request: op 0
+  for (int block = 0; block < 2; ++block)
+    for (int c = 0; c < C; ++c)
+      for (const int e : events) {
+        if (e < 0) { vs += kPlanVec; continue; }
+        const bool more = e + 1 < n;
+        const int next = more ? e + 1 : 0;
+        const long issued = kPlanRows + ((leaf(next) && (more || c + 1 < C)) ? 1 : 0);
+        const long d = vs - cur + (leaf(e) ? issued : 0);
+        // (the wave's very first op has nothing of a pass in front of it, and the prologue's drain serves it anyway)
+        if (!(block == 0 && c == 0 && e == 0) && (dist[e] < 0 || d < dist[e])) dist[e] = d;
+        vs += issued;
+        cur = vs;
+      }
+  for (int i = 0; i < n; ++i) {
+    hm->wait_dist.push_back((int)dist[i]);
+    hm->wait_imm.push_back(planned_wait_imm((int)dist[i]));
+  }
+  const int skew = g_wait_skew.exchange(-1);
+  if (skew >= 0 && skew < n) hm->wait_imm[skew] += 1;
+}
 
 // the plain stream and the load schedule: the row-reusing cherry visit (cmx_walk.h, kCherryRows) for unfused models
 template <bool CR>
@@ -222,6 +255,7 @@ void record_plain(HostModel* hm) {
     // prefetchable: its producer store is issued before the previous load (where the prefetch is issued)
     hm->ldsched.push_back(load_word(e.arr, e.slot, j > 0 && e.src >= 0 && e.src < rc.loads[j - 1].t));
   }
+  plan_waits(hm, rc.vm_events);
 }
 
 // ---- SlotProbe: the workspace transfers of a pass with the record that issues each, in the Recorder's program-order time
@@ -307,6 +341,29 @@ void record_walk(HostModel* hm) {
   if (hm->fuse == 1) record_plain<true>(hm);
   else record_plain<false>(hm);
 }
+
+std::vector<PlanEntry> planned_stream(const HostModel& hm) {
+  const int n = (int)(hm.msched.size() / 2), C = hm.dC, copies = planned_stream_copies(C);
+  const long long unit = (long long)mat_unit(hm.dS) * 8, stride = (long long)hm.MC * unit;   // bytes of an operator, of a class block
+  std::vector<PlanEntry> out;
+  out.reserve((size_t)copies * (n + 2));
+  for (int copy = 0; copy < copies; ++copy) {
+    const bool last = copy != 0;            // (planned_stream_copy: copy 0 continues the site block)
+    const int step = last ? copy - C : 1;   // classes from this pass's block to the next pass's
+    for (int j = 0; j < n + 2; ++j) {
+      const int e = j < n ? j : j - n;
+      PlanEntry p;
+      p.off = hm.msched[2 * (size_t)e] * unit + (j == n ? step * stride : 0);
+      p.tx = hm.msched[2 * (size_t)e + 1];
+      if (p.tx >= 0 && j == n && last) p.tx = kPlanLeafNoSymbols;
+      p.w = hm.wait_imm[(size_t)((e + n - 1) % n)];   // the wait of the op in front: the one that holds this entry when it waits
+      out.push_back(p);
+    }
+  }
+  return out;
+}
+
+int wait_plan_skew(int entry) { return g_wait_skew.exchange(entry < 0 ? -1 : entry); }
 
 void build_walk_program(HostModel* hm) {
   const int S = hm->S, C = hm->C;

@@ -175,6 +175,115 @@ NumericResult run_numeric(const HostModel& hm) {
   return {nm.err, nm.mi, nm.fi, nm.code, nm.cnt, nm.Lg, nm.counted};
 }
 
+// ---- WaitModel: the wait plan (cmx_layout.h) against a model of the wave's in-order VMEM queue, the way Numeric models
+// the LDS slot's occupant.  The backend follows the walk over consecutive passes as the device's planned walk issues it: a
+// leaf op requests the next op's operator (and symbols) and then waits with its planned immediate, a product waits and
+// then requests; a workspace vector through HBM is kPlanVec instructions, an LDS-slot transfer none.  A requested stage
+// buffer or symbol slot is "not landed" until a wait executes whose immediate is at most the number of counted
+// instructions issued behind the request (VMEM completes in order); an op that reads one that has not landed, or one
+// requested for another op, and a request into a buffer whose last reader has not run, are refused.  The kernel drains the
+// queue in front of a site block (map_sites_wave's prologue) and requests the symbols of the block's op 0 there.
+struct WaitModel : RegisterOpsIgnored {
+  static constexpr bool kCherryTables = false, kCherryRows = true, kLdsSlot = true;
+  struct Buf {
+    long last = 0, end = 0;   // the request's last instruction; instructions issued when the whole request (symbols too) was out
+    long op = -1;             // the dynamic op it was requested for
+    bool used = true;         // ... has read it
+  };
+  const HostModel& hm;
+  const int n;                // ops of a pass
+  long issued = kPlanRows, landed = 0;   // counted instructions so far; instructions 1 .. landed have completed
+  Buf stage[2], sym[2];
+  int par = 0, mi = 0;
+  long dyn = 0;               // ops executed so far, over all passes
+  bool last_of_block = false;
+  std::vector<long> mind;     // smallest modelled distance of each entry
+  std::string err;
+  explicit WaitModel(const HostModel& h) : hm(h), n((int)(h.msched.size() / 2)), mind(n, -1) {
+    stage[0] = {kPlanRows, kPlanRows, 0, false};   // the kernel's first request: op 0
+  }
+  void fail(const std::string& m) { if (err.empty()) err = "wait plan refused: " + m; }
+  bool leaf_entry(int i) const { return hm.msched[2 * (size_t)i + 1] >= 0; }
+  void rec(int v, int (&r)[16]) const { copy_record(hm, v, r); }
+  void begin_block() {
+    landed = issued;   // the prologue's drain
+    if (leaf_entry(0)) sym[par] = {0, 0, dyn, false};   // ... and its request of op 0's symbols, drained as well
+  }
+  void begin_pass(bool last) { mi = 0; last_of_block = last; }
+  void request_next() {
+    const bool more = mi + 1 < n;
+    const int next = more ? mi + 1 : 0;
+    Buf& b = stage[par ^ 1];
+    if (!b.used) return fail("op " + std::to_string(mi) + " requests into a stage buffer whose operator nobody has read");
+    issued += kPlanRows;
+    b = {issued, issued, dyn + 1, false};
+    if (leaf_entry(next) && (more || !last_of_block)) {
+      Buf& s = sym[par ^ 1];
+      if (!s.used) return fail("op " + std::to_string(mi) + " requests into a symbol slot nobody has read");
+      issued += 1;
+      s = {issued, issued, dyn + 1, false};
+      b.end = issued;
+    }
+  }
+  void wait() {
+    if (mi >= n || (size_t)mi >= hm.wait_imm.size()) return fail("more ops than planned waits");
+    const int imm = hm.wait_imm[mi];
+    if (imm < 0 || imm > 63) return fail("entry " + std::to_string(mi) + ": " + std::to_string(imm) + " is no vmcnt value");
+    if (!planned_wait_dispatchable(imm, leaf_entry(mi)))
+      return fail("entry " + std::to_string(mi) + ": the device has no wait for vmcnt(" + std::to_string(imm) + ") at this kind of op");
+    landed = std::max(landed, issued - imm);
+    const long d = issued - stage[par].end;
+    if (dyn > 0 && (mind[mi] < 0 || d < mind[mi])) mind[mi] = d;   // (the wave's first op: behind the drain, nothing of a pass in front)
+  }
+  void use(bool leaf) {
+    auto check = [&](Buf& b, const char* what) {
+      if (b.op != dyn) return fail("op " + std::to_string(mi) + " finds " + what + " requested for another op");
+      if (b.last > landed)
+        return fail("op " + std::to_string(mi) + " reads " + what + " that has not landed: vmcnt(" + std::to_string(hm.wait_imm[mi]) + ") with " +
+                    std::to_string(issued - b.last) + " instructions issued behind it");
+      b.used = true;
+    };
+    check(stage[par], "a stage buffer");
+    if (leaf) check(sym[par], "a symbol slot");
+  }
+  void end() { par ^= 1; ++mi; ++dyn; }
+  void leaf_op() { if (!err.empty()) return; request_next(); wait(); use(true); end(); }
+  template <int D> void lset(int, int) { leaf_op(); }
+  template <int S, int D> void lmul(int, int) { leaf_op(); }
+  template <int S> void ldot(int, int, int) { leaf_op(); }
+  template <int S, int D, bool TR> void mv(int, int) { if (!err.empty()) return; wait(); use(false); request_next(); end(); }
+  template <int D> void load(int, int) { issued += kPlanVec; }
+  template <int S> void store(int, int) { issued += kPlanVec; }
+  template <int D> void lload(int, int) {}
+  template <int S> void lstore(int, int) {}
+  template <int S> void lcopy(int, int) {}
+};
+
+// whole: site blocks of all classes, as every launch but the class-split one walks them (the plan's distances are the
+// smallest of these instances: checked entry by entry); else one pass per block, the class-split launch
+std::string check_wait_plan(const HostModel& hm, bool whole) {
+  WaitModel wm(hm);
+  const int C = hm.dC, passes = whole ? C : 1, blocks = whole ? 2 : 2 * std::max(C, 2);
+  for (int b = 0; b < blocks; ++b) {
+    wm.begin_block();
+    for (int c = 0; c < passes; ++c) {
+      wm.begin_pass(c + 1 == passes);
+      walk_pass(wm, hm.NV, hm.K);
+      if (!wm.err.empty()) return wm.err;
+      if (wm.mi != wm.n) return "wait plan refused: a pass has " + std::to_string(wm.mi) + " ops, the stream " + std::to_string(wm.n);
+    }
+  }
+  if (!whole) return std::string();
+  for (int i = 0; i < wm.n; ++i) {
+    if (hm.wait_dist[i] != wm.mind[i])
+      return "wait plan refused: entry " + std::to_string(i) + " is planned at distance " + std::to_string(hm.wait_dist[i]) + ", the queue model counts " + std::to_string(wm.mind[i]);
+    if (hm.wait_imm[i] != planned_wait_imm((int)wm.mind[i]))
+      return "wait plan refused: entry " + std::to_string(i) + " waits with vmcnt(" + std::to_string(hm.wait_imm[i]) + "), distance " + std::to_string(wm.mind[i]) +
+             " takes vmcnt(" + std::to_string(planned_wait_imm((int)wm.mind[i])) + ")";
+  }
+  return std::string();
+}
+
 bool close(double a, double b) { return std::fabs(a - b) <= 1e-9 * (std::fabs(a) + std::fabs(b)) + 1e-290; }
 
 // site likelihoods and joint counts of a numeric pass against the direct computation; tables: the cherry-table walk's wording
@@ -200,6 +309,14 @@ std::string verify_walk(const HostModel& hm) {
   if (!nm.err.empty()) return nm.err;
   if (2 * nm.mi != hm.msched.size()) return "tree-walk self-check failed: unused operators in the stream";
   if (nm.fi != hm.ldsched.size()) return "tree-walk self-check failed: unused workspace loads in the schedule";
+  // the wait plan of the 64-site protein walk: a wait that is too lax is a race no test on the device can exclude
+  if (S == 20 && F == 1) {
+    if (2 * hm.wait_imm.size() != hm.msched.size() || hm.wait_dist.size() != hm.wait_imm.size()) return "wait plan refused: not one wait per operator use";
+    for (const bool whole : {true, false}) {
+      const std::string bad = check_wait_plan(hm, whole);
+      if (!bad.empty()) return bad;
+    }
+  }
   // the cherry-table walk: same site, same reference
   NumericResult nt;
   const bool tables = !hm.msched_r.empty();

@@ -92,6 +92,47 @@ constexpr int cherry_entry(int taxon1, int taxon2) { return kCherryFlag | taxon1
 constexpr int cherry_taxon1(int entry) { return entry & 0x7fff; }
 constexpr int cherry_taxon2(int entry) { return (entry >> 15) & 0x7fff; }
 
+// ---- Wait plan of the 64-site protein walk (20 states, unfused; cmx_host_tree.cpp: plan_waits).  An op waits
+// for its operator with s_waitcnt vmcnt(n), n = the counted VMEM instructions the walk issues between the operator's request
+// and that wait: kPlanRows DMA rows of the next request (+ 1 with symbols) and kPlanVec per workspace vector moved through HBM
+// in between.  That count is a function of the tree, the LDS-slot plan and the place in the stream: the host records it per
+// stream entry and the device reads the immediate from the entry.
+constexpr int kPlanRows = 4, kPlanVec = 10;
+// the immediate for a counted distance: what the run-time count of the other mapping kernels (cmx_map.hip: wait_vm<20, 20>)
+// chooses -- every distance up to a request's own instructions is exact, above that the multiples of a vector, and the
+// counter's reach ends at three vectors.  A smaller immediate than the distance only waits for more.
+constexpr int planned_wait_imm(int distance) {
+  const int v = distance % kPlanVec < 7 ? distance % kPlanVec : 6, q = distance / kPlanVec;
+  return q <= 2 ? q * kPlanVec + v : 3 * kPlanVec;
+}
+// The immediates the device can dispatch on: a product waits with nothing newly issued (multiples of a vector), a leaf op
+// behind its own request (its rows, + 1 with symbols).  Every distance the walk can produce maps into its op's set; a plan
+// with another immediate is refused (verify_walk) and never uploaded.
+constexpr bool planned_wait_dispatchable(int imm, bool leaf) {
+  if (!leaf) return imm == 0 || imm == 10 || imm == 20 || imm == 30;
+  return imm == 4 || imm == 5 || imm == 14 || imm == 15 || imm == 24 || imm == 25 || imm == 30;
+}
+// Entry of the planned device stream (one 16-byte scalar load per op): entry j describes op j of a class pass and carries
+// the wait of the op in front of it, which is the op that holds entry j when it waits.
+//   off  byte offset of op j's operator from the base of the pass's class block (one 64-bit scalar add)
+//   tx   symbol row of a leaf op, kPlanProduct for a product, kPlanLeafNoSymbols for a leaf op whose symbols are not
+//        requested with its operator (op 0 of the next site block: other sites)
+//   w    the vmcnt immediate of op j - 1's wait
+// A pass reads entries 0 .. nmv + 1: entry nmv is op 0 of the pass that follows (requested by the last op, so its offset
+// carries the distance between the two class blocks), entry nmv + 1 is op 1 of that pass, relative to the new base.  The
+// stream is stored once per possible successor of a pass (planned_stream_copy): which copy a pass reads is decided at the
+// pass boundary, and nothing in the per-op path knows about the wrap.
+struct PlanEntry {
+  long long off;
+  int tx, w;
+};
+static_assert(sizeof(PlanEntry) == 16, "one s_load_dwordx4 per op");
+constexpr int kPlanProduct = -1, kPlanLeafNoSymbols = -2;
+// copy 0: the pass that follows is the next class of the same site block (symbols requested); copy 1 + (C - 1) + d: the
+// pass is the block's last one and the next block starts d classes further (d = -(C - 1) .. C - 1)
+constexpr int planned_stream_copies(int C) { return 2 * C; }
+constexpr int planned_stream_copy(int C, bool last_of_block, int class_step) { return last_of_block ? C + class_step : 0; }
+
 // Load-schedule word of a workspace load: bit 31 prefetchable, bit 30 array (WS_M / WS_U), low 24 bits slot
 constexpr int load_word(int arr, int slot, bool prefetchable) {
   return (int)((unsigned)slot | (arr ? 0x40000000u : 0u) | (prefetchable ? 0x80000000u : 0u));

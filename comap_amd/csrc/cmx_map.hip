@@ -10,7 +10,13 @@
 //   The SxS operator of an edge is the same for all 64 lanes: every operator use of a class pass (products on
 //   internal edges, row gathers by observed symbol on leaf edges) is listed by the host in one op stream and staged
 //   in LDS by LDS-DMA one op ahead (an op requests the next op's operator and waits for its own; a product of the 64-site
-//   protein walk requests from the gaps between its first matrix instructions); products run on the matrix cores
+//   protein walk requests from the gaps between its first matrix instructions).  How long an op may leave later requests
+//   in flight when it waits -- the vmcnt immediate -- is counted at run time (OpState::vs) by every instantiation but the
+//   64-site protein walk, which reads it from its stream entry: the host has counted it per entry and proved the plan on a
+//   model of the wave's memory queue (cmx_layout.h: wait plan; cmx_host_verify.cpp: WaitModel).  That walk's stream entry
+//   is one 16-byte scalar load per op from a running pointer: the operator's offset from the pass's class block, the
+//   symbol row, the immediate; the wrap into the next pass is in the copy of the stream a pass reads, chosen at the pass
+//   boundary.  Products run on the matrix cores
 //   (v_mfma_f64_4x4x4_4b, 100 per 20x20 product; the
 //   64-site protein walk: 20 v_mfma_f64_16x16x4_f64 for states 0..15 and 20 v_mfma_f64_4x4x4_4b for states 16..19) in
 //   a layout where lane = (state inside a 4-state tile, site of a group of 16).
@@ -456,12 +462,31 @@ struct ConstModel {
 // code issued and knows about (DMA rows, vector stores); an asynchronous transfer remembers vs right after its issue,
 // and "wait for X" is s_waitcnt vmcnt(vs - X_seq): VMEM completes in order, so the instructions issued after X may stay
 // in flight.  Instructions that are not counted only make the wait stricter.
+// The 64-site protein walk (kMfma16) counts nothing at run time: the distance vs - cur_seq of an op is a function of the tree,
+// the LDS-slot plan and the op's place in the stream, the host records it per stream entry (cmx_layout.h: wait plan; proved
+// against a model of this queue by verify_walk before a context exists) and the entry carries the immediate.  Its stream
+// entry is a PlanEntry: pre_off / pre_tx / pre_w, and vs / cur_seq / pre_mat are dead.
 struct OpState {
-  int pre_mat, pre_tx;  // op-stream entry of the NEXT op, loaded one op early (its latency hides behind the current op)
-  unsigned par;      // stage buffer / code slot of the current operator op
-  unsigned vs;       // counted VMEM instructions issued so far
-  unsigned cur_seq;  // vs right after the current operator op's operator (and symbols) were requested
+  // (the members keep their order: the class-fused kernels' text depends on it)
+  int pre_mat;       // run-time count only: the NEXT op's operator, element offset in a class block
+  int pre_tx;        // both walks: op-stream entry of the NEXT op, loaded one op early (its latency hides behind the current op)
+  unsigned par;      // both walks: stage buffer / code slot of the current operator op
+  unsigned vs;       // run-time count only: counted VMEM instructions issued so far
+  unsigned cur_seq;  // run-time count only: vs right after the current operator op's operator (and symbols) were requested
+  // planned walk only (the run-time-count members above are never written by it)
+  long long pre_off; // planned walk: byte offset of the NEXT op's operator from the pass's class block
+  int pre_w;         // planned walk: the vmcnt immediate of the CURRENT op's wait (it travels with the next op's entry)
 };
+// an entry as the scalar load sees it: four dwords (off low, off high, tx, w), read through the constant address space
+typedef int cmx_i4 __attribute__((ext_vector_type(4)));
+typedef const cmx_i4 __attribute__((address_space(4)))* cmx_cplan;
+static_assert(offsetof(PlanEntry, off) == 0 && offsetof(PlanEntry, tx) == 8 && offsetof(PlanEntry, w) == 12, "dwords of an entry");
+__device__ __forceinline__ void plan_entry(cmx_cplan p, OpState& os) {
+  const cmx_i4 q = *p;
+  os.pre_off = (long long)(((unsigned long long)(unsigned)q[1] << 32) | (unsigned)q[0]);
+  os.pre_tx = q[2];
+  os.pre_w = q[3];
+}
 
 // Device backend of the tree walk (cmx_walk.h): registers R0..R3 are S-vectors of the wave's sites in the matrix-core
 // layout.  The walk names what it wants, workspace slots included; the operator stream (m.msched) -- recorded from the
@@ -477,6 +502,7 @@ struct DevWalk {
   static constexpr int kVecInstrs = (VL + 1) / 2;   // VMEM instructions of one workspace vector
   static constexpr bool kCherryTables = RESOLVED && DIAG;   // cmx_walk.h: cset / cdot instead of a cherry's operator ops
   static constexpr bool kCherryRows = FUSE == 1;            // cmx_walk.h: a cherry's outside visit keeps its leaf rows in registers
+  static constexpr bool kPlanned = kMfma16<S, NG, DIAG>;    // the planned stream and its waits (OpState)
   // cmx_walk.h: one workspace vector per wave stays in LDS where the records say so (the 64-site protein walk in all its
   // modes; the 16-site shape shares the records and ignores the bits, like every backend without a slot)
   static constexpr bool kLdsSlot = map_lds_slot(S, FUSE, NG);
@@ -487,7 +513,9 @@ struct DevWalk {
   const ConstModel& cm;
   const double* pi;            // root frequencies (vector loads: lane-dependent index)
   int nmv;
-  const double *mat_c, *mat_after;
+  const double *mat_c, *mat_after;   // (run-time count only: the planned walk has op_base)
+  const uint8_t* op_base;      // planned walk: the pass's class block (wave-uniform); an operator is op_base + its entry's offset
+  cmx_cplan sp;                // planned walk: the stream entry the next op loads; set at the pass boundary, bumped per op
   double *wsM, *wsU, *pcnt;
   const uint8_t* gcodes;
   size_t gstride;
@@ -496,7 +524,7 @@ struct DevWalk {
   int lane, c, c_end;
   double pc;
   double Lg[FUSE];
-  int mi;
+  int mi;                      // op of the pass (run-time count only: the planned walk has no use for it)
 
   __device__ __forceinline__ DevWalk(OpState& os_, const ConstModel& cm_) : os(os_), cm(cm_) {}
 
@@ -524,7 +552,7 @@ struct DevWalk {
     else return R3;
   }
   __device__ __forceinline__ void begin_pass() {
-    mi = 0;
+    if constexpr (!kPlanned) mi = 0;
 #pragma unroll
     for (int g = 0; g < FUSE; ++g) Lg[g] = 0.0;
   }
@@ -558,8 +586,8 @@ struct DevWalk {
   // wait: for this op's operator; it returns its buffer.  op_begin requests, then waits: a leaf op has no matrix
   // instructions to hide the request behind, and every product but those of the 64-site protein walk keeps this order.
   // (One function on purpose: as two, op_request and op_wait, hipcc orders a few instructions of the request otherwise in
-  // thirteen kernels that are to keep their text.)  A product of the 64-site protein walk waits (op_wait), then requests
-  // from inside the product (ProductRequest).
+  // thirteen kernels that are to keep their text.)  The 64-site protein walk does not come here: its leaf ops run
+  // leaf_begin, its products wait (wait_planned_product) and then request from inside the product (ProductRequest).
   // The request overwrites the other stage buffer and code slot, whose last readers are the LDS reads of the op before:
   // op_begin waits for them (lgkmcnt(0)) first.
   __device__ __forceinline__ const uint8_t* op_begin(unsigned& nseq) {
@@ -570,16 +598,8 @@ struct DevWalk {
     {
       const double* src = (more ? mat_c : mat_after) + emat;   // element offset, premultiplied on the host
       const uint32_t dst = lds_stage + (os.par ^ 1u) * MatStage<S>::BYTES;
-      if constexpr (kMfma16<S, NG, DIAG>) {
-        // the 64-site protein walk addresses the rows as (wave-uniform base in SGPRs) + (16 x lane), here and in
-        // ProductRequest: no 64-bit address per lane.  Three full rows and a partial one, whatever the next op is.
-        static_assert(MatStage<S>::FULL == 3 && MatPart<kLeafBytes>::FULL == 3 && kProductBytes == MatStage<S>::BYTES, "rows of a request");
-        const int l = vlane();
-        const int tl = etx >= 0 ? MatPart<kLeafBytes>::TAIL : MatStage<S>::TAIL;
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
-        if (l < tl) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
-        issued = MatStage<S>::ROWS;
-      } else if constexpr (kProductBytes == MatStage<S>::BYTES && kLeafBytes == MatStage<S>::BYTES) {
+      static_assert(!kPlanned, "the planned walk: leaf_begin");
+      if constexpr (kProductBytes == MatStage<S>::BYTES && kLeafBytes == MatStage<S>::BYTES) {
         mat_dma_l<S>(src, dst, vlane());
         issued = MatStage<S>::ROWS;
       } else if (etx >= 0) {   // (wave-uniform: the next op is a leaf op -- or a cherry-table op)
@@ -615,11 +635,65 @@ struct DevWalk {
     nseq = os.vs;
     return stage + os.par * MatStage<S>::BYTES;
   }
-  // wait for this op's operator with nothing newly issued: what os.vs has counted since its request may stay in flight
-  __device__ __forceinline__ const uint8_t* op_wait() {
-    wait_vm<S, VL>((int)(os.vs - os.cur_seq));
+  // ---- The planned walk's halves of an op (kPlanned).  The wait is a dispatch on the entry's immediate over the values that
+  // occur at this kind of op (cmx_layout.h: planned_wait_dispatchable; the host uploads no other).  ONE asm statement with
+  // its own branches: written as nested ifs around seven asm waits, hipcc structurises the tree with an s_mov_b64 -1 /
+  // s_andn2 vcc / s_cbranch_vccnz triple per arm -- 16 instructions to reach vmcnt(4) or vmcnt(5).  Here the most frequent
+  // immediate is reached last and falls out of the statement: vmcnt(0) of a product (96 % of the benchmark tree's) in 3
+  // instructions, vmcnt(5) / vmcnt(4) of a leaf op (71 %) in 5 / 6, vmcnt(14) / vmcnt(15) (26 %) in 7 / 8, the rest one
+  // level deeper.  An arm that takes a range gives its smallest value to everything but the value it names: never a laxer wait.
+  __device__ __forceinline__ static void wait_planned_product(int w) {
+    asm volatile("s_cmp_lt_i32 %0, 10\n\ts_cbranch_scc1 8f\n\t"
+                 "s_cmp_lt_i32 %0, 20\n\ts_cbranch_scc1 7f\n\t"
+                 "s_cmp_lt_i32 %0, 30\n\ts_cbranch_scc1 6f\n\t"
+                 "s_waitcnt vmcnt(30)\n\ts_branch 9f\n"
+                 "6:\ts_waitcnt vmcnt(20)\n\ts_branch 9f\n"
+                 "7:\ts_waitcnt vmcnt(10)\n\ts_branch 9f\n"
+                 "8:\ts_waitcnt vmcnt(0)\n"
+                 "9:" ::"s"(w) : "scc", "memory");
+  }
+  __device__ __forceinline__ static void wait_planned_leaf(int w) {
+    asm volatile("s_cmp_lt_i32 %0, 14\n\ts_cbranch_scc1 7f\n\t"
+                 "s_cmp_lt_i32 %0, 24\n\ts_cbranch_scc1 5f\n\t"
+                 "s_cmp_lt_i32 %0, 30\n\ts_cbranch_scc1 3f\n\t"
+                 "s_waitcnt vmcnt(30)\n\ts_branch 9f\n"
+                 "3:\ts_cmp_eq_u32 %0, 25\n\ts_cbranch_scc1 4f\n\t"
+                 "s_waitcnt vmcnt(24)\n\ts_branch 9f\n"
+                 "4:\ts_waitcnt vmcnt(25)\n\ts_branch 9f\n"
+                 "5:\ts_cmp_eq_u32 %0, 15\n\ts_cbranch_scc1 6f\n\t"
+                 "s_waitcnt vmcnt(14)\n\ts_branch 9f\n"
+                 "6:\ts_waitcnt vmcnt(15)\n\ts_branch 9f\n"
+                 "7:\ts_cmp_eq_u32 %0, 5\n\ts_cbranch_scc1 8f\n\t"
+                 "s_waitcnt vmcnt(4)\n\ts_branch 9f\n"
+                 "8:\ts_waitcnt vmcnt(5)\n"
+                 "9:" ::"s"(w) : "scc", "memory");
+  }
+  // the entry two ops ahead: one 16-byte scalar load from the running pointer
+  __device__ __forceinline__ void next_entry() {
+    plan_entry(sp, os);
+    ++sp;
+  }
+  // a leaf op: request the next op's operator (and symbols), then wait for this op's.  The rows are addressed as
+  // (wave-uniform operator address in SGPRs) + (16 x lane), here and in ProductRequest: no 64-bit address per lane.  Three
+  // full rows and a partial one, whatever the next op is.
+  __device__ __forceinline__ const uint8_t* leaf_begin() {
+    static_assert(kPlanned && MatStage<S>::FULL == 3 && MatPart<kLeafBytes>::FULL == 3 && kProductBytes == MatStage<S>::BYTES, "rows of a request");
+    const uint8_t* src = op_base + os.pre_off;
+    const int etx = os.pre_tx, w = os.pre_w;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS reads of the other buffer are done
+    {
+      const uint32_t dst = lds_stage + (os.par ^ 1u) * MatStage<S>::BYTES;
+      const int l = vlane();
+      const int tl = etx != kPlanProduct ? MatPart<kLeafBytes>::TAIL : MatStage<S>::TAIL;
+      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
+      if (l < tl) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
+    }
+    if (etx >= 0) code_dma_l(gcodes + (size_t)etx * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
+    next_entry();
+    wait_planned_leaf(w);
     return stage + os.par * MatStage<S>::BYTES;
   }
+  __device__ __forceinline__ void planned_end() { os.par ^= 1u; }
   __device__ __forceinline__ void op_end(unsigned nseq) {
     os.par ^= 1u;
     os.cur_seq = nseq;
@@ -634,11 +708,11 @@ struct DevWalk {
   // The rows are addressed as (wave-uniform base in SGPRs) + (16 x lane): no 64-bit address per lane.
   // What op_begin requests, transfer for transfer, in another place; why each point holds there:
   //  * DMA overwrite.  The pieces write the other stage buffer and code slot; their last readers are LDS reads of earlier
-  //    ops, all of them in front of op_wait's asm in program order (a "memory" clobber: no access moves across it), hence
+  //    ops, all of them in front of the wait's asm in program order (a "memory" clobber: no access moves across it), hence
   //    issued before the product's first operand read.  Slot 0 lies behind the product's first matrix instruction, which
   //    reads that operand: the wave has executed an lgkmcnt wait that covers it (lgkmcnt(0) if a scalar load is in
   //    flight), and LDS reads return in order, so every earlier LDS read has returned.  No lgkmcnt(0) of our own is needed.
-  //  * Workspace loads in front of the product are counted in os.vs and stay in flight across op_wait as before.
+  //  * Workspace loads in front of the product are counted in the plan (kPlanVec each) and stay in flight across the wait.
   //  * Scheduling.  A slot begins with an empty asm that names the accumulator the 16x16x4 in front of it wrote ("+v": it
   //    cannot rise above that instruction) and the operand of the 4x4x4_4b behind it, as every DMA asm does (the 4x4x4_4b
   //    cannot rise above them); volatile asm statements keep their order, and the lane index the address arithmetic
@@ -651,21 +725,17 @@ struct DevWalk {
   static_assert(req_slot(kReqPieces - 1) < 4, "step 0");
   struct ProductRequest {
     DevWalk& w;
-    bool more;
     int etx, tail;       // the next op's stream entry; lanes of its operator's last DMA row
-    unsigned issued;     // VMEM instructions of the request
-    const double* src;   // wave-uniform
+    const uint8_t* src;  // wave-uniform
     uint32_t dst;
     __device__ __forceinline__ explicit ProductRequest(DevWalk& w_) : w(w_) {
       static_assert(kMfma16<S, NG, DIAG> && !kCherryTables && kProductBytes == MatStage<S>::BYTES, "the 64-site protein walk");
       static_assert(MatStage<S>::FULL == 3 && MatPart<kLeafBytes>::FULL == 3 && MatStage<S>::TAIL > 0 && MatPart<kLeafBytes>::TAIL > 0,
                     "three full rows and a partial one, whatever the next op is");
-      more = (w.mi + 1 < w.nmv);
       etx = w.os.pre_tx;
-      src = (more ? w.mat_c : w.mat_after) + w.os.pre_mat;
+      src = w.op_base + w.os.pre_off;
       dst = w.lds_stage + (w.os.par ^ 1u) * MatStage<S>::BYTES;
-      tail = etx >= 0 ? MatPart<kLeafBytes>::TAIL : MatStage<S>::TAIL;   // (a leaf op's operator may be shorter: kLeafBytes)
-      issued = MatStage<S>::ROWS;
+      tail = etx != kPlanProduct ? MatPart<kLeafBytes>::TAIL : MatStage<S>::TAIL;   // (a leaf op's operator may be shorter: kLeafBytes)
     }
     template <int P, int SLOT>
     __device__ __forceinline__ void piece(int l, d4& acc, double& t) {
@@ -677,15 +747,9 @@ struct DevWalk {
           if (l < tail)
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
         } else if constexpr (P == 4) {
-          if (etx >= 0 && (more || w.c + 1 < w.c_end)) {
-            code_dma_l(w.gcodes + (size_t)etx * w.gstride, w.lds_codes + (w.os.par ^ 1u) * kCodeSlotBytes);
-            issued += 1;
-          }
+          if (etx >= 0) code_dma_l(w.gcodes + (size_t)etx * w.gstride, w.lds_codes + (w.os.par ^ 1u) * kCodeSlotBytes);
         } else {
-          const int i2 = more ? w.mi + 2 : 1;   // as op_begin
-          w.os.pre_mat = w.cm.msched[2 * i2];
-          w.os.pre_tx = w.cm.msched[2 * i2 + 1];
-          w.os.vs += issued;
+          w.next_entry();   // as leaf_begin
         }
       }
     }
@@ -706,10 +770,11 @@ struct DevWalk {
   template <int SRC, int DST, bool TR>
   __device__ __forceinline__ void mv(int, int) {
     if constexpr (kMfma16<S, NG, DIAG>) {
-      const uint8_t* buf = op_wait();
+      wait_planned_product(os.pre_w);
+      const uint8_t* buf = stage + os.par * MatStage<S>::BYTES;
       ProductRequest req(*this);
       matvec_stage<S, TR, NG, DIAG>(buf, vlane(), reg<SRC>(), reg<DST>(), req); asm volatile("" :: "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
-      op_end(os.vs);
+      planned_end();
     } else {
       unsigned nseq;
       const uint8_t* buf = op_begin(nseq);
@@ -721,15 +786,18 @@ struct DevWalk {
   // a leaf op, or a cherry-table op (cmx_walk.h): the table is staged like a leaf operator, its row named by two symbols
   template <bool CHERRY, int MODE, int SRC, int DST>
   __device__ __forceinline__ double row_op() {
-    unsigned nseq;
-    const uint8_t* buf = op_begin(nseq);
+    unsigned nseq = 0;
+    const uint8_t* buf;
+    if constexpr (kPlanned) buf = leaf_begin();
+    else buf = op_begin(nseq);
     const int vl = vlane();
     const uint8_t* codes = cslot + os.par * kCodeSlotBytes + 4 * (vl & 15);
     double tot;
     if constexpr (CHERRY) tot = cherry_apply<S, MODE, NG, DIAG>(buf, codes, cslot2 + os.par * kCodeSlotBytes + 4 * (vl & 15), vl, reg<SRC>(), reg<DST>());
     else tot = leaf_apply<S, MODE, NG, DIAG>(buf, codes, vl, reg<SRC>(), reg<DST>());
     asm volatile("" :: "v"(tot), "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
-    op_end(nseq);
+    if constexpr (kPlanned) planned_end();
+    else op_end(nseq);
     return tot;
   }
   // per-class count of row `row` of this lane's site (P; class-split mode: S)
@@ -756,7 +824,7 @@ struct DevWalk {
       const int vl = vlane();
       load_vec<VL, POL::v_load>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<D>(), vl);
     }
-    os.vs += kVecInstrs;
+    if constexpr (!kPlanned) os.vs += kVecInstrs;   // (the planned walk: the host has counted it, cmx_layout.h: kPlanVec)
   }
   template <int SRC>
   __device__ __forceinline__ void store(int arr, int slot) {
@@ -764,15 +832,18 @@ struct DevWalk {
       const int vl = vlane();
       store_vec<VL, POL::v_store>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<SRC>(), vl);
     }
-    os.vs += kVecInstrs;
+    if constexpr (!kPlanned) os.vs += kVecInstrs;
   }
   // LDS slot (kLdsSlot): the vector in the workspace layout [VL/2][64 lanes][2], one 16-byte access per lane and row (no
   // bank conflict).  Plain accesses: the compiler's own lgkmcnt waits cover them, and they are not VMEM, so os.vs does
-  // not count them.
+  // not count them.  Through a pointer that SAYS local memory: where the walk chooses between lstore and store (lload and
+  // load) on a record's flag, hipcc otherwise sinks the two arms' accesses into one run of flat_store / flat_load on a
+  // selected generic address -- the vector's LDS transfers become VMEM instructions the wait plan has not counted, and
+  // the HBM arm loses its cache policy.
   template <int D>
   __device__ __forceinline__ void lload(int, int) {
     static_assert(kLdsSlot && VL % 2 == 0, "LDS slot");
-    const d2* p = reinterpret_cast<const d2*>(vslot) + vlane();
+    const __attribute__((address_space(3))) d2* p = (const __attribute__((address_space(3))) d2*)vslot + vlane();
 #pragma unroll
     for (int i = 0; i < VL / 2; ++i) {
       const d2 t = p[i * kWave];
@@ -783,7 +854,7 @@ struct DevWalk {
   template <int SRC>
   __device__ __forceinline__ void lstore(int, int) {
     static_assert(kLdsSlot && VL % 2 == 0, "LDS slot");
-    d2* p = reinterpret_cast<d2*>(vslot) + vlane();
+    __attribute__((address_space(3))) d2* p = (__attribute__((address_space(3))) d2*)vslot + vlane();
 #pragma unroll
     for (int i = 0; i < VL / 2; ++i) {
       d2 t;
@@ -907,8 +978,16 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
   }
   for (int c = c_begin; c < c_end; ++c) {
     // operators of this class and of the class of the pass that follows (its first operator is requested by our last op)
-    be.mat_c = m.MAT + (size_t)c * m.MC * MatStage<S>::UNIT;
-    be.mat_after = m.MAT + (size_t)((c + 1 < c_end) ? c + 1 : c_after) * m.MC * MatStage<S>::UNIT;
+    if constexpr (DevWalk<S, FUSE, NG, RESOLVED, POL>::kPlanned) {
+      // the planned walk: the pass's class block, and the copy of the stream whose entries behind the last one lead to the
+      // pass that follows (cmx_layout.h: planned_stream_copy) -- the wrap is settled here, no op knows about it
+      const bool last = c + 1 >= c_end;
+      be.op_base = reinterpret_cast<const uint8_t*>(m.MAT + (size_t)c * m.MC * MatStage<S>::UNIT);
+      be.sp = (cmx_cplan)m.plan + ((size_t)planned_stream_copy(C, last, last ? c_after - c : 1) * (size_t)(m.nmv + 2) + 2);
+    } else {
+      be.mat_c = m.MAT + (size_t)c * m.MC * MatStage<S>::UNIT;
+      be.mat_after = m.MAT + (size_t)((c + 1 < c_end) ? c + 1 : c_after) * m.MC * MatStage<S>::UNIT;
+    }
     const double pc = FUSE > 1 ? 1.0 : cm.probs[c];  // fused: the class probabilities are folded into the count operators
     be.pc = pc;
     be.c = c;
@@ -1045,10 +1124,14 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
     const int c0 = (MODE == kModeObservedSplit) ? wave % m.C : 0;   // class of this wave's first pass
     mat_dma<S>(m.MAT + (size_t)c0 * m.MC * MatStage<S>::UNIT + cm.msched[0], cmx_smem + lds_off, lane);
   }
-  os.vs = MatStage<S>::ROWS;
-  os.cur_seq = os.vs;
-  os.pre_mat = cm.msched[2];   // entry 1 (the stream is padded with copies of its first entries)
-  os.pre_tx = cm.msched[3];
+  if constexpr (kMfma16<S, NG, (FUSE > 1 && S / FUSE == 4)>) {   // the planned walk: entry 1, the same in every copy
+    plan_entry((cmx_cplan)m.plan + 1, os);
+  } else {
+    os.vs = MatStage<S>::ROWS;
+    os.cur_seq = os.vs;
+    os.pre_mat = cm.msched[2];   // entry 1 (the stream is padded with copies of its first entries)
+    os.pre_tx = cm.msched[3];
+  }
   if (MODE == kModeObservedSplit) {
     const size_t ntasks = nblocks * (size_t)m.C, BK = (size_t)m.B * m.K;
     for (size_t task = wave; task < ntasks; task += nwaves) {
@@ -1173,6 +1256,7 @@ hipError_t launch_map(const MapArgs& a_in, int mode, int grid_blocks, hipStream_
   if ((int)lds > lim) return hipErrorInvalidValue;
   // (the null instantiations of the class-fused layouts read the cherry-table walk's stream)
   if ((mode == kModeNull || mode == kModeNullPatterns) && a.m.fuse > 1 && a.m.msched_r == nullptr) return hipErrorInvalidValue;
+  if (a.m.S == 20 && a.m.fuse == 1 && a.m.plan == nullptr) return hipErrorInvalidValue;   // the 64-site protein walk reads the planned stream
   if (mode == kModeNullPatterns && (!a.rep_site || !a.npat || !a.counts || !a.post_rate || !a.rate_class || !a.norm)) return hipErrorInvalidValue;
   // 16-site wave-tasks (one site group): small alignments, four times the waves
   if (split16)

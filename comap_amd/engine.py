@@ -59,7 +59,7 @@ EXPORTS = [
     "cmx_hclust", "cmx_hclust_dev", "cmx_cluster_sites", "cmx_cluster_sites_dev", "cmx_cluster_null",
     "cmx_intra_compact_range_dev", "cmx_intra_gram_prefetch_dev", "cmx_expand_compact_rows", "cmx_vector_matrix",
     "cmx_scratch_check", "cmx_debug_lds_slot", "cmx_debug_map_queue", "cmx_debug_map_grid", "cmx_debug_scratch_guard", "cmx_debug_scratch_guard_failures", "cmx_debug_scratch_shrink",
-    "cmx_set_null_patterns", "cmx_null_pattern_count", "cmx_debug_null_hash_bits",
+    "cmx_set_null_patterns", "cmx_null_pattern_count", "cmx_debug_null_hash_bits", "cmx_debug_wait_plan", "cmx_debug_wait_skew", "cmx_debug_map_small_blocks",
 ]
 # clustering.distance / clustering.method options of the reference (CoMap/CoMap.cpp:402-428, :460-472)
 DIST_CORRELATION, DIST_COMPENSATION, DIST_EUCLIDIAN = range(3)
@@ -90,6 +90,13 @@ def map_queue(on=None):
     blocks to the waves through a queue (None = query); returns the previous state.  Off = the fixed strided assignment."""
     lib = load_library()
     return bool(lib.cmx_debug_map_queue(ctypes.c_int(-1 if on is None else int(bool(on)))))
+
+
+def map_small_blocks(on=None):
+    """cmx_debug_map_small_blocks (include/comap_mi355x.h): whether the class-split launch of a small protein alignment maps
+    16-site blocks (None = query); returns the previous state.  Off = 64-site blocks, map_kernel<20, split, 1, NG = 4>."""
+    lib = load_library()
+    return bool(lib.cmx_debug_map_small_blocks(ctypes.c_int(-1 if on is None else int(bool(on)))))
 
 
 def map_grid(workgroups=None):
@@ -295,6 +302,34 @@ def debug_walk(parent, blen, leaf_of_taxon, Q, pi, rates, probs, Bk=None):
                 products=int(stats[2]), leaf_ops=int(stats[3]), products_tables=int(stats[4]), leaf_ops_tables=int(stats[5]),
                 cherry_tables=int(stats[6]), lds_loads=int(stats[7]) & 0xfffff, lds_stores=(int(stats[7]) >> 20) & 0xfffff,
                 lds_copies=(int(stats[7]) >> 40) & 0xfffff)
+
+
+def debug_wait_plan(parent, blen, leaf_of_taxon, Q, pi, rates, probs, Bk=None):
+    """cmx_debug_wait_plan (no GPU): the wait plan of the 64-site walk of a 20-state model, per op of debug_walk's msched:
+    dict(distance[nops], immediate[nops]).  Empty arrays for models without a plan; the call fails if the plan does not
+    pass the engine's model of the wave's memory queue."""
+    lib = load_library()
+    keep = [np.ascontiguousarray(parent, dtype=np.int32), _f64(blen), np.ascontiguousarray(leaf_of_taxon, dtype=np.int32),
+            _f64(Q), _f64(pi), _f64(rates), _f64(probs), None if Bk is None else _f64(Bk)]
+    p, bl, lot, Qa, pia, ra, pr, Bka = keep
+    S, C = len(pia), len(ra)
+    K = 1 if Bka is None else Bka.reshape(-1, S, S).shape[0]
+    model = _Model(S, C, K, _vp(Qa), _vp(pia), _vp(ra), _vp(pr), _vp(Bka), 0, 1, _vp(None))
+    tree = _Tree(len(p), _vp(p), _vp(bl), len(lot), _vp(lot))
+    cap = 64 * len(p) * max(K, 1) + 64
+    dist, imm = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+    n = ctypes.c_size_t(0)
+    st = lib.cmx_debug_wait_plan(ctypes.byref(model), ctypes.byref(tree), _vp(dist), _vp(imm), _sz(cap), ctypes.byref(n))
+    if st != 0:
+        raise CmxError(st, lib.cmx_last_error(None).decode())
+    return dict(distance=dist[: n.value].copy(), immediate=imm[: n.value].copy())
+
+
+def wait_skew(entry=None):
+    """cmx_debug_wait_skew (include/comap_mi355x.h): the next wait plan built gets the immediate of `entry` raised by one
+    (None or negative = clear); returns the previous value (-1: none)"""
+    lib = load_library()
+    return int(lib.cmx_debug_wait_skew(ctypes.c_int(-1 if entry is None else int(entry))))
 
 
 def debug_candidate_cursor(norm_windows, analysable, min_sim, norms, max_trials):

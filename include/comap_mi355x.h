@@ -154,6 +154,17 @@ cmx_status cmx_debug_walk(const cmx_model* model, const cmx_tree* tree, int32_t*
                                             models), cherries with tables (0: that walk is the first one); [7]: of those loads
                                             and stores, the ones the wave's LDS slot serves instead of HBM (loads in bits 0-19,
                                             stores in bits 20-39) and the messages written to both (bits 40-59)*/);
+/* host-side only (no GPU needed): the wait plan of the 64-site walk of 20-state models, one entry per operator use of
+ * msched -- the number of counted memory instructions the walk issues between the request of the op's operator and the
+ * op's wait for it (the smallest over the op's instances), and the s_waitcnt vmcnt immediate the device waits with.  The
+ * plan has passed the engine's model of the wave's memory queue.  *n = 0 for models without a plan.
+ * cmx_debug_wait_skew(k): test hook, process-wide -- the next plan built (cmx_ctx_create, cmx_debug_walk or
+ * cmx_debug_wait_plan of a 20-state model) gets the immediate of entry k raised by one, a wait that is too lax: that build
+ * must fail.  Only a build that makes a plan consumes the hook: models of other alphabets, and builds that fail before
+ * the walk is recorded, leave it set, until a plan is built or it is cleared.  k < 0 clears; returns the previous value. */
+cmx_status cmx_debug_wait_plan(const cmx_model* model, const cmx_tree* tree, int32_t* distance, int32_t* immediate, size_t cap,
+                               size_t* n);
+int cmx_debug_wait_skew(int entry);
 /* The mapping walk keeps short-lived workspace vectors in one LDS slot per wave where the tree allows it (20-state models;
  * results are the same bits either way).  cmx_debug_lds_slot(0) makes contexts created from now on plan the slot empty, i.e.
  * every vector goes through HBM (A/B runs, tests).  on < 0: query only; returns the previous state.  Process-wide, host only. */
@@ -167,6 +178,11 @@ int cmx_debug_lds_slot(int on);
  * rounds of blocks on a few waves).  Negative argument: query only; both return the previous value.  Process-wide, host only. */
 int cmx_debug_map_queue(int on);
 int cmx_debug_map_grid(int workgroups);
+/* The class-split launch of a small protein alignment maps 16-site blocks whenever the alignment is small enough for the
+ * launch at all, so its 64-site shape is reached by no call.  cmx_debug_map_small_blocks(0) makes the launches issued
+ * from now on keep 64-site blocks (tests; the same results either way); on < 0: query only; returns the previous state.
+ * Process-wide, host only, read at each call. */
+int cmx_debug_map_small_blocks(int on);
 
 /* ---- substitution mapping: replaces DRHomogeneousTreeLikelihood::initialize + getLogLikelihoodPerSite /
  * getPosteriorRatePerSite / getRateClassWithMaxPostProbPerSite + computeSubstitutionVectors + computeNormForSite
