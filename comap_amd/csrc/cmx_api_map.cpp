@@ -97,21 +97,17 @@ static cmx_status map_plain(cmx_ctx* ctx, const MapIn& in, MapOut out, void* str
   a.counts = out.counts; a.ldc = out.ldc;
   double* buf;
   CMX_TRY(scratch(ctx, full_grid ? "va_nodes_null" : "va_nodes_obs", plain_node_doubles(a.S, h.C, h.nn, a.chunk), &buf));
-  if (ctx->scaling) {   // the exponents beside the vectors, per caller like them
-    int32_t* exps;
-    CMX_TRY(scratch(ctx, full_grid ? "va_exps_null" : "va_exps_obs", plain_exponent_ints(h.C, h.nn, a.chunk), &exps));
-    HIP_TRY(ctx, launch_scaled_map(a, in.nsites, buf, exps, out.norm, (hipStream_t)stream));
-    return CMX_OK;
-  }
-  // the default mapping of the plain path's alphabets: the matrix-core kernels of cmx_map_wide.hip, unless
+  int32_t* exps = nullptr;   // likelihood scaling: the exponents beside the vectors, per caller like them
+  if (ctx->scaling) CMX_TRY(scratch(ctx, full_grid ? "va_exps_null" : "va_exps_obs", plain_exponent_ints(h.C, h.nn, a.chunk), &exps));
+  // the default mapping of the plain path's alphabets without scaling: the matrix-core kernels of cmx_map_wide.hip, unless
   // cmx_debug_map_wide_plain forces the plain ones (read at each call)
-  if (h.plain && a.mode == M::Joint && !map_wide_plain(-1)) {
+  if (h.plain && a.mode == M::Joint && !ctx->scaling && !map_wide_plain(-1)) {
     double* part;
     CMX_TRY(scratch(ctx, full_grid ? "va_part_null" : "va_part_obs", wide_part_doubles(h.C, h.B, h.K, a.chunk), &part));
     HIP_TRY(ctx, launch_wide_map(a, ctx->va_wide, in.nsites, buf, part, out.norm, (hipStream_t)stream));
     return CMX_OK;
   }
-  HIP_TRY(ctx, launch_plain_map(a, in.nsites, buf, out.norm, (hipStream_t)stream));
+  HIP_TRY(ctx, launch_plain_map(a, in.nsites, buf, exps, out.norm, (hipStream_t)stream));
   return CMX_OK;
 }
 
@@ -291,13 +287,9 @@ cmx_status cmx_ancestral_states_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t n
   a.chunk = plain_sites_per_pass(a.S, h.C, h.nn, nsites, kAsrScratchBytes, true);
   double* buf;
   CMX_TRY(scratch(ctx, "asr_nodes", plain_node_doubles(a.S, h.C, h.nn, a.chunk), &buf));
-  if (ctx->scaling) {
-    int32_t* exps;
-    CMX_TRY(scratch(ctx, "asr_exps", plain_exponent_ints(h.C, h.nn, a.chunk), &exps));
-    HIP_TRY(ctx, launch_scaled_ancestral(a, nsites, buf, exps, ctx->asr_inner, ctx->asr_n_inner, d_states, lds, d_post, ldp, (hipStream_t)stream));
-    return CMX_OK;
-  }
-  HIP_TRY(ctx, launch_ancestral(a, nsites, buf, ctx->asr_inner, ctx->asr_n_inner, d_states, lds, d_post, ldp, (hipStream_t)stream));
+  int32_t* exps = nullptr;
+  if (ctx->scaling) CMX_TRY(scratch(ctx, "asr_exps", plain_exponent_ints(h.C, h.nn, a.chunk), &exps));
+  HIP_TRY(ctx, launch_ancestral(a, nsites, buf, exps, ctx->asr_inner, ctx->asr_n_inner, d_states, lds, d_post, ldp, (hipStream_t)stream));
   return CMX_OK;
 }
 

@@ -66,8 +66,8 @@ struct cmx_ctx {
   bool leaf_rows_custom = false;   // the leaf operators' ambiguity rows were built from a caller's mask table
   bool map_average = true;         // nijt.average (cmx_set_mapping_options); false: the no-averaging mapping of cmx_variants.hip
   bool map_joint = true;           // nijt.joint; false: the ...Marginal variants of cmx_variants.hip
-  // cmx_set_likelihood_scaling: every mapping, null and ancestral-state call goes through the scaled plain kernels
-  // (cmx_scaled.hip), the walk and the fused null are not used
+  // cmx_set_likelihood_scaling: every mapping, null and ancestral-state call goes through the scaled entry points of the
+  // plain kernels (cmx_variants.hip), the walk and the fused null are not used
   bool scaling = false;
   // Statistic::setWeights (cmx_set_statistic_weights): the normalised branch weights, host copy + device copy (B doubles,
   // allocated at the first set); empty = unweighted

@@ -214,7 +214,7 @@ hipError_t launch_mi_pairs_block(int B, const PairOperand& a, const PairOperand&
 hipError_t launch_mi_pairs_diag(int B, const PairOperand& a, const PairOperand& b, size_t n, double* d_out, hipStream_t stream);
 hipError_t launch_mi_group(int B, const PairOperand& g, const int64_t* d_offsets, const int32_t* d_sites, size_t ngroups,
                            double* d_out, hipStream_t stream);
-// (cmx_variants.hip) the plain kernels: one thread per (site, class), (site, branch) or (site, internal node) over per-node
+// (cmx_variants.hip over cmx_plain.h) the plain kernels: one thread per (site, class), (site, branch) or (site, internal node) over per-node
 // vectors in a global scratch.  Four uses: nijt.average = no; nijt.joint = no (the two marginal mappings); the default
 // mapping, likelihood and site scalars of the alphabets the matrix-core walk does not serve (states padded to
 // kPlainStates); marginal ancestral states.
@@ -248,11 +248,16 @@ static_assert(sizeof(PlainArgs) == 240 && offsetof(PlainArgs, mode) == 24 && off
 // passes and a remainder (the mapping)
 size_t plain_node_doubles(int S, int C, int nn, size_t chunk);
 size_t plain_sites_per_pass(int S, int C, int nn, size_t nsites, size_t budget_bytes, bool balanced);
-// scratch: plain_node_doubles(a.S, a.C, a.nn, a.chunk) doubles; d_norm (or null) over all nsites_total sites after the last pass
-hipError_t launch_plain_map(PlainArgs a, size_t nsites_total, double* scratch, double* d_norm, hipStream_t stream);
+// the exponents of a context with per-site likelihood scaling (cmx_set_likelihood_scaling): int32s of the inside
+// and the outside vectors' exponents of `chunk` sites (eD, then eU), outside the pass budget
+size_t plain_exponent_ints(int C, int nn, size_t chunk);
+// scratch: plain_node_doubles(a.S, a.C, a.nn, a.chunk) doubles; exps: null, or plain_exponent_ints(a.C, a.nn, a.chunk) int32s for
+// the scaled kernels (every mode and the site scalars at 4, 20 and kPlainStates states); d_norm (or null) over all
+// nsites_total sites after the last pass
+hipError_t launch_plain_map(PlainArgs a, size_t nsites_total, double* scratch, int32_t* exps, double* d_norm, hipStream_t stream);
 // asr.method = marginal (cmx_ancestral_states*): states [n_inner][lds], optional posterior [n_inner][Sreal][ldp]
-hipError_t launch_ancestral(PlainArgs a, size_t nsites_total, double* scratch, const int* d_inner, int n_inner, uint8_t* d_states,
-                            size_t lds, double* d_post, size_t ldp, hipStream_t stream);
+hipError_t launch_ancestral(PlainArgs a, size_t nsites_total, double* scratch, int32_t* exps, const int* d_inner, int n_inner,
+                            uint8_t* d_states, size_t lds, double* d_post, size_t ldp, hipStream_t stream);
 // computeNormForSite over branch-major counts [B*K][ldc] of n sites (what launch_plain_map ends with)
 hipError_t launch_counts_norm(const double* d_counts, size_t ldc, int B, int K, size_t n, double* d_norm, hipStream_t stream);
 // the site scalars of one pass of the plain path (site_scalars_kernel on the root's a.D; a.S == kPlainStates), for the wide mapping
@@ -270,13 +275,6 @@ int map_wide_plain(int on);   // cmx_debug_map_wide_plain: set (on >= 0) / query
 size_t wide_part_doubles(int C, int B, int K, size_t chunk);
 hipError_t launch_wide_map(PlainArgs a, const WideOps& o, size_t nsites_total, double* scratch, double* part, double* d_norm,
                            hipStream_t stream);
-// (cmx_scaled.hip) the same stage with per-site likelihood scaling (cmx_set_likelihood_scaling): `scratch` as above, and
-// plain_exponent_ints(a.C, a.nn, a.chunk) int32 exponents of the inside and outside vectors in `exps`.  Every mode and the
-// site scalars at 4, 20 and kPlainStates states.
-size_t plain_exponent_ints(int C, int nn, size_t chunk);
-hipError_t launch_scaled_map(PlainArgs a, size_t nsites_total, double* scratch, int32_t* exps, double* d_norm, hipStream_t stream);
-hipError_t launch_scaled_ancestral(PlainArgs a, size_t nsites_total, double* scratch, int32_t* exps, const int* d_inner, int n_inner,
-                                   uint8_t* d_states, size_t lds, double* d_post, size_t ldp, hipStream_t stream);
 // (cmx_mica_post.hip) Mica post-processing
 hipError_t launch_mica_average(const double* d_mi, size_t n, size_t ld, double* d_avg, double* d_full, hipStream_t stream);
 hipError_t launch_mica_zscore(int which, const double* d_mi, size_t n, size_t ld, const double* d_avg, const double* d_full,

@@ -20,10 +20,10 @@
 // order c = 0 .. C-1, then divides by L, as joint_kernel does.  No atomics; a site's results depend on its column alone.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <atomic>
 
-#include "cmx_device.h"
+#include "cmx_plain.h"
+#include "cmx_plain_passes.h"
 
 namespace cmx {
 
@@ -206,17 +206,11 @@ __global__ __launch_bounds__(kTileWaves * 64) __attribute__((amdgpu_waves_per_eu
   }
 }
 
-// the site likelihood, site_likelihood of cmx_variants.hip term for term, once per site for wide_counts_kernel
+// the site likelihood (site_likelihood, cmx_plain.h), once per site for wide_counts_kernel
 __global__ __launch_bounds__(256) void wide_likelihood_kernel(const PlainArgs a, double* __restrict__ lik) {
   const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= a.nsites) return;
-  double L = 0.0;
-  for (int c = 0; c < a.C; ++c) {
-    double s = 0.0;
-    for (int x = 0; x < S; ++x) s += a.pi[x] * a.D[(((size_t)c * a.nn + a.root) * S + x) * a.chunk + j];
-    L += a.probs[c] * s;
-  }
-  lik[j] = L;
+  lik[j] = site_likelihood<S>(a, j).L;
 }
 
 // class terms in the order c = 0 .. C-1, then the division by L (joint_kernel's order); one thread per (site, branch)
@@ -235,28 +229,27 @@ __global__ __launch_bounds__(256) void wide_counts_kernel(const PlainArgs a, con
 
 }  // namespace
 
-// the plain stage's pass loop (plain_passes, cmx_variants.hip) with the wide kernels: per pass the inside kernel, the site
+// the plain stage's pass loop (plain_passes, cmx_plain_passes.h) with the wide kernels: per pass the inside kernel, the site
 // scalars that are asked for (site_scalars_kernel itself) and -- if counts are asked for -- the likelihood, the outside kernel
 // and the class sum; then the norms of all sites
 hipError_t launch_wide_map(PlainArgs a, const WideOps& o, size_t nsites_total, double* scratch, double* part, double* d_norm,
                            hipStream_t stream) {
   if (a.S != S || a.mode != PlainMode::Joint) return hipErrorInvalidValue;
-  const size_t per = plain_node_doubles(S, a.C, a.nn, a.chunk) / 4;
-  a.D = scratch; a.M = scratch + per; a.U = scratch + 2 * per; a.Up = scratch + 3 * per;
   double* lik = part + (size_t)a.C * a.B * a.K * a.chunk;
-  for (a.site0 = 0; a.site0 < nsites_total; a.site0 += a.chunk) {
-    a.nsites = std::min(a.chunk, nsites_total - a.site0);
-    const size_t tiles = (a.nsites + kTileSites - 1) / kTileSites;
-    const dim3 grid((unsigned)((tiles + kTileWaves - 1) / kTileWaves), a.C);
-    const unsigned gx = (unsigned)((a.nsites + 255) / 256);
-    hipLaunchKernelGGL(wide_inside_kernel, grid, dim3(kTileWaves * 64), 0, stream, a, o);
-    if (a.logL || a.post_rate || a.rate_class)
-      if (hipError_t e = launch_plain_site_scalars(a, stream); e != hipSuccess) return e;
-    if (!a.counts) continue;
-    hipLaunchKernelGGL(wide_likelihood_kernel, dim3(gx), dim3(256), 0, stream, a, lik);
-    hipLaunchKernelGGL(wide_outside_kernel, grid, dim3(kTileWaves * 64), 0, stream, a, o, part);
-    hipLaunchKernelGGL(wide_counts_kernel, dim3(gx, a.B), dim3(256), 0, stream, a, (const double*)part, (const double*)lik);
-  }
+  const auto grid = [](const PlainPass& p) {
+    const size_t tiles = (p.a.nsites + kTileSites - 1) / kTileSites;
+    return dim3((unsigned)((tiles + kTileWaves - 1) / kTileWaves), p.a.C);
+  };
+  const hipError_t e = plain_passes(
+      a, nsites_total, scratch, nullptr, a.counts != nullptr,
+      [&](const PlainPass& p) { hipLaunchKernelGGL(wide_inside_kernel, grid(p), dim3(kTileWaves * 64), 0, stream, p.a, o); },
+      [&](const PlainPass& p) { return launch_plain_site_scalars(p.a, stream); },
+      [&](const PlainPass& p) {
+        hipLaunchKernelGGL(wide_likelihood_kernel, dim3(p.gx), dim3(256), 0, stream, p.a, lik);
+        hipLaunchKernelGGL(wide_outside_kernel, grid(p), dim3(kTileWaves * 64), 0, stream, p.a, o, part);
+        hipLaunchKernelGGL(wide_counts_kernel, dim3(p.gx, p.a.B), dim3(256), 0, stream, p.a, (const double*)part, (const double*)lik);
+      });
+  if (e != hipSuccess) return e;
   if (d_norm && a.counts) return launch_counts_norm(a.counts, a.ldc, a.B, a.K, nsites_total, d_norm, stream);
   return hipGetLastError();
 }

@@ -1,5 +1,6 @@
-"""Per-site likelihood scaling (cmx_set_likelihood_scaling, cmx_scaled.hip) on the device, against tests/scaled_reference.py
-(pinned on the CPU by tests/test_scaled_reference.py) and, where nothing underflows, against the oracle and the unscaled call.
+"""Per-site likelihood scaling (cmx_set_likelihood_scaling, the scaled kernels of cmx_variants.hip) on the device, against
+tests/scaled_reference.py (pinned on the CPU by tests/test_scaled_reference.py) and, where nothing underflows, against the
+oracle and the unscaled call.
 
 Tolerances: the project's plain-kernel bars (tests/test_gpu_codon_alphabets.py, _check_map("c61")) -- counts and norm 1e-9
 (atol 1e-300), logL and post_rate 1e-12, rate_class equal -- unless a test says otherwise.  Where a mapping variant chooses
@@ -206,6 +207,33 @@ def test_mapping_crosses_a_pass_at_600_taxa():
     idx = np.array([0, 1, 100, 254, 255, 256])
     ref = _reference(case, np.ascontiguousarray(case["aln"][:, idx]))
     _check_plain({k: full[k][idx] for k in KEYS}, ref)
+
+
+def _asr_sites_per_pass(C, nn, device_states, nsites, budget=2 << 30):
+    """the ancestral states' rule: 2 GiB of per-node vectors a pass, balanced passes rounded up to whole workgroups"""
+    most = max(256, budget // (32 * C * nn * device_states) // 256 * 256)
+    passes = -(-nsites // most)
+    return min(nsites, (-(-nsites // passes) + 255) // 256 * 256)
+
+
+def test_ancestral_states_cross_a_pass_at_600_taxa():
+    case = _taxa600()
+    aln = np.ascontiguousarray(np.tile(case["aln"], (1, 2))[:, :513])
+    first = _asr_sites_per_pass(4, len(case["parent"]), 20, aln.shape[1])
+    assert first == 512 < aln.shape[1] == 513               # a pass of 512 and a pass of 1
+    eng = _engine(case)
+    eng.set_likelihood_scaling(True)
+    full = eng.ancestral_states(aln, want_posterior=True)
+    parts = [eng.ancestral_states(np.ascontiguousarray(a), want_posterior=True) for a in (aln[:, :first], aln[:, first:])]
+    for k in ("states", "post"):
+        assert np.array_equal(full[k], np.concatenate([p[k] for p in parts], axis=1)), k
+    idx = np.array([0, first - 1, first])
+    ref = sr.ancestral_states(case["parent"], case["blen"], case["lot"], np.ascontiguousarray(aln[:, idx]), case["Q"], case["pi"],
+                              case["rates"], case["probs"], ops=case["ops"])
+    assert full["nodes"] == ref["nodes"] and np.isfinite(full["post"]).all()
+    assert np.max(np.abs(full["post"][:, idx] - ref["post"])) <= 1e-9
+    clear = ref["gap"] > 1e-9
+    assert clear.any() and np.array_equal(full["states"][:, idx][clear], ref["states"][clear])
 
 
 def test_ancestral_states_where_fp64_underflows():
