@@ -191,15 +191,24 @@ void build_branch_matrices(const cmx_model* model, const std::vector<Eig>& eig, 
   Mat E(S2), Phi(S2);
   // P(t) of branch b and, per substitution type, either P o N^k (the joint count operator of the averaged mapping) or the
   // conditional expectation N^k itself (nijt.average = no picks single entries of it)
-  auto branch_mats = [&](int b, double t, double* P, double* outK /*[K][S2]*/, bool conditional) {
+  auto branch_mats = [&](int b, double t, double* P, double* outK /*[K][S2]*/, bool conditional, bool rate_zero) {
     const Eig& e = eig[model_of[b]];
     const Mat &V = e.V, &Vi = e.Vi;
     const std::vector<double>& lam = e.lam;
     const std::vector<Mat>& W = e.W;
-    for (int x = 0; x < S; ++x)
-      for (int j = 0; j < S; ++j) E[(size_t)x * S + j] = V[(size_t)x * S + j] * std::exp(lam[j] * t);
-    Mat Pm = matmul(S, E, Vi);
-    std::memcpy(P, Pm.data(), sizeof(double) * S2);
+    if (rate_zero) {
+      // a rate-zero class (Invariant + Gamma): P = I exactly, and the rest below runs at t = 0 (J = 0).  V Vinv is I only
+      // to rounding, with off-diagonals of either sign; a star of some 40 leaves multiplies them into vectors of mixed
+      // signs, which break the rescaling rule of the scaled kernels (largest element of a non-negative vector; DESIGN.md
+      // 2).  A zero-length branch under a positive rate keeps the eigen product and its bits.
+      std::fill(P, P + S2, 0.0);
+      for (int x = 0; x < S; ++x) P[(size_t)x * S + x] = 1.0;
+    } else {
+      for (int x = 0; x < S; ++x)
+        for (int j = 0; j < S; ++j) E[(size_t)x * S + j] = V[(size_t)x * S + j] * std::exp(lam[j] * t);
+      Mat Pm = matmul(S, E, Vi);
+      std::memcpy(P, Pm.data(), sizeof(double) * S2);
+    }
     for (int k = 0; k < K; ++k) {
       double* Ok = outK + (size_t)k * S2;
       if (model->count_method == CMX_COUNT_NAIVE) {
@@ -209,11 +218,20 @@ void build_branch_matrices(const cmx_model* model, const std::vector<Eig>& eig, 
         }
         continue;
       }
-      // J = V [ (Vinv B V) o Phi ] Vinv; Phi through expm1 (accurate O(t^2) diagonal on 1e-6 branches)
+      // J = V [ (Vinv B V) o Phi ] Vinv; Phi through expm1 (accurate O(t^2) diagonal on 1e-6 branches).
+      // Saturated branches: e^{lam_j t} expm1(d) is (underflow) x (overflow) once d nears 709.78, and the Bio++ guard below
+      // would then zero every count of the branch.  Phi is symmetric in (i, j), so above kPhiSymmetricAbove it is taken from
+      // the larger eigenvalue, t e^{max(lam_i, lam_j) t} (-expm1(-|d|)) / |d|, finite for every t >= 0.  The threshold: at
+      // d <= 680 expm1(d) is finite, and a term whose e^{lam_j t} has left the normal range (lam_j t < -708) has
+      // lam_i t < -28, under 1e-12 of t; it stays above the d of every branch the suite and the benchmark have used so far
+      // (t = 120 at rate 2.9 of JTT: d = 653), whose operators keep their bits.
+      constexpr double kPhiSymmetricAbove = 680.0;
       for (int i = 0; i < S; ++i)
         for (int j = 0; j < S; ++j) {
           const double d = (lam[i] - lam[j]) * t;
-          const double phi = std::fabs(d) < 1e-14 ? t * std::exp(lam[i] * t) : t * std::exp(lam[j] * t) * std::expm1(d) / d;
+          const double phi = std::fabs(d) < 1e-14 ? t * std::exp(lam[i] * t)
+                             : d > kPhiSymmetricAbove ? t * std::exp(lam[i] * t) * -std::expm1(-d) / d
+                                                      : t * std::exp(lam[j] * t) * std::expm1(d) / d;
           Phi[(size_t)i * S + j] = W[k][(size_t)i * S + j] * phi;
         }
       Mat J = matmul(S, matmul(S, V, Phi), Vi);
@@ -222,21 +240,26 @@ void build_branch_matrices(const cmx_model* model, const std::vector<Eig>& eig, 
         if (std::isnan(nxy) || std::isinf(nxy)) nxy = 0.0;
         if (model->clamp_negative && nxy < 0.0) nxy = 0.0;
         Ok[i] = conditional ? nxy : P[i] * nxy;
+        // An entry of P below P's own rounding (off-diagonals carry +-1e-17 ... 1e-15: a 1e-100 branch, rates of 1e-5 on
+        // a 1e-12 branch) can come out <= 0, and the guards above then drop a positive J(x, y) from the joint operator,
+        // which needs no quotient: keep J itself there.  P > 0 gives P (J / P) = J whatever P's error, so no other entry
+        // moves.
+        if (!conditional && model->clamp_negative && !(P[i] > 0.0) && J[i] > 0.0) Ok[i] = J[i];
       }
     }
   };
   for (int c = 0; c < C; ++c)
     for (int b = 0; b < B; ++b)
-      branch_mats(b, hm->blen[b] * hm->rates[c], &hm->P[((size_t)c * B + b) * S2], &hm->PN[((size_t)c * B + b) * K * S2], false);
+      branch_mats(b, hm->blen[b] * hm->rates[c], &hm->P[((size_t)c * B + b) * S2], &hm->PN[((size_t)c * B + b) * K * S2], false, hm->rates[c] == 0.0);
   // N^k(x, y; t_b) at the branch length itself: computeSubstitutionVectorsNoAveraging reads single entries of it; and at
   // r_c t_b per class: computeSubstitutionVectorsMarginal weights it with the two marginal posteriors
   hm->N1.assign((size_t)B * K * S2, 0.0);
   hm->NC.assign((size_t)C * B * K * S2, 0.0);
   {
     Mat P1(S2);
-    for (int b = 0; b < B; ++b) branch_mats(b, hm->blen[b], P1.data(), &hm->N1[(size_t)b * K * S2], true);
+    for (int b = 0; b < B; ++b) branch_mats(b, hm->blen[b], P1.data(), &hm->N1[(size_t)b * K * S2], true, false);
     for (int c = 0; c < C; ++c)
-      for (int b = 0; b < B; ++b) branch_mats(b, hm->blen[b] * hm->rates[c], P1.data(), &hm->NC[((size_t)c * B + b) * K * S2], true);
+      for (int b = 0; b < B; ++b) branch_mats(b, hm->blen[b] * hm->rates[c], P1.data(), &hm->NC[((size_t)c * B + b) * K * S2], true, hm->rates[c] == 0.0);
   }
 }
 

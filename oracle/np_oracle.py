@@ -126,6 +126,12 @@ def eigen_reversible(Q, pi):
     return lam, V, Vinv
 
 
+def class_transition_matrix(lam, V, Vinv, blen, rate):
+    """P of a branch under a rate class: I exactly for a rate-zero class (V Vinv is I only to rounding, with off-diagonals of
+    +-1e-15 of either sign), as oracle.c's class_transition and the engine; the eigen product otherwise"""
+    return np.eye(len(lam)) if rate == 0 else transition_matrix(lam, V, Vinv, blen * rate)
+
+
 def transition_matrix(lam, V, Vinv, t):
     return (V * np.exp(lam * t)[None, :]) @ Vinv
 
@@ -154,11 +160,14 @@ def count_matrix_uniformization(Q, Bm, t):
 
 
 def count_matrix_decomposition(lam, V, Vinv, Bm, t):
-    """J = V [ (Vinv B V) o Phi(t) ] Vinv (DecompositionSubstitutionCount)."""
+    """J = V [ (Vinv B V) o Phi(t) ] Vinv (DecompositionSubstitutionCount).  Phi_ij as oracle.c's
+    orc_count_decomp evaluates it: through expm1 (the plain difference quotient cancels on short branches), and from the
+    larger eigenvalue once d = (lam_i - lam_j) t > 680, where e^{lam_j t} expm1(d) would be (underflow) x (overflow)."""
     e = np.exp(lam * t)
-    dl = lam[:, None] - lam[None, :]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        Phi = np.where(np.abs(dl) > 1e-12 * (1 + np.abs(lam[:, None])), (e[:, None] - e[None, :]) / dl, t * e[:, None])
+    d = (lam[:, None] - lam[None, :]) * t
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        Phi = np.where(np.abs(d) < 1e-14, t * e[:, None],
+                       np.where(d > 680.0, t * e[:, None] * -np.expm1(-d) / d, t * e[None, :] * np.expm1(d) / d))
     return V @ ((Vinv @ Bm @ V) * Phi) @ Vinv
 
 
@@ -221,7 +230,7 @@ def map_sites(parent, blen, leaf_of_taxon, aln, masks, Q, pi, rates, probs, Bk_l
     P = np.zeros((nn, C, S, S))
     for e in range(B):
         for c in range(C):
-            P[e, c] = transition_matrix(*eig[mob[e]], blen[e] * rates[c])
+            P[e, c] = class_transition_matrix(*eig[mob[e]], blen[e], rates[c])
     for n in range(nn):
         if not ch[n]:
             lp = leaf_partials(aln[taxon_of_leaf[n]], masks, S)
@@ -265,6 +274,10 @@ def map_sites(parent, blen, leaf_of_taxon, aln, masks, Q, pi, rates, probs, Bk_l
                             J = count_matrix_decomposition(*eig[mob[n]], Bks[mob[n]][k], t)
                         Nm = conditional_counts(J, P[n, c], nonneg if nonneg is not None else True)
                     JJ = P[n, c] * Nm
+                    if method != "naive" and (nonneg if nonneg is not None else True):
+                        # an entry of P below its own rounding can be <= 0 and the guards then drop a positive J(x, y):
+                        # the joint operator keeps it (oracle.c joint_count_matrix)
+                        JJ = np.where(~(P[n, c] > 0) & (J > 0), J, JJ)
                     tot += probs[c] * np.einsum("nx,xy,ny->n", U[c], JJ, D[n][c])
                 counts[:, n, k] = tot / L
             if ch[n]:

@@ -112,6 +112,18 @@ void orc_transition(int S, const double* lam, const double* V, const double* Vin
     }
 }
 
+/* P of a branch under a rate class.  A rate-zero class (Invariant + Gamma) has P = I exactly: V Vinv is I only to
+ * rounding, with off-diagonals of +-1e-15 of either sign, and a star of some 40 leaves multiplies them into vectors of
+ * mixed signs that no rescaling rule survives.  A zero-length branch under a positive rate keeps the eigen product. */
+static void class_transition(int S, const double* lam, const double* V, const double* Vinv, double blen, double rate,
+                             double* P) {
+  if (rate == 0) {
+    for (int i = 0; i < S * S; i++) P[i] = (i / S) == (i % S);
+    return;
+  }
+  orc_transition(S, lam, V, Vinv, blen * rate, P);
+}
+
 /* Uniformization (reference default nijt, doc/comap.texi:155):
  * J(t) = sum_n Pois(n+1; mu t)/mu * sum_{l=0..n} R^l B R^{n-l},  R = I + Q/mu. */
 void orc_count_unif(int S, const double* Q, const double* Bm, double t, double* J) {
@@ -157,6 +169,10 @@ void orc_count_decomp(int S, const double* lam, const double* V, const double* V
     for (int j = 0; j < S; j++) {
       double d = (lam[i] - lam[j]) * t, phi;
       if (fabs(d) < 1e-14) phi = t * exp(lam[i] * t);
+      /* saturated branches: e^{lj t} expm1(d) is (underflow) x (overflow) once d nears 709.78; Phi is symmetric, so
+       * from 680 on it is taken from the larger eigenvalue (d > 0: li), finite for every t >= 0.  Below 680 expm1(d) is
+       * finite and a term whose e^{lj t} has left the normal range has li t < -28, under 1e-12 of t. */
+      else if (d > 680.0) phi = t * exp(lam[i] * t) * -expm1(-d) / d;
       else phi = t * exp(lam[j] * t) * expm1(d) / d;
       W[i * S + j] *= phi;
     }
@@ -189,6 +205,9 @@ static void joint_count_matrix(int S, const double* J, const double* P, int nonn
     if (isnan(nxy) || isinf(nxy)) nxy = 0;
     if (nonneg && nxy < 0) nxy = 0;
     PN[i] = P[i] * nxy;
+    /* an entry of P below P's own rounding can come out <= 0; the guards then drop a positive J(x, y), which the joint
+     * operator has without the quotient: keep it (P > 0 gives P (J / P) = J whatever P's error) */
+    if (nonneg && !(P[i] > 0) && J[i] > 0) PN[i] = J[i];
   }
 }
 
@@ -237,7 +256,7 @@ int orc_map_sites(int nn, const int* parent, const double* blen, int T, const in
       SET_GEN(b);
       double t = blen[b] * rates[c];
       double* Pbc = P + ((size_t)b * C + c) * S2;
-      orc_transition(S, lam, V, Vinv, t, Pbc);
+      class_transition(S, lam, V, Vinv, blen[b], rates[c], Pbc);
       for (int k = 0; k < K; k++) {
         double* PNk = PN + (((size_t)b * C + c) * K + k) * S2;
         if (method == 2) {
@@ -382,7 +401,7 @@ int orc_map_sites_noavg(int nn, const int* parent, const double* blen, int T, co
   for (int b = 0; b < B; b++) {
     SET_EIG(b);
     SET_GEN(b);
-    for (int c = 0; c < C; c++) orc_transition(S, lam, V, Vinv, blen[b] * rates[c], P + ((size_t)b * C + c) * S2);
+    for (int c = 0; c < C; c++) class_transition(S, lam, V, Vinv, blen[b], rates[c], P + ((size_t)b * C + c) * S2);
     orc_transition(S, lam, V, Vinv, blen[b], P1);
     for (int k = 0; k < K; k++) {
       double* Nk = N1 + ((size_t)b * K + k) * S2;
@@ -522,7 +541,7 @@ int orc_map_sites_marginal(int nn, const int* parent, const double* blen, int T,
       SET_EIG(b);
       SET_GEN(b);
       double t = blen[b] * (c < C ? rates[c] : 1.0);
-      orc_transition(S, lam, V, Vinv, t, Pt);
+      class_transition(S, lam, V, Vinv, blen[b], c < C ? rates[c] : 1.0, Pt);
       if (c < C) memcpy(P + ((size_t)b * C + c) * S2, Pt, sizeof(double) * S2);
       for (int k = 0; k < K; k++) {
         double* Nk = NC + (((size_t)b * (C + 1) + c) * K + k) * S2;
@@ -732,7 +751,7 @@ void orc_simulate(int nn, const int* parent, const double* blen, int T, const in
   double* P = (double*)malloc(sizeof(double) * (size_t)B * C * S2);
   for (int b = 0; b < B; b++) {
     SET_EIG(b);
-    for (int c = 0; c < C; c++) orc_transition(S, lam, V, Vinv, blen[b] * rates[c], P + ((size_t)b * C + c) * S2);
+    for (int c = 0; c < C; c++) class_transition(S, lam, V, Vinv, blen[b], rates[c], P + ((size_t)b * C + c) * S2);
   }
   int* taxon_of = (int*)malloc(sizeof(int) * nn);
   for (int i = 0; i < nn; i++) taxon_of[i] = -1;

@@ -31,7 +31,8 @@ def has_extended_range():
 
 
 def operators(parent, blen, Q, pi, rates, Bk=None, nonneg=True):
-    """fp64 operators of a homogeneous model: dict(P [C, nn, S, S], NC [C, nn, K, S, S] conditional counts at r_c t_b,
+    """fp64 operators of a homogeneous model: dict(P [C, nn, S, S], PN [C, nn, K, S, S] the joint count operator P o NC,
+    NC [C, nn, K, S, S] conditional counts at r_c t_b,
     N1 [nn, K, S, S] conditional counts at t_b itself); the root's entries stay 0"""
     Q, pi = np.asarray(Q, dtype=np.float64), np.asarray(pi, dtype=np.float64)
     S, C, nn = len(pi), len(rates), len(parent)
@@ -41,17 +42,24 @@ def operators(parent, blen, Q, pi, rates, Bk=None, nonneg=True):
     eig = npo.eigen_reversible(Q, pi)
     P, NC, N1 = np.zeros((C, nn, S, S)), np.zeros((C, nn, K, S, S)), np.zeros((nn, K, S, S))
 
-    def cond(t, Pt):
-        return np.stack([npo.conditional_counts(npo.count_matrix_uniformization(Q, B, t), Pt, nonneg) for B in Bk])
+    PN = np.zeros((C, nn, K, S, S))
+
+    def cond(t, Pt, joint=None):
+        Js = [npo.count_matrix_uniformization(Q, B, t) for B in Bk]
+        N = np.stack([npo.conditional_counts(J, Pt, nonneg) for J in Js])
+        if joint is not None:       # P o N, keeping a positive J(x, y) where P is not positive (oracle.c joint_count_matrix)
+            for k, J in enumerate(Js):
+                joint[k] = np.where(~(Pt > 0) & (J > 0), J, Pt * N[k]) if nonneg else Pt * N[k]
+        return N
 
     for b in range(nn):
         if parent[b] < 0:
             continue
         N1[b] = cond(blen[b], npo.transition_matrix(*eig, blen[b]))
         for c in range(C):
-            P[c, b] = npo.transition_matrix(*eig, blen[b] * rates[c])
-            NC[c, b] = cond(blen[b] * rates[c], P[c, b])
-    return dict(P=P, NC=NC, N1=N1)
+            P[c, b] = npo.class_transition_matrix(*eig, blen[b], rates[c])
+            NC[c, b] = cond(blen[b] * rates[c], P[c, b], PN[c, b])
+    return dict(P=P, NC=NC, N1=N1, PN=PN)
 
 
 def _ilogb(m):
@@ -167,6 +175,7 @@ def map_sites(parent, blen, lot, aln, Q, pi, rates, probs, masks=None, ops=None,
     v = vectors(parent, lot, aln, ops, pi, probs, masks, dtype, scale)
     rates_t, probs_t = np.asarray(rates, dtype=dtype), np.asarray(probs, dtype=dtype)
     P, NC, N1 = ops["P"].astype(dtype), ops["NC"].astype(dtype), ops["N1"]
+    PN = ops["PN"].astype(dtype) if "PN" in ops else P[:, :, None] * NC
     C, S, N, nn, root = v.C, v.S, v.N, v.nn, v.root
     B, K = nn - 1, NC.shape[2]
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -191,7 +200,7 @@ def map_sites(parent, blen, lot, aln, Q, pi, rates, probs, masks=None, ops=None,
                 for k in range(K):
                     tot = np.zeros(N, dtype=dtype)
                     for c in range(C):
-                        vc = np.einsum("nx,xy,ny->n", v.U[b][c], P[c, b] * NC[c, b, k], v.D[b][c])
+                        vc = np.einsum("nx,xy,ny->n", v.U[b][c], PN[c, b, k], v.D[b][c])
                         tot = tot + _shift(probs_t[c] * vc, sh[c])
                     counts[:, b, k] = tot / v.L
             elif joint:
