@@ -30,6 +30,17 @@ static std::vector<double> pack_wide(const std::vector<double>& m, bool transpos
   return o;
 }
 
+// 20 x 20 row-major matrices packed for the 20-state shape of the wide mapping (wide20_op_offset: 32 x 20, rows 20 .. 31 zero)
+static std::vector<double> pack_wide20(const std::vector<double>& m, bool transpose) {
+  constexpr int S = 20, U = kWide20Rows * S;
+  const size_t nm = m.size() / ((size_t)S * S);
+  std::vector<double> o(nm * U, 0.0);
+  for (size_t q = 0; q < nm; ++q)
+    for (int x = 0; x < S; ++x)
+      for (int y = 0; y < S; ++y) o[q * U + (transpose ? wide20_op_offset(y, x) : wide20_op_offset(x, y))] = m[(q * S + x) * S + y];
+  return o;
+}
+
 // the operators of the plain kernels (cmx_variants.hip), uploaded at the first use by the mapping variants or by the
 // ancestral states (padded with zeros to kPlainStates on the plain path)
 static cmx_status upload_variant_operators(cmx_ctx* ctx) {
@@ -54,6 +65,12 @@ static cmx_status upload_variant_operators(cmx_ctx* ctx) {
   }
   // the scaled default mapping at 4 / 20 states reads the joint counts too: at its first use, whatever was uploaded before
   if (ctx->scaling && !ctx->va_PN) CMX_TRY(upload(ctx, h.PN, &ctx->va_PN));
+  // and at 20 states the three operators of its matrix-core kernels (cmx_map_wide.hip), packed
+  if (ctx->scaling && h.S == 20 && !ctx->va_wide.P) {
+    CMX_TRY(upload(ctx, pack_wide20(h.P, false), &ctx->va_wide.P));
+    CMX_TRY(upload(ctx, pack_wide20(h.P, true), &ctx->va_wide.PT));
+    CMX_TRY(upload(ctx, pack_wide20(h.PN, false), &ctx->va_wide.PN));
+  }
   return CMX_OK;
 }
 
@@ -99,12 +116,15 @@ static cmx_status map_plain(cmx_ctx* ctx, const MapIn& in, MapOut out, void* str
   CMX_TRY(scratch(ctx, full_grid ? "va_nodes_null" : "va_nodes_obs", plain_node_doubles(a.S, h.C, h.nn, a.chunk), &buf));
   int32_t* exps = nullptr;   // likelihood scaling: the exponents beside the vectors, per caller like them
   if (ctx->scaling) CMX_TRY(scratch(ctx, full_grid ? "va_exps_null" : "va_exps_obs", plain_exponent_ints(h.C, h.nn, a.chunk), &exps));
-  // the default mapping of the plain path's alphabets without scaling: the matrix-core kernels of cmx_map_wide.hip, unless
-  // cmx_debug_map_wide_plain forces the plain ones (read at each call)
-  if (h.plain && a.mode == M::Joint && !ctx->scaling && !map_wide_plain(-1)) {
-    double* part;
-    CMX_TRY(scratch(ctx, full_grid ? "va_part_null" : "va_part_obs", wide_part_doubles(h.C, h.B, h.K, a.chunk), &part));
-    HIP_TRY(ctx, launch_wide_map(a, ctx->va_wide, in.nsites, buf, part, out.norm, (hipStream_t)stream));
+  // the default mapping on the matrix-core kernels of cmx_map_wide.hip: the plain path's alphabets without scaling unless
+  // cmx_debug_map_wide_plain forces the plain kernels, and with scaling these and 20 states unless
+  // cmx_debug_map_scaled_plain does (each read at each call; neither touches the other's calls)
+  const bool wide = a.mode == M::Joint && (ctx->scaling ? (h.plain || h.S == 20) && !map_scaled_plain(-1) : h.plain && !map_wide_plain(-1));
+  if (wide) {
+    void* part;
+    const size_t bytes = ctx->scaling ? wide_scaled_part_bytes(h.C, h.B, h.K, a.chunk) : sizeof(double) * wide_part_doubles(h.C, h.B, h.K, a.chunk);
+    CMX_TRY(scratch(ctx, full_grid ? "va_part_null" : "va_part_obs", bytes, &part));
+    HIP_TRY(ctx, launch_wide_map(a, ctx->va_wide, in.nsites, buf, exps, (double*)part, out.norm, (hipStream_t)stream));
     return CMX_OK;
   }
   HIP_TRY(ctx, launch_plain_map(a, in.nsites, buf, exps, out.norm, (hipStream_t)stream));
@@ -112,6 +132,7 @@ static cmx_status map_plain(cmx_ctx* ctx, const MapIn& in, MapOut out, void* str
 }
 
 int cmx_debug_map_wide_plain(int on) { return map_wide_plain(on); }
+int cmx_debug_map_scaled_plain(int on) { return map_scaled_plain(on); }
 
 // ------------------------------------------------------------------------------------------------ mapping
 // The matrix-core walk of a 4- or 20-state mapping (cmx_map.hip).  full_grid: use the whole-chip workspace of the null launches

@@ -84,7 +84,7 @@ struct cmx_ctx {
   const double *va_P = nullptr, *va_N1 = nullptr, *va_NC = nullptr;   // their operators, uploaded at first use
   const double *va_PN = nullptr, *va_pi = nullptr;                     // plain path: joint counts and frequencies, padded (va_PN also: scaled mapping at 4 / 20 states)
   const int *va_first = nullptr, *va_next = nullptr;
-  WideOps va_wide{};   // plain path: va_P, its transpose and va_PN once more, packed for the wide mapping (cmx_map_wide.hip)
+  WideOps va_wide{};   // va_P, its transpose and va_PN once more, packed for the wide mapping (cmx_map_wide.hip): plain path, or 20 states at the first scaled use
   const int* asr_inner = nullptr;   // cmx_ancestral_states*: the internal nodes, ascending (uploaded at first use)
   int asr_n_inner = 0;
   // the fused null's distinct columns (cmx_set_null_patterns): -1 automatic, 0 off, 1 on; what the last null mapped

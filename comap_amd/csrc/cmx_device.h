@@ -262,19 +262,29 @@ hipError_t launch_ancestral(PlainArgs a, size_t nsites_total, double* scratch, i
 hipError_t launch_counts_norm(const double* d_counts, size_t ldc, int B, int K, size_t n, double* d_norm, hipStream_t stream);
 // the site scalars of one pass of the plain path (site_scalars_kernel on the root's a.D; a.S == kPlainStates), for the wide mapping
 hipError_t launch_plain_site_scalars(const PlainArgs& pass, hipStream_t stream);
-// (cmx_map_wide.hip) PlainMode::Joint and the site scalars at kPlainStates states on the f64 matrix instruction: the pass
-// structure, the scratch and the arithmetic of launch_plain_map, which it replaces by default for contexts without likelihood
-// scaling.  Operators packed by wide_op_offset (cmx_layout.h), uploaded beside the plain ones.
+// the same under likelihood scaling (scaled_site_scalars_kernel; a.S == 20 or kPlainStates), eD / eU: the pass's exponents
+hipError_t launch_scaled_site_scalars(const PlainArgs& pass, int32_t* eD, int32_t* eU, hipStream_t stream);
+// (cmx_map_wide.hip) PlainMode::Joint and the site scalars on the f64 matrix instruction: the pass structure, the scratch and
+// the arithmetic of launch_plain_map, which it replaces by default at kPlainStates states without likelihood scaling and, with
+// it, at kPlainStates and at 20 states.  Operators packed by wide_op_offset / wide20_op_offset (cmx_layout.h), uploaded beside
+// the plain ones.
 struct WideOps {
-  const double* P;    // [C][B][S*S] transition matrices
-  const double* PT;   // [C][B][S*S] their transposes
-  const double* PN;   // [C][B][K][S*S] joint counts P o N^k
+  const double* P;    // [C][B] transition matrices
+  const double* PT;   // [C][B] their transposes
+  const double* PN;   // [C][B][K] joint counts P o N^k
 };
-int map_wide_plain(int on);   // cmx_debug_map_wide_plain: set (on >= 0) / query, returns the previous state
-// part: wide_part_doubles(a.C, a.B, a.K, a.chunk) doubles, the per-class partial counts [C][B*K][chunk] and the likelihoods [chunk]
+int map_wide_plain(int on);     // cmx_debug_map_wide_plain: set (on >= 0) / query, returns the previous state
+int map_scaled_plain(int on);   // cmx_debug_map_scaled_plain, likewise
+// part: the per-class partial counts [C][B*K][chunk] and the likelihoods [chunk] (unscaled: wide_part_doubles doubles), with
+// likelihood scaling the likelihoods' int32 exponents [chunk] behind them (wide_scaled_part_bytes bytes)
 size_t wide_part_doubles(int C, int B, int K, size_t chunk);
-hipError_t launch_wide_map(PlainArgs a, const WideOps& o, size_t nsites_total, double* scratch, double* part, double* d_norm,
-                           hipStream_t stream);
+size_t wide_scaled_part_bytes(int C, int B, int K, size_t chunk);
+// exps: null, or the plain_exponent_ints(a.C, a.nn, a.chunk) int32s of launch_plain_map for the scaled kernels
+hipError_t launch_wide_map(PlainArgs a, const WideOps& o, size_t nsites_total, double* scratch, int32_t* exps, double* part,
+                           double* d_norm, hipStream_t stream);
+// (cmx_map_wide20.hip) its 20-state shape, scaled only; launch_wide_map dispatches to it
+hipError_t launch_wide20_scaled_map(const PlainArgs& a, const WideOps& o, size_t nsites_total, double* scratch, int32_t* exps, double* part,
+                                    double* d_norm, hipStream_t stream);
 // (cmx_mica_post.hip) Mica post-processing
 hipError_t launch_mica_average(const double* d_mi, size_t n, size_t ld, double* d_avg, double* d_full, hipStream_t stream);
 hipError_t launch_mica_zscore(int which, const double* d_mi, size_t n, size_t ld, const double* d_avg, const double* d_full,

@@ -42,8 +42,9 @@ constexpr int mfma16_a_offset(int lane, int i, bool tr, int S) {
 // 16 p + 15) and k-step i (columns 4 i .. 4 i + 3) is (row 16 p + (l & 15), column 4 i + (l >> 4)) in lane l.  Packed, that is
 // double l of the 64 consecutive doubles of (p, i): one coalesced 512-byte read per wave and step.  The host packer
 // (cmx_api_map.cpp: pack_wide) and the kernels both place an element with this one function.
-constexpr int wide_op_offset(int row, int col) {
-  return ((row >> 4) * (kPlainStates / 4) + (col >> 2)) * 64 + (col & 3) * 16 + (row & 15);
+// S: the states of the shape, kPlainStates or 20 (below).
+constexpr int wide_op_offset(int row, int col, int S = kPlainStates) {
+  return ((row >> 4) * (S / 4) + (col >> 2)) * 64 + (col & 3) * 16 + (row & 15);
 }
 constexpr bool wide_op_offset_is_bijection() {
   bool seen[kPlainStates * kPlainStates] = {};
@@ -66,6 +67,30 @@ constexpr bool wide_op_offset_is_lane_major() {
 static_assert(kPlainStates == 64, "wide_op_offset: four panels of sixteen k-steps");
 static_assert(wide_op_offset_is_bijection(), "wide_op_offset must be a bijection onto 64 x 64");
 static_assert(wide_op_offset_is_lane_major() && wide_op_offset(0, 0) == 0, "a step's A operand is 64 consecutive doubles, lane-major");
+// The same for the 20-state shape of the wide mapping (20-state models under likelihood scaling): two output panels of 16
+// rows and five k-steps.  An operator is packed as kWide20Rows x 20 with rows 20 .. 31 zero, so that a panel is a whole
+// instruction; 640 doubles instead of 400.
+constexpr int kWide20Rows = 32;
+constexpr int wide20_op_offset(int row, int col) { return wide_op_offset(row, col, 20); }
+constexpr bool wide20_op_offset_is_bijection() {
+  bool seen[kWide20Rows * 20] = {};
+  for (int r = 0; r < kWide20Rows; ++r)
+    for (int c = 0; c < 20; ++c) {
+      const int o = wide20_op_offset(r, c);
+      if (o < 0 || o >= kWide20Rows * 20 || seen[o]) return false;
+      seen[o] = true;
+    }
+  return true;
+}
+constexpr bool wide20_op_offset_is_lane_major() {
+  for (int p = 0; p < kWide20Rows / 16; ++p)
+    for (int i = 0; i < 20 / 4; ++i)
+      for (int l = 0; l < 64; ++l)
+        if (wide20_op_offset(16 * p + (l & 15), 4 * i + (l >> 4)) != wide20_op_offset(16 * p, 4 * i) + l) return false;
+  return true;
+}
+static_assert(wide20_op_offset_is_bijection(), "wide20_op_offset must be a bijection onto 32 x 20");
+static_assert(wide20_op_offset_is_lane_major() && wide20_op_offset(0, 0) == 0, "a step's A operand is 64 consecutive doubles, lane-major");
 
 // A class block of HostModel::MAT / DevModel::MAT: per device class one run of count() matrices of mat_unit doubles.
 // `which` names an operator of a branch as in cmx_walk.h: OPER_P (< 0) = transition matrix, k >= 0 = count operator k.

@@ -15,7 +15,8 @@
 //      site scalars (site_scalars_kernel).  At 4 / 20 states the scalars do not depend on the option and stay the walk's.
 //      By default cmx_map_wide.hip serves this use on the matrix cores, inside the same passes and with site_scalars_kernel
 //      itself (launch_plain_site_scalars); joint_kernel and the inside / outside kernels at 64 states run for it under
-//      cmx_debug_map_wide_plain(1) only.
+//      cmx_debug_map_wide_plain(1) only.  Under likelihood scaling the same holds at 20 states too (cmx_map_wide20.hip,
+//      launch_scaled_site_scalars, cmx_debug_map_scaled_plain).
 //   4. marginal ancestral states (asr.method = marginal): ancestral_kernel.
 // Every kernel is written once, in cmx_plain_kernels.inc, over a scaling policy (cmx_plain.h); this file includes that text
 // twice, which gives each kernel two entry points: NAME<S>(PlainArgs) runs it without scaling, scaled_NAME<S>(ScaledArgs)
@@ -167,6 +168,15 @@ hipError_t launch_plain_map(PlainArgs a, size_t nsites_total, double* scratch, i
 hipError_t launch_plain_site_scalars(const PlainArgs& pass, hipStream_t stream) {
   if (pass.S != kPlainStates) return hipErrorInvalidValue;
   hipLaunchKernelGGL(site_scalars_kernel<kPlainStates>, dim3((unsigned)((pass.nsites + 255) / 256)), dim3(256), 0, stream, pass);
+  return hipGetLastError();
+}
+
+hipError_t launch_scaled_site_scalars(const PlainArgs& pass, int32_t* eD, int32_t* eU, hipStream_t stream) {
+  const dim3 grid((unsigned)((pass.nsites + 255) / 256));
+  const ScaledArgs args{pass, {eD, eU}};
+  if (pass.S == kPlainStates) hipLaunchKernelGGL(scaled_site_scalars_kernel<kPlainStates>, grid, dim3(256), 0, stream, args);
+  else if (pass.S == 20) hipLaunchKernelGGL(scaled_site_scalars_kernel<20>, grid, dim3(256), 0, stream, args);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

@@ -53,7 +53,7 @@ EXPORTS = [
     "cmx_simulate_continuous_dev", "cmx_null_intra_continuous", "cmx_null_intra_continuous_dev", "cmx_mi_pairs_dev",
     "cmx_pair_stats", "cmx_pair_stats_dev", "cmx_null_intra", "cmx_null_simulate_dev", "cmx_null_intra_dev", "cmx_null_inter",
     "cmx_null_inter_dev", "cmx_intra_pvalues", "cmx_intra_rows", "cmx_intra_rows_dev", "cmx_intra_rows_range_dev",
-    "cmx_intra_pvalues_dev", "cmx_inter_rows", "cmx_inter_rows_dev", "cmx_mica_bootstrap_indices", "cmx_mica_parametric_null", "cmx_mi_columns", "cmx_mi_columns_dev", "cmx_mi_pairs", "cmx_debug_mica_wide_plain", "cmx_debug_map_wide_plain",
+    "cmx_intra_pvalues_dev", "cmx_inter_rows", "cmx_inter_rows_dev", "cmx_mica_bootstrap_indices", "cmx_mica_parametric_null", "cmx_mi_columns", "cmx_mi_columns_dev", "cmx_mi_pairs", "cmx_debug_mica_wide_plain", "cmx_debug_map_wide_plain", "cmx_debug_map_scaled_plain",
     "cmx_mica_permutation_test", "cmx_mica_permutation_test_dev", "cmx_mica_permutation_test_masks", "cmx_mica_permutation_test_masks_dev", "cmx_mica_permutation_test_states", "cmx_mica_permutation_test_states_dev", "cmx_mica_average_mi", "cmx_mica_average_mi_dev", "cmx_mica_zscore_null", "cmx_mica_zscore_null_dev",
     "cmx_group_stats", "cmx_group_stats_dev", "cmx_candidate_groups", "cmx_debug_candidate_cursor",
     "cmx_hclust", "cmx_hclust_dev", "cmx_cluster_sites", "cmx_cluster_sites_dev", "cmx_cluster_null",
@@ -118,6 +118,13 @@ def map_wide_plain(on=None):
     the plain kernels instead of the matrix-core ones (None = query); returns the previous state"""
     lib = load_library()
     return bool(lib.cmx_debug_map_wide_plain(ctypes.c_int(-1 if on is None else int(bool(on)))))
+
+
+def map_scaled_plain(on=None):
+    """cmx_debug_map_scaled_plain (include/comap_mi355x.h): whether the default mapping under likelihood scaling runs the scaled
+    plain kernels instead of the matrix-core ones (None = query); returns the previous state"""
+    lib = load_library()
+    return bool(lib.cmx_debug_map_scaled_plain(ctypes.c_int(-1 if on is None else int(bool(on)))))
 
 
 def scratch_guard_failures(clear=False):

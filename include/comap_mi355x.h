@@ -203,6 +203,13 @@ cmx_status cmx_map_sites_dev(cmx_ctx* ctx, const uint8_t* d_aln, size_t nsites, 
  * restores; on < 0: query only.  Returns the previous state; the default is 0.  Read at each call, no context keeps it.
  * Process-wide, host only. */
 int cmx_debug_map_wide_plain(int on);
+/* Under likelihood scaling (cmx_set_likelihood_scaling) the default mapping and its site scalars run matrix-core kernels at 20
+ * states and at every alphabet other than 4 states; cmx_debug_map_scaled_plain(1) makes them run the scaled plain kernels
+ * instead, as the variants, the ancestral states and 4-state models do (A/B runs, a cross-check for tests; the two agree to
+ * rounding, not as bits); 0 restores; on < 0: query only.  Returns the previous state; the default is 0.  Read at each call,
+ * no context keeps it.  Process-wide, host only.  cmx_debug_map_wide_plain does not touch scaled calls, nor this one unscaled
+ * calls. */
+int cmx_debug_map_scaled_plain(int on);
 /* nijt.average / nijt.joint (CoMap/CoETools.cpp:393-406, CoMap/AnalysisTools.cpp:598-633: which of
  * LegacySubstitutionMappingTools::computeSubstitutionVectors{, NoAveraging, Marginal, NoAveragingMarginal} maps the
  * sites; "for benchmarking only" in the reference, but nijt = Label with the MI statistic requires average = no,
