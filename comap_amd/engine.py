@@ -859,6 +859,26 @@ class Engine:
                                                  _sz(0 if counts2 is None else counts2.stride(0)), _vp(out),
                                                  _sz(out.stride(0)), self._stream()))
 
+    def hclust_dev(self, linkage, dist, merge, dmax, size):
+        """dist: float64 CUDA tensor [n, n] or [batch, n, n], rows ld = stride of the row axis apart and matrices n * ld
+        apart (destroyed; NaN -> +inf in its n columns); merge: int32 [batch, n-1, 2], dmax: float64 [batch, n-1],
+        size: int32 [batch, n-1] (asynchronous on the current stream)"""
+        n, ld = dist.shape[-1], dist.stride(-2)
+        batch = 1 if dist.dim() == 2 else dist.shape[0]
+        if dist.stride(-1) != 1 or (dist.dim() == 3 and batch > 1 and dist.stride(0) != n * ld):
+            raise CmxError(-1, "hclust_dev: dist must be [batch, n, n] with the rows ld and the matrices n * ld apart")
+        self._check(self._lib.cmx_hclust_dev(self._ctx, int(linkage), _vp(dist), _sz(n), _sz(ld), _sz(batch), _vp(merge),
+                                             _vp(dmax), _vp(size), self._stream()))
+
+    def cluster_sites_dev(self, dist_kind, linkage, counts, norm, merge, dmax, size, stat, nmin, dist=None):
+        """counts: float64 [B*K, ldc] CUDA tensor (as map_sites_dev writes them), norm: [n]; merge: int32 [n-1, 2],
+        size: int32 [n-1], dmax / stat / nmin: float64 [n-1], dist: contiguous float64 [n, n] or None (asynchronous on
+        the current stream)"""
+        n = norm.shape[0]
+        self._check(self._lib.cmx_cluster_sites_dev(self._ctx, int(dist_kind), int(linkage), _vp(counts), _sz(n),
+                                                    _sz(counts.stride(0)), _vp(norm), _vp(dist), _vp(merge), _vp(dmax), _vp(size),
+                                                    _vp(stat), _vp(nmin), self._stream()))
+
     def null_simulate_dev(self, seed, rep_begin, rep_end, rep_ram, aln):
         """the null's simulated alignments into `aln` (uint8 CUDA tensor, >= nrep * 2 * T * rep_ram bytes, laid out
         [replicate][batch][taxon][rep_ram]): what null_intra_dev takes as `supplied`"""

@@ -43,14 +43,13 @@ d = (d + d.transpose(1, 2)) / 2
 merge = torch.empty((batch, n - 1, 2), dtype=torch.int32, device="cuda")
 dmax = torch.empty((batch, n - 1), dtype=torch.float64, device="cuda")
 size = torch.empty((batch, n - 1), dtype=torch.int32, device="cuda")
-lib, vp, sz = eng._lib, engine._vp, engine._sz
 work = d.clone()
-eng._check(lib.cmx_hclust_dev(eng._ctx, link, vp(work), sz(n), sz(n), sz(batch), vp(merge), vp(dmax), vp(size), eng._stream()))
+eng.hclust_dev(link, work, merge, dmax, size)
 torch.cuda.synchronize()
 work.copy_(d)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()
-eng._check(lib.cmx_hclust_dev(eng._ctx, link, vp(work), sz(n), sz(n), sz(batch), vp(merge), vp(dmax), vp(size), eng._stream()))
+eng.hclust_dev(link, work, merge, dmax, size)
 e1.record()
 torch.cuda.synchronize()
 hc_ms = e0.elapsed_time(e1)

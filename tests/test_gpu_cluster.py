@@ -1,6 +1,8 @@
 """Clustering analysis on the device against oracle/cluster.py, through the C-ABI.
 The agglomeration is integer/compare work plus one explicitly rounded formula: merges, sizes and join distances must be
-bit-identical for the same input matrix.  Distances and group statistics are floating point: 1e-6 relative."""
+bit-identical for the same input matrix (every kernel shape: tests/test_gpu_cluster_shapes.py).  The distances are pinned
+to their definitions by test_clustering_distances in tests/test_gpu_pair_stat_edges.py; here they and the group statistics
+are only held near the oracle's, which is what keeps the two trees the same."""
 import numpy as np
 import pytest
 
@@ -225,8 +227,7 @@ def test_random_cluster_configurations_against_oracle(seed):
     om, eng = _setup(nstates, int(rng.integers(8, 16)) if nstates == 20 else 18, 40 + seed, Bk=dist == oc.DIST_COMPENSATION)
     n = int(rng.integers(2, 90))
     aln, _ = oracle.simulate(om, 77 + seed, 0, n)
-    if np.unique(aln, axis=1).shape[1] != n:
-        pytest.skip("simulated columns not distinct for this seed")
+    _no_duplicate_columns(aln)      # holds for all ten seeds; should one ever fail, change that seed
     counts = oracle.map_sites(om, aln)["counts"]
     g = eng.cluster_sites(dist, link, counts)
     d = oc.distance_matrix(dist, counts)
