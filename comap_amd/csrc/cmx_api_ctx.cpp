@@ -22,6 +22,9 @@ std::atomic<int> g_lds_slot{1};         // cmx_debug_lds_slot: 0 = the mapping w
 std::atomic<int> g_pat_hash_bits{64};   // (tests force collisions with it)
 std::atomic<int> g_map_queue{1};        // cmx_debug_map_queue: 0 = strided block assignment in every mapping launch (A/B runs, tests)
 std::atomic<int> g_map_small_blocks{1};      // cmx_debug_map_small_blocks: 0 = the class-split launch of a protein alignment keeps 64-site blocks (tests)
+std::atomic<int> g_sim_chain{1};                     // cmx_debug_sim_chain (A/B runs, tests)
+std::atomic<long long> g_sim_lds_min_sites{-1};
+std::atomic<long long> g_sim_four_batch_sites{-1};
 std::atomic<int> g_map_grid{0};         // cmx_debug_map_grid: cap of a new context's grid_blocks / obs_blocks (tests: many rounds of blocks on few waves)
 
 bool guard_on() {
@@ -249,6 +252,8 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
     UP(simg); UP(simord);
     d.nsimg = (int)(h.simg.size() / 16);
     UP(eigV); UP(eigVi); UP(eigLam); UP(model_of); UP(blen);
+    ctx->d_simtab = nullptr;
+    if (!h.simtab.empty()) CMX_TRY(upload(ctx, h.simtab, &ctx->d_simtab));
     UP(CP); UP(CPG); UP(pi); UP(rates); UP(probs); UP(cum_pi); UP(cum_probs);
 #undef UP
     if (h.plain) return CMX_OK;   // simulator tables and tree only
@@ -402,6 +407,29 @@ cmx_status cmx_debug_wait_plan(const cmx_model* model, const cmx_tree* tree, int
 
 int cmx_debug_wait_skew(int entry) { return wait_plan_skew(entry); }
 
+cmx_status cmx_debug_sim_tables(const cmx_model* model, const cmx_tree* tree, double* cum, size_t cum_cap, uint8_t* guide,
+                                size_t guide_cap, uint8_t* blocks, size_t blocks_cap, size_t* blocks_bytes, int32_t* row) {
+  HostModel hm;
+  int code = CMX_OK;
+  const std::string msg = build_host_model(model, tree, &hm, &code);
+  if (!msg.empty()) {
+    g_create_error = msg;
+    return (cmx_status)code;
+  }
+  const size_t ncum = (size_t)hm.C * hm.nn * hm.S * hm.S, nguide = (size_t)hm.C * hm.nn * hm.S * 32;   // (CP's padding is not part of it)
+  if (blocks_bytes) *blocks_bytes = hm.simtab.size();
+  if (row) *row = sim_thr_row(hm.S);
+  if (!cum && !guide && !blocks) return CMX_OK;   // the sizes only
+  if (!cum || !guide || !blocks || cum_cap < ncum || guide_cap < nguide || blocks_cap < hm.simtab.size()) {
+    g_create_error = "cmx_debug_sim_tables: a buffer is missing or too small";
+    return CMX_ERR_INVALID;
+  }
+  std::memcpy(cum, hm.CP.data(), ncum * sizeof(double));
+  std::memcpy(guide, hm.CPG.data(), nguide);
+  if (!hm.simtab.empty()) std::memcpy(blocks, hm.simtab.data(), hm.simtab.size());
+  return CMX_OK;
+}
+
 cmx_status cmx_synchronize(cmx_ctx* ctx) {
   if (!ctx) return CMX_ERR_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -432,6 +460,14 @@ int cmx_debug_lds_slot(int on) {
 int cmx_debug_map_queue(int on) {
   const int was = g_map_queue.load();
   if (on >= 0) g_map_queue.store(on ? 1 : 0);
+  return was;
+}
+
+int cmx_debug_sim_chain(int on, long long min_sites, long long four_batch_sites) {
+  const int was = g_sim_chain.load();
+  if (on >= 0) g_sim_chain.store(on ? 1 : 0);
+  if (min_sites >= -1) g_sim_lds_min_sites.store(min_sites);
+  if (four_batch_sites >= -1) g_sim_four_batch_sites.store(four_batch_sites);
   return was;
 }
 

@@ -59,6 +59,7 @@ struct cmx_ctx {
   struct GuardedFixed { std::string name; void* p; size_t bytes; };
   std::vector<GuardedFixed> guarded_fixed;   // CMX_SCRATCH_GUARD: the per-wave workspaces, each with a canary after its last byte
   uint32_t* d_default_masks = nullptr;
+  const uint8_t* d_simtab = nullptr;   // HostModel::simtab (null: the model has none)
   unsigned stat_mean_turn = 0;
   // host copies of asynchronously uploaded parameter blocks (mean vectors, MI bounds): the source of a hipMemcpyAsync must
   // outlive the copy, and the caller's array need not
@@ -119,6 +120,9 @@ extern std::map<std::string, size_t> g_guard_shrink;   // test hook: logical siz
 extern std::atomic<int> g_pat_hash_bits;               // cmx_debug_null_hash_bits: the fused null's column hash keeps only its low bits
 extern std::atomic<int> g_map_queue;                   // cmx_debug_map_queue: 0 = every mapping launch keeps the strided block assignment
 extern std::atomic<int> g_map_small_blocks;                 // cmx_debug_map_small_blocks: 0 = no 16-site blocks in the class-split launch
+extern std::atomic<int> g_sim_chain;                   // cmx_debug_sim_chain: 0 = simulate_lds_kernel where simulate_chain_kernel could run
+extern std::atomic<long long> g_sim_lds_min_sites;     // ... sites of a launch from which an LDS-table simulator runs (< 0: built in)
+extern std::atomic<long long> g_sim_four_batch_sites;  // ... from which the chain kernel draws four batches per workgroup (< 0: built in)
 extern std::atomic<int> g_map_grid;                    // cmx_debug_map_grid: workgroups a new context's mapping launches may use (0: no cap)
 
 inline cmx_status fail(cmx_ctx* ctx, cmx_status s, const std::string& msg) {

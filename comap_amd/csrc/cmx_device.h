@@ -198,8 +198,15 @@ hipError_t launch_simulate(const DevModel& m, uint64_t seed, uint64_t g0, size_t
                            int32_t* d_classes, uint8_t* d_states, hipStream_t stream, size_t rep_ram = 0, uint64_t gstep = 0);
 hipError_t launch_simulate_continuous(const DevModel& m, uint64_t seed, uint64_t g0, size_t n, double alpha, double p_inv,
                                       uint8_t* d_aln, size_t ld, double* d_rates, uint8_t* d_states, hipStream_t stream);
+// what the null's simulator launches besides the gather kernel (the caller's: cmx_debug_sim_chain, cmx_api_ctx.cpp)
+struct SimChoice {
+  const uint8_t* simtab;        // HostModel::simtab on the device, or null: the model has none (simulate_lds_kernel serves it)
+  bool chain;                   // false: simulate_lds_kernel also where simulate_chain_kernel could run
+  long long lds_min_sites;      // sites of a launch from which an LDS-table kernel runs; < 0: the built-in constants
+  long long four_batch_sites;   // ... from which the chain kernel draws four batches per workgroup; < 0: the built-in constant
+};
 hipError_t launch_simulate_blocked(const DevModel& m, uint64_t seed, uint64_t g0, size_t nsites, size_t blk, uint8_t* d_aln,
-                                   uint8_t* d_states, size_t chunk, hipStream_t stream);
+                                   uint8_t* d_states, size_t chunk, hipStream_t stream, const SimChoice& choice);
 // (cmx_pairs.hip) the operand of st.gk into o (d_mvec: this data set's mean vector or null; blk: an operand block per `blk` sites,
 // 0: one block); the statistic of all pairs of a's and b's sites, rows irow0 .. of the full matrix
 hipError_t launch_pair_prep(const Stat& st, const double* d_counts, size_t n, size_t ldc, const double* d_mvec, size_t blk,

@@ -397,6 +397,33 @@ void build_sim_tables(HostModel* hm) {
       hm->CPG[r * 32 + k] = (uint8_t)st;
     }
   }
+  // The chain kernel's copy.  A node draw is u = w / 2^32 of a 32-bit word w, and the search counts the running sums with
+  // u >= cum, i.e. w >= cum * 2^32 (exact: a power of two), i.e. w > ceil(cum * 2^32) - 1 for an integer w: the threshold
+  // kept here, 2^32 - 1 ("never") from cum >= 1 on and for the row's last sum and the padding, which the search does not
+  // count.  A sum <= 0 ("always") has no such threshold and needs none: the guide starts every search behind the sums
+  // that are <= k/32, k >= 0.  The thresholds of a row are made non-decreasing (rounding can leave the sums of a
+  // zero-length branch out of order by an ulp): the search counts the thresholds below w wherever they stand, and on a
+  // non-decreasing row that is where draw_guided's scan stops.
+  hm->simtab.clear();
+  if (S > 4 && sim_node_bytes(S, C) <= kSimNodeBytesMax) {
+    const int rs = sim_thr_row(S);
+    const size_t nodeb = sim_node_bytes(S, C), tabb = (size_t)C * S * rs * 4;
+    hm->simtab.assign((size_t)nn * nodeb, 0);
+    for (int b = 0; b < B; ++b)
+      for (int c = 0; c < C; ++c)
+        for (int x = 0; x < S; ++x) {
+          const size_t r = ((size_t)c * nn + b) * S + x;
+          uint32_t thr[kPlainStates + kSimThrPad + 3];
+          for (int y = 0; y < rs; ++y) {
+            const double t = y < S - 1 ? std::ceil(std::ldexp(hm->CP[r * S + y], 32)) - 1.0 : 4294967295.0;
+            thr[y] = t <= 0.0 ? 0u : t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
+            if (y > 0) thr[y] = std::max(thr[y], thr[y - 1]);
+          }
+          uint8_t* node = &hm->simtab[(size_t)b * nodeb];
+          std::memcpy(node + ((size_t)c * S + x) * rs * 4, thr, (size_t)rs * 4);
+          std::memcpy(node + tabb + ((size_t)c * S + x) * 32, &hm->CPG[r * 32], 32);
+        }
+  }
   hm->cum_pi.resize(S);
   hm->cum_probs.resize(C);
   double cum = 0.0;

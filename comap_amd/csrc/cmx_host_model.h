@@ -35,6 +35,9 @@ struct HostModel {
   std::vector<int> model_of;                  // [B] generator of each branch (all 0 for a homogeneous model)
   std::vector<double> CP;   // [C][nn][S][S]    running row sums of P
   std::vector<uint8_t> CPG; // [C][nn][S][32]   guide table of the simulator's inverse-CDF search (cmx_simulate.hip: draw_guided)
+  // [nn][sim_node_bytes(S, C)] the same tables as simulate_chain_kernel stages them (cmx_layout.h), thresholds instead of
+  // running sums; empty for nucleotides and for models whose node block exceeds kSimNodeBytesMax (they take other kernels)
+  std::vector<uint8_t> simtab;
   std::vector<int> simg;    // [nsimg][16] simulator: groups of four nodes of equal depth (DevModel::simg)
   std::vector<int> simord;  // [nn - 1] the non-root nodes by depth (DevModel::simord)
   int NV = 0;               // visited nodes of the binary device tree (internal, not inlined; pseudo nodes included)

@@ -9,6 +9,14 @@ namespace cmx {
 // transition matrix of this length per thread.
 constexpr int kPlainStates = 64;
 
+// The tables of the null's LDS simulator (cmx_simulate.hip: simulate_chain_kernel), one block per node: [C][S] rows of
+// sim_thr_row(S) 32-bit thresholds of the inverse-CDF search, then the [C][S][32] guide bytes.  A row ends in at least
+// kSimThrPad thresholds no draw exceeds, so a search reads kSimThrPad entries at a time without a bounds test.
+constexpr int kSimThrPad = 4;
+constexpr int sim_thr_row(int S) { return (S + kSimThrPad + 3) & ~3; }
+constexpr unsigned long sim_node_bytes(int S, int C) { return (unsigned long)C * S * (sim_thr_row(S) * 4 + 32); }   // a multiple of 16
+constexpr unsigned long kSimNodeBytesMax = 3ul * 512 * 16;   // three 16-byte pieces per thread of a 512-thread workgroup
+
 // Ambiguous symbols (alignment codes >= S) are served from extra rows S .. S+A-1 appended to every transposed leaf
 // operator: row S+a = sum of the rows of the states compatible with ambiguity id a (filled per call from the caller's
 // mask table, default "every state").  A = 12 for nucleotides (IUPAC + gap), 4 for proteins (B, Z, J, X/gap).

@@ -1,5 +1,5 @@
-// The sequence simulators: simulate_kernel, the null's simulate_blocked_kernel / simulate_lds_kernel (the same draws in the
-// layout the null-mode mapping kernel reads) and simulate_continuous_kernel, all on the counter RNG below.
+// The sequence simulators: simulate_kernel, the null's simulate_blocked_kernel / simulate_chain_kernel / simulate_lds_kernel
+// (the same draws in the layout the null-mode mapping kernel reads) and simulate_continuous_kernel, all on the counter RNG below.
 #include <algorithm>
 
 #include "cmx_device.h"
@@ -311,26 +311,191 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
   }
 }
 
-// Tables in LDS (a node's tables are copied once per 1 024 sites) from about two workgroups per CU on (cfg3's 500 000
-// sites: 0.61 ms against the gather kernel's 0.66); a workgroup's walk over the nodes with two barriers each takes
-// ~0.6 ms however few there are, so below that the gather kernel, one thread per site and no barrier, is quicker
+// simulate_lds_kernel rebuilt around what its counters showed: the vector unit issues for most of the kernel,
+// so the gain is in instructions, and only then in the latencies of a node.  Same draws, same bytes.
+//  * integer search.  A node draw is u = w / 2^32 of a 32-bit Philox word: the guide entry is w >> 27 and "u >= cum" is
+//    "w > threshold" against the host's 32-bit thresholds (cmx_layout.h, HostModel::simtab) -- no conversion to double,
+//    no 64-bit compares, and a row ends in thresholds nobody exceeds instead of a bounds test per running sum.  A node's
+//    block is two thirds of the bytes and arrives as one contiguous copy.
+//  * the tables are staged once per NB batches of 2 NT sites, drawn one after the other (a loop over batches, not wider
+//    searches): barriers, table bytes and their addressing per site fall by NB at a few registers per batch.
+//  * one barrier per node, not two: the next node's tables go into the other buffer BEFORE the barrier (every thread
+//    stopped reading that buffer at the previous node's barrier).
+//  * the parent's states of node it + 1 are loaded at the top of node it, beside the table prefetch; a node whose parent
+//    is the node just drawn (the root's first child, caterpillar chains) takes them from the registers they were drawn into.
+//  * a leaf's states go to the alignment only: nobody reads them back from `states`.
+template <int NB /* batches of 2 NT sites per workgroup */, int NCH /* 16-byte pieces of a node's block per thread */, int NT, int WAVES, int STEP>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void simulate_chain_kernel(const DevModel m, const uint8_t* __restrict__ tabs, uint64_t seed, uint64_t g0, size_t s0, size_t n,
+                                                           size_t blk, uint8_t* __restrict__ aln, uint8_t* __restrict__ states) {
+  static_assert(STEP <= kSimThrPad, "a search reads STEP thresholds past its index");
+  extern __shared__ __attribute__((aligned(16))) uint8_t sim_smem[];
+  const int S0 = m.S0, C0 = m.C0, tid = threadIdx.x;
+  const int rs = sim_thr_row(S0), tabb = C0 * S0 * rs * 4, nodeb = (int)sim_node_bytes(S0, C0), nch = nodeb / 16;
+  // batch b of this thread: the sites jb0 + b * 2 NT and its neighbour (g0, s0, n even: one Philox call per node, the pair's
+  // states one 16-bit word; both inside n or both outside)
+  const size_t jb0 = (size_t)blockIdx.x * NB * (2 * NT) + (size_t)(2 * tid);
+  const uint64_t gp0 = (g0 + s0 + jb0) >> 1;
+  uint8_t* out[NB];
+  unsigned crow[NB], xc[NB];   // class rows of the pair (16 bits each); the parent's states of the pair (8 bits each)
+  unsigned on = 0, wrap = 0;   // per batch: inside n; the pair's second site opens the next replicate block (odd blk only)
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    const size_t jj = jb0 + (size_t)b * (2 * NT);
+    const bool in = jj < n;
+    const size_t s = s0 + (in ? jj : 0);   // (a batch outside n draws site 0 again and stores nothing)
+    const uint64_t g = g0 + s;
+    const size_t col = s % blk;
+    out[b] = aln + (s / blk) * (size_t)m.T * blk + col;
+    on |= (in ? 1u : 0u) << b;
+    wrap |= (col == blk - 1 ? 1u : 0u) << b;
+    const int c0 = draw_index(philox_uniform(seed, g, 0), m.cum_probs, C0), c1 = draw_index(philox_uniform(seed, g + 1, 0), m.cum_probs, C0);
+    crow[b] = (unsigned)(c0 * S0) | ((unsigned)(c1 * S0) << 16);
+    const int r0 = draw_index(philox_uniform(seed, g, 1), m.cum_pi, S0), r1 = draw_index(philox_uniform(seed, g + 1, 1), m.cum_pi, S0);
+    xc[b] = (unsigned)r0 | ((unsigned)r1 << 8);
+    if (in) *reinterpret_cast<unsigned short*>(states + (size_t)m.root * n + jj) = (unsigned short)xc[b];
+  }
+  const cmx_cint ord = (cmx_cint)m.simord;
+  int buf = 0;
+  for (int q = tid; q < nch; q += NT)
+    reinterpret_cast<cmx_i4*>(sim_smem)[q] = reinterpret_cast<const cmx_i4*>(tabs + (size_t)ord[0] * nodeb)[q];
+  __syncthreads();
+  // (ord[0] is a child of the root: xc holds its parent's states)
+  for (int it = 0; it < m.nn - 1; ++it) {
+    const int node = ord[it];
+    const bool more = it + 1 < m.nn - 1;
+    cmx_i4 nxt[NCH];
+    unsigned xn[NB];
+    bool chain = false;
+    if (more) {
+      const int nnode = ord[it + 1], npar = ((cmx_cint)m.parent)[nnode];
+      const cmx_i4* src = reinterpret_cast<const cmx_i4*>(tabs + (size_t)nnode * nodeb);
+#pragma unroll
+      for (int i = 0; i < NCH; ++i)
+        if (tid + NT * i < nch) nxt[i] = src[tid + NT * i];
+      chain = npar == node;
+      if (!chain) {
+        const uint8_t* sp = states + (size_t)npar * n + (unsigned)jb0;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) xn[b] = (on >> b & 1) ? *reinterpret_cast<const unsigned short*>(sp + b * (2 * NT)) : 0u;
+      }
+    }
+    const uint32_t* T_ = reinterpret_cast<const uint32_t*>(sim_smem + (size_t)buf * nodeb);
+    const uint8_t* G_ = sim_smem + (size_t)buf * nodeb + tabb;
+    const int tx = ((cmx_cint)m.taxon_of)[node];
+    uint8_t* sn = states + (size_t)node * n + (unsigned)jb0;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      uint32_t w[2];
+      philox_words(seed, gp0 + (uint64_t)(b * NT), 2u + (uint32_t)node, w[0], w[1]);
+      int idx[2];
+      const uint32_t* thr[2];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int row = (int)((crow[b] >> (16 * k)) & 0xffffu) + (int)((xc[b] >> (8 * k)) & 0xffu);
+        idx[k] = G_[row * 32 + (int)(w[k] >> 27)];
+        thr[k] = T_ + __mul24(row, rs);
+      }
+      // STEP thresholds per search and LDS round trip; the thresholds rise along a row, so the ones below w come first
+      bool any;
+      do {
+        uint32_t tv[2][STEP];
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+          for (int d = 0; d < STEP; ++d) tv[k][d] = thr[k][idx[k] + d];
+        any = false;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          int adv = 0;
+#pragma unroll
+          for (int d = 0; d < STEP; ++d) adv += w[k] > tv[k][d] ? 1 : 0;
+          idx[k] += adv;
+          any |= adv == STEP;
+        }
+      } while (any);
+      const unsigned pair = (unsigned)idx[0] | ((unsigned)idx[1] << 8);
+      if (chain) xn[b] = pair;
+      if (on >> b & 1) {
+        if (tx < 0) {
+          *reinterpret_cast<unsigned short*>(sn + b * (2 * NT)) = (unsigned short)pair;
+        } else if (((blk | (size_t)(uintptr_t)aln) & 1) == 0) {   // (an even rep_ram: the pair sits in one replicate block, at an even address)
+          *reinterpret_cast<unsigned short*>(out[b] + (size_t)tx * blk) = (unsigned short)pair;
+        } else {
+          uint8_t* o = out[b] + (size_t)tx * blk;
+          o[0] = (uint8_t)idx[0];
+          o[(wrap >> b & 1) ? 1 + (size_t)(m.T - 1) * blk : (size_t)1] = (uint8_t)idx[1];
+        }
+      }
+    }
+    if (more) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) xc[b] = xn[b];
+#pragma unroll
+      for (int i = 0; i < NCH; ++i)
+        if (tid + NT * i < nch) reinterpret_cast<cmx_i4*>(sim_smem + (size_t)(buf ^ 1) * nodeb)[tid + NT * i] = nxt[i];
+      __syncthreads();   // the next node's tables are in place, and nobody reads this node's any more
+      buf ^= 1;
+    }
+  }
+}
+
+// From how many sites of a launch on the tables go through LDS; below, the gather kernel, one thread per site and no
+// barrier, is quicker.  A workgroup's walk over the 126 nodes of the target's tree takes simulate_chain_kernel 0.15 ms
+// however few workgroups there are (the gather kernel: 0.14 ms at 50 000 sites, 0.18 at 100 000, 0.50 at 450 000);
+// simulate_lds_kernel, two barriers per node, took 0.31 - 0.36 ms and paid from about two workgroups per CU on.
+constexpr size_t kSimChainMinSites = 75000;
 constexpr size_t kSimLdsMinSites = 450000;
+// Four batches per workgroup once they fill every workgroup slot of the chip (256 CUs x 4) at least once: 4.04 ms
+// against 5.09 for the target's 2 * 10^7 sites, but 0.51 against 0.30 ms for 10^6, where a quarter of the CUs would work.
+constexpr size_t kSimChainFourBatches = (size_t)4 * 1024 * 1024;
 // nsites sites with global indices g0 .. in passes of at most `chunk` (the states scratch holds nn * chunk bytes)
 hipError_t launch_simulate_blocked(const DevModel& m, uint64_t seed, uint64_t g0, size_t nsites, size_t blk, uint8_t* d_aln,
-                                   uint8_t* d_states, size_t chunk, hipStream_t stream) {
+                                   uint8_t* d_states, size_t chunk, hipStream_t stream, const SimChoice& choice) {
   // tables in LDS when a node's rows + guides fit 8 pieces per thread (every model this engine takes: S <= 20, C <= 8)
   const size_t bufb = ((size_t)m.C0 * m.S0 * (m.S0 * 8 + 32) + 15) & ~(size_t)15;
   // (DNA: 512-byte tables that sit in L1 / L2 anyway, and 2 barriers x 511 nodes: gathering is faster, cfg4 step 11.7 vs 13.0 ms)
   const bool lds = m.S0 > 4 && bufb <= (size_t)kSimLdsChunks * 256 * 16;
+  // the chain kernel wherever the host built its tables (HostModel::simtab: a node block of at most kSimNodeBytesMax; of
+  // the models the line above lets through that leaves out five states with more than 61 classes, which stay with
+  // simulate_lds_kernel)
+  const uint8_t* d_simtab = choice.simtab;
+  const size_t nodeb = sim_node_bytes(m.S0, m.C0);
+  const bool chain = lds && d_simtab && nodeb <= kSimNodeBytesMax && choice.chain;
+  const size_t min_sites = choice.lds_min_sites >= 0 ? (size_t)choice.lds_min_sites : chain ? kSimChainMinSites : kSimLdsMinSites;
+  const size_t four_sites = choice.four_batch_sites >= 0 ? (size_t)choice.four_batch_sites : kSimChainFourBatches;
   for (size_t s0 = 0; s0 < nsites; s0 += chunk) {
     const size_t n = std::min(chunk, nsites - s0);
-    // (the LDS kernel pairs the sites 2 k, 2 k + 1 of the global numbering and stores a pair's symbols as one 16-bit word at
+    // (the LDS kernels pair the sites 2 k, 2 k + 1 of the global numbering and store a pair's symbols as one 16-bit word at
     // column s0 + j of its replicate block: g0, s0 and n all have to be even, not just g0 + s0)
-    if (lds && n >= kSimLdsMinSites && (g0 & 1) == 0 && (s0 & 1) == 0 && (n & 1) == 0) {
+    if (lds && n >= min_sites && (g0 & 1) == 0 && (s0 & 1) == 0 && (n & 1) == 0) {
+      if (chain) {
+        // 512 threads, a pair of sites each per batch, eight waves per SIMD; two 16-byte pieces of a node's block per thread
+        // up to five classes of 20 states, three up to eight.  One batch: 38 / 44 registers, four thresholds per round trip
+        // of a search; four batches: 64 registers (8 / 12 spilled), two thresholds (four: 4.27 ms, more spills).
+        // LDS: two node blocks, 20 480 B for the target's model.
+        const bool two = nodeb <= (size_t)2 * 512 * 16;
+        if (n >= four_sites) {
+          const dim3 grid((unsigned)((n + 4095) / 4096));
+          if (two)
+            hipLaunchKernelGGL((simulate_chain_kernel<4, 2, 512, 8, 2>), grid, dim3(512), 2 * nodeb, stream, m, d_simtab, seed, g0, s0, n, blk,
+                               d_aln, d_states);
+          else
+            hipLaunchKernelGGL((simulate_chain_kernel<4, 3, 512, 8, 2>), grid, dim3(512), 2 * nodeb, stream, m, d_simtab, seed, g0, s0, n, blk,
+                               d_aln, d_states);
+        } else {
+          const dim3 grid((unsigned)((n + 1023) / 1024));
+          if (two)
+            hipLaunchKernelGGL((simulate_chain_kernel<1, 2, 512, 8, 4>), grid, dim3(512), 2 * nodeb, stream, m, d_simtab, seed, g0, s0, n, blk,
+                               d_aln, d_states);
+          else
+            hipLaunchKernelGGL((simulate_chain_kernel<1, 3, 512, 8, 4>), grid, dim3(512), 2 * nodeb, stream, m, d_simtab, seed, g0, s0, n, blk,
+                               d_aln, d_states);
+        }
+      }
       // 512 threads with two sites each: 56 registers = eight waves per SIMD (the kernel is bound by vector issue -- half of
       // it Philox's quarter-rate multiplies -- once enough waves hide the LDS round trips: four sites per thread at three
       // waves per SIMD 14.8 ms per target step, at five 11.6, this shape 10.2)
-      if (bufb <= (size_t)2 * 512 * 16)
+      else if (bufb <= (size_t)2 * 512 * 16)
         hipLaunchKernelGGL((simulate_lds_kernel<2, 2, 512, 8>), dim3((unsigned)((n + 1023) / 1024)), dim3(512), 2 * bufb, stream, m, seed, g0, s0,
                            n, blk, d_aln, d_states);
       else

@@ -183,6 +183,22 @@ int cmx_debug_map_grid(int workgroups);
  * from now on keep 64-site blocks (tests; the same results either way); on < 0: query only; returns the previous state.
  * Process-wide, host only, read at each call. */
 int cmx_debug_map_small_blocks(int on);
+/* The null's simulator (cmx_null_simulate_dev and the nulls that simulate) draws large calls of models with more than four
+ * states with a node's tables in LDS, small ones with a gather kernel; the LDS kernel draws one batch of 1 024 sites per
+ * workgroup and copy of a node's tables, or four in very large launches; the same bytes on every path.
+ * cmx_debug_sim_chain(0, ..) makes the launches issued from now on use the LDS kernel that preceded the current one (A/B
+ * runs, tests), on < 0 leaves the choice; min_sites >= 0 sets the sites of a launch from which an LDS kernel runs (0: every
+ * even launch; tests), four_batch_sites >= 0 those from which a workgroup draws four batches (0: always; tests); -1 restores
+ * the built-in threshold, < -1 leaves it.  Returns the previous choice.  Process-wide, host only, read at each call. */
+int cmx_debug_sim_chain(int on, long long min_sites, long long four_batch_sites);
+/* Host only, no GPU: the simulator's tables of a model and tree.  cum [C][nnodes][S][S] doubles, the running row sums of P,
+ * and guide [C][nnodes][S][32] bytes (what the gather kernels read); blocks, the per-node blocks of 32-bit thresholds and guide
+ * bytes the LDS kernel reads: nnodes * C * S * (4 * row + 32) bytes, rows of `row` thresholds (the constants of
+ * cmx_layout.h), or 0 bytes for models that kernel does not serve.  The capacities are in elements of each buffer; with all
+ * three buffers null only *blocks_bytes and *row are set.  A threshold t stands for the running sum c with
+ * "w > t  <=>  w / 2^32 >= c" for every 32-bit w. */
+cmx_status cmx_debug_sim_tables(const cmx_model* model, const cmx_tree* tree, double* cum, size_t cum_cap, uint8_t* guide,
+                                size_t guide_cap, uint8_t* blocks, size_t blocks_cap, size_t* blocks_bytes, int32_t* row);
 
 /* ---- substitution mapping: replaces DRHomogeneousTreeLikelihood::initialize + getLogLikelihoodPerSite /
  * getPosteriorRatePerSite / getRateClassWithMaxPostProbPerSite + computeSubstitutionVectors + computeNormForSite
