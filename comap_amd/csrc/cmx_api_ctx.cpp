@@ -22,8 +22,7 @@ std::atomic<int> g_lds_slot{1};         // cmx_debug_lds_slot: 0 = the mapping w
 std::atomic<int> g_pat_hash_bits{64};   // (tests force collisions with it)
 std::atomic<int> g_map_queue{1};        // cmx_debug_map_queue: 0 = strided block assignment in every mapping launch (A/B runs, tests)
 std::atomic<int> g_map_small_blocks{1};      // cmx_debug_map_small_blocks: 0 = the class-split launch of a protein alignment keeps 64-site blocks (tests)
-std::atomic<int> g_sim_chain{1};                     // cmx_debug_sim_chain (A/B runs, tests)
-std::atomic<long long> g_sim_lds_min_sites{-1};
+std::atomic<long long> g_sim_min_sites{-1};          // cmx_debug_sim_sites (tests: the chain kernel's shapes at small sizes)
 std::atomic<long long> g_sim_four_batch_sites{-1};
 std::atomic<int> g_map_grid{0};         // cmx_debug_map_grid: cap of a new context's grid_blocks / obs_blocks (tests: many rounds of blocks on few waves)
 
@@ -463,12 +462,9 @@ int cmx_debug_map_queue(int on) {
   return was;
 }
 
-int cmx_debug_sim_chain(int on, long long min_sites, long long four_batch_sites) {
-  const int was = g_sim_chain.load();
-  if (on >= 0) g_sim_chain.store(on ? 1 : 0);
-  if (min_sites >= -1) g_sim_lds_min_sites.store(min_sites);
+void cmx_debug_sim_sites(long long min_sites, long long four_batch_sites) {
+  if (min_sites >= -1) g_sim_min_sites.store(min_sites);
   if (four_batch_sites >= -1) g_sim_four_batch_sites.store(four_batch_sites);
-  return was;
 }
 
 int cmx_debug_map_small_blocks(int on) {

@@ -1,6 +1,7 @@
 // C-ABI, Mica stage: mutual information of alignment columns, the bootstrap nulls, averages / z-scores, the permutation test.
 #include "cmx_ctx.h"
 #include "cmx_mica_perm.h"
+#include "cmx_philox.h"
 
 // the 256 compatibility masks of an alphabet: a state is itself, every other code "unknown" (compatible with all states)
 // unless the caller's table says otherwise (an empty mask there is an unknown too)
@@ -168,28 +169,15 @@ cmx_status cmx_mi_pairs(cmx_ctx* ctx, int nalpha, int ntaxa, const uint32_t* mas
 }
 
 // ---- Mica's bootstrap nulls.  Site indices of the non-parametric bootstrap (SiteContainerTools::sampleSites,
-// CoMap/Mica.cpp:426-430) come from the engine's counter RNG (cmx_simulate.hip philox_uniform: Philox2x32-10, key from the
+// CoMap/Mica.cpp:426-430) come from the engine's counter RNG (cmx_philox.h philox_uniform: Philox2x32-10, key from the
 // seed, counter = (g, draw)), so that every binding -- this library's C++ adapter, the Python mirror, a Mica.cpp linked
 // against the C-ABI -- draws the same pairs: idx_h[r * rep_ram + j] = floor(u(seed, g = (r * 2 + h) * rep_ram + j, draw 0) * nsites).
-static double host_philox_uniform(uint64_t seed, uint64_t g, uint32_t draw) {
-  uint32_t c0 = (uint32_t)g, c1 = ((uint32_t)(g >> 32) & 0x7fffu) | (draw << 15);
-  uint32_t k = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x9E3779B9u) ^ 0x434d5832u;
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p = (uint64_t)0xD256D193u * (uint64_t)c0;
-    c0 = (uint32_t)(p >> 32) ^ k ^ c1;
-    c1 = (uint32_t)p;
-    k += 0x9E3779B9u;
-  }
-  const uint64_t bits = (((uint64_t)c0 << 32) | c1) >> 11;
-  return (double)bits * (1.0 / 9007199254740992.0);
-}
-
 cmx_status cmx_mica_bootstrap_indices(uint64_t seed, size_t nsites, size_t nrep_cpu, size_t nrep_ram, int64_t* idx1, int64_t* idx2) {
   if (nsites == 0 || !idx1 || !idx2 || (uint64_t)nrep_cpu * 2 * nrep_ram > (1ull << 47)) return CMX_ERR_INVALID;
   for (size_t r = 0; r < nrep_cpu; ++r)
     for (size_t j = 0; j < nrep_ram; ++j)
       for (int h = 0; h < 2; ++h) {
-        size_t v = (size_t)(host_philox_uniform(seed, ((uint64_t)r * 2 + h) * nrep_ram + j, 0) * (double)nsites);
+        size_t v = (size_t)(philox_uniform(seed, ((uint64_t)r * 2 + h) * nrep_ram + j, 0) * (double)nsites);
         if (v >= nsites) v = nsites - 1;
         (h ? idx2 : idx1)[r * nrep_ram + j] = (int64_t)v;
       }

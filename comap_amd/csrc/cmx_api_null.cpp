@@ -27,7 +27,7 @@ cmx_status cmx_null_simulate_dev(cmx_ctx* ctx, uint64_t seed, size_t rep_begin, 
   const size_t chunk = std::min<size_t>(nsites, std::max<size_t>((size_t)1 << 21, (((size_t)4 << 30) / (size_t)ctx->hm.nn) & ~(size_t)1023));
   uint8_t* d_states;
   CMX_TRY(scratch(ctx, "null_states", (size_t)ctx->hm.nn * chunk, &d_states));
-  const SimChoice choice{ctx->d_simtab, g_sim_chain.load() != 0, g_sim_lds_min_sites.load(), g_sim_four_batch_sites.load()};
+  const SimChoice choice{ctx->d_simtab, g_sim_min_sites.load(), g_sim_four_batch_sites.load()};
   HIP_TRY(ctx, launch_simulate_blocked(ctx->dm, seed, (uint64_t)rep_begin * 2 * rep_ram, nsites, rep_ram, d_aln, d_states, chunk,
                                        (hipStream_t)stream, choice));
   return CMX_OK;

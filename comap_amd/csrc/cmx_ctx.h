@@ -120,9 +120,8 @@ extern std::map<std::string, size_t> g_guard_shrink;   // test hook: logical siz
 extern std::atomic<int> g_pat_hash_bits;               // cmx_debug_null_hash_bits: the fused null's column hash keeps only its low bits
 extern std::atomic<int> g_map_queue;                   // cmx_debug_map_queue: 0 = every mapping launch keeps the strided block assignment
 extern std::atomic<int> g_map_small_blocks;                 // cmx_debug_map_small_blocks: 0 = no 16-site blocks in the class-split launch
-extern std::atomic<int> g_sim_chain;                   // cmx_debug_sim_chain: 0 = simulate_lds_kernel where simulate_chain_kernel could run
-extern std::atomic<long long> g_sim_lds_min_sites;     // ... sites of a launch from which an LDS-table simulator runs (< 0: built in)
-extern std::atomic<long long> g_sim_four_batch_sites;  // ... from which the chain kernel draws four batches per workgroup (< 0: built in)
+extern std::atomic<long long> g_sim_min_sites;         // cmx_debug_sim_sites: sites of a launch from which simulate_chain_kernel runs (< 0: built in)
+extern std::atomic<long long> g_sim_four_batch_sites;  // ... from which it draws four batches per workgroup (< 0: built in)
 extern std::atomic<int> g_map_grid;                    // cmx_debug_map_grid: workgroups a new context's mapping launches may use (0: no cap)
 
 inline cmx_status fail(cmx_ctx* ctx, cmx_status s, const std::string& msg) {
@@ -222,7 +221,7 @@ inline const double* stat_weights(const cmx_ctx* ctx, int kind) {
   return nullptr;
 }
 
-// the simulator's counter layout (cmx_simulate.hip philox_uniform): 47 bits of simulated-site index, 17 bits of draw index
+// the simulator's counter layout (cmx_philox.h philox_uniform): 47 bits of simulated-site index, 17 bits of draw index
 inline cmx_status rng_range(cmx_ctx* ctx, uint64_t g_end, const char* who) {
   if (g_end > (1ull << 47) || (uint64_t)ctx->hm.nn + 2 > (1ull << 17))
     return fail(ctx, CMX_ERR_UNSUPPORTED, std::string(who) + ": simulated-site index beyond 2^47 or more than 2^17 - 2 nodes");

@@ -198,12 +198,12 @@ hipError_t launch_simulate(const DevModel& m, uint64_t seed, uint64_t g0, size_t
                            int32_t* d_classes, uint8_t* d_states, hipStream_t stream, size_t rep_ram = 0, uint64_t gstep = 0);
 hipError_t launch_simulate_continuous(const DevModel& m, uint64_t seed, uint64_t g0, size_t n, double alpha, double p_inv,
                                       uint8_t* d_aln, size_t ld, double* d_rates, uint8_t* d_states, hipStream_t stream);
-// what the null's simulator launches besides the gather kernel (the caller's: cmx_debug_sim_chain, cmx_api_ctx.cpp)
+// when the null's simulator launches simulate_chain_kernel instead of the gather kernel (the sizes are the caller's:
+// cmx_debug_sim_sites, cmx_api_ctx.cpp)
 struct SimChoice {
-  const uint8_t* simtab;        // HostModel::simtab on the device, or null: the model has none (simulate_lds_kernel serves it)
-  bool chain;                   // false: simulate_lds_kernel also where simulate_chain_kernel could run
-  long long lds_min_sites;      // sites of a launch from which an LDS-table kernel runs; < 0: the built-in constants
-  long long four_batch_sites;   // ... from which the chain kernel draws four batches per workgroup; < 0: the built-in constant
+  const uint8_t* simtab;        // HostModel::simtab on the device, or null: the model has none and takes the gather kernel
+  long long min_sites;          // sites of a launch from which the chain kernel runs; < 0: the built-in constant
+  long long four_batch_sites;   // ... from which it draws four batches per workgroup; < 0: the built-in constant
 };
 hipError_t launch_simulate_blocked(const DevModel& m, uint64_t seed, uint64_t g0, size_t nsites, size_t blk, uint8_t* d_aln,
                                    uint8_t* d_states, size_t chunk, hipStream_t stream, const SimChoice& choice);

@@ -405,7 +405,7 @@ void build_sim_tables(HostModel* hm) {
   // zero-length branch out of order by an ulp): the search counts the thresholds below w wherever they stand, and on a
   // non-decreasing row that is where draw_guided's scan stops.
   hm->simtab.clear();
-  if (S > 4 && sim_node_bytes(S, C) <= kSimNodeBytesMax) {
+  if (sim_has_tables(S, C)) {
     const int rs = sim_thr_row(S);
     const size_t nodeb = sim_node_bytes(S, C), tabb = (size_t)C * S * rs * 4;
     hm->simtab.assign((size_t)nn * nodeb, 0);

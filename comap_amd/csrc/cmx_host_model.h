@@ -36,7 +36,7 @@ struct HostModel {
   std::vector<double> CP;   // [C][nn][S][S]    running row sums of P
   std::vector<uint8_t> CPG; // [C][nn][S][32]   guide table of the simulator's inverse-CDF search (cmx_simulate.hip: draw_guided)
   // [nn][sim_node_bytes(S, C)] the same tables as simulate_chain_kernel stages them (cmx_layout.h), thresholds instead of
-  // running sums; empty for nucleotides and for models whose node block exceeds kSimNodeBytesMax (they take other kernels)
+  // running sums; empty unless sim_has_tables(S, C) (a model without them takes the gather kernel)
   std::vector<uint8_t> simtab;
   std::vector<int> simg;    // [nsimg][16] simulator: groups of four nodes of equal depth (DevModel::simg)
   std::vector<int> simord;  // [nn - 1] the non-root nodes by depth (DevModel::simord)

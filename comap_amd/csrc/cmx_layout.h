@@ -16,6 +16,10 @@ constexpr int kSimThrPad = 4;
 constexpr int sim_thr_row(int S) { return (S + kSimThrPad + 3) & ~3; }
 constexpr unsigned long sim_node_bytes(int S, int C) { return (unsigned long)C * S * (sim_thr_row(S) * 4 + 32); }   // a multiple of 16
 constexpr unsigned long kSimNodeBytesMax = 3ul * 512 * 16;   // three 16-byte pieces per thread of a 512-thread workgroup
+// Which models get these tables (HostModel::simtab), and with them simulate_chain_kernel for the null's large launches;
+// every other model is drawn by the gather kernel.  Nucleotides are left out: their rows are 512 bytes per node, which
+// sit in L1 / L2 anyway, and a barrier per node over cfg4's 511 nodes costs more than gathering does.
+constexpr bool sim_has_tables(int S, int C) { return S > 4 && sim_node_bytes(S, C) <= kSimNodeBytesMax; }
 
 // Ambiguous symbols (alignment codes >= S) are served from extra rows S .. S+A-1 appended to every transposed leaf
 // operator: row S+a = sum of the rows of the states compatible with ambiguity id a (filled per call from the caller's

@@ -28,7 +28,7 @@
 //   protein walk adds one workspace vector (DevWalk::kLdsSlot) for the short-lived vectors the host's plan names.
 //   DESIGN.md 4.1 has the full description and the measurements.
 //   MODE == kModeNull: map (x2 batches) -> per-pair statistic of AnalysisTools::getNullDistributionIntraDR
-//   (CoMap/AnalysisTools.cpp:587-653) per wave, on alignments simulated beforehand by simulate_lds_kernel /
+//   (CoMap/AnalysisTools.cpp:587-653) per wave, on alignments simulated beforehand by simulate_chain_kernel /
 //   simulate_blocked_kernel at full occupancy.
 //   MODE == kModeNullPatterns: the same walk over the null's distinct columns, one lane per pattern; the pairs are scored
 //   by null_pattern_pairs_kernel (cmx_null_patterns.hip).
@@ -1205,7 +1205,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
         const size_t rep_local = s / a.rep_ram, j = s % a.rep_ram;
         const uint8_t* gbase;
         size_t gstride;
-        // the alignments were simulated by simulate_lds_kernel / simulate_blocked_kernel (cmx_null_simulate_dev) or
+        // the alignments were simulated by simulate_chain_kernel / simulate_blocked_kernel (cmx_null_simulate_dev) or
         // supplied by the caller: [replicate][batch][taxon][rep_ram]
         gbase = a.supplied + ((rep_local * 2 + h) * (size_t)m.T) * a.rep_ram + j;
         gstride = a.rep_ram;

@@ -1,41 +1,14 @@
-// The sequence simulators: simulate_kernel, the null's simulate_blocked_kernel / simulate_chain_kernel / simulate_lds_kernel
-// (the same draws in the layout the null-mode mapping kernel reads) and simulate_continuous_kernel, all on the counter RNG below.
+// The sequence simulators: simulate_kernel, the null's simulate_blocked_kernel / simulate_chain_kernel (the same draws in
+// the layout the null-mode mapping kernel reads) and simulate_continuous_kernel, all on the counter RNG of cmx_philox.h.
 #include <algorithm>
 
 #include "cmx_device.h"
 #include "cmx_lanes.h"
+#include "cmx_philox.h"
 
 namespace cmx {
 
-// Philox2x32-10 (Random123): counter = (g_lo, g_hi[14:0] | draw << 15), key = seed_lo ^ seed_hi * 0x9E3779B9 ^ 'CMX2'.
-// Same scheme as oracle/oracle.c (DESIGN.md "RNG").  One 32 x 32 -> 64 multiply per round: the 4x32 variant (two per
-// round, 128 output bits) cost the fused null kernel 4.7 % of its time in quarter-rate integer multiplies.
-// g < 2^47, draw < 2^17.
-//   draw 0 (rate class / continuous rate) and 1 (root state): counter from the site's g, the 64 output bits give one
-//   53-bit uniform (philox_uniform);
-//   draw 2 + node (state at the lower end of a branch): the sites 2k and 2k + 1 SHARE the call with counter g >> 1 and
-//   take its first and second output word as a 32-bit uniform (philox_node_uniform): the node draws are 99 % of a
-//   simulation's calls, a category's probability is resolved to 2^-32 either way, and a thread that holds both sites of
-//   a pair (simulate_lds_kernel) makes one call for two draws.
-__device__ __forceinline__ void philox_words(uint64_t seed, uint64_t g, uint32_t draw, uint32_t& w0, uint32_t& w1) {
-  uint32_t c0 = (uint32_t)g, c1 = ((uint32_t)(g >> 32) & 0x7fffu) | (draw << 15);
-  uint32_t k = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x9E3779B9u) ^ 0x434d5832u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p = (uint64_t)0xD256D193u * (uint64_t)c0;   // one v_mad_u64_u32 instead of v_mul_hi + v_mul_lo
-    c0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p >> 32), k, c1, 0x96);   // three-way xor in one v_bitop3_b32
-    c1 = (uint32_t)p;
-    k += 0x9E3779B9u;
-  }
-  w0 = c0;
-  w1 = c1;
-}
-__device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t g, uint32_t draw) {
-  uint32_t c0, c1;
-  philox_words(seed, g, draw, c0, c1);
-  const uint64_t bits = (((uint64_t)c0 << 32) | c1) >> 11;
-  return (double)bits * (1.0 / 9007199254740992.0);
-}
+// a node draw of site g: its word of the call the sites g & ~1 and g | 1 share (cmx_philox.h)
 __device__ __forceinline__ double philox_node_uniform(uint64_t seed, uint64_t g, uint32_t node) {
   uint32_t w0, w1;
   philox_words(seed, g >> 1, 2u + node, w0, w1);
@@ -56,19 +29,28 @@ __device__ __forceinline__ int draw_guided(double u, const double* __restrict__ 
   while (idx < n - 1 && u >= cum[idx]) ++idx;
   return idx;
 }
+// the two draws a site makes for itself: its rate class (draw 0, on DevModel::cum_probs) and its state at the root
+// (draw 1, on cum_pi).  They take the table and its length, not the model: a kernel holds S0 and C0 already, and the
+// text hipcc emits for simulate_chain_kernel changes when the helpers read them from the model again.
+__device__ __forceinline__ int draw_class(const double* cum_probs, int C0, uint64_t seed, uint64_t g) {
+  return draw_index(philox_uniform(seed, g, 0), cum_probs, C0);
+}
+__device__ __forceinline__ int draw_root(const double* cum_pi, int S0, uint64_t seed, uint64_t g) {
+  return draw_index(philox_uniform(seed, g, 1), cum_pi, S0);
+}
 
 // ------------------------------------------------------------------------------------------------ stand-alone simulator
 // rep_ram != 0: the n sites are blocks of rep_ram (the replicates of one side of a null, side by side in the alignment);
-// block r holds the global sites g0 + r * gstep ..  (one launch for all replicates of a side: round 3 launched per replicate)
+// block r holds the global sites g0 + r * gstep ..  (one launch for all replicates of a side)
 __global__ void simulate_kernel(const DevModel m, uint64_t seed, uint64_t g0, size_t n, uint8_t* aln, size_t ld,
                                 int32_t* classes, uint8_t* states, size_t rep_ram, uint64_t gstep) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const uint64_t g = rep_ram ? g0 + (uint64_t)(j / rep_ram) * gstep + (uint64_t)(j % rep_ram) : g0 + j;
   const int S = m.S0;
-  const int c = draw_index(philox_uniform(seed, g, 0), m.cum_probs, m.C0);
+  const int c = draw_class(m.cum_probs, m.C0, seed, g);
   if (classes) classes[j] = c;
-  states[(size_t)m.root * ld + j] = (uint8_t)draw_index(philox_uniform(seed, g, 1), m.cum_pi, S);
+  states[(size_t)m.root * ld + j] = (uint8_t)draw_root(m.cum_pi, S, seed, g);
   for (int node = m.nn - 2; node >= 0; --node) {
     const int x = states[(size_t)m.parent[node] * ld + j];
     const size_t row = ((size_t)c * m.nn + node) * S + x;
@@ -87,14 +69,13 @@ hipError_t launch_simulate(const DevModel& m, uint64_t seed, uint64_t g0, size_t
   return hipGetLastError();
 }
 
-// The null's simulator since round 2 (cmx_null_intra_dev): the SAME draws as simulate_kernel / the fused loop of
-// map_kernel<S, null>, but one thread per site at full occupancy instead of 64 sites inside a mapping wave that holds
-// half a SIMD's registers.  Inside the mapping kernel the simulator was 7.8 % of a wave's time, all of it dependent L2
-// gathers that two waves per SIMD cannot hide; here thousands of waves hide them (cfg3, same box: fused 12.96 ms,
-// mapping of supplied alignments 11.98 ms + this kernel).  Nodes are drawn level by level in groups of four (m.simg),
-// four running sums per round trip of the search, exactly as the fused loop does.
+// The null's simulator (cmx_null_simulate_dev), the gather kernel: the SAME draws as simulate_kernel, one thread per site
+// at full occupancy.  A mapping wave holds half a SIMD's registers, and simulating its 64 sites inside it was 7.8 % of
+// the wave's time, all of it dependent L2 gathers that two waves per SIMD cannot hide; here thousands of waves hide them
+// (cfg3, same box: simulated inside the mapping kernel 12.96 ms, mapping of supplied alignments 11.98 ms + this kernel).
+// Nodes are drawn level by level in groups of four (m.simg), four running sums per round trip of the search.
 // Sites s = 0 .. of one null launch: g = g0 + s; (replicate, batch) block s / blk, column s % blk of an alignment stored
-// as [block][taxon][blk] -- the layout map_kernel<S, null> reads supplied alignments in.
+// as [block][taxon][blk] -- the layout map_kernel<S, kModeNull> reads its alignments in.
 __global__ __launch_bounds__(256) void simulate_blocked_kernel(const DevModel m, uint64_t seed, uint64_t g0, size_t s0, size_t n,
                                                                size_t blk, uint8_t* __restrict__ aln,
                                                                uint8_t* __restrict__ states /*[nn][n]*/) {
@@ -104,8 +85,8 @@ __global__ __launch_bounds__(256) void simulate_blocked_kernel(const DevModel m,
   const uint64_t g = g0 + s;
   const int S0 = m.S0;
   uint8_t* out = aln + (s / blk) * (size_t)m.T * blk + s % blk;
-  const int c = draw_index(philox_uniform(seed, g, 0), m.cum_probs, m.C0);
-  states[(size_t)m.root * n + j] = (uint8_t)draw_index(philox_uniform(seed, g, 1), m.cum_pi, S0);
+  const int c = draw_class(m.cum_probs, m.C0, seed, g);
+  states[(size_t)m.root * n + j] = (uint8_t)draw_root(m.cum_pi, S0, seed, g);
   for (int gi = 0; gi < m.nsimg; ++gi) {
     const cmx_cint q = (cmx_cint)m.simg + gi * 16;   // [0..3] node, [4..7] its parent, [8..11] its taxon or -1
     int x[4], idx[4];
@@ -149,178 +130,24 @@ __global__ __launch_bounds__(256) void simulate_blocked_kernel(const DevModel m,
   }
 }
 
-// The same simulator with the tables of the node being drawn in LDS.  A draw needs one guide byte and a few running
-// sums of ONE of C * S rows of its node; gathered from L2 by every thread that is ~100 bytes of traffic per draw
-// (2.5e9 draws per target launch: the gather kernel above was L2-bound, 22 ms).  Here a workgroup draws 1 024 sites
-// (four per thread), node by node, parents first: the node's C * S rows (12.8 KB for proteins) and guide bytes are copied
-// into LDS once per workgroup, double-buffered (global -> registers while the current node is drawn, registers -> LDS
-// behind a barrier), and every search runs on LDS.  Same draws, same states as simulate_kernel.
-constexpr int kSimStep = 2;        // running sums per search and LDS round trip in simulate_lds_kernel
-constexpr int kSimLdsChunks = 8;   // 16-byte pieces of a node's tables per thread (256 threads): up to 32 KiB per buffer
-template <int SPT, int NCH /* 16-byte pieces of a node's tables per thread */, int NT /* threads */, int WAVES>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void simulate_lds_kernel(const DevModel m, uint64_t seed, uint64_t g0, size_t s0, size_t n,
-                                                           size_t blk, uint8_t* __restrict__ aln, uint8_t* __restrict__ states) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t sim_smem[];
-  const int S0 = m.S0, C0 = m.C0, tid = threadIdx.x;
-  const int rowb = S0 * 8, tabb = C0 * S0 * rowb, guib = C0 * S0 * 32;       // bytes: one row of sums, all rows, all guides
-  const int bufb = (tabb + guib + 15) & ~15, nch = bufb / 16;
-  // piece q (16 bytes) of node `node`'s tables: the sums of class q / (S0 * rowb / 16) ... are contiguous per class in CP,
-  // the guide bytes per class in CPG
-  auto piece_src = [&](int node, int q) -> const cmx_i4* {
-    const int off = q * 16;
-    if (off < tabb) {
-      const int c = off / (S0 * rowb), r = off % (S0 * rowb);
-      return reinterpret_cast<const cmx_i4*>(reinterpret_cast<const uint8_t*>(m.CP + ((size_t)c * m.nn + node) * S0 * S0) + r);
-    }
-    const int o2 = off - tabb, c = o2 / (S0 * 32), r = o2 % (S0 * 32);
-    return reinterpret_cast<const cmx_i4*>(m.CPG + ((size_t)c * m.nn + node) * S0 * 32 + r);
-  };
-  size_t j[SPT];
-  uint64_t g[SPT];
-  int cls[SPT];
-  uint8_t* out[SPT];
-  bool on[SPT];
-#pragma unroll
-  for (int k = 0; k < SPT; ++k) {
-    // a thread's sites are neighbours: sites 2 q and 2 q + 1 share a Philox call for their node draws (g0 + s0 is even:
-    // launch_simulate_blocked checks it), and their states are neighbouring bytes
-    j[k] = (size_t)blockIdx.x * SPT * NT + (size_t)(SPT * tid + k);
-    on[k] = j[k] < n;
-    // (n is even: a thread's two sites are both inside or both outside; the outside ones repeat the last pair)
-    const size_t jj = on[k] ? j[k] : n - 2 + (k & 1), s = s0 + jj;
-    j[k] = jj;
-    g[k] = g0 + s;
-    out[k] = aln + (s / blk) * (size_t)m.T * blk + s % blk;
-    cls[k] = draw_index(philox_uniform(seed, g[k], 0), m.cum_probs, C0);
-    if (on[k]) states[(size_t)m.root * n + jj] = (uint8_t)draw_index(philox_uniform(seed, g[k], 1), m.cum_pi, S0);
-  }
-  // this thread's pieces of a node's tables: where they start for node 0, and the node's stride (sums: S0 * S0 doubles,
-  // guides: S0 * 32 bytes) -- loop-invariant, so that the node loop adds one 24-bit product instead of dividing and
-  // multiplying per node (quarter-rate 32-bit multiplies were a quarter of the loop's vector cycles)
-  const uint8_t* psrc[NCH];
-  unsigned pstride[NCH];
-  bool pok[NCH];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    const int q = tid + NT * i;
-    pok[i] = q < nch && q * 16 < tabb + guib;
-    psrc[i] = reinterpret_cast<const uint8_t*>(piece_src(0, pok[i] ? q : 0));
-    pstride[i] = (unsigned)(q * 16 < tabb ? S0 * rowb : S0 * 32);
-  }
-  int crow[SPT];
-#pragma unroll
-  for (int k = 0; k < SPT; ++k) crow[k] = cls[k] * S0;
-  // tables of the first node
-  const cmx_cint ord = (cmx_cint)m.simord;
-  int buf = 0;
-  for (int q = tid; q < nch; q += NT)
-    reinterpret_cast<cmx_i4*>(sim_smem)[q] = (q * 16 < tabb + guib) ? *piece_src(ord[0], q) : cmx_i4{0, 0, 0, 0};
-  __syncthreads();
-  // nodes level by level (m.simord): the parent's state was written a whole level ago, not by the previous iteration
-  for (int it = 0; it < m.nn - 1; ++it) {
-    const int node = ord[it];
-    const bool more = it + 1 < m.nn - 1;
-    cmx_i4 nxt[NCH];
-    if (more) {
-      const int nnode = ord[it + 1];
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        if (pok[i]) nxt[i] = *reinterpret_cast<const cmx_i4*>(psrc[i] + __umul24((unsigned)nnode, pstride[i]));
-      }
-    }
-    const double* T_ = reinterpret_cast<const double*>(sim_smem + (size_t)buf * bufb);
-    const uint8_t* G_ = sim_smem + (size_t)buf * bufb + tabb;
-    const int par = ((cmx_cint)m.parent)[node], tx = ((cmx_cint)m.taxon_of)[node];   // scalar loads: the products with n and blk stay scalar
-    // the SPT searches side by side: parents' states, uniforms, guide bytes, then kSimStep running sums per search and round
-    // trip (a `while (u >= cum[idx]) ++idx` per site is a chain of dependent LDS reads under a divergent branch: 36
-    // branches and 110 scalar instructions per wave and draw).  Reads past a row's end stay inside the buffer (the guide
-    // bytes follow the sums) and are not counted.
-    int x[SPT], idx[SPT];
-    double u[SPT];
-    const double* cum[SPT];
-    // the states of a thread's two sites are neighbouring bytes at an even address (n, j[0] even): one 16-bit access
-    static_assert(SPT % 2 == 0, "sites in pairs");
-    const uint8_t* sp = states + (size_t)par * n;
-#pragma unroll
-    for (int k = 0; k < SPT; k += 2) {
-      const unsigned xx = *reinterpret_cast<const unsigned short*>(sp + (unsigned)j[k]);
-      x[k] = (int)(xx & 0xffu);
-      x[k + 1] = (int)(xx >> 8);
-    }
-#pragma unroll
-    for (int k = 0; k < SPT; k += 2) {
-      // (g[k] is even and g[k + 1] its neighbour -- or g[k] again, the clamped slot behind the last site of an odd n)
-      uint32_t w0, w1;
-      philox_words(seed, g[k] >> 1, 2u + (uint32_t)node, w0, w1);
-      u[k] = (double)((g[k] & 1) ? w1 : w0) * (1.0 / 4294967296.0);
-      if (k + 1 < SPT) {
-        u[k + 1] = (double)((g[k + 1] & 1) ? w1 : w0) * (1.0 / 4294967296.0);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < SPT; ++k) {
-      const int row = crow[k] + x[k];
-      idx[k] = G_[row * 32 + (int)(u[k] * 32.0)];
-      cum[k] = T_ + __mul24(row, S0);
-    }
-    bool any;
-    do {
-      double cv[SPT][kSimStep];
-#pragma unroll
-      for (int k = 0; k < SPT; ++k)
-#pragma unroll
-        for (int d = 0; d < kSimStep; ++d) cv[k][d] = cum[k][idx[k] + d];
-      any = false;
-#pragma unroll
-      for (int k = 0; k < SPT; ++k) {
-        bool go = true;
-        int adv = 0;
-#pragma unroll
-        for (int d = 0; d < kSimStep; ++d) {
-          go = go && idx[k] + d < S0 - 1 && u[k] >= cv[k][d];
-          adv += go ? 1 : 0;
-        }
-        idx[k] += adv;
-        any |= adv == kSimStep;
-      }
-    } while (any);
-    uint8_t* sn = states + (size_t)node * n;
-#pragma unroll
-    for (int k = 0; k < SPT; k += 2)
-      if (on[k]) {
-        *reinterpret_cast<unsigned short*>(sn + (unsigned)j[k]) = (unsigned short)(idx[k] | (idx[k + 1] << 8));
-        if (tx >= 0) {
-          if (((blk | (size_t)(uintptr_t)aln) & 1) == 0) {   // (an even rep_ram: the pair sits in one replicate block, at an even address)
-            *reinterpret_cast<unsigned short*>(out[k] + (size_t)tx * blk) = (unsigned short)(idx[k] | (idx[k + 1] << 8));
-          } else {
-            out[k][(size_t)tx * blk] = (uint8_t)idx[k];
-            out[k + 1][(size_t)tx * blk] = (uint8_t)idx[k + 1];
-          }
-        }
-      }
-    if (more) {
-      __syncthreads();   // nobody reads the other buffer any more (it held the previous node)
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        const int q = tid + NT * i;
-        if (q < nch && q * 16 < tabb + guib) reinterpret_cast<cmx_i4*>(sim_smem + (size_t)(buf ^ 1) * bufb)[q] = nxt[i];
-      }
-      __syncthreads();
-      buf ^= 1;
-    }
-  }
-}
-
-// simulate_lds_kernel rebuilt around what its counters showed: the vector unit issues for most of the kernel,
-// so the gain is in instructions, and only then in the latencies of a node.  Same draws, same bytes.
+// The same simulator with the tables of the node being drawn in LDS.  A draw needs one guide byte and a few entries of
+// ONE of C * S rows of its node; gathered from L2 by every thread that is ~100 bytes of traffic per draw (2.5e9 draws per
+// target launch: the gather kernel above took 22 ms there, L2-bound).  Here a workgroup draws batches of 2 NT sites (a
+// pair per thread), node by node, parents first (m.simord, level by level): the node's
+// block is copied into LDS once per workgroup, double-buffered (global -> registers while the current node is drawn,
+// registers -> the other buffer), and every search runs on LDS.  The vector unit issues for most of the kernel
+// (DESIGN 6), so the kernel is built to save instructions first and a node's latencies second.  Same draws, same states
+// as simulate_kernel.
 //  * integer search.  A node draw is u = w / 2^32 of a 32-bit Philox word: the guide entry is w >> 27 and "u >= cum" is
 //    "w > threshold" against the host's 32-bit thresholds (cmx_layout.h, HostModel::simtab) -- no conversion to double,
 //    no 64-bit compares, and a row ends in thresholds nobody exceeds instead of a bounds test per running sum.  A node's
-//    block is two thirds of the bytes and arrives as one contiguous copy.
+//    block is two thirds of the bytes of its running sums and guides and arrives as one contiguous copy.
+//  * STEP thresholds per search and LDS round trip, the pair's two searches side by side (a `while (w > thr[idx]) ++idx`
+//    per site is a chain of dependent LDS reads under a divergent branch).
 //  * the tables are staged once per NB batches of 2 NT sites, drawn one after the other (a loop over batches, not wider
 //    searches): barriers, table bytes and their addressing per site fall by NB at a few registers per batch.
-//  * one barrier per node, not two: the next node's tables go into the other buffer BEFORE the barrier (every thread
-//    stopped reading that buffer at the previous node's barrier).
+//  * one barrier per node: the next node's tables go into the other buffer BEFORE the barrier (every thread stopped
+//    reading that buffer at the previous node's barrier).
 //  * the parent's states of node it + 1 are loaded at the top of node it, beside the table prefetch; a node whose parent
 //    is the node just drawn (the root's first child, caterpillar chains) takes them from the registers they were drawn into.
 //  * a leaf's states go to the alignment only: nobody reads them back from `states`.
@@ -348,9 +175,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     out[b] = aln + (s / blk) * (size_t)m.T * blk + col;
     on |= (in ? 1u : 0u) << b;
     wrap |= (col == blk - 1 ? 1u : 0u) << b;
-    const int c0 = draw_index(philox_uniform(seed, g, 0), m.cum_probs, C0), c1 = draw_index(philox_uniform(seed, g + 1, 0), m.cum_probs, C0);
+    const int c0 = draw_class(m.cum_probs, C0, seed, g), c1 = draw_class(m.cum_probs, C0, seed, g + 1);
     crow[b] = (unsigned)(c0 * S0) | ((unsigned)(c1 * S0) << 16);
-    const int r0 = draw_index(philox_uniform(seed, g, 1), m.cum_pi, S0), r1 = draw_index(philox_uniform(seed, g + 1, 1), m.cum_pi, S0);
+    const int r0 = draw_root(m.cum_pi, S0, seed, g), r1 = draw_root(m.cum_pi, S0, seed, g + 1);
     xc[b] = (unsigned)r0 | ((unsigned)r1 << 8);
     if (in) *reinterpret_cast<unsigned short*>(states + (size_t)m.root * n + jj) = (unsigned short)xc[b];
   }
@@ -441,70 +268,48 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
 
 // From how many sites of a launch on the tables go through LDS; below, the gather kernel, one thread per site and no
 // barrier, is quicker.  A workgroup's walk over the 126 nodes of the target's tree takes simulate_chain_kernel 0.15 ms
-// however few workgroups there are (the gather kernel: 0.14 ms at 50 000 sites, 0.18 at 100 000, 0.50 at 450 000);
-// simulate_lds_kernel, two barriers per node, took 0.31 - 0.36 ms and paid from about two workgroups per CU on.
+// however few workgroups there are (the gather kernel: 0.14 ms at 50 000 sites, 0.18 at 100 000, 0.50 at 450 000).
 constexpr size_t kSimChainMinSites = 75000;
-constexpr size_t kSimLdsMinSites = 450000;
 // Four batches per workgroup once they fill every workgroup slot of the chip (256 CUs x 4) at least once: 4.04 ms
 // against 5.09 for the target's 2 * 10^7 sites, but 0.51 against 0.30 ms for 10^6, where a quarter of the CUs would work.
 constexpr size_t kSimChainFourBatches = (size_t)4 * 1024 * 1024;
+
+// 512 threads, a pair of sites each per batch, eight waves per SIMD; two 16-byte pieces of a node's block per thread up
+// to six classes of 20 states (16 384 B), three up to kSimNodeBytesMax.  One batch: 38 / 44 registers, four thresholds per round
+// trip of a search; four batches: 64 registers (8 / 12 spilled), two thresholds (four: 4.27 ms, more spills).
+// LDS: two node blocks, 20 480 B for the target's model.
+template <int NB, int STEP>
+static void launch_simulate_chain(const DevModel& m, const uint8_t* d_simtab, uint64_t seed, uint64_t g0, size_t s0, size_t n, size_t blk,
+                                  uint8_t* d_aln, uint8_t* d_states, hipStream_t stream) {
+  const size_t nodeb = sim_node_bytes(m.S0, m.C0);
+  const dim3 grid((unsigned)((n + NB * 1024 - 1) / (NB * 1024)));
+  if (nodeb <= (size_t)2 * 512 * 16)
+    hipLaunchKernelGGL((simulate_chain_kernel<NB, 2, 512, 8, STEP>), grid, dim3(512), 2 * nodeb, stream, m, d_simtab, seed, g0, s0, n, blk,
+                       d_aln, d_states);
+  else
+    hipLaunchKernelGGL((simulate_chain_kernel<NB, 3, 512, 8, STEP>), grid, dim3(512), 2 * nodeb, stream, m, d_simtab, seed, g0, s0, n, blk,
+                       d_aln, d_states);
+}
+
 // nsites sites with global indices g0 .. in passes of at most `chunk` (the states scratch holds nn * chunk bytes)
 hipError_t launch_simulate_blocked(const DevModel& m, uint64_t seed, uint64_t g0, size_t nsites, size_t blk, uint8_t* d_aln,
                                    uint8_t* d_states, size_t chunk, hipStream_t stream, const SimChoice& choice) {
-  // tables in LDS when a node's rows + guides fit 8 pieces per thread (every model this engine takes: S <= 20, C <= 8)
-  const size_t bufb = ((size_t)m.C0 * m.S0 * (m.S0 * 8 + 32) + 15) & ~(size_t)15;
-  // (DNA: 512-byte tables that sit in L1 / L2 anyway, and 2 barriers x 511 nodes: gathering is faster, cfg4 step 11.7 vs 13.0 ms)
-  const bool lds = m.S0 > 4 && bufb <= (size_t)kSimLdsChunks * 256 * 16;
-  // the chain kernel wherever the host built its tables (HostModel::simtab: a node block of at most kSimNodeBytesMax; of
-  // the models the line above lets through that leaves out five states with more than 61 classes, which stay with
-  // simulate_lds_kernel)
-  const uint8_t* d_simtab = choice.simtab;
-  const size_t nodeb = sim_node_bytes(m.S0, m.C0);
-  const bool chain = lds && d_simtab && nodeb <= kSimNodeBytesMax && choice.chain;
-  const size_t min_sites = choice.lds_min_sites >= 0 ? (size_t)choice.lds_min_sites : chain ? kSimChainMinSites : kSimLdsMinSites;
+  const size_t min_sites = choice.min_sites >= 0 ? (size_t)choice.min_sites : kSimChainMinSites;
   const size_t four_sites = choice.four_batch_sites >= 0 ? (size_t)choice.four_batch_sites : kSimChainFourBatches;
   for (size_t s0 = 0; s0 < nsites; s0 += chunk) {
     const size_t n = std::min(chunk, nsites - s0);
-    // (the LDS kernels pair the sites 2 k, 2 k + 1 of the global numbering and store a pair's symbols as one 16-bit word at
-    // column s0 + j of its replicate block: g0, s0 and n all have to be even, not just g0 + s0)
-    if (lds && n >= min_sites && (g0 & 1) == 0 && (s0 & 1) == 0 && (n & 1) == 0) {
-      if (chain) {
-        // 512 threads, a pair of sites each per batch, eight waves per SIMD; two 16-byte pieces of a node's block per thread
-        // up to five classes of 20 states, three up to eight.  One batch: 38 / 44 registers, four thresholds per round trip
-        // of a search; four batches: 64 registers (8 / 12 spilled), two thresholds (four: 4.27 ms, more spills).
-        // LDS: two node blocks, 20 480 B for the target's model.
-        const bool two = nodeb <= (size_t)2 * 512 * 16;
-        if (n >= four_sites) {
-          const dim3 grid((unsigned)((n + 4095) / 4096));
-          if (two)
-            hipLaunchKernelGGL((simulate_chain_kernel<4, 2, 512, 8, 2>), grid, dim3(512), 2 * nodeb, stream, m, d_simtab, seed, g0, s0, n, blk,
-                               d_aln, d_states);
-          else
-            hipLaunchKernelGGL((simulate_chain_kernel<4, 3, 512, 8, 2>), grid, dim3(512), 2 * nodeb, stream, m, d_simtab, seed, g0, s0, n, blk,
-                               d_aln, d_states);
-        } else {
-          const dim3 grid((unsigned)((n + 1023) / 1024));
-          if (two)
-            hipLaunchKernelGGL((simulate_chain_kernel<1, 2, 512, 8, 4>), grid, dim3(512), 2 * nodeb, stream, m, d_simtab, seed, g0, s0, n, blk,
-                               d_aln, d_states);
-          else
-            hipLaunchKernelGGL((simulate_chain_kernel<1, 3, 512, 8, 4>), grid, dim3(512), 2 * nodeb, stream, m, d_simtab, seed, g0, s0, n, blk,
-                               d_aln, d_states);
-        }
-      }
-      // 512 threads with two sites each: 56 registers = eight waves per SIMD (the kernel is bound by vector issue -- half of
-      // it Philox's quarter-rate multiplies -- once enough waves hide the LDS round trips: four sites per thread at three
-      // waves per SIMD 14.8 ms per target step, at five 11.6, this shape 10.2)
-      else if (bufb <= (size_t)2 * 512 * 16)
-        hipLaunchKernelGGL((simulate_lds_kernel<2, 2, 512, 8>), dim3((unsigned)((n + 1023) / 1024)), dim3(512), 2 * bufb, stream, m, seed, g0, s0,
-                           n, blk, d_aln, d_states);
+    // the chain kernel wherever the model has its tables (cmx_layout.h: sim_has_tables) and the pass is large enough.  It
+    // pairs the sites 2 k, 2 k + 1 of the global numbering and stores a pair's symbols as one 16-bit word at column
+    // s0 + j of its replicate block: g0, s0 and n all have to be even, not just g0 + s0.
+    if (choice.simtab && n >= min_sites && (g0 & 1) == 0 && (s0 & 1) == 0 && (n & 1) == 0) {
+      if (n >= four_sites)
+        launch_simulate_chain<4, 2>(m, choice.simtab, seed, g0, s0, n, blk, d_aln, d_states, stream);
       else
-        hipLaunchKernelGGL((simulate_lds_kernel<4, kSimLdsChunks, 256, 4>), dim3((unsigned)((n + 1023) / 1024)), dim3(256), 2 * bufb, stream, m,
-                           seed, g0, s0, n, blk, d_aln, d_states);
-    }
-    else
+        launch_simulate_chain<1, 4>(m, choice.simtab, seed, g0, s0, n, blk, d_aln, d_states, stream);
+    } else {
       hipLaunchKernelGGL(simulate_blocked_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, m, seed, g0, s0, n, blk,
                          d_aln, d_states);
+    }
   }
   return hipGetLastError();
 }
@@ -584,7 +389,7 @@ __global__ void simulate_continuous_kernel(const DevModel m, uint64_t seed, uint
   double r = 0.0;
   if (u0 >= p_inv) r = cmx_gamma_quantile(alpha, (u0 - p_inv) / (1.0 - p_inv)) / alpha / (1.0 - p_inv);
   if (rates) rates[j] = r;
-  states[(size_t)m.root * ld + j] = (uint8_t)draw_index(philox_uniform(seed, g, 1), m.cum_pi, S);
+  states[(size_t)m.root * ld + j] = (uint8_t)draw_root(m.cum_pi, S, seed, g);
   for (int node = m.nn - 2; node >= 0; --node) {
     const int x = states[(size_t)m.parent[node] * ld + j];
     const double u = philox_node_uniform(seed, g, (uint32_t)node);

@@ -59,7 +59,7 @@ EXPORTS = [
     "cmx_hclust", "cmx_hclust_dev", "cmx_cluster_sites", "cmx_cluster_sites_dev", "cmx_cluster_null",
     "cmx_intra_compact_range_dev", "cmx_intra_gram_prefetch_dev", "cmx_expand_compact_rows", "cmx_vector_matrix",
     "cmx_scratch_check", "cmx_debug_lds_slot", "cmx_debug_map_queue", "cmx_debug_map_grid", "cmx_debug_scratch_guard", "cmx_debug_scratch_guard_failures", "cmx_debug_scratch_shrink",
-    "cmx_set_null_patterns", "cmx_null_pattern_count", "cmx_debug_null_hash_bits", "cmx_debug_wait_plan", "cmx_debug_wait_skew", "cmx_debug_map_small_blocks", "cmx_debug_sim_chain", "cmx_debug_sim_tables",
+    "cmx_set_null_patterns", "cmx_null_pattern_count", "cmx_debug_null_hash_bits", "cmx_debug_wait_plan", "cmx_debug_wait_skew", "cmx_debug_map_small_blocks", "cmx_debug_sim_sites", "cmx_debug_sim_tables",
 ]
 # clustering.distance / clustering.method options of the reference (CoMap/CoMap.cpp:402-428, :460-472)
 DIST_CORRELATION, DIST_COMPENSATION, DIST_EUCLIDIAN = range(3)
@@ -92,16 +92,14 @@ def map_queue(on=None):
     return bool(lib.cmx_debug_map_queue(ctypes.c_int(-1 if on is None else int(bool(on)))))
 
 
-def sim_chain(on=None, min_sites=None, four_batch_sites=None):
-    """cmx_debug_sim_chain (include/comap_mi355x.h): which LDS-table kernel the null's simulator launches from now on, True =
-    simulate_chain_kernel (the default), False = the simulate_lds_kernel it replaced (None = leave); from how many sites of
-    a call on the LDS-table kernels run instead of the gather kernel, and from how many on a workgroup of the chain kernel
-    draws four batches (-1 = the built-in threshold, None = leave).  The same bytes on every path.  Returns the previous
-    kernel choice."""
+def sim_sites(min_sites=None, four_batch_sites=None):
+    """cmx_debug_sim_sites (include/comap_mi355x.h): from how many sites of a call on the null's simulator launches
+    simulate_chain_kernel instead of the gather kernel, and from how many on a workgroup of it draws four batches (-1 =
+    the built-in threshold, None = leave).  The same bytes on every path."""
     lib = load_library()
-    return bool(lib.cmx_debug_sim_chain(ctypes.c_int(-1 if on is None else int(bool(on))),
-                                        ctypes.c_longlong(-2 if min_sites is None else int(min_sites)),
-                                        ctypes.c_longlong(-2 if four_batch_sites is None else int(four_batch_sites))))
+    lib.cmx_debug_sim_sites.restype = None
+    lib.cmx_debug_sim_sites(ctypes.c_longlong(-2 if min_sites is None else int(min_sites)),
+                            ctypes.c_longlong(-2 if four_batch_sites is None else int(four_batch_sites)))
 
 
 def map_small_blocks(on=None):
@@ -347,7 +345,7 @@ def debug_wait_plan(parent, blen, leaf_of_taxon, Q, pi, rates, probs, Bk=None):
 def debug_sim_tables(parent, blen, leaf_of_taxon, Q, pi, rates, probs):
     """cmx_debug_sim_tables (no GPU): the simulator's tables -> dict(cum[C, nn, S, S], guide[C, nn, S, 32], row = R, the
     thresholds of a row (cmx_layout.h: sim_thr_row), thresholds[nn, C, S, R] uint32 and block_guide[nn, C, S, 32] -- the
-    per-node blocks of the LDS kernel, None for models it does not serve)"""
+    per-node blocks of the LDS kernel, None for models it does not serve, blocks_bytes = their size, 0 for those)"""
     lib = load_library()
     keep = [np.ascontiguousarray(parent, dtype=np.int32), _f64(blen), np.ascontiguousarray(leaf_of_taxon, dtype=np.int32),
             _f64(Q), _f64(pi), _f64(rates), _f64(probs)]
@@ -368,7 +366,7 @@ def debug_sim_tables(parent, blen, leaf_of_taxon, Q, pi, rates, probs):
     blocks = np.zeros(max(nbytes.value, 1), dtype=np.uint8)
     call(cum, guide, blocks)
     R = row.value
-    out = dict(cum=cum, guide=guide, row=R, thresholds=None, block_guide=None)
+    out = dict(cum=cum, guide=guide, row=R, blocks_bytes=nbytes.value, thresholds=None, block_guide=None)
     if nbytes.value:
         assert nbytes.value == nn * C * S * (4 * R + 32)
         b = blocks.reshape(nn, C * S * (4 * R + 32))

@@ -184,13 +184,13 @@ int cmx_debug_map_grid(int workgroups);
  * Process-wide, host only, read at each call. */
 int cmx_debug_map_small_blocks(int on);
 /* The null's simulator (cmx_null_simulate_dev and the nulls that simulate) draws large calls of models with more than four
- * states with a node's tables in LDS, small ones with a gather kernel; the LDS kernel draws one batch of 1 024 sites per
- * workgroup and copy of a node's tables, or four in very large launches; the same bytes on every path.
- * cmx_debug_sim_chain(0, ..) makes the launches issued from now on use the LDS kernel that preceded the current one (A/B
- * runs, tests), on < 0 leaves the choice; min_sites >= 0 sets the sites of a launch from which an LDS kernel runs (0: every
- * even launch; tests), four_batch_sites >= 0 those from which a workgroup draws four batches (0: always; tests); -1 restores
- * the built-in threshold, < -1 leaves it.  Returns the previous choice.  Process-wide, host only, read at each call. */
-int cmx_debug_sim_chain(int on, long long min_sites, long long four_batch_sites);
+ * states with a node's tables in LDS, where the model's tables fit (otherwise, and for small calls, with a gather kernel);
+ * the LDS kernel draws one batch of 1 024 sites per workgroup and copy of a node's tables, or four in very large launches;
+ * the same bytes on every path.  cmx_debug_sim_sites sets the two sizes for the launches issued from now on (tests: the
+ * LDS kernel's shapes at a few thousand sites): min_sites >= 0 the sites of a launch from which the LDS kernel runs (0:
+ * every even launch), four_batch_sites >= 0 those from which a workgroup draws four batches (0: always); -1 restores the
+ * built-in threshold, < -1 leaves it.  Process-wide, host only, read at each call. */
+void cmx_debug_sim_sites(long long min_sites, long long four_batch_sites);
 /* Host only, no GPU: the simulator's tables of a model and tree.  cum [C][nnodes][S][S] doubles, the running row sums of P,
  * and guide [C][nnodes][S][32] bytes (what the gather kernels read); blocks, the per-node blocks of 32-bit thresholds and guide
  * bytes the LDS kernel reads: nnodes * C * S * (4 * row + 32) bytes, rows of `row` thresholds (the constants of

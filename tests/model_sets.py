@@ -6,12 +6,15 @@ two children of the root on generators 0 and 1, and every generator on some bran
 device layout they reach):
 
     p20x4   protein matrix-core walk, pattern null by default     9 leaves, rooted, random
-    p20x6   six classes: the second LDS-table simulator shape     the same tree
+    p20x6   six classes: the largest two-piece node block         the same tree
+    p20x9   nine classes: the largest protein model with tables   the same tree
     n4x4    class-fused nucleotide walk, cherry tables            the same tree
     n4x5    fuse 5                                                13 leaves, balanced (six cherries)
     n4x2    unfused nucleotide                                    6 leaves
     c61x2   plain kernels, continuous simulator above 20 states   6 leaves
     s7x2    plain kernels (mapping only)                          6 leaves
+    c61x1, w64x1   simulator only: the widest models with tables  6 leaves
+    s7x50          simulator only: no tables (like c61x2)         6 leaves
     p20x3:<shape>, n4x4:<shape>                                   the rooted 2-, 3- and 4-leaf shapes of SHAPES
 
 The simulator inputs are listed here, not in the GPU tests, so that tests/test_oracle_model_sets.py can bound the share of
@@ -92,14 +95,14 @@ def _tree(name, seed):
         blen = np.random.default_rng(seed).uniform(0.03, 0.4, size=len(parent))
         blen[-1] = 0.0
         return parent, blen, lot
-    return rooted_random_tree(9 if name in ("p20x4", "p20x6", "n4x4") else 6, 31)
+    return rooted_random_tree(9 if name in ("p20x4", "p20x6", "p20x9", "n4x4") else 6, 31)
 
 
 @lru_cache(maxsize=None)
 def case(name, variant=0):
     """the case of that name; variant 1: the second data set of the two-data-set null -- the same topology with other
     generators, another assignment of them, other root frequencies and scaled branch lengths"""
-    S, C = {"p": 20, "n": 4, "c": 61, "s": 7}[name[0]], int(name.split(":")[0].split("x")[1])
+    S, C = {"p": 20, "n": 4, "c": 61, "s": 7, "w": 64}[name[0]], int(name.split(":")[0].split("x")[1])
     seed = sum(map(ord, name)) + 1000 * variant
     rng = np.random.default_rng(seed)
     parent, blen, lot = _tree(name, sum(map(ord, name)))
@@ -163,8 +166,14 @@ def alignment(c, nsites=70, ambiguous=False):
 # ---------------------------------------------------------------------------------------------- simulator inputs
 SIM_SEED, SIM_G0, SIM_N = 987654321, 12345, 3000          # eng.simulate of every simulator case (an odd g0)
 GATHER = dict(seed=77, rep_begin=3, rep_end=5, rep_ram=700)
-LDS = [("p20x4", dict(seed=77, rep_begin=0, rep_end=1, rep_ram=225_000)),      # 450 000 sites: the LDS kernel's threshold
-       ("p20x6", dict(seed=77, rep_begin=1, rep_end=3, rep_ram=225_001))]      # 900 004 sites: the other LDS instantiation
+CHAIN = [("p20x4", dict(seed=77, rep_begin=0, rep_end=1, rep_ram=37_500)),     # 75 000 sites: the LDS-table kernel's threshold
+         ("p20x6", dict(seed=77, rep_begin=1, rep_end=3, rep_ram=18_751))]     # 75 004 sites, an odd rep_ram, two replicates
+# the LDS-table kernel at a few thousand sites (tests/test_gpu_simulator_chain.py): models with a node block of 23 040,
+# 19 456 and 18 544 bytes (three 16-byte pieces per thread), and two without tables (28 000 and 37 088 bytes; the limit
+# is 24 576)
+CHAIN_EDGE_CASES = ["p20x9", "w64x1", "c61x1", "s7x50", "c61x2"]
+CHAIN_EDGE_CALLS = [(0, 1, 513), (1, 2, 2050), (2, 4, 1536)]                   # (rep_begin, rep_end, rep_ram)
+CHAIN_EDGE_SEED = 4711
 CONTINUOUS = dict(seed=77, g0=1000, n=600, rates=((0.5, 0.0), (1.7, 0.2)))
 CONTINUOUS_NULL = dict(seed=5, rep_begin=2, rep_end=4, rep_ram=64, alpha=0.5, p_inv=0.1)
 NULL = dict(seed=777, nrep=3, rep_ram=50)
@@ -182,7 +191,9 @@ def discrete_inputs():
     """[(label, case, seed, g0, n)]: every range of global site indices that a GPU test has the discrete simulator draw"""
     out = [(f"simulate:{n}", case(n), SIM_SEED, SIM_G0, SIM_N) for n in SIMULATOR_CASES]
     out += [(f"gather:{n}", case(n), GATHER["seed"], *_null_range(**GATHER)) for n in SIMULATOR_CASES]
-    out += [(f"lds:{n}", case(n), kw["seed"], *_null_range(**kw)) for n, kw in LDS]
+    out += [(f"chain:{n}", case(n), kw["seed"], *_null_range(**kw)) for n, kw in CHAIN]
+    out += [(f"chain-edge:{n}:{rb}", case(n), CHAIN_EDGE_SEED, *_null_range(rb, re, ram)) for n in CHAIN_EDGE_CASES
+            for rb, re, ram in CHAIN_EDGE_CALLS]
     for n in NULL_CASES:
         out.append((f"null:{n}", case(n), NULL["seed"], 0, NULL["nrep"] * 2 * NULL["rep_ram"]))
         out.append((f"supplied:{n}", case(n), 5, 0, NULL["nrep"] * 2 * NULL["rep_ram"]))

@@ -177,14 +177,14 @@ def test_discrete_simulator(name):
     _same_symbols(f"null simulator {name}", got, wo, near)
 
 
-@pytest.mark.parametrize("name,k", ms.LDS, ids=[n for n, _ in ms.LDS])
+@pytest.mark.parametrize("name,k", ms.CHAIN, ids=[n for n, _ in ms.CHAIN])
 def test_lds_table_simulator(name, k):
-    """450 000 sites with everything even is the threshold of the LDS-table kernel; six classes take its other shape"""
+    """75 000 sites with everything even is the threshold of the LDS-table kernel; six classes are the largest node block of its two-piece shape"""
     import torch
     c, eng = ms.case(name), _eng(name)
     T, nrep, ram = len(c["lot"]), k["rep_end"] - k["rep_begin"], k["rep_ram"]
     n = nrep * 2 * ram
-    assert n >= 450_000 and n % 2 == 0 and (k["rep_begin"] * 2 * ram) % 2 == 0
+    assert n >= 75_000 and n % 2 == 0 and (k["rep_begin"] * 2 * ram) % 2 == 0
     buf = torch.empty(n * T, dtype=torch.uint8, device="cuda:0")
     eng.null_simulate_dev(k["seed"], k["rep_begin"], k["rep_end"], ram, buf)
     torch.cuda.synchronize()

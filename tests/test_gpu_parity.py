@@ -954,9 +954,9 @@ def test_null_simulator_kernels_and_passes_agree_with_the_plain_simulator(tmp_pa
     eng = _engine(case)
     dev = torch.device("cuda:0")
     T = len(case["lot"])
-    case6 = make_case(8, 10, 20, 6, ncat=6)                     # six classes: a node's tables exceed 16 KB (the other LDS shape)
+    case6 = make_case(8, 10, 20, 6, ncat=6)                     # six classes: a node block of 15 360 B, the largest of the two-piece shape
     for e, rb, re, ram in ((eng, 3, 5, 700), (eng, 0, 2, 600_000), (_engine(case6), 1, 3, 550_001)):
-        # 2 800 sites (gather kernel); 2.4 M and 2.2 M sites (LDS-table kernel, 512 x 2 and 256 x 4 sites per workgroup)
+        # 2 800 sites (gather kernel); 2.4 M and 2.2 M sites (LDS-table kernel, one batch of 1 024 sites per workgroup)
         n = (re - rb) * 2 * ram
         buf = torch.empty(n * T, dtype=torch.uint8, device=dev)
         e.null_simulate_dev(77, rb, re, ram, buf)

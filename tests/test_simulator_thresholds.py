@@ -12,13 +12,19 @@ counts the thresholds of the row below w instead, from the same guide entry on, 
   guide's steps and next to a sample of the thresholds;
 * the guide bytes of a node's block are the gather kernel's, and the blocks follow the layout of cmx_layout.h.
 Trees with branches of length 0 (sums of exactly 0 and 1, some an ulp out of order), 1e-9, 1e-12 (sums within 2^-32 of 0
-and 1), 60 and ordinary ones; protein models of 4 and 6 classes; nucleotides get no blocks."""
+and 1), 60 and ordinary ones; protein models of 4 and 6 classes; nucleotides get no blocks.
+Which models get blocks at all is one rule, more than four states and a node block of at most 24 576 bytes: models on both
+sides of it, 20 states with 8 / 9 / 10 classes and 61 with 1 / 2 among them, and the size of the blocks."""
+import os
+
 import numpy as np
 import pytest
 
-from comap_amd import engine, synthetic
+import model_sets as ms
+from comap_amd import engine, protein_models as pm, synthetic
 from tree_shapes import _balanced
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _tables(ncat, nstates=20):
     parent, lot = _balanced(8)
@@ -68,3 +74,35 @@ def test_thresholds_stand_for_the_running_sums(ncat):
 def test_nucleotides_get_no_blocks():
     t, _ = _tables(4, nstates=4)
     assert t["thresholds"] is None and t["cum"].shape[-1] == 4
+
+
+# (states, classes) with a node block of at most kSimNodeBytesMax = 24 576 bytes and more than four states -- the one rule
+# for "this model has simulator tables" (cmx_layout.h: sim_has_tables) -- and without
+WITH_BLOCKS = [(20, 8), (20, 9), (61, 1), (64, 1), (16, 13)]
+WITHOUT_BLOCKS = [(4, 4), (20, 10), (61, 2), (7, 50), (5, 62), (14, 16)]
+
+
+@pytest.mark.parametrize("S,C", WITH_BLOCKS + WITHOUT_BLOCKS)
+def test_which_models_get_blocks(S, C):
+    parent, lot = _balanced(4)
+    nn = len(parent)
+    blen = np.array([0.1, 0.0, 0.4, 1e-9, 0.2, 0.3, 0.0])
+    Qs, pis = ms._generators(S, 7)
+    rates, probs = pm.gamma_rates(0.6, C)
+    t = engine.debug_sim_tables(parent, blen, lot, Qs[0], pis[0], rates, probs)
+    row = (S + 4 + 3) // 4 * 4
+    assert t["row"] == row
+    if (S, C) in WITH_BLOCKS:
+        assert t["blocks_bytes"] == nn * C * S * (4 * row + 32) > 0
+        assert t["blocks_bytes"] // nn <= 24576
+        assert t["thresholds"].shape == (nn, C, S, row) and t["block_guide"].shape == (nn, C, S, 32)
+    else:
+        assert t["blocks_bytes"] == 0 and t["thresholds"] is None and t["block_guide"] is None
+        assert S <= 4 or C * S * (4 * row + 32) > 24576
+
+
+def test_size_hook_is_exported_and_declared():
+    assert "cmx_debug_sim_sites" in engine.EXPORTS
+    assert hasattr(engine.load_library(), "cmx_debug_sim_sites")
+    with open(os.path.join(ROOT, "include", "comap_mi355x.h")) as f:
+        assert "void cmx_debug_sim_sites(long long min_sites, long long four_batch_sites);" in f.read()
