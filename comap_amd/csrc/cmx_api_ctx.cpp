@@ -4,6 +4,7 @@
 // This file: the context, the scratch buffers and their guard, settings and debug hooks.  The stages are in
 // cmx_api_map.cpp, cmx_api_null.cpp, cmx_api_pairs.cpp, cmx_api_mica.cpp and cmx_api_cluster.cpp.
 #include "cmx_ctx.h"
+#include "cmx_host_parts.h"   // children(), OPER_P: the cherry message table's operators
 
 thread_local std::string g_create_error;
 
@@ -19,6 +20,7 @@ std::vector<std::string> g_guard_failures;
 std::map<std::string, size_t> g_guard_shrink;
 
 std::atomic<int> g_lds_slot{1};         // cmx_debug_lds_slot: 0 = the mapping walk's LDS slot is planned empty (A/B runs, tests)
+std::atomic<int> g_cherry_msg{1};       // cmx_debug_cherry_msg: 0 = no cherry message table, the null of a 20-state model walks the plain stream (A/B runs, tests)
 std::atomic<int> g_pat_hash_bits{64};   // (tests force collisions with it)
 std::atomic<int> g_map_queue{1};        // cmx_debug_map_queue: 0 = strided block assignment in every mapping launch (A/B runs, tests)
 std::atomic<int> g_map_small_blocks{1};      // cmx_debug_map_small_blocks: 0 = the class-split launch of a protein alignment keeps 64-site blocks (tests)
@@ -186,6 +188,7 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
   if (model) {
     int code = CMX_OK;
     ctx->hm.lds_slot = g_lds_slot.load() != 0;
+    ctx->hm.cherry_msg = g_cherry_msg.load() != 0;
     std::string msg = build_host_model(model, tree, &ctx->hm, &code);
     if (!msg.empty()) {
       ctx->err = msg;
@@ -246,6 +249,20 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
       if (!h.msched_r.empty()) CMX_TRY(up_stream(h.msched_r, &d.msched_r, &d.nmv_r));   // the cherry-table walk's stream
       d.plan = nullptr;
       if (!h.wait_imm.empty()) CMX_TRY(upload(ctx, planned_stream(h), &d.plan));   // the 64-site protein walk reads this one
+      if (h.n_cherry_msg > 0) {
+        // the resolved walk of the null with the cherry message table (cmx_layout.h): its stream, its planned copy, and the
+        // table behind its node index; cherry_msg_kernel fills the rows below, after the leaf operators are complete
+        CMX_TRY(up_stream(h.msched_m, &d.msched_r, &d.nmv_r));
+        CMX_TRY(upload(ctx, planned_stream(h, true), &ctx->d_plan_r));
+        const size_t head = cherry_msg_header_bytes(h.nn), bytes = head + h.cherry_msg_bytes();
+        void* p = nullptr;
+        HIP_TRY(ctx, hipMalloc(&p, bytes));
+        ctx->model_allocs.push_back(p);
+        ctx->d_cherry_msg = static_cast<uint8_t*>(p);
+        std::vector<int> ref(head / sizeof(int), -1);
+        for (int n = 0; n < h.nn; ++n) ref[n] = h.taxon_of[n] >= 0 ? h.taxon_of[n] : h.cherry_of[n];
+        HIP_TRY(ctx, hipMemcpy(p, ref.data(), head, hipMemcpyHostToDevice));
+      }
       UP(nrec);
     }
     UP(simg); UP(simord);
@@ -258,6 +275,21 @@ cmx_status cmx_ctx_create(const cmx_model* model, const cmx_tree* tree, int devi
     if (h.plain) return CMX_OK;   // simulator tables and tree only
     // ambiguity rows of the leaf operators: default "every state compatible" until a call brings a mask table
     HIP_TRY(ctx, launch_extend_leaf_rows(d, nullptr, nullptr));
+    if (ctx->d_cherry_msg) {
+      const ClassBlock blk = h.block();
+      std::vector<int> ops((size_t)h.n_cherry_msg * 4, 0);
+      for (int n = 0; n < h.nn; ++n) {
+        const int ci = h.cherry_of[n];
+        if (ci < 0) continue;
+        const std::vector<int> ch = children(h, n);   // an inlined cherry: two leaves, in the records' order
+        ops[4 * (size_t)ci] = blk.leaf(h.taxon_of[ch[0]], OPER_P);
+        ops[4 * (size_t)ci + 1] = blk.leaf(h.taxon_of[ch[1]], OPER_P);
+        ops[4 * (size_t)ci + 2] = blk.internal(h.slot[n], OPER_P);
+      }
+      const int* d_ops = nullptr;
+      CMX_TRY(upload(ctx, ops, &d_ops));
+      HIP_TRY(ctx, launch_cherry_msg(d, d_ops, h.n_cherry_msg, ctx->d_cherry_msg + cherry_msg_header_bytes(h.nn), nullptr));
+    }
     HIP_TRY(ctx, hipDeviceSynchronize());
     ctx->leaf_rows_custom = false;
     // ambiguity masks default: code c >= S compatible with every state; fix the table for this S
@@ -363,6 +395,7 @@ cmx_status cmx_debug_walk(const cmx_model* model, const cmx_tree* tree, int32_t*
   HostModel hm;
   int code = CMX_OK;
   hm.lds_slot = g_lds_slot.load() != 0;
+  hm.cherry_msg = g_cherry_msg.load() != 0;
   const std::string msg = build_host_model(model, tree, &hm, &code);
   if (!msg.empty()) {
     g_create_error = msg;
@@ -389,6 +422,7 @@ cmx_status cmx_debug_wait_plan(const cmx_model* model, const cmx_tree* tree, int
   HostModel hm;
   int code = CMX_OK;
   hm.lds_slot = g_lds_slot.load() != 0;
+  hm.cherry_msg = g_cherry_msg.load() != 0;
   const std::string msg = build_host_model(model, tree, &hm, &code);
   if (!msg.empty()) {
     g_create_error = msg;
@@ -405,6 +439,70 @@ cmx_status cmx_debug_wait_plan(const cmx_model* model, const cmx_tree* tree, int
 }
 
 int cmx_debug_wait_skew(int entry) { return wait_plan_skew(entry); }
+
+// what cmx_get_cherry_msg_info and cmx_debug_cherry_msg_walk report (include/comap_mi355x.h)
+static void cherry_msg_stats(const HostModel& hm, uint64_t* stats) {
+  const bool on = hm.n_cherry_msg > 0;
+  stats[0] = (uint64_t)hm.n_cherry_msg; stats[1] = on ? (uint64_t)hm.cherry_msg_bytes() : 0;
+  stats[2] = on ? hm.msg.products : hm.n_products; stats[3] = on ? hm.msg.leaf_ops : hm.n_leaf_ops; stats[4] = hm.msg.gathers;
+  stats[5] = on ? hm.msg.loads : hm.n_loads; stats[6] = on ? hm.msg.stores : hm.n_stores;
+  stats[7] = on ? hm.msg.lds_loads : hm.n_lds_loads; stats[8] = on ? hm.msg.lds_stores : hm.n_lds_stores; stats[9] = on ? hm.msg.lds_copies : hm.n_lds_copies;
+  stats[10] = (uint64_t)kCherryMsgMaxBytes; stats[11] = 0;
+}
+
+cmx_status cmx_get_cherry_msg_info(const cmx_ctx* ctx, uint64_t* stats) {
+  if (!ctx || !stats || !ctx->has_model) return CMX_ERR_INVALID;
+  cherry_msg_stats(ctx->hm, stats);
+  return CMX_OK;
+}
+
+cmx_status cmx_debug_cherry_msg_walk(const cmx_model* model, const cmx_tree* tree, uint64_t* stats, int32_t* msched, size_t m_cap, size_t* m_n,
+                                     int32_t* distance, int32_t* immediate) {
+  HostModel hm;
+  int code = CMX_OK;
+  hm.lds_slot = g_lds_slot.load() != 0;
+  hm.cherry_msg = g_cherry_msg.load() != 0;
+  const std::string msg = build_host_model(model, tree, &hm, &code);
+  if (!msg.empty()) {
+    g_create_error = msg;
+    return (cmx_status)code;
+  }
+  if (!stats || !m_n || hm.msched_m.size() > m_cap) {
+    g_create_error = "cmx_debug_cherry_msg_walk: a buffer is missing or too small";
+    return CMX_ERR_INVALID;
+  }
+  cherry_msg_stats(hm, stats);
+  *m_n = hm.msched_m.size();
+  if (msched) std::memcpy(msched, hm.msched_m.data(), hm.msched_m.size() * sizeof(int32_t));
+  if (distance) std::memcpy(distance, hm.wait_dist_m.data(), hm.wait_dist_m.size() * sizeof(int32_t));
+  if (immediate) std::memcpy(immediate, hm.wait_imm_m.data(), hm.wait_imm_m.size() * sizeof(int32_t));
+  return CMX_OK;
+}
+
+cmx_status cmx_debug_cherry_msg_table(cmx_ctx* ctx, double* table, size_t cap, int32_t* cherries) {
+  CMX_TRY(need_model(ctx));
+  const HostModel& h = ctx->hm;
+  const size_t need = (size_t)h.C * h.n_cherry_msg * kCherryMsgPairs * 20;
+  if (!ctx->d_cherry_msg || !table || cap < need) return fail(ctx, CMX_ERR_INVALID, "cmx_debug_cherry_msg_table: no table, or the buffer is missing or too small");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  std::vector<double> raw(h.cherry_msg_bytes() / sizeof(double));
+  HIP_TRY(ctx, hipMemcpy(raw.data(), ctx->d_cherry_msg + cherry_msg_header_bytes(h.nn), h.cherry_msg_bytes(), hipMemcpyDeviceToHost));
+  const size_t tab = kCherryMsgTableBytes / sizeof(double);
+  for (int c = 0; c < h.C; ++c)
+    for (int ci = 0; ci < h.n_cherry_msg; ++ci)
+      for (int p = 0; p < kCherryMsgPairs; ++p)
+        for (int x = 0; x < 20; ++x)
+          table[(((size_t)c * h.n_cherry_msg + ci) * kCherryMsgPairs + p) * 20 + x] = raw[((size_t)ci * h.C + c) * tab + cherry_msg_offset(p, x)];
+  if (cherries)
+    for (int n = 0; n < h.nn; ++n)
+      if (h.cherry_of[n] >= 0) {
+        const std::vector<int> ch = children(h, n);
+        int32_t* o = cherries + 3 * (size_t)h.cherry_of[n];
+        o[0] = n; o[1] = ch[0]; o[2] = ch[1];
+      }
+  return CMX_OK;
+}
 
 cmx_status cmx_debug_sim_tables(const cmx_model* model, const cmx_tree* tree, double* cum, size_t cum_cap, uint8_t* guide,
                                 size_t guide_cap, uint8_t* blocks, size_t blocks_cap, size_t* blocks_bytes, int32_t* row) {
@@ -453,6 +551,12 @@ int cmx_debug_scratch_guard(int on) {
 int cmx_debug_lds_slot(int on) {
   const int was = g_lds_slot.load();
   if (on >= 0) g_lds_slot.store(on ? 1 : 0);
+  return was;
+}
+
+int cmx_debug_cherry_msg(int on) {
+  const int was = g_cherry_msg.load();
+  if (on >= 0) g_cherry_msg.store(on ? 1 : 0);
   return was;
 }
 

@@ -176,7 +176,7 @@ static cmx_status null_patterns_dev(cmx_ctx* ctx, const Stat& sk, MapArgs a, siz
     const size_t blocks_needed = ((n + ks - 1) / ks + kWavesPerBlock - 1) / kWavesPerBlock;
     const int grid = (int)std::min<size_t>(blocks_needed, (size_t)ctx->grid_blocks);
     CMX_TRY(map_queue_take(ctx, (n + ks - 1) / ks, grid, (hipStream_t)stream, &a.queue));
-    HIP_TRY(ctx, launch_map(a, kModeNullPatterns, grid, (hipStream_t)stream));
+    HIP_TRY(ctx, launch_map(a, a.cherry_msg ? kModeNullPatternsMsg : kModeNullPatterns, grid, (hipStream_t)stream));
     if (moments)
       HIP_TRY(ctx, launch_null_pattern_moments(h.B, h.K, cnt, (int)ks, (int)ks, a.npat, n, pmean, pss, (hipStream_t)stream));
     HIP_TRY(ctx, launch_null_pattern_pairs(sk, cnt, (int)ks, (int)ks, pmean, pss, SiteCols{rc, pr, nm}, b.pat_of, rep_ram, n / 2, out.at(r0 * rep_ram),
@@ -234,13 +234,14 @@ cmx_status cmx_null_intra_dev(cmx_ctx* ctx, int kind, const double* params, uint
   a.stat_kind = kind; a.stat_param = sk.param; a.stat_mean = sk.d_mean;
   a.rep_ram = rep_ram; a.supplied = d_supplied;
   a.null_stat = d_stat; a.null_rcmin = d_rcmin; a.null_prmin = d_prmin; a.null_nmin = d_nmin;
+  a.plan_r = ctx->d_plan_r; a.cherry_msg = ctx->d_cherry_msg;   // (a model with a cherry message table: the walk gathers the cherries' messages)
   const size_t reps_per_pass = null_pattern_reps(ctx, rep_ram);
   if (reps_per_pass) return null_patterns_dev(ctx, sk, a, rep_end - rep_begin, reps_per_pass, stream);
   const size_t ks = (size_t)map_sites_per_wave(ctx->hm.dS);
   const size_t blocks_needed = ((a.nsites + ks - 1) / ks + kWavesPerBlock - 1) / kWavesPerBlock;
   const int grid = (int)std::min<size_t>(blocks_needed, (size_t)ctx->grid_blocks);
   CMX_TRY(map_queue_take(ctx, (a.nsites + ks - 1) / ks, grid, (hipStream_t)stream, &a.queue));
-  HIP_TRY(ctx, launch_map(a, kModeNull, grid, (hipStream_t)stream));
+  HIP_TRY(ctx, launch_map(a, a.cherry_msg ? kModeNullMsg : kModeNull, grid, (hipStream_t)stream));
   ctx->null_mapped_host += 2 * a.nsites;
   return CMX_OK;
 }

@@ -60,6 +60,10 @@ struct cmx_ctx {
   std::vector<GuardedFixed> guarded_fixed;   // CMX_SCRATCH_GUARD: the per-wave workspaces, each with a canary after its last byte
   uint32_t* d_default_masks = nullptr;
   const uint8_t* d_simtab = nullptr;   // HostModel::simtab (null: the model has none)
+  // the cherry message table of a 20-state model (cmx_layout.h; null: none) behind its node index, and the planned copy of the
+  // resolved stream (MapArgs::cherry_msg / plan_r of the null's launches; the stream itself is dm.msched_r)
+  uint8_t* d_cherry_msg = nullptr;
+  const PlanEntry* d_plan_r = nullptr;
   unsigned stat_mean_turn = 0;
   // host copies of asynchronously uploaded parameter blocks (mean vectors, MI bounds): the source of a hipMemcpyAsync must
   // outlive the copy, and the caller's array need not
@@ -117,6 +121,7 @@ extern std::atomic<int> g_guard;                       // CMX_SCRATCH_GUARD: -1 
 extern std::mutex g_guard_mu;
 extern std::vector<std::string> g_guard_failures;      // buffers found trampled, in the order found
 extern std::map<std::string, size_t> g_guard_shrink;   // test hook: logical size override per buffer name
+extern std::atomic<int> g_cherry_msg;                  // cmx_debug_cherry_msg: 0 = contexts created from now on get no cherry message table
 extern std::atomic<int> g_pat_hash_bits;               // cmx_debug_null_hash_bits: the fused null's column hash keeps only its low bits
 extern std::atomic<int> g_map_queue;                   // cmx_debug_map_queue: 0 = every mapping launch keeps the strided block assignment
 extern std::atomic<int> g_map_small_blocks;                 // cmx_debug_map_small_blocks: 0 = no 16-site blocks in the class-split launch

@@ -44,7 +44,10 @@ struct DevModel {
   const int* msched;       // operator uses in program order: pairs (element offset in the class block, taxon or -1),
                            // followed by copies of its first two pairs (the op two ahead is read without a wrap test)
   int nmv;                 // number of pairs
-  const int* msched_r;     // the cherry-table walk's stream (class-fused nucleotide models, resolved alignments: the null), or null
+  // the stream of the walk over resolved alignments (the null's) where it differs from msched, or null: the cherry-table
+  // walk's (class-fused nucleotide models), or the 64-site protein walk's with the cherry message table (cmx_walk.h:
+  // kCherryMsg; the kernels read its first entries here and the planned copy at MapArgs::plan_r)
+  const int* msched_r;
   int nmv_r;
   // the planned stream of the 64-site protein walk (cmx_layout.h: PlanEntry): planned_stream_copies(C) copies of nmv + 2
   // entries; null for every other model.  (In the slot of the load schedule the device once read: the kernel-argument
@@ -88,7 +91,12 @@ struct Workspace {
 // 32 site blocks: one task per wave would be four class passes of pure latency), classes summed by map_finalize_kernel
 // kModeNullPatterns: the fused null's distinct columns: lane = pattern, walked as kModeNull walks a site, with
 // counts / post rate / norm / rate class written per pattern as in observed mode; the pairs are scored afterwards
-enum MapMode { kModeObserved = 0, kModeNull = 1, kModeObservedSplit = 2, kModeNullPatterns = 3 };
+// kModeNullMsg / kModeNullPatternsMsg: kModeNull / kModeNullPatterns of a 20-state model with a cherry message table
+// (cmx_layout.h): the walk gathers an inlined cherry's message from the table (cmx_walk.h: kCherryMsg) and follows the
+// resolved stream (DevModel::msched_r, MapArgs::plan_r).  Own modes, so that the other instantiations keep their symbols.
+enum MapMode { kModeObserved = 0, kModeNull = 1, kModeObservedSplit = 2, kModeNullPatterns = 3, kModeNullMsg = 4, kModeNullPatternsMsg = 5 };
+constexpr bool map_mode_msg(int mode) { return mode == kModeNullMsg || mode == kModeNullPatternsMsg; }
+constexpr int map_mode_base(int mode) { return mode == kModeNullMsg ? (int)kModeNull : (mode == kModeNullPatternsMsg ? (int)kModeNullPatterns : mode); }
 
 struct MapArgs {
   DevModel m;
@@ -112,8 +120,9 @@ struct MapArgs {
   int stat_kind;
   double stat_param;       // discrete-MI threshold
   const double* stat_mean; // CorrectedCorrelation: [2][B] mean vectors of the two operands (device), else null
-  uint64_t seed;           // unused: the alignments are simulated before the launch; the slot keeps the kernel-argument layout
-  size_t rep_begin;        // unused: as seed
+  // (the two slots once held the in-kernel simulator's seed and first replicate: the kernel-argument layout is the parent's)
+  const PlanEntry* plan_r; // kModeNullMsg / kModeNullPatternsMsg: the planned copy of the resolved stream (layout of DevModel::plan), else null
+  const uint8_t* cherry_msg;   // ... and the cherry message table behind its node index (cmx_layout.h: cherry_msg_header_bytes), else null
   size_t rep_ram;
   const uint8_t* supplied; // [nrep][2][T][rep_ram] or null
   double* null_stat;       // [nsites]
@@ -134,7 +143,7 @@ struct MapArgs {
 // The code hipcc emits for the mapping kernels depends on where these structures' fields sit in the kernel argument
 // (DESIGN.md 4.5.4): an unused field keeps its slot.
 static_assert(sizeof(DevModel) == 256 && sizeof(Workspace) == 56 && sizeof(MapArgs) == 520 && offsetof(MapArgs, rep_site) == 496 &&
-                  offsetof(MapArgs, queue) == 512,
+                  offsetof(MapArgs, queue) == 512 && offsetof(MapArgs, plan_r) == 432 && offsetof(MapArgs, cherry_msg) == 440,
               "kernel-argument layout of the mapping kernels");
 
 // ---- the pair stage's shapes: host structures (the kernels keep taking their pointers one by one, as with MicaSide)
@@ -188,6 +197,9 @@ hipError_t launch_map_queue_init(unsigned long long* queue, unsigned long long f
 hipError_t launch_map_finalize(const MapArgs& a, hipStream_t stream);
 // fills rows S.. of every leaf operator from d_masks[S .. S+max_ambig(S)) (null: every state compatible)
 hipError_t launch_extend_leaf_rows(const DevModel& m, const uint32_t* d_masks, hipStream_t stream);
+// fills the cherry message table of a 20-state model (cmx_layout.h) with the walk's own code: d_ops [cherries][4] = matrix index
+// in a class block of the leaf operators of l1 and l2 and of the cherry's P, pad; d_table: the rows behind the header
+hipError_t launch_cherry_msg(const DevModel& m, const int* d_ops, int cherries, uint8_t* d_table, hipStream_t stream);
 // pairs (j of data set 1, j of data set 2), j < n: the members of `out` that are set
 hipError_t launch_pair_diag(const Stat& st, const double* c1, size_t ld1, const SiteCols& s1, const double* c2, size_t ld2,
                             const SiteCols& s2, size_t n, const PairOut& out, hipStream_t stream);

@@ -63,6 +63,16 @@ struct HostModel {
   // Of n_loads / n_stores, the transfers the slot serves instead of HBM; n_lds_copies: messages written to both.
   bool lds_slot = true;
   size_t n_lds_loads = 0, n_lds_stores = 0, n_lds_copies = 0;
+  // Cherry message table (cmx_walk.h, kCherryMsg; cmx_layout.h: cherry_msg_eligible): on fully resolved alignments (the
+  // null's) the 64-site protein walk gathers an inlined cherry's message from a device-built table instead of rebuilding it.
+  // cherry_msg is an input of build_host_model (false = no table).  n_cherry_msg: cherries with a table, 0 = the resolved walk
+  // is the plain one.  msched_m: the resolved walk's operator stream -- the plain one less the cherries' message ops, a
+  // gather adds no entry -- with its own wait plan; records, load schedule and LDS-slot plan are shared with the plain walk.
+  bool cherry_msg = true;
+  int n_cherry_msg = 0;
+  std::vector<int> msched_m, wait_dist_m, wait_imm_m;
+  struct WalkCounts { size_t loads = 0, stores = 0, products = 0, leaf_ops = 0, lds_loads = 0, lds_stores = 0, lds_copies = 0, gathers = 0; } msg;
+  size_t cherry_msg_bytes() const { return cherry_msg_table_bytes(C, n_cherry_msg); }
 };
 
 // The walk of a rate-class pass lives in cmx_walk.h.  build_records: the per-node records it reads; record_walk: the
@@ -73,10 +83,13 @@ void build_records(HostModel* hm);
 void plan_lds_slot(HostModel* hm);   // after build_records, before record_walk: sets the FLAG_LDS_* bits of the records
 void record_walk(HostModel* hm);   // ... and the wait plan of the 20-state unfused walk
 std::string verify_walk(const HostModel& hm);
-// the device stream of a model with a wait plan (cmx_layout.h: PlanEntry), every copy: [planned_stream_copies(dC)][nmv + 2]
-std::vector<PlanEntry> planned_stream(const HostModel& hm);
+// the device stream of a model with a wait plan (cmx_layout.h: PlanEntry), every copy: [planned_stream_copies(dC)][nmv + 2];
+// resolved: the stream of the walk with the cherry message table (msched_m), same layout
+std::vector<PlanEntry> planned_stream(const HostModel& hm, bool resolved = false);
 // test hook (host only, process-wide): the NEXT wait plan built gets the immediate of entry `entry` raised by one -- a wait
 // that is too lax, which verify_walk has to refuse before a context exists.  entry < 0 clears; returns the previous value.
+// kWaitSkewResolved + k names entry k of the resolved walk's plan (the cherry message table's stream) instead.
+constexpr int kWaitSkewResolved = 1 << 20;
 int wait_plan_skew(int entry);
 
 // (cmx_host_model.cpp) returns empty string on success, otherwise the error message (status in *code)

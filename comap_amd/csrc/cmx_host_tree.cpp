@@ -160,11 +160,14 @@ void build_records(HostModel* hm) {
 }
 
 namespace {
-// ---- Recorder: the operator stream (matrix index in a class block, taxon or -1) and the workspace loads of a pass
-template <bool CT, bool CR>
+// ---- Recorder: the operator stream (matrix index in a class block, taxon or -1) and the workspace loads of a pass.
+// CM: the resolved protein walk with the cherry message table (cmx_walk.h, kCherryMsg) -- its own stream (msched_m) and
+// counts (HostModel::msg); a gather adds nothing to the stream and no counted event to the wait plan.
+template <bool CT, bool CR, bool CM = false>
 struct Recorder : RegisterOpsIgnored {
-  static constexpr bool kCherryTables = CT, kCherryRows = CR;
+  static constexpr bool kCherryTables = CT, kCherryRows = CR, kCherryMsg = CM;
   static constexpr bool kLdsSlot = !CT;   // the plain walk follows the plan's flags; the cherry-table walk has none (fused models)
+  static_assert(!(CT && CM), "one kind of cherry table per walk");
   HostModel* hm;
   const ClassBlock blk;
   long t = 0;
@@ -175,15 +178,16 @@ struct Recorder : RegisterOpsIgnored {
   // through HBM -- the device's OpState bookkeeping of the run-time count (vs += kVecInstrs), nothing for LDS-slot transfers
   std::vector<int> vm_events;
   explicit Recorder(HostModel* h) : hm(h), blk(h->block()) { store_time[0].assign(h->NIW, -1); store_time[1].assign(h->NIW, -1); }
+  std::vector<int>& stream() { return CM ? hm->msched_m : (CT ? hm->msched_r : hm->msched); }
   void op(int mat, int tx) {
-    std::vector<int>& ms = CT ? hm->msched_r : hm->msched;
+    std::vector<int>& ms = stream();
     vm_events.push_back((int)(ms.size() / 2));
     ms.push_back(mat); ms.push_back(tx); ++t;
   }
   void leaf_use(int leaf, int which) {
     const int tx = hm->taxon_of[leaf];
     op(blk.leaf(tx, which), tx);
-    (CT ? hm->n_leaf_ops_r : hm->n_leaf_ops)++;
+    (CM ? hm->msg.leaf_ops : (CT ? hm->n_leaf_ops_r : hm->n_leaf_ops))++;
   }
   // cherry-table ops: the table's matrix index, both taxa in the stream entry; counted with the leaf ops
   void cherry_use(int node, int l1, int l2, int table) {
@@ -194,17 +198,29 @@ struct Recorder : RegisterOpsIgnored {
   template <int D> void lset(int leaf, int which) { leaf_use(leaf, which); }
   template <int S, int D> void lmul(int leaf, int which) { leaf_use(leaf, which); }
   template <int S> void ldot(int leaf, int which, int) { leaf_use(leaf, which); }
-  template <int D> void cset(int node, int l1, int l2) { cherry_use(node, l1, l2, 0); }
+  template <int D> void cset(int node, int l1, int l2) {
+    if constexpr (CM) { ++t; hm->msg.gathers++; }
+    else cherry_use(node, l1, l2, 0);
+  }
   template <int S> void cdot(int node, int l1, int l2, int table, int) { cherry_use(node, l1, l2, table); }
-  template <int S, int D, bool TR> void mv(int node, int which) { op(blk.internal(hm->slot[node], which), -1); (CT ? hm->n_products_r : hm->n_products)++; }
-  void note_load(int arr, int slot) { loads.push_back({arr, slot, t++, store_time[arr][slot]}); if (!CT) hm->n_loads++; }
-  void note_store(int arr, int slot) { store_time[arr][slot] = t++; if (!CT) hm->n_stores++; }
+  template <int S, int D, bool TR> void mv(int node, int which) {
+    op(blk.internal(hm->slot[node], which), -1);
+    (CM ? hm->msg.products : (CT ? hm->n_products_r : hm->n_products))++;
+  }
+  void note_load(int arr, int slot) {
+    loads.push_back({arr, slot, t++, store_time[arr][slot]});
+    if (CM) hm->msg.loads++; else if (!CT) hm->n_loads++;
+  }
+  void note_store(int arr, int slot) {
+    store_time[arr][slot] = t++;
+    if (CM) hm->msg.stores++; else if (!CT) hm->n_stores++;
+  }
   template <int D> void load(int arr, int slot) { note_load(arr, slot); vm_events.push_back(-1); }
   template <int S> void store(int arr, int slot) { note_store(arr, slot); vm_events.push_back(-1); }
   // transfers the LDS slot serves: still loads and stores of the walk (n_loads, n_stores, ldsched), counted beside them
-  template <int D> void lload(int arr, int slot) { note_load(arr, slot); hm->n_lds_loads++; }
-  template <int S> void lstore(int arr, int slot) { note_store(arr, slot); hm->n_lds_stores++; }
-  template <int S> void lcopy(int, int) { ++t; hm->n_lds_copies++; }
+  template <int D> void lload(int arr, int slot) { note_load(arr, slot); (CM ? hm->msg.lds_loads : hm->n_lds_loads)++; }
+  template <int S> void lstore(int arr, int slot) { note_store(arr, slot); (CM ? hm->msg.lds_stores : hm->n_lds_stores)++; }
+  template <int S> void lcopy(int, int) { ++t; (CM ? hm->msg.lds_copies : hm->n_lds_copies)++; }
 };
 
 std::atomic<int> g_wait_skew{-1};   // wait_plan_skew
@@ -216,12 +232,17 @@ std::atomic<int> g_wait_skew{-1};   // wait_plan_skew
 // and the smallest distance is kept: a smaller immediate only waits for more.  Op 0 of a block's first pass finds its
 // operator behind the block prologue's drain and is served by any immediate.  Uncounted VMEM -- the epilogue between two
 // blocks, compiler spills -- only adds instructions in flight behind the one waited for.
-void plan_waits(HostModel* hm, const std::vector<int>& events) {
-  hm->wait_dist.clear();
-  hm->wait_imm.clear();
+// resolved: the plan of the walk with the cherry message table, over its own stream (a gather is not an event: its loads are
+// uncounted VMEM).
+void plan_waits(HostModel* hm, const std::vector<int>& events, bool resolved = false) {
+  const std::vector<int>& ms = resolved ? hm->msched_m : hm->msched;
+  std::vector<int>& wait_dist = resolved ? hm->wait_dist_m : hm->wait_dist;
+  std::vector<int>& wait_imm = resolved ? hm->wait_imm_m : hm->wait_imm;
+  wait_dist.clear();
+  wait_imm.clear();
   if (hm->S != 20 || hm->fuse != 1) return;
-  const int n = (int)(hm->msched.size() / 2), C = hm->C;   // (unfused: the device's classes are the model's)
-  auto leaf = [&](int i) { return hm->msched[2 * (size_t)i + 1] >= 0; };
+  const int n = (int)(ms.size() / 2), C = hm->C;   // (unfused: the device's classes are the model's)
+  auto leaf = [&](int i) { return ms[2 * (size_t)i + 1] >= 0; };
   std::vector<long> dist(n, -1);
   long vs = kPlanRows, cur = vs;   // the kernel's first request: op 0
   for (int block = 0; block < 2; ++block)
@@ -238,11 +259,15 @@ void plan_waits(HostModel* hm, const std::vector<int>& events) {
         cur = vs;
       }
   for (int i = 0; i < n; ++i) {
-    hm->wait_dist.push_back((int)dist[i]);
-    hm->wait_imm.push_back(planned_wait_imm((int)dist[i]));
+    wait_dist.push_back((int)dist[i]);
+    wait_imm.push_back(planned_wait_imm((int)dist[i]));
   }
-  const int skew = g_wait_skew.exchange(-1);
-  if (skew >= 0 && skew < n) hm->wait_imm[skew] += 1;
+  // the hook names an entry of one of the two plans; the plan it names spends it
+  const int held = g_wait_skew.load();
+  if (held >= 0 && (held >= kWaitSkewResolved) == resolved) {
+    const int skew = g_wait_skew.exchange(-1) - (resolved ? kWaitSkewResolved : 0);
+    if (skew >= 0 && skew < n) wait_imm[skew] += 1;
+  }
 }
 
 // the plain stream and the load schedule: the row-reusing cherry visit (cmx_walk.h, kCherryRows) for unfused models
@@ -258,9 +283,17 @@ void record_plain(HostModel* hm) {
   plan_waits(hm, rc.vm_events);
 }
 
+// the resolved protein walk with the cherry message table: its stream, counts and wait plan (records and load schedule are
+// the plain walk's: verify_walk holds it to them)
+void record_cherry_msg(HostModel* hm) {
+  Recorder<false, true, true> rc(hm);
+  walk_pass(rc, hm->NV, hm->K);
+  plan_waits(hm, rc.vm_events, true);
+}
+
 // ---- SlotProbe: the workspace transfers of a pass with the record that issues each, in the Recorder's program-order time
 struct SlotProbe : RegisterOpsIgnored {
-  static constexpr bool kCherryTables = false, kCherryRows = true, kLdsSlot = false;
+  static constexpr bool kCherryTables = false, kCherryRows = true, kCherryMsg = false, kLdsSlot = false;
   const HostModel* hm;
   long t = 0;
   int cur = -1;
@@ -340,10 +373,17 @@ void record_walk(HostModel* hm) {
   }
   if (hm->fuse == 1) record_plain<true>(hm);
   else record_plain<false>(hm);
+  hm->msched_m.clear();
+  hm->wait_dist_m.clear();
+  hm->wait_imm_m.clear();
+  hm->msg = HostModel::WalkCounts();
+  if (hm->n_cherry_msg > 0) record_cherry_msg(hm);
 }
 
-std::vector<PlanEntry> planned_stream(const HostModel& hm) {
-  const int n = (int)(hm.msched.size() / 2), C = hm.dC, copies = planned_stream_copies(C);
+std::vector<PlanEntry> planned_stream(const HostModel& hm, bool resolved) {
+  const std::vector<int>& ms = resolved ? hm.msched_m : hm.msched;
+  const std::vector<int>& wait_imm = resolved ? hm.wait_imm_m : hm.wait_imm;
+  const int n = (int)(ms.size() / 2), C = hm.dC, copies = planned_stream_copies(C);
   const long long unit = (long long)mat_unit(hm.dS) * 8, stride = (long long)hm.MC * unit;   // bytes of an operator, of a class block
   std::vector<PlanEntry> out;
   out.reserve((size_t)copies * (n + 2));
@@ -353,10 +393,10 @@ std::vector<PlanEntry> planned_stream(const HostModel& hm) {
     for (int j = 0; j < n + 2; ++j) {
       const int e = j < n ? j : j - n;
       PlanEntry p;
-      p.off = hm.msched[2 * (size_t)e] * unit + (j == n ? step * stride : 0);
-      p.tx = hm.msched[2 * (size_t)e + 1];
+      p.off = ms[2 * (size_t)e] * unit + (j == n ? step * stride : 0);
+      p.tx = ms[2 * (size_t)e + 1];
       if (p.tx >= 0 && j == n && last) p.tx = kPlanLeafNoSymbols;
-      p.w = hm.wait_imm[(size_t)((e + n - 1) % n)];   // the wait of the op in front: the one that holds this entry when it waits
+      p.w = wait_imm[(size_t)((e + n - 1) % n)];   // the wait of the op in front: the one that holds this entry when it waits
       out.push_back(p);
     }
   }
@@ -371,10 +411,13 @@ void build_walk_program(HostModel* hm) {
   if (hm->plain) return;
   build_records(hm);
   plan_lds_slot(hm);
-  // cherry tables only for the class-fused nucleotide layout (16 symbol pairs; 400 for proteins would not fit a stage buffer)
+  // staged cherry tables only for the class-fused nucleotide layout (16 symbol pairs; 400 for proteins would not fit a stage
+  // buffer: their message table is gathered from global memory, below)
   // (a fused model without a single cherry still gets the second stream -- identical to the first: the null's kernel
   // instantiation reads it unconditionally)
   hm->cherry_base = (S == 4 && C >= 4) ? hm->block().cherry_base() : 0;
+  // the cherry message table of the 64-site protein walk (cmx_layout.h): every inlined cherry, if the whole table is small enough
+  hm->n_cherry_msg = (hm->cherry_msg && cherry_msg_eligible(S, hm->fuse, C, hm->ncherry)) ? hm->ncherry : 0;
   if (hm->cherry_base == 0) hm->ncherry = 0;
   record_walk(hm);
 }

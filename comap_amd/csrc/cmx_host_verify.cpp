@@ -10,9 +10,11 @@ namespace {
 
 // ---- Numeric: the pass in plain doubles for one site, operators read from HostModel::MAT in their device layouts
 // and selected by the recorded stream exactly as the device selects them; every register starts as NaN.
-template <bool CT, bool CR>
+// CM: the resolved protein walk with the cherry message table -- cset computes what the device's table holds from the host
+// matrices, M_c = P_c (P_l1[:, s1] o P_l2[:, s2]), and consumes no stream entry.
+template <bool CT, bool CR, bool CM = false>
 struct Numeric {
-  static constexpr bool kCherryTables = CT, kCherryRows = CR;
+  static constexpr bool kCherryTables = CT, kCherryRows = CR, kCherryMsg = CM;
   static constexpr bool kLdsSlot = !CT;
   std::vector<double> lds;                 // the LDS slot: a fifth vector, NaN until written and again after each read
   int lds_arr = -1, lds_slot = -1;         // its occupant
@@ -45,7 +47,7 @@ struct Numeric {
   void fail(const std::string& m) { if (err.empty()) err = "tree-walk self-check failed: " + m; }
   void rec(int v, int (&r)[16]) const { copy_record(hm, v, r); }
   // the operator the stream stages for this op; `want` = what the walk asked for
-  const std::vector<int>& stream() const { return CT ? hm.msched_r : hm.msched; }
+  const std::vector<int>& stream() const { return CM ? hm.msched_m : (CT ? hm.msched_r : hm.msched); }
   int staged(int want_mat, int want_tx) {
     if (2 * mi + 1 >= stream().size()) { fail("more operator uses than the stream holds"); return -1; }
     const int mat = stream()[2 * mi], tx = stream()[2 * mi + 1];
@@ -68,6 +70,17 @@ struct Numeric {
     return blk[(size_t)mat * MU + (size_t)(4 * code[hm.taxon_of[l1]] + code[hm.taxon_of[l2]]) * leaf_row_stride(dS) + leaf_col(X, dS)];
   }
   template <int D> void cset(int node, int l1, int l2) {
+    if constexpr (CM) {
+      if (node < 0 || node >= hm.nn || hm.cherry_of[node] < 0 || hm.slot[node] < 0) return fail("message gather on a node without a table");
+      if (l1 < 0 || l1 >= hm.nn || l2 < 0 || l2 >= hm.nn || hm.taxon_of[l1] < 0 || hm.taxon_of[l2] < 0) return fail("message gather on a non-leaf");
+      const int ml1 = mats.leaf(hm.taxon_of[l1], OPER_P), ml2 = mats.leaf(hm.taxon_of[l2], OPER_P), mp = mats.internal(hm.slot[node], OPER_P);
+      std::vector<double> ab(dS), out(dS, 0.0);
+      for (int x = 0; x < dS; ++x) ab[x] = leafrow(ml1, l1, x) * leafrow(ml2, l2, x);
+      for (int r = 0; r < dS; ++r)
+        for (int c = 0; c < dS; ++c) out[r] += packed(mp, r, c) * ab[c];
+      R[D] = out;
+      return;
+    }
     const int mat = cherry_mat(node, l1, l2, 0);
     if (mat < 0) return;
     for (int x = 0; x < dS; ++x) R[D][x] = cherryrow(mat, l1, l2, x);
@@ -168,9 +181,9 @@ struct NumericResult {
   std::vector<double> cnt, Lg;
   std::vector<char> counted;
 };
-template <bool CT, bool CR>
+template <bool CT, bool CR, bool CM = false>
 NumericResult run_numeric(const HostModel& hm) {
-  Numeric<CT, CR> nm(hm);
+  Numeric<CT, CR, CM> nm(hm);
   walk_pass(nm, hm.NV, hm.K);
   return {nm.err, nm.mi, nm.fi, nm.code, nm.cnt, nm.Lg, nm.counted};
 }
@@ -182,31 +195,40 @@ NumericResult run_numeric(const HostModel& hm) {
 // buffer or symbol slot is "not landed" until a wait executes whose immediate is at most the number of counted
 // instructions issued behind the request (VMEM completes in order); an op that reads one that has not landed, or one
 // requested for another op, and a request into a buffer whose last reader has not run, are refused.  The kernel drains the
-// queue in front of a site block (map_sites_wave's prologue) and requests the symbols of the block's op 0 there.
+// CM: the resolved walk with the cherry message table.  A gather (cset) is kCherryMsgLoads VMEM instructions the plan does
+// not count: they enter the queue (`extra`) behind whatever is in flight, so a planned wait executed after them waits for
+// at least what it would without them -- positions in the queue are counted + uncounted instructions, immediates and the
+// plan's distances are counted ones.  A gather issues no request: the operator of the op behind it was requested by the op
+// in front of it and lies in front of the gather's loads.
+template <bool CM>
 struct WaitModel : RegisterOpsIgnored {
-  static constexpr bool kCherryTables = false, kCherryRows = true, kLdsSlot = true;
+  static constexpr bool kCherryTables = false, kCherryRows = true, kCherryMsg = CM, kLdsSlot = true;
   struct Buf {
-    long last = 0, end = 0;   // the request's last instruction; instructions issued when the whole request (symbols too) was out
+    long last = 0, end = 0;   // the request's last instruction (queue position); counted instructions issued when the whole request (symbols too) was out
     long op = -1;             // the dynamic op it was requested for
     bool used = true;         // ... has read it
   };
   const HostModel& hm;
+  const std::vector<int>& ms;        // the walk's stream
+  const std::vector<int>& wait_imm;  // ... and its plan
   const int n;                // ops of a pass
-  long issued = kPlanRows, landed = 0;   // counted instructions so far; instructions 1 .. landed have completed
+  long issued = kPlanRows, landed = 0;   // counted instructions so far; queue positions 1 .. landed have completed
+  long extra = 0;             // uncounted instructions so far (gathers)
   Buf stage[2], sym[2];
   int par = 0, mi = 0;
   long dyn = 0;               // ops executed so far, over all passes
   bool last_of_block = false;
   std::vector<long> mind;     // smallest modelled distance of each entry
   std::string err;
-  explicit WaitModel(const HostModel& h) : hm(h), n((int)(h.msched.size() / 2)), mind(n, -1) {
+  explicit WaitModel(const HostModel& h)
+      : hm(h), ms(CM ? h.msched_m : h.msched), wait_imm(CM ? h.wait_imm_m : h.wait_imm), n((int)(ms.size() / 2)), mind(n, -1) {
     stage[0] = {kPlanRows, kPlanRows, 0, false};   // the kernel's first request: op 0
   }
   void fail(const std::string& m) { if (err.empty()) err = "wait plan refused: " + m; }
-  bool leaf_entry(int i) const { return hm.msched[2 * (size_t)i + 1] >= 0; }
+  bool leaf_entry(int i) const { return ms[2 * (size_t)i + 1] >= 0; }
   void rec(int v, int (&r)[16]) const { copy_record(hm, v, r); }
   void begin_block() {
-    landed = issued;   // the prologue's drain
+    landed = issued + extra;   // the prologue's drain
     if (leaf_entry(0)) sym[par] = {0, 0, dyn, false};   // ... and its request of op 0's symbols, drained as well
   }
   void begin_pass(bool last) { mi = 0; last_of_block = last; }
@@ -216,22 +238,22 @@ struct WaitModel : RegisterOpsIgnored {
     Buf& b = stage[par ^ 1];
     if (!b.used) return fail("op " + std::to_string(mi) + " requests into a stage buffer whose operator nobody has read");
     issued += kPlanRows;
-    b = {issued, issued, dyn + 1, false};
+    b = {issued + extra, issued, dyn + 1, false};
     if (leaf_entry(next) && (more || !last_of_block)) {
       Buf& s = sym[par ^ 1];
       if (!s.used) return fail("op " + std::to_string(mi) + " requests into a symbol slot nobody has read");
       issued += 1;
-      s = {issued, issued, dyn + 1, false};
+      s = {issued + extra, issued, dyn + 1, false};
       b.end = issued;
     }
   }
   void wait() {
-    if (mi >= n || (size_t)mi >= hm.wait_imm.size()) return fail("more ops than planned waits");
-    const int imm = hm.wait_imm[mi];
+    if (mi >= n || (size_t)mi >= wait_imm.size()) return fail("more ops than planned waits");
+    const int imm = wait_imm[mi];
     if (imm < 0 || imm > 63) return fail("entry " + std::to_string(mi) + ": " + std::to_string(imm) + " is no vmcnt value");
     if (!planned_wait_dispatchable(imm, leaf_entry(mi)))
       return fail("entry " + std::to_string(mi) + ": the device has no wait for vmcnt(" + std::to_string(imm) + ") at this kind of op");
-    landed = std::max(landed, issued - imm);
+    landed = std::max(landed, issued + extra - imm);
     const long d = issued - stage[par].end;
     if (dyn > 0 && (mind[mi] < 0 || d < mind[mi])) mind[mi] = d;   // (the wave's first op: behind the drain, nothing of a pass in front)
   }
@@ -239,8 +261,8 @@ struct WaitModel : RegisterOpsIgnored {
     auto check = [&](Buf& b, const char* what) {
       if (b.op != dyn) return fail("op " + std::to_string(mi) + " finds " + what + " requested for another op");
       if (b.last > landed)
-        return fail("op " + std::to_string(mi) + " reads " + what + " that has not landed: vmcnt(" + std::to_string(hm.wait_imm[mi]) + ") with " +
-                    std::to_string(issued - b.last) + " instructions issued behind it");
+        return fail("op " + std::to_string(mi) + " reads " + what + " that has not landed: vmcnt(" + std::to_string(wait_imm[mi]) + ") with " +
+                    std::to_string(issued + extra - b.last) + " instructions issued behind it");
       b.used = true;
     };
     check(stage[par], "a stage buffer");
@@ -257,12 +279,16 @@ struct WaitModel : RegisterOpsIgnored {
   template <int D> void lload(int, int) {}
   template <int S> void lstore(int, int) {}
   template <int S> void lcopy(int, int) {}
+  template <int D> void cset(int, int, int) { extra += kCherryMsgLoads; }
 };
 
 // whole: site blocks of all classes, as every launch but the class-split one walks them (the plan's distances are the
 // smallest of these instances: checked entry by entry); else one pass per block, the class-split launch
+template <bool CM>
 std::string check_wait_plan(const HostModel& hm, bool whole) {
-  WaitModel wm(hm);
+  WaitModel<CM> wm(hm);
+  const std::vector<int>& wait_dist = CM ? hm.wait_dist_m : hm.wait_dist;
+  const std::vector<int>& wait_imm = CM ? hm.wait_imm_m : hm.wait_imm;
   const int C = hm.dC, passes = whole ? C : 1, blocks = whole ? 2 : 2 * std::max(C, 2);
   for (int b = 0; b < blocks; ++b) {
     wm.begin_block();
@@ -275,10 +301,10 @@ std::string check_wait_plan(const HostModel& hm, bool whole) {
   }
   if (!whole) return std::string();
   for (int i = 0; i < wm.n; ++i) {
-    if (hm.wait_dist[i] != wm.mind[i])
-      return "wait plan refused: entry " + std::to_string(i) + " is planned at distance " + std::to_string(hm.wait_dist[i]) + ", the queue model counts " + std::to_string(wm.mind[i]);
-    if (hm.wait_imm[i] != planned_wait_imm((int)wm.mind[i]))
-      return "wait plan refused: entry " + std::to_string(i) + " waits with vmcnt(" + std::to_string(hm.wait_imm[i]) + "), distance " + std::to_string(wm.mind[i]) +
+    if (wait_dist[i] != wm.mind[i])
+      return "wait plan refused: entry " + std::to_string(i) + " is planned at distance " + std::to_string(wait_dist[i]) + ", the queue model counts " + std::to_string(wm.mind[i]);
+    if (wait_imm[i] != planned_wait_imm((int)wm.mind[i]))
+      return "wait plan refused: entry " + std::to_string(i) + " waits with vmcnt(" + std::to_string(wait_imm[i]) + "), distance " + std::to_string(wm.mind[i]) +
              " takes vmcnt(" + std::to_string(planned_wait_imm((int)wm.mind[i])) + ")";
   }
   return std::string();
@@ -313,9 +339,26 @@ std::string verify_walk(const HostModel& hm) {
   if (S == 20 && F == 1) {
     if (2 * hm.wait_imm.size() != hm.msched.size() || hm.wait_dist.size() != hm.wait_imm.size()) return "wait plan refused: not one wait per operator use";
     for (const bool whole : {true, false}) {
-      const std::string bad = check_wait_plan(hm, whole);
+      const std::string bad = check_wait_plan<false>(hm, whole);
       if (!bad.empty()) return bad;
     }
+  }
+  // the resolved walk with the cherry message table: same site, same reference, the plain walk's loads, stores and LDS slot
+  NumericResult nr;
+  const bool msg = !hm.msched_m.empty();
+  const char* const rtag = " (resolved walk with the cherry message table)";
+  if (msg) {
+    nr = run_numeric<false, true, true>(hm);
+    if (!nr.err.empty()) return nr.err + rtag;
+    if (2 * nr.mi != hm.msched_m.size()) return std::string("tree-walk self-check failed: unused operators in the stream") + rtag;
+    if (nr.fi != hm.ldsched.size()) return std::string("tree-walk self-check failed: other workspace loads than the plain walk's") + rtag;
+    if (hm.msg.loads != hm.n_loads || hm.msg.stores != hm.n_stores || hm.msg.lds_loads != hm.n_lds_loads || hm.msg.lds_stores != hm.n_lds_stores ||
+        hm.msg.lds_copies != hm.n_lds_copies)
+      return std::string("tree-walk self-check failed: other workspace transfers than the plain walk's") + rtag;
+    if (2 * hm.wait_imm_m.size() != hm.msched_m.size() || hm.wait_dist_m.size() != hm.wait_imm_m.size()) return std::string("wait plan refused: not one wait per operator use") + rtag;
+    // (whole site blocks only: the class-split launch maps observed alignments, which never take this walk)
+    const std::string bad = check_wait_plan<true>(hm, true);
+    if (!bad.empty()) return bad + rtag;
   }
   // the cherry-table walk: same site, same reference
   NumericResult nt;
@@ -364,6 +407,10 @@ std::string verify_walk(const HostModel& hm) {
   const int classes = std::min(F, hm.C);
   std::string bad = compare(nm, Lref, ref, classes, K, false);
   if (bad.empty() && tables) bad = compare(nt, Lref, ref, classes, K, true);
+  if (bad.empty() && msg) {
+    bad = compare(nr, Lref, ref, classes, K, false);
+    if (!bad.empty()) bad += rtag;
+  }
   return bad;
 }
 

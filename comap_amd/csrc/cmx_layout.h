@@ -129,6 +129,31 @@ constexpr int cherry_entry(int taxon1, int taxon2) { return kCherryFlag | taxon1
 constexpr int cherry_taxon1(int entry) { return entry & 0x7fff; }
 constexpr int cherry_taxon2(int entry) { return (entry >> 15) & 0x7fff; }
 
+// ---- Cherry message table of the 64-site protein walk on resolved alignments (cmx_walk.h, kCherryMsg).  Per
+// device class and inlined cherry 400 rows, row 20 s1 + s2 = the message M_c = P_c (P_l1[:, s1] o P_l2[:, s2]) of the
+// cherry whose leaves show the symbols s1 and s2, written by the walk's own code (cmx_map.hip: cherry_msg_kernel).  A row
+// is laid out for the lane that gathers it: quad q = lane >> 4 holds the states 4 sb + q, sb = 0 .. 4, consecutively in a
+// 48-byte slot (40 used) -- two 16-byte loads and one 8-byte load per site group, each naturally aligned.
+// Tables are ordered [cherry][class]; the device buffer starts with a node index of nn ints -- the cherry index of an inlined
+// cherry's node, the alignment row of a leaf, -1 elsewhere -- which the gather reads through the scalar cache (the walk's
+// records name tree nodes), padded to cherry_msg_header_bytes.
+constexpr int kCherryMsgPairs = 400, kCherryMsgQuadBytes = 48, kCherryMsgRowBytes = 4 * kCherryMsgQuadBytes;
+constexpr unsigned long kCherryMsgTableBytes = (unsigned long)kCherryMsgPairs * kCherryMsgRowBytes;   // one cherry, one class
+constexpr unsigned long cherry_msg_table_bytes(int C, int cherries) { return (unsigned long)C * cherries * kCherryMsgTableBytes; }
+constexpr unsigned long cherry_msg_header_bytes(int nn) { return ((unsigned long)nn * 4 + 255) / 256 * 256; }
+// where state x of row `pair` sits in a table, in doubles
+constexpr int cherry_msg_offset(int pair, int x) { return (pair * kCherryMsgRowBytes + (x % 4) * kCherryMsgQuadBytes) / 8 + x / 4; }
+// The largest table a model gets (C x cherries x 76 800 bytes); a model over it walks the plain stream.  The gathers are
+// served from L2 and the Infinity Cache (256 MiB): an eighth of the latter leaves the operators, the workspace traffic and
+// the alignments their room.  Only the benchmark's size, 5.5 MB, has been measured.
+constexpr unsigned long kCherryMsgMaxBytes = 32ul << 20;
+// VMEM instructions of one gather: the two symbols, then per site group two 16-byte loads and one 8-byte load.  None is
+// counted in the wait plan (an uncounted instruction behind a request only makes the planned wait stricter).
+constexpr int kCherryMsgLoads = 2 + 4 * 3;
+constexpr bool cherry_msg_eligible(int S, int fuse, int C, int cherries) {
+  return S == 20 && fuse == 1 && cherries > 0 && cherry_msg_table_bytes(C, cherries) <= kCherryMsgMaxBytes;
+}
+
 // ---- Wait plan of the 64-site protein walk (20 states, unfused; cmx_host_tree.cpp: plan_waits).  An op waits
 // for its operator with s_waitcnt vmcnt(n), n = the counted VMEM instructions the walk issues between the operator's request
 // and that wait: kPlanRows DMA rows of the next request (+ 1 with symbols) and kPlanVec per workspace vector moved through HBM

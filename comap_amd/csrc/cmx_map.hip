@@ -32,6 +32,8 @@
 //   simulate_blocked_kernel at full occupancy.
 //   MODE == kModeNullPatterns: the same walk over the null's distinct columns, one lane per pattern; the pairs are scored
 //   by null_pattern_pairs_kernel (cmx_null_patterns.hip).
+//   MODE == kModeNullMsg / kModeNullPatternsMsg: the two null modes of a 20-state model with a cherry message table
+//   (cmx_layout.h; filled by cherry_msg_kernel below): an inlined cherry's message is gathered from the table.
 #include "cmx_device.h"
 #include "cmx_lanes.h"
 #include "cmx_pairstat.h"
@@ -493,7 +495,8 @@ __device__ __forceinline__ void plan_entry(cmx_cplan p, OpState& os) {
 // same walk on the host and checked numerically there -- says where the operators are.
 // RESOLVED: every symbol of the alignment is a state (the null's simulated or supplied alignments): leaf ops then stage the
 // S0 state rows of the transposed operator only, not its ambiguity rows
-template <int S, int FUSE, int NG, bool RESOLVED, class POL>
+// MSG: the walk gathers an inlined cherry's message from the cherry message table (cmx_walk.h: kCherryMsg)
+template <int S, int FUSE, int NG, bool RESOLVED, class POL, bool MSG = false>
 struct DevWalk {
   static constexpr int VL = S / 4 * NG, kSites = 16 * NG;
   static constexpr bool DIAG = FUSE > 1 && S / FUSE == 4;
@@ -503,6 +506,8 @@ struct DevWalk {
   static constexpr bool kCherryTables = RESOLVED && DIAG;   // cmx_walk.h: cset / cdot instead of a cherry's operator ops
   static constexpr bool kCherryRows = FUSE == 1;            // cmx_walk.h: a cherry's outside visit keeps its leaf rows in registers
   static constexpr bool kPlanned = kMfma16<S, NG, DIAG>;    // the planned stream and its waits (OpState)
+  static constexpr bool kCherryMsg = MSG;                   // cmx_walk.h: a cherry's message is a gathered table row
+  static_assert(!MSG || (kPlanned && RESOLVED && !kCherryTables && S == 20), "the message table serves the 64-site protein walk on resolved alignments");
   // cmx_walk.h: one workspace vector per wave stays in LDS where the records say so (the 64-site protein walk in all its
   // modes; the 16-site shape shares the records and ignores the bits, like every backend without a slot)
   static constexpr bool kLdsSlot = map_lds_slot(S, FUSE, NG);
@@ -519,6 +524,9 @@ struct DevWalk {
   double *wsM, *wsU, *pcnt;
   const uint8_t* gcodes;
   size_t gstride;
+  const uint8_t* cmsg;         // kCherryMsg: the message tables of the pass's class, table of cherry i at i * C * kCherryMsgTableBytes (wave-uniform)
+  cmx_cint cmsg_ref;           // kCherryMsg: the table's node index (cmx_layout.h)
+  size_t cmsg_stride;          // kCherryMsg: bytes from a cherry's table to the next cherry's
   uint8_t *stage, *cslot, *cslot2, *vslot;
   uint32_t lds_stage, lds_codes, lds_codes2;
   int lane, c, c_end;
@@ -808,7 +816,37 @@ struct DevWalk {
     const double tot = row_op<false, LEAF_DOT, SRC, SRC>();
     part_store(row, pc * tot);
   }
-  template <int D> __device__ __forceinline__ void cset(int, int, int) { (void)row_op<true, LEAF_SET, D, D>(); }
+  // kCherryMsg: row 20 s1 + s2 of the cherry's table straight into the destination register, which the walk has killed.  No
+  // stream entry, no request, no stage buffer: the lane loads the two symbols of its own site (plain loads: the alignments
+  // were written by earlier kernels), fetches the row indices of its four site groups from the lanes that hold those sites,
+  // and issues per group two 16-byte loads and one 8-byte load (cmx_layout.h: a row's quad slot).  All of it compiler-
+  // visible, so hipcc waits for it; none of it counted in the wait plan: the operator of the op behind was requested by the
+  // op in front and completes, in order, in front of these loads, and a planned wait that finds them in the queue only
+  // waits for more (cmx_host_verify.cpp: WaitModel models them so).
+  template <int D> __device__ __forceinline__ void cset(int node, int l1, int l2) {
+    if constexpr (MSG) {
+      const int ci = cmsg_ref[node], t1 = cmsg_ref[l1], t2 = cmsg_ref[l2];   // cherry index, alignment rows (scalar loads)
+      const int vl = vlane();
+      unsigned s1 = gcodes[(size_t)t1 * gstride], s2 = gcodes[(size_t)t2 * gstride];
+      s1 = s1 < 19u ? s1 : 19u;
+      s2 = s2 < 19u ? s2 : 19u;
+      const int row = (int)(20u * s1 + s2);
+      const uint8_t* quad = cmsg + (size_t)ci * cmsg_stride + (vl >> 4) * kCherryMsgQuadBytes;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const uint8_t* p = quad + (size_t)__shfl(row, 16 * g + (vl & 15)) * kCherryMsgRowBytes;
+        const d2 a = *reinterpret_cast<const d2*>(p), b = *reinterpret_cast<const d2*>(p + 16);
+        const double e = *reinterpret_cast<const double*>(p + 32);
+        reg<D>()[vr(0, g)] = a[0];
+        reg<D>()[vr(1, g)] = a[1];
+        reg<D>()[vr(2, g)] = b[0];
+        reg<D>()[vr(3, g)] = b[1];
+        reg<D>()[vr(4, g)] = e;
+      }
+    } else {
+      (void)row_op<true, LEAF_SET, D, D>();
+    }
+  }
   template <int SRC> __device__ __forceinline__ void cdot(int, int, int, int, int row) {
     const double tot = row_op<true, LEAF_DOT, SRC, SRC>();
     part_store(row, pc * tot);
@@ -930,15 +968,15 @@ struct DevWalk {
 // cnt[(b*K+k)*64 + lane] holds the final counts n(b, site, k) and the scalars are per lane; without (class-split
 // observed mode) only part[] and L_out = sum of p_c L_c over the processed classes are produced.
 // part: [C][B*K][64] per-class joint counts (written once each, summed at the end: no read-modify-write in the loop).
-template <int S, int FUSE, int NG, bool RESOLVED, class POL>
+template <int S, int FUSE, int NG, bool RESOLVED, class POL, bool MSG = false>
 __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restrict__ wsM, double* __restrict__ wsU,
                                                double* __restrict__ part, double* __restrict__ cnt, int lds_off,
                                                const uint8_t* __restrict__ gcodes, size_t gstride, int lane,
                                                OpState& os, double& L_out, double& pr_out, int& rc_out,
                                                double& norm_out, int c_begin, int c_end, int c_after, bool finalize) {
   const DevModel& m = a.m;
-  constexpr bool kTables = DevWalk<S, FUSE, NG, RESOLVED, POL>::kCherryTables;   // (the launcher guarantees m.msched_r then)
-  const ConstModel cm(m, kTables);
+  constexpr bool kTables = DevWalk<S, FUSE, NG, RESOLVED, POL, MSG>::kCherryTables;   // (the launcher guarantees m.msched_r then)
+  const ConstModel cm(m, kTables || MSG);   // (MSG: the resolved stream, likewise)
   constexpr int kSites = 16 * NG;      // sites per wave (NG site groups of 16; an S-vector is S / 4 * NG doubles per lane)
   // site of this lane inside the wave's block for per-site scalars and arrays: NG = 4: the lane itself; NG = 1: lanes
   // l, l ^ 16, l ^ 32 and l ^ 48 all carry site l & 15 and do the per-site work redundantly (identical values)
@@ -946,9 +984,9 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
   const int C = m.C, K = m.K;
   double Lsum = 0.0, prsum = 0.0, best = -1.0;
   int bestc = 0;
-  DevWalk<S, FUSE, NG, RESOLVED, POL> be(os, cm);
+  DevWalk<S, FUSE, NG, RESOLVED, POL, MSG> be(os, cm);
   be.pi = m.pi;
-  be.nmv = kTables ? m.nmv_r : m.nmv;
+  be.nmv = (kTables || MSG) ? m.nmv_r : m.nmv;
   be.wsM = wsM;
   be.wsU = wsU;
   be.gcodes = gcodes;
@@ -962,6 +1000,10 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
   be.lds_codes2 = lds_addr(be.cslot2);
   be.lane = lane;
   be.c_end = c_end;
+  if constexpr (MSG) {
+    be.cmsg_ref = (cmx_cint)reinterpret_cast<const int*>(a.cherry_msg);
+    be.cmsg_stride = (size_t)m.C * kCherryMsgTableBytes;
+  }
   {  // symbols of op 0 if it is a leaf op (the previous site block could not request them).  Everything this wave
      // wrote before (simulated symbols) is in L2 first; the request is not counted, so drain it here.
     const int tx0 = cm.msched[1];
@@ -978,7 +1020,13 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
   }
   for (int c = c_begin; c < c_end; ++c) {
     // operators of this class and of the class of the pass that follows (its first operator is requested by our last op)
-    if constexpr (DevWalk<S, FUSE, NG, RESOLVED, POL>::kPlanned) {
+    if constexpr (MSG) {
+      // the planned walk over the resolved stream, and the class's message tables
+      const bool last = c + 1 >= c_end;
+      be.op_base = reinterpret_cast<const uint8_t*>(m.MAT + (size_t)c * m.MC * MatStage<S>::UNIT);
+      be.sp = (cmx_cplan)a.plan_r + ((size_t)planned_stream_copy(C, last, last ? c_after - c : 1) * (size_t)(m.nmv_r + 2) + 2);
+      be.cmsg = a.cherry_msg + cherry_msg_header_bytes(m.nn) + (size_t)c * kCherryMsgTableBytes;
+    } else if constexpr (DevWalk<S, FUSE, NG, RESOLVED, POL>::kPlanned) {
       // the planned walk: the pass's class block, and the copy of the stream whose entries behind the last one lead to the
       // pass that follows (cmx_layout.h: planned_stream_copy) -- the wrap is settled here, no op knows about it
       const bool last = c + 1 >= c_end;
@@ -1094,14 +1142,16 @@ __device__ __forceinline__ size_t next_block(unsigned long long* queue, size_t s
   return (size_t)(((unsigned long long)hi << 32) | lo);
 }
 
-template <int S, int MODE, int FUSE, int NG = map_ng(S)>
+template <int S, int MODE_ARG, int FUSE, int NG = map_ng(S)>
 __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void map_kernel(const MapArgs a) {
+  constexpr int MODE = map_mode_base(MODE_ARG);     // what the kernel does; MSG: how its walk gets a cherry's message
+  constexpr bool MSG = map_mode_msg(MODE_ARG);
   constexpr int VL = S / 4 * NG, kSites = 16 * NG;
   using POL = StatePolicy<S, MODE, FUSE, NG>;
   const DevModel& m = a.m;
   // the null's alignments are fully resolved: class-fused nucleotide models walk them with the cherry tables' stream
   constexpr bool kTables = (MODE == kModeNull || MODE == kModeNullPatterns) && DevWalk<S, FUSE, NG, true, POL>::kCherryTables;
-  const ConstModel cm(m, kTables);
+  const ConstModel cm(m, kTables || MSG);
   const int lane = threadIdx.x & (kWave - 1);
   const int sidx = NG == 4 ? lane : (lane & 15);   // site of this lane in the wave's block
   // wave index through readfirstlane: the compiler cannot see that threadIdx.x >> 6 is wave-uniform and would keep every
@@ -1125,7 +1175,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
     mat_dma<S>(m.MAT + (size_t)c0 * m.MC * MatStage<S>::UNIT + cm.msched[0], cmx_smem + lds_off, lane);
   }
   if constexpr (kMfma16<S, NG, (FUSE > 1 && S / FUSE == 4)>) {   // the planned walk: entry 1, the same in every copy
-    plan_entry((cmx_cplan)m.plan + 1, os);
+    plan_entry((cmx_cplan)(MSG ? a.plan_r : m.plan) + 1, os);
   } else {
     os.vs = MatStage<S>::ROWS;
     os.cur_seq = os.vs;
@@ -1166,7 +1216,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
       // tile sb of the pattern table is this wave's count block: the class-sum epilogue writes the final counts there,
       // once, with its own row stride (lanes past npat write their clamped copy into the last tile's spare columns)
       double* tile = a.counts + sb * ((size_t)m.B * m.K * kSites);
-      map_sites_wave<S, FUSE, NG, true, POL>(a, wsD, wsU, part, tile, lds_off, a.supplied + rh * (size_t)m.T * a.rep_ram + j, a.rep_ram,
+      map_sites_wave<S, FUSE, NG, true, POL, MSG>(a, wsD, wsU, part, tile, lds_off, a.supplied + rh * (size_t)m.T * a.rep_ram + j, a.rep_ram,
                                         lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
       if (active) {
         a.post_rate[p] = pr;
@@ -1211,7 +1261,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
         gstride = a.rep_ram;
         double L, pr, nrm;
         int rc;
-        map_sites_wave<S, FUSE, NG, true, POL>(a, wsD, wsU, part, h ? cnt1 : cnt0, lds_off, gbase, gstride, lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
+        map_sites_wave<S, FUSE, NG, true, POL, MSG>(a, wsD, wsU, part, h ? cnt1 : cnt0, lds_off, gbase, gstride, lane, os, L, pr, rc, nrm, 0, m.C, 0, true);
         if (h == 0) { prmin = pr; nmin = nrm; rcmin = rc; }
         else { prmin = pr < prmin ? pr : prmin; nmin = nrm < nmin ? nrm : nmin; rcmin = rc < rcmin ? rc : rcmin; }
       }
@@ -1242,6 +1292,12 @@ static hipError_t launch_map_mode(int mode, const MapArgs& a, dim3 grid, dim3 bl
     case kModeObserved: return launch_map_as<S, kModeObserved, FUSE>(a, grid, block, lds, lim, stream);
     case kModeObservedSplit: return launch_map_as<S, kModeObservedSplit, FUSE>(a, grid, block, lds, lim, stream);
     case kModeNullPatterns: return launch_map_as<S, kModeNullPatterns, FUSE>(a, grid, block, lds, lim, stream);
+    case kModeNullMsg:
+      if constexpr (S == 20 && FUSE == 1) return launch_map_as<S, kModeNullMsg, FUSE>(a, grid, block, lds, lim, stream);
+      else return hipErrorInvalidValue;
+    case kModeNullPatternsMsg:
+      if constexpr (S == 20 && FUSE == 1) return launch_map_as<S, kModeNullPatternsMsg, FUSE>(a, grid, block, lds, lim, stream);
+      else return hipErrorInvalidValue;
     default: return launch_map_as<S, kModeNull, FUSE>(a, grid, block, lds, lim, stream);
   }
 }
@@ -1256,8 +1312,10 @@ hipError_t launch_map(const MapArgs& a_in, int mode, int grid_blocks, hipStream_
   if ((int)lds > lim) return hipErrorInvalidValue;
   // (the null instantiations of the class-fused layouts read the cherry-table walk's stream)
   if ((mode == kModeNull || mode == kModeNullPatterns) && a.m.fuse > 1 && a.m.msched_r == nullptr) return hipErrorInvalidValue;
+  // (... and those of a model with a cherry message table the resolved stream, its planned copy and the table)
+  if (map_mode_msg(mode) && (a.m.S != 20 || a.m.fuse != 1 || !a.m.msched_r || !a.plan_r || !a.cherry_msg)) return hipErrorInvalidValue;
   if (a.m.S == 20 && a.m.fuse == 1 && a.m.plan == nullptr) return hipErrorInvalidValue;   // the 64-site protein walk reads the planned stream
-  if (mode == kModeNullPatterns && (!a.rep_site || !a.npat || !a.counts || !a.post_rate || !a.rate_class || !a.norm)) return hipErrorInvalidValue;
+  if (map_mode_base(mode) == kModeNullPatterns && (!a.rep_site || !a.npat || !a.counts || !a.post_rate || !a.rate_class || !a.norm)) return hipErrorInvalidValue;
   // 16-site wave-tasks (one site group): small alignments, four times the waves
   if (split16)
     return launch_map_as<20, kModeObservedSplit, 1, 1>(a, grid, block, lds, lim, stream);
@@ -1358,6 +1416,52 @@ hipError_t launch_extend_leaf_rows(const DevModel& m, const uint32_t* d_masks, h
   const size_t total = (size_t)m.C * nleaf * A * m.S;
   hipLaunchKernelGGL(extend_leaf_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, m.MAT, m.C, m.MC,
                      ClassBlock{m.NI, m.K, m.T, 0}.first_leaf(), nleaf, m.S0, m.S, A, mat_unit(m.S), leaf_row_stride(m.S), d_masks);
+  return hipGetLastError();
+}
+
+// The cherry message table of a 20-state model (cmx_layout.h, cmx_walk.h: kCherryMsg), filled by the walk's own code so that
+// a gathered row is the bits the walk would compute.  One wave per (cherry, class, 64 symbol pairs): the pairs take the place
+// of the wave's 64 sites -- "site" j of block b shows the symbols (p / 20, p % 20), p = 64 b + j -- and the wave runs what
+// walk_cherry_message runs without a table: lset<3>(l1), lmul<3, 3>(l2), mv<3, 1, false>(node) on the three operators copied
+// from MAT into LDS, with the 64-site protein walk's leaf_apply and matvec_stage (the 16x16x4 path).  It stores R1 in the
+// row layout of the gather.  Pairs past 399 (the last block) repeat pair 399 and store nothing.
+constexpr int kCherryMsgBlocks = (kCherryMsgPairs + kWave - 1) / kWave;
+__global__ __launch_bounds__(kWave) void cherry_msg_kernel(const double* __restrict__ MAT, int C, int MC, const int* __restrict__ ops,
+                                                          uint8_t* __restrict__ table) {
+  constexpr int S = 20, NG = 4, VL = S / 4 * NG, OPB = MatStage<S>::BYTES;
+  __shared__ __attribute__((aligned(16))) uint8_t smem[3 * OPB + 2 * kCodeSlotBytes];
+  const int lane = threadIdx.x, blk = blockIdx.x, c = blockIdx.y, ci = blockIdx.z;
+  for (int o = 0; o < 3; ++o) {   // P_l1^T, P_l2^T (leaf operators), P_c (packed): 16-byte pieces
+    const d2* src = reinterpret_cast<const d2*>(MAT + ((size_t)c * MC + ops[4 * ci + o]) * MatStage<S>::UNIT);
+    d2* dst = reinterpret_cast<d2*>(smem + o * OPB);
+    for (int i = lane; i < OPB / 16; i += kWave) dst[i] = src[i];
+  }
+  const int pair = blk * kWave + lane, pc = pair < kCherryMsgPairs ? pair : kCherryMsgPairs - 1;
+  uint32_t* slot1 = reinterpret_cast<uint32_t*>(smem + 3 * OPB);   // one dword per site, as a code slot of the walk
+  uint32_t* slot2 = slot1 + kWave;
+  slot1[lane] = (uint32_t)(pc / S);
+  slot2[lane] = (uint32_t)(pc % S);
+  __syncthreads();
+  double R1[VL], R3[VL];
+  (void)leaf_apply<S, LEAF_SET, NG, false>(smem, reinterpret_cast<const uint8_t*>(slot1) + 4 * (lane & 15), lane, R3, R3);
+  (void)leaf_apply<S, LEAF_MUL, NG, false>(smem + OPB, reinterpret_cast<const uint8_t*>(slot2) + 4 * (lane & 15), lane, R3, R3);
+  NoRequest req;
+  matvec_stage<S, false, NG, false>(smem + 2 * OPB, lane, R3, R1, req);
+  uint8_t* tab = table + ((size_t)ci * C + c) * kCherryMsgTableBytes + (lane >> 4) * kCherryMsgQuadBytes;
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int p = blk * kWave + 16 * g + (lane & 15);   // the pair whose states 4 sb + (lane >> 4) this lane holds in group g
+    if (p < kCherryMsgPairs) {
+      double* q = reinterpret_cast<double*>(tab + (size_t)p * kCherryMsgRowBytes);
+#pragma unroll
+      for (int sb = 0; sb < S / 4; ++sb) q[sb] = R1[vreg<S, NG, false>(sb, g)];
+    }
+  }
+}
+
+hipError_t launch_cherry_msg(const DevModel& m, const int* d_ops, int cherries, uint8_t* d_table, hipStream_t stream) {
+  if (m.S != 20 || m.fuse != 1 || cherries <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cherry_msg_kernel, dim3(kCherryMsgBlocks, m.C, cherries), dim3(kWave), 0, stream, m.MAT, m.C, m.MC, d_ops, d_table);
   return hipGetLastError();
 }
 

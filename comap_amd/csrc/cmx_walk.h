@@ -75,9 +75,13 @@ enum { OPER_P = -1 };         // which operator of a branch: OPER_P = transition
 //   message still occupies R1), instead of 2 + 4 K.  Every product and every sum keeps its operands (IEEE multiplication
 //   commutes; dot3 and ldot both compute fma((W o A), Bv, sum) over the same state order), so the counts are the same bits.
 //   Class-fused nucleotide models keep the plain visit: their null runs on the cherry tables.
+//   static constexpr bool kCherryMsg  (the 64-site protein walk on resolved alignments, where the model has a cherry message
+//   table, cmx_layout.h): cset<D>(node, l1, l2) takes the place of the 2 leaf ops and the product of a cherry's MESSAGE, in
+//   the inside pass and where the outside pass rebuilds it.  The table holds what those three ops compute, so D is the same
+//   bits.  The cherry's outside visit is untouched (kCherryRows): a count taken from a table row would round differently.
 template <class BE>
 CMX_HD void walk_cherry_message(BE& be, int node, int l1, int l2) {   // M of an inlined cherry -> R1, through R3
-  if constexpr (BE::kCherryTables) {
+  if constexpr (BE::kCherryTables || BE::kCherryMsg) {
     be.template kill<1>();
     be.template cset<1>(node, l1, l2);
     return;
@@ -216,7 +220,7 @@ CMX_HD void walk_pass(BE& be, int NV, int K) {
         } else {
           be.template load<0>(WS_M, r[REC_A + CH_SLOT]);
         }
-      } else if constexpr (BE::kCherryTables) {
+      } else if constexpr (BE::kCherryTables || BE::kCherryMsg) {
         be.template cset<0>(r[REC_A + CH_NODE], r[REC_A + CH_L1], r[REC_A + CH_L2]);
       } else {
         be.template lset<3>(r[REC_A + CH_L1], OPER_P);

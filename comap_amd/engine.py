@@ -60,6 +60,7 @@ EXPORTS = [
     "cmx_intra_compact_range_dev", "cmx_intra_gram_prefetch_dev", "cmx_expand_compact_rows", "cmx_vector_matrix",
     "cmx_scratch_check", "cmx_debug_lds_slot", "cmx_debug_map_queue", "cmx_debug_map_grid", "cmx_debug_scratch_guard", "cmx_debug_scratch_guard_failures", "cmx_debug_scratch_shrink",
     "cmx_set_null_patterns", "cmx_null_pattern_count", "cmx_debug_null_hash_bits", "cmx_debug_wait_plan", "cmx_debug_wait_skew", "cmx_debug_map_small_blocks", "cmx_debug_sim_sites", "cmx_debug_sim_tables",
+    "cmx_debug_cherry_msg", "cmx_get_cherry_msg_info", "cmx_debug_cherry_msg_walk", "cmx_debug_cherry_msg_table",
 ]
 # clustering.distance / clustering.method options of the reference (CoMap/CoMap.cpp:402-428, :460-472)
 DIST_CORRELATION, DIST_COMPENSATION, DIST_EUCLIDIAN = range(3)
@@ -83,6 +84,18 @@ def lds_slot(on=None):
     walk's LDS slot (None = query); returns the previous state.  Off = every workspace vector goes through HBM."""
     lib = load_library()
     return bool(lib.cmx_debug_lds_slot(ctypes.c_int(-1 if on is None else int(bool(on)))))
+
+
+def cherry_msg(on=None):
+    """cmx_debug_cherry_msg (include/comap_mi355x.h): whether engines (and debug_cherry_msg_walk) created from now on build
+    the cherry message table of 20-state models, from which the null's mapping walk gathers the messages of inlined cherries
+    (None = query); returns the previous state.  Off = the null walks the plain stream; the same bits either way."""
+    lib = load_library()
+    return bool(lib.cmx_debug_cherry_msg(ctypes.c_int(-1 if on is None else int(bool(on)))))
+
+
+_CHERRY_MSG_STATS = ("tables", "table_bytes", "products", "leaf_ops", "gathers", "loads", "stores", "lds_loads", "lds_stores",
+                     "lds_copies", "max_bytes")
 
 
 def map_queue(on=None):
@@ -342,6 +355,36 @@ def debug_wait_plan(parent, blen, leaf_of_taxon, Q, pi, rates, probs, Bk=None):
     return dict(distance=dist[: n.value].copy(), immediate=imm[: n.value].copy())
 
 
+def debug_cherry_msg_walk(parent, blen, leaf_of_taxon, Q, pi, rates, probs, Bk=None):
+    """cmx_debug_cherry_msg_walk (no GPU): the walk of fully resolved alignments (the null's) of a 20-state model with the
+    cherry message table -> dict(tables, table_bytes, products, leaf_ops, gathers, loads, stores, lds_loads, lds_stores,
+    lds_copies, max_bytes, msched[nops, 2], distance[nops], immediate[nops]); counts are per rate-class pass.  tables = 0: the
+    model has no table, the counts are the plain walk's and the arrays are empty.  The call fails if the engine's numerical
+    self-check of either walk, or its queue model of either wait plan, does."""
+    lib = load_library()
+    keep = [np.ascontiguousarray(parent, dtype=np.int32), _f64(blen), np.ascontiguousarray(leaf_of_taxon, dtype=np.int32),
+            _f64(Q), _f64(pi), _f64(rates), _f64(probs), None if Bk is None else _f64(Bk)]
+    p, bl, lot, Qa, pia, ra, pr, Bka = keep
+    S, C = len(pia), len(ra)
+    K = 1 if Bka is None else Bka.reshape(-1, S, S).shape[0]
+    model = _Model(S, C, K, _vp(Qa), _vp(pia), _vp(ra), _vp(pr), _vp(Bka), 0, 1, _vp(None))
+    tree = _Tree(len(p), _vp(p), _vp(bl), len(lot), _vp(lot))
+    cap = 64 * len(p) * max(K, 1) + 64
+    ms, dist, imm = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+    stats = np.zeros(12, dtype=np.uint64)
+    n = ctypes.c_size_t(0)
+    st = lib.cmx_debug_cherry_msg_walk(ctypes.byref(model), ctypes.byref(tree), _vp(stats), _vp(ms), _sz(cap), ctypes.byref(n),
+                                       _vp(dist), _vp(imm))
+    if st != 0:
+        raise CmxError(st, lib.cmx_last_error(None).decode())
+    out = {k: int(v) for k, v in zip(_CHERRY_MSG_STATS, stats)}
+    out.update(msched=ms[: n.value].reshape(-1, 2).copy(), distance=dist[: n.value // 2].copy(), immediate=imm[: n.value // 2].copy())
+    return out
+
+
+WAIT_SKEW_RESOLVED = 1 << 20     # wait_skew(WAIT_SKEW_RESOLVED + k): entry k of the resolved walk's plan (debug_cherry_msg_walk)
+
+
 def debug_sim_tables(parent, blen, leaf_of_taxon, Q, pi, rates, probs):
     """cmx_debug_sim_tables (no GPU): the simulator's tables -> dict(cum[C, nn, S, S], guide[C, nn, S, 32], row = R, the
     thresholds of a row (cmx_layout.h: sim_thr_row), thresholds[nn, C, S, R] uint32 and block_guide[nn, C, S, 32] -- the
@@ -546,6 +589,22 @@ class Engine:
         """cmx_set_null_patterns: the fused null maps each distinct simulated column once (True), every site of every pair
         (False), or decides by model (None, the default: 20-state models).  The same results either way."""
         self._check(self._lib.cmx_set_null_patterns(self._ctx, -1 if on is None else int(bool(on))))
+
+    def cherry_msg_info(self):
+        """cmx_get_cherry_msg_info: the walk of resolved alignments (the null's) with this engine's cherry message table ->
+        dict(tables, table_bytes, products, leaf_ops, gathers, loads, stores, lds_loads, lds_stores, lds_copies, max_bytes),
+        counts per rate-class pass; tables = 0: no table, the counts are the plain walk's"""
+        stats = np.zeros(12, dtype=np.uint64)
+        self._check(self._lib.cmx_get_cherry_msg_info(self._ctx, _vp(stats)))
+        return {k: int(v) for k, v in zip(_CHERRY_MSG_STATS, stats)}
+
+    def cherry_msg_table(self):
+        """cmx_debug_cherry_msg_table: the device's cherry message table -> (table[C, cherries, 400, 20] in state order, row
+        20 s1 + s2; cherries[cherries, 3] = tree nodes (cherry, leaf 1, leaf 2)); fails for an engine without a table"""
+        n = self.cherry_msg_info()["tables"]
+        table, nodes = np.zeros((self.C, max(n, 1), 400, 20)), np.zeros((max(n, 1), 3), dtype=np.int32)
+        self._check(self._lib.cmx_debug_cherry_msg_table(self._ctx, _vp(table), _sz(table.size if n else 0), _vp(nodes)))
+        return table, nodes
 
     def null_pattern_count(self):
         """columns the last null of this engine mapped (its distinct patterns when it deduplicated); synchronises"""

@@ -165,6 +165,28 @@ cmx_status cmx_debug_walk(const cmx_model* model, const cmx_tree* tree, int32_t*
 cmx_status cmx_debug_wait_plan(const cmx_model* model, const cmx_tree* tree, int32_t* distance, int32_t* immediate, size_t cap,
                                size_t* n);
 int cmx_debug_wait_skew(int entry);
+/* Cherry message table (20-state models; comap_amd/csrc/cmx_layout.h).  On fully resolved alignments -- the null's -- the
+ * message of an inlined cherry depends only on the rate class, the cherry and the two symbols its leaves show.  A context
+ * therefore builds, on the device and with the mapping walk's own code, a table of the 400 messages per class and inlined
+ * cherry, and the null's mapping walk gathers a row where it would rebuild the message from two leaf operators and a
+ * product: the same bits.  The cherry's outside visit (counts) is unchanged.  A model whose tables together exceed 32 MiB,
+ * or without an inlined cherry, gets none and walks as before.
+ * cmx_debug_cherry_msg(0) makes contexts (and the debug calls below) created from now on build no table (A/B runs, tests);
+ * on < 0: query only; returns the previous state.  Process-wide, host only, read when a context builds its model.
+ * cmx_get_cherry_msg_info / cmx_debug_cherry_msg_walk (host only, no GPU needed; the latter builds the model like
+ * cmx_debug_walk) report the walk of resolved alignments, stats[12]: [0] cherries with a table (0: that walk is the plain
+ * one and the figures below are its own), [1] bytes of all tables, [2] products and [3] leaf ops per pass, [4] gathers per
+ * pass, [5] workspace loads, [6] stores, [7] loads and [8] stores the LDS slot serves, [9] messages written to both, [10]
+ * the byte limit, [11] 0.  msched (or NULL; capacity m_cap int32, size in *m_n): that walk's operator stream as in
+ * cmx_debug_walk, empty without a table; distance / immediate (or NULL, m_cap / 2 entries): its wait plan as in
+ * cmx_debug_wait_plan.  cmx_debug_wait_skew(1048576 + k) raises entry k of THIS plan instead of the plain walk's.
+ * cmx_debug_cherry_msg_table: the device's table in state order, [nclasses][cherries][400][20] doubles (row 20 s1 + s2), and
+ * per cherry the tree nodes (cherry, leaf 1, leaf 2) in cherries[cherries][3] (or NULL); CMX_ERR_INVALID without a table. */
+int cmx_debug_cherry_msg(int on);
+cmx_status cmx_get_cherry_msg_info(const cmx_ctx* ctx, uint64_t* stats);
+cmx_status cmx_debug_cherry_msg_walk(const cmx_model* model, const cmx_tree* tree, uint64_t* stats, int32_t* msched, size_t m_cap,
+                                     size_t* m_n, int32_t* distance, int32_t* immediate);
+cmx_status cmx_debug_cherry_msg_table(cmx_ctx* ctx, double* table, size_t cap, int32_t* cherries);
 /* The mapping walk keeps short-lived workspace vectors in one LDS slot per wave where the tree allows it (20-state models;
  * results are the same bits either way).  cmx_debug_lds_slot(0) makes contexts created from now on plan the slot empty, i.e.
  * every vector goes through HBM (A/B runs, tests).  on < 0: query only; returns the previous state.  Process-wide, host only. */
