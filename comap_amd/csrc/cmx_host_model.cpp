@@ -245,6 +245,10 @@ void build_branch_matrices(const cmx_model* model, const std::vector<Eig>& eig, 
         // which needs no quotient: keep J itself there.  P > 0 gives P (J / P) = J whatever P's error, so no other entry
         // moves.
         if (!conditional && model->clamp_negative && !(P[i] > 0.0) && J[i] > 0.0) Ok[i] = J[i];
+        // A signed register keeps every finite quotient (P (J / P) = J for P < 0 too); only an entry of P that is exactly
+        // 0 (a 1e-100 branch: the off-diagonals of V Vinv are multiples of 1e-17, now and then 0) has none, and lost
+        // J(x, y) of either sign to the non-finite guard.
+        if (!conditional && !model->clamp_negative && P[i] == 0.0) Ok[i] = J[i];
       }
     }
   };

@@ -278,6 +278,8 @@ def map_sites(parent, blen, leaf_of_taxon, aln, masks, Q, pi, rates, probs, Bk_l
                         # an entry of P below its own rounding can be <= 0 and the guards then drop a positive J(x, y):
                         # the joint operator keeps it (oracle.c joint_count_matrix)
                         JJ = np.where(~(P[n, c] > 0) & (J > 0), J, JJ)
+                    elif method != "naive":     # a signed register: only P == 0 exactly has no finite quotient
+                        JJ = np.where(P[n, c] == 0, J, JJ)
                     tot += probs[c] * np.einsum("nx,xy,ny->n", U[c], JJ, D[n][c])
                 counts[:, n, k] = tot / L
             if ch[n]:

@@ -208,6 +208,9 @@ static void joint_count_matrix(int S, const double* J, const double* P, int nonn
     /* an entry of P below P's own rounding can come out <= 0; the guards then drop a positive J(x, y), which the joint
      * operator has without the quotient: keep it (P > 0 gives P (J / P) = J whatever P's error) */
     if (nonneg && !(P[i] > 0) && J[i] > 0) PN[i] = J[i];
+    /* a signed register keeps every finite quotient (P (J / P) = J for P < 0 too); only an entry of P that is exactly 0
+     * (a 1e-100 branch: V Vinv's off-diagonals are multiples of 1e-17, now and then 0) has none, and lost J(x, y) */
+    if (!nonneg && P[i] == 0) PN[i] = J[i];
   }
 }
 

@@ -146,8 +146,10 @@ def spectrum(gen):
     return _spectra[gen]
 
 
-def solve_case(name):
-    c = oe.Inputs(name)
+def solve_case(name, inputs=None, variants=None, store_P=True):
+    """inputs: the case's oe.Inputs (or an object like it; default oe.Inputs(name)); variants: whether the three other
+    nijt options are solved too (default oe.has_variants(name)); store_P: P of the cases with S <= 7"""
+    c = oe.Inputs(name) if inputs is None else inputs
     sp = spectrum(c.gen)
     aln, cls = c.draw()
     S, C, K = c.S, len(c.rates), len(sp.regs)
@@ -174,7 +176,7 @@ def solve_case(name):
     J = [[[sp.J(k, sp.regs[k], times[cc][b]) for k in range(K)] for b in range(B)] for cc in range(C)]
     pr = [mpf(float(p)) for p in c.probs]
     rt = [mpf(float(r)) for r in c.rates]
-    variants = oe.has_variants(name)
+    variants = oe.has_variants(name) if variants is None else variants
     if variants:        # the conditional counts N = J / P (0 where P = 0: no time), unsigned registers clamped at 0
         def cond(Jm, Pm):
             N_ = [[(Jm[x][y] / Pm[x][y] if Pm[x][y] != 0 else mpf(0)) for y in range(S)] for x in range(S)]
@@ -270,7 +272,7 @@ def solve_case(name):
                post_rate=prate, rate_class=rclass, class_clear=clear)
     if variants:
         out.update(var)
-    if S <= 7:
+    if S <= 7 and store_P:
         out["P"] = np.array([[to_np(P[cc][b]) for b in range(B)] for cc in range(C)])
     sp._P.clear()
     sp._J.clear()
@@ -287,6 +289,20 @@ def operators_of(gen):
     sp._P.clear()
     sp._J.clear()
     return out
+
+
+def write_npz(path, out):
+    """fixed zip timestamps: the same results give the same bytes"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k in sorted(out):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(out[k]), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            z.writestr(info, buf.getvalue())
+    print("wrote", path, os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":
@@ -309,15 +325,4 @@ if __name__ == "__main__":
         print(f"{name} ({time.time() - t0:.0f} s)", flush=True)
     if only:            # a trial run of some cases: nothing is written
         sys.exit(0)
-    path = os.path.join(ROOT, "tests", "golden", "operator_edges.npz")
-    # fixed zip timestamps: the same results give the same bytes
-    import zipfile
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
-        for k in sorted(out):
-            import io
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.ascontiguousarray(out[k]), allow_pickle=False)
-            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            z.writestr(info, buf.getvalue())
-    print("wrote", path, os.path.getsize(path), "bytes")
+    write_npz(os.path.join(ROOT, "tests", "golden", "operator_edges.npz"), out)

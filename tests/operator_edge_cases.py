@@ -12,6 +12,18 @@ Conventions are the engine's: nodes in post-order, root last, branch b = the bra
             2   the cherry (a, b): both at 0            6   terminal a and internal ab at 150 (past where the old form failed)
             3   the internal branch ab at 0             7   terminal c at 10000 (Bio++'s upper bound)
             4   every branch at 1e-12                   8   terminal b at 120 (the old form still finite: bits pinned)
+
+tests/golden/null_walk_edges.npz (make_null_walk_fixture.py; DEEP_CASES) adds a tree whose walk stores and loads workspace
+vectors, uses the LDS slot and a wait plan, and has cherries with more than the root above them:
+
+    tree "t12"  ((((a,b),c),d),((e,f),(g,h)),(i,(j,(k,l)))):  a 0, b 1, ab 2, c 3, abc 4, d 5, abcd 6, e 7, f 8, ef 9, g 10,
+                h 11, gh 12, efgh 13, i 14, j 15, k 16, l 17, kl 18, jkl 19, ijkl 20, root 21: a trifurcating root, four
+                inlined cherries, a ladder above (a, b) and one below i, a balanced quartet; ordinary lengths in [0.05, 0.4]
+
+    profile q1  the cherry (a, b): both at 0; terminal k at 1e-100
+            q2  the branch above (a, b) at 0; the branch above ((e,f),(g,h)) and terminal g at 150
+            q3  the six branches inside ((e,f),(g,h)) at 1e-12: counts of 1e-12 beside counts of order 1 in one vector
+            q4  terminal c at 10000; the branch above (k, l) at 120
 """
 import numpy as np
 
@@ -25,6 +37,12 @@ TREES = {
     "t5": (np.array([2, 2, 7, 5, 5, 7, 7, -1], dtype=np.int32), np.array([0.05, 0.12, 0.2, 0.3, 0.08, 0.15, 0.25, 0.0]),
            np.array([0, 1, 3, 4, 6], dtype=np.int32)),
 }
+_T12_BLEN = np.round(np.random.default_rng(1212).uniform(0.05, 0.4, size=22), 3)
+_T12_BLEN[-1] = 0.0
+TREES["t12"] = (np.array([2, 2, 4, 4, 6, 6, 21, 9, 9, 13, 12, 12, 13, 21, 20, 19, 18, 18, 19, 20, 21, -1], dtype=np.int32),
+                _T12_BLEN, np.array([0, 1, 3, 5, 7, 8, 10, 11, 14, 15, 16, 17], dtype=np.int32))
+DEEP_PROFILES = {"q1": {0: 0.0, 1: 0.0, 16: 1e-100}, "q2": {2: 0.0, 13: 150.0, 10: 150.0},
+                 "q3": {b: 1e-12 for b in range(7, 13)}, "q4": {3: 10000.0, 18: 120.0}}
 PROFILES = {1: {0: 0.0}, 2: {0: 0.0, 1: 0.0}, 3: {2: 0.0}, 4: "all 1e-12", 5: {3: 1e-100}, 6: {0: 150.0, 2: 150.0},
             7: {3: 10000.0}, 8: {1: 120.0}}
 # times at which the operators themselves are stored (S <= 20): the profiles' lengths and their products with the Gamma(4)
@@ -35,7 +53,7 @@ OPERATOR_TIMES_DEGENERATE = [0.0, 1e-12, 0.3, 120.0, 434.0, 28940.0]
 
 def blen_of(tree, profile):
     blen = TREES[tree][1].copy()
-    p = PROFILES[profile]
+    p = DEEP_PROFILES[profile] if profile in DEEP_PROFILES else PROFILES[profile]
     if isinstance(p, str):
         blen[:-1] = 1e-12
     else:
@@ -112,6 +130,20 @@ GRID = [
     ("s61", "g4", "t4", (1, 4, 6, 8)),
 ]
 CASES = [f"{g}-{r}-{t}-p{p}" for g, r, t, ps in GRID for p in ps]
+# the cases of null_walk_edges.npz: 45 columns each, no unknowns; counts, logL, post_rate, rate_class, class_clear only
+DEEP_NSITES = 45
+DEEP_GRID = [
+    ("protein", "g4", ("q1", "q2", "q3", "q4")),
+    ("protein", "ig5", ("q1", "q2")),
+    ("jc20", "g4", ("q2",)),
+    ("protein_k2", "g4", ("q2",)),
+    ("protein_signed", "g4", ("q1",)),
+    ("dna", "g4", ("q1", "q2", "q3", "q4")),
+    ("dna", "ig5", ("q1", "q2")),
+    ("dna", "c1", ("q1", "q2")),
+    ("jc4", "g4", ("q2",)),
+]
+DEEP_CASES = [f"{g}-{r}-t12-{q}" for g, r, qs in DEEP_GRID for q in qs]
 OPERATOR_MODELS = ["dna", "jc4", "jcp4", "protein", "protein_signed", "jc20", "jcp20", "s7"]
 
 
@@ -153,20 +185,23 @@ class Inputs:
 
     def __init__(self, name):
         gen, rs, tree, prof = name.split("-")
-        self.name, self.gen, self.rs, self.tree, self.profile = name, gen, rs, tree, int(prof[1:])
+        self.deep = prof in DEEP_PROFILES
+        self.name, self.gen, self.rs, self.tree, self.profile = name, gen, rs, tree, prof if self.deep else int(prof[1:])
         self.parent, _, self.lot = TREES[tree]
         self.blen = blen_of(tree, self.profile)
         self.Q, self.pi, self.Bk, self.clamp = generator(gen)
         self.rates, self.probs = rate_set(rs)
         self.S = len(self.pi)
-        self.seed = 9000 + CASES.index(name)
+        self.seed = 9500 + DEEP_CASES.index(name) if self.deep else 9000 + CASES.index(name)
 
     def oracle_model(self, method=oracle.METHOD_UNIF):
         return oracle.Model(self.parent, self.blen, self.lot, self.Q, self.pi, self.rates, self.probs, Bk=self.Bk,
                             method=method, nonneg=self.clamp)
 
     def draw(self):
-        """-> (aln [T, NSITES] with the unknowns set, the drawn classes)"""
+        """-> (aln [T, NSITES] with the unknowns set, the drawn classes); a DEEP_CASES case: DEEP_NSITES, no unknowns"""
+        if self.deep:
+            return oracle.simulate(self.oracle_model(), self.seed, 0, DEEP_NSITES)
         aln, cls = oracle.simulate(self.oracle_model(), self.seed, 0, NSITES)
         aln = aln.copy()
         aln[1, 5] = aln[2, 40] = aln[0, 66] = aln[len(self.lot) - 1, 69] = self.S

@@ -49,7 +49,7 @@ def operators(parent, blen, Q, pi, rates, Bk=None, nonneg=True):
         N = np.stack([npo.conditional_counts(J, Pt, nonneg) for J in Js])
         if joint is not None:       # P o N, keeping a positive J(x, y) where P is not positive (oracle.c joint_count_matrix)
             for k, J in enumerate(Js):
-                joint[k] = np.where(~(Pt > 0) & (J > 0), J, Pt * N[k]) if nonneg else Pt * N[k]
+                joint[k] = np.where(~(Pt > 0) & (J > 0), J, Pt * N[k]) if nonneg else np.where(Pt == 0, J, Pt * N[k])
         return N
 
     for b in range(nn):
