@@ -404,6 +404,53 @@ cmx_status cmx_intra_compact_range_dev(cmx_ctx* ctx, int kind, const double* par
   return CMX_OK;
 }
 
+// cmx_intra_compact_range_dev with the window index of the context (cmx_window_null_dev) in the place of the class table: the
+// same row blocks, Gram blocks (kept ones too) and positions; the record pass counts in the window of min(norm_i, norm_j)
+cmx_status cmx_intra_window_range_dev(cmx_ctx* ctx, int kind, const double* params, const double* d_counts, size_t n, size_t ldc,
+                                      const double* d_norm, int lower, size_t row_begin, size_t row_end, cmx_pair_window* d_out,
+                                      size_t capacity, void* stream) {
+  RowRange r{kind, params, d_counts, n, ldc, d_norm, nullptr, nullptr, 0, 0, row_begin, row_end};
+  CMX_TRY(row_range_check(ctx, "cmx_intra_window_range", r, !(capacity && !d_out)));
+  CMX_TRY(need_window(ctx, "cmx_intra_window_range"));
+  hipStream_t st = (hipStream_t)stream;
+  if (row_begin == row_end) return CMX_OK;
+  const cmx_ctx::GramKept gk0 = ctx->gram_kept;
+  ctx->gram_kept.valid = false;
+  const double* kept = gk0.valid && gk0.kind == kind && gk0.counts == d_counts && gk0.n == n && gk0.ldc == ldc && gk0.row_begin == row_begin &&
+                               gk0.row_end == row_end ? gk0.stat : nullptr;
+  CMX_TRY(row_range_prepare(ctx, r, kept, st));
+  uint32_t *lo, *hi;
+  CMX_TRY(scratch(ctx, "win_site_lo", n, &lo));
+  CMX_TRY(scratch(ctx, "win_site_hi", n, &hi));
+  HIP_TRY(ctx, launch_window_site_bounds(ctx->window.ix, d_norm, n, lo, hi, st));
+  double* blk_stat = nullptr;
+  if (!kept) CMX_TRY(scratch(ctx, "blk_stat", r.RB * n, &blk_stat));
+  for (size_t i0 = row_begin; i0 < row_end; i0 += r.RB) {
+    const size_t rb = std::min(r.RB, row_end - i0);
+    if (!kept) CMX_TRY(pair_block(ctx, r.sk, r.x, i0, rb, r.x, kPairUpperRows, blk_stat, n, st));
+    HIP_TRY(ctx, launch_pair_window(kept ? kept + (i0 - row_begin) * n : blk_stat, n, n, d_norm, ctx->window.ix, lo, hi, lower, d_out, capacity, st,
+                                    i0, rb, row_begin));
+  }
+  return CMX_OK;
+}
+
+cmx_status cmx_window_pvalues_from_records(size_t n, size_t row_begin, size_t row_end, const double* norm, const cmx_pair_window* records,
+                                           size_t npairs, const cmx_window_params* params, double* pvalue) {
+  if (!norm || !params || row_begin > row_end || row_end > n || n > 0x7fffffffull || (npairs && (!records || !pvalue))) return CMX_ERR_INVALID;
+  if (npairs != (row_end - row_begin) * (n - 1) - (row_end * (row_end - 1) - row_begin * (row_begin - 1)) / 2) return CMX_ERR_INVALID;
+  const cmx_pair_window* c = records;
+  double* p = pvalue;
+  for (size_t i = row_begin; i < row_end; ++i)
+    for (size_t j = i + 1; j < n; ++j, ++c, ++p) {
+      // the same rule and the same one IEEE division as window_test_kernel on the device
+      const double m = norm[i] < norm[j] ? norm[i] : norm[j];
+      *p = __builtin_nan("");
+      if (m < params->conserved_nmin) *p = 1.0;
+      else if (m == m && c->nobs >= params->min_nobs && c->count != 0xffffffffu) *p = (double)(c->count + 1u) / (double)(c->nobs + 1u);
+    }
+  return CMX_OK;
+}
+
 cmx_status cmx_expand_compact_rows(size_t n, size_t row_begin, size_t row_end, const int32_t* rate_class, const double* post_rate,
                                    const double* norm, const cmx_pair_compact* compact, size_t npairs, cmx_pair_row* rows, int nthreads) {
   if (!rate_class || !post_rate || !norm || row_begin > row_end || row_end > n || n > 0x7fffffffull || (npairs && (!compact || !rows)))

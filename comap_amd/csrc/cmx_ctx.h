@@ -84,6 +84,8 @@ struct cmx_ctx {
   std::vector<long long> perm_dF_host;
   std::vector<uint8_t> perm_tab_host;
   PermTable perm_F, permw_F;
+  // cmx_window_null_dev: the index of the sliding-window p-values (scratch "win_*"), read by every later window call
+  struct WindowKept { bool built = false; WindowIndex ix{}; } window;
   // cmx_intra_gram_prefetch_dev: the Gram blocks kept for the next cmx_intra_compact_range_dev with the same arguments
   struct GramKept { bool valid = false; int kind = 0; const double* counts = nullptr; size_t n = 0, ldc = 0, row_begin = 0, row_end = 0; const double* stat = nullptr; } gram_kept;
   const double *va_P = nullptr, *va_N1 = nullptr, *va_NC = nullptr;   // their operators, uploaded at first use
@@ -137,6 +139,12 @@ inline cmx_status fail(cmx_ctx* ctx, cmx_status s, const std::string& msg) {
 inline cmx_status need_model(cmx_ctx* ctx) {
   if (!ctx) return CMX_ERR_INVALID;
   if (!ctx->has_model) return fail(ctx, CMX_ERR_INVALID, "this context was created without a model/tree");
+  return CMX_OK;
+}
+
+inline cmx_status need_window(cmx_ctx* ctx, const char* who) {
+  if (!ctx) return CMX_ERR_INVALID;
+  if (!ctx->window.built) return fail(ctx, CMX_ERR_INVALID, std::string(who) + ": no window index was built (cmx_window_null_dev comes first)");
   return CMX_OK;
 }
 

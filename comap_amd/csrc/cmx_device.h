@@ -469,4 +469,40 @@ size_t mica4_info_words(size_t n);
 size_t mica4_image_bytes(int Tp, size_t n2);
 hipError_t launch_mica4(int T, const MicaWork& wk, int intra, double* d_mi, double* d_hj, size_t ldo, hipStream_t stream);
 hipError_t launch_mica_dna4(int T, const MicaWork& wk, int intra, double* d_mi, double* d_hj, size_t ldo, hipStream_t stream);
+// (cmx_window.hip) The sliding-window conditional p-values of R/CoMapFunctions.R:168-215: the null as a wavelet
+// matrix.  All n null entries are indexed; the dropped ones (a NaN statistic or Nmin) sort behind the nkept kept ones in both
+// orders, so no query range or rank ever reaches them.
+struct WindowHead {          // on the device: what the build finds out about the null
+  uint32_t nkept, pad;
+  double ws;                 // (max nmin - min nmin) * window / 2 over the kept entries; 0 when there are none
+  double nmin_min, nmin_max; // NaN when there are none
+};
+struct WindowIndex {
+  const double* nmin;        // [n] the Nmin of the entries, ascending
+  const double* stat;        // [n] the statistics, ascending: position = rank
+  const uint2* levels;       // [L][units] per level {ones before the unit, the unit's 32 bits}: bit of an entry = bit L-1-l of its rank
+  const uint32_t* zeros;     // [L] zero bits of the level
+  const WindowHead* head;
+  uint32_t n, units;         // units = ceil(n / 32) + 1: a rank query at position n reads the last one
+  int L;                     // max(1, ceil(log2 n))
+};
+inline int window_levels(size_t n) { int L = 1; while (((size_t)1 << L) < n) ++L; return L; }
+inline size_t window_units(size_t n) { return (n + 31) / 32 + 1; }
+// the build's temporaries, all [n] but cnt / ones [units]; d_tmp == nullptr: only tmp_bytes (rocPRIM's) is set
+struct WindowBuild {
+  uint64_t *key_a, *key_b;
+  uint32_t *val_a, *val_b, *seq_a, *seq_b, *cnt, *ones;
+  void* tmp;
+  size_t tmp_bytes;
+};
+hipError_t launch_window_build(const double* d_null_stat, const double* d_null_nmin, size_t n, double window, WindowBuild& b, double* d_nmin,
+                               double* d_stat, uint2* d_levels, uint32_t* d_zeros, WindowHead* d_head, hipStream_t stream);
+hipError_t launch_window_test(const WindowIndex& ix, const double* d_stat, const double* d_nmin, size_t nq, const cmx_window_params& p,
+                              double* d_pvalue, uint32_t* d_count, uint32_t* d_nobs, hipStream_t stream);
+// per site the window of its norm as positions [lo, hi) of the index: the pair loop's m = min(norm_i, norm_j) is one of them
+hipError_t launch_window_site_bounds(const WindowIndex& ix, const double* d_norm, size_t n, uint32_t* d_lo, uint32_t* d_hi, hipStream_t stream);
+// the record pass of cmx_intra_window_range_dev: launch_pair_compact's rows, positions and arguments
+hipError_t launch_pair_window(const double* d_stat, size_t ldo, size_t n, const double* d_norm, const WindowIndex& ix, const uint32_t* d_lo,
+                              const uint32_t* d_hi, int lower, cmx_pair_window* d_out, size_t capacity, hipStream_t stream, size_t irow0,
+                              size_t nrows, size_t row_begin);
 }  // namespace cmx

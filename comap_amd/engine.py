@@ -58,6 +58,8 @@ EXPORTS = [
     "cmx_group_stats", "cmx_group_stats_dev", "cmx_candidate_groups", "cmx_debug_candidate_cursor",
     "cmx_hclust", "cmx_hclust_dev", "cmx_cluster_sites", "cmx_cluster_sites_dev", "cmx_cluster_null",
     "cmx_intra_compact_range_dev", "cmx_intra_gram_prefetch_dev", "cmx_expand_compact_rows", "cmx_vector_matrix",
+    "cmx_window_null_dev", "cmx_window_null_info", "cmx_window_test_dev", "cmx_window_test", "cmx_intra_window_range_dev",
+    "cmx_window_pvalues_from_records",
     "cmx_scratch_check", "cmx_debug_lds_slot", "cmx_debug_map_queue", "cmx_debug_map_grid", "cmx_debug_scratch_guard", "cmx_debug_scratch_guard_failures", "cmx_debug_scratch_shrink",
     "cmx_set_null_patterns", "cmx_null_pattern_count", "cmx_debug_null_hash_bits", "cmx_debug_wait_plan", "cmx_debug_wait_skew", "cmx_debug_map_small_blocks", "cmx_debug_sim_sites", "cmx_debug_sim_tables",
     "cmx_debug_cherry_msg", "cmx_get_cherry_msg_info", "cmx_debug_cherry_msg_walk", "cmx_debug_cherry_msg_table",
@@ -257,6 +259,29 @@ def expand_compact_rows(n, row_begin, row_end, rate_class, post_rate, norm, comp
         raise CmxError(st, "cmx_expand_compact_rows: bad arguments")
     return rows
 
+# cmx_pair_window: the unfiltered pair loop against the window index; count = 0xffffffff: the statistic is NaN
+PAIR_WINDOW = np.dtype([("stat", np.float64), ("count", np.uint32), ("nobs", np.uint32)])
+
+
+class WindowParams(ctypes.Structure):
+    """cmx_window_params (include/comap_mi355x.h); the defaults are those of the reference's R scripts"""
+    _fields_ = [("window", ctypes.c_double), ("conserved_nmin", ctypes.c_double), ("min_nobs", ctypes.c_uint32), ("lower", ctypes.c_int32)]
+
+    def __init__(self, window=0.2, conserved_nmin=0.01, min_nobs=1, lower=False):
+        super().__init__(float(window), float(conserved_nmin), int(min_nobs), int(bool(lower)))
+
+
+def window_pvalues_from_records(n, row_begin, row_end, norm, records, conserved_nmin=0.01, min_nobs=1):
+    """cmx_window_pvalues_from_records (host side, no GPU): the p-values of PAIR_WINDOW records of the rows [row_begin, row_end)"""
+    lib = load_library()
+    records = np.ascontiguousarray(records).view(PAIR_WINDOW).ravel()
+    pv = np.zeros(len(records))
+    prm = WindowParams(1.0, conserved_nmin, min_nobs)
+    st = lib.cmx_window_pvalues_from_records(_sz(n), _sz(row_begin), _sz(row_end), _vp(_f64(norm)), _vp(records), _sz(len(records)),
+                                             ctypes.byref(prm), _vp(pv))
+    if st != 0:
+        raise CmxError(st, "cmx_window_pvalues_from_records: bad arguments")
+    return pv
 
 
 class _Info(ctypes.Structure):
@@ -729,6 +754,22 @@ class Engine:
                                                 _vp(nm), _sz(len(ns)), _vp(pv), _vp(nsim)))
         return pv, nsim
 
+    def window_test(self, null_stat, null_nmin, stat, nmin, window=0.2, conserved_nmin=0.01, min_nobs=1, lower=False):
+        """the sliding-window conditional p-values of `test` (R/CoMapFunctions.R:168-215) for the queries (stat, nmin) against a
+        null, index built and queried in one call -> (pvalue float64, count uint32, nobs uint32)"""
+        ns, nm, s, m = _f64(null_stat).ravel(), _f64(null_nmin).ravel(), _f64(stat).ravel(), _f64(nmin).ravel()
+        pv, cnt, nobs = np.zeros(len(s)), np.zeros(len(s), dtype=np.uint32), np.zeros(len(s), dtype=np.uint32)
+        prm = WindowParams(window, conserved_nmin, min_nobs, lower)
+        self._check(self._lib.cmx_window_test(self._ctx, _vp(ns), _vp(nm), _sz(len(ns)), _vp(s), _vp(m), _sz(len(s)), ctypes.byref(prm),
+                                              _vp(pv), _vp(cnt), _vp(nobs)))
+        return pv, cnt, nobs
+
+    def window_null_info(self):
+        """what the last window_null_dev found: kept entries, half-width ws, the kept entries' Nmin range (waits for the device)"""
+        nk, ws, lo, hi = ctypes.c_size_t(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        self._check(self._lib.cmx_window_null_info(self._ctx, ctypes.byref(nk), ctypes.byref(ws), ctypes.byref(lo), ctypes.byref(hi)))
+        return dict(nkept=nk.value, ws=ws.value, nmin_min=lo.value, nmin_max=hi.value)
+
     def intra_rows(self, kind, counts, rate_class, post_rate, norm, null_stat=None, null_nmin=None, nclasses=10,
                    filters=None, capacity=None, threshold=0.99, mean_vectors=None):
         """statistics.txt rows (structured array PAIR_ROW, reference order), compacted on the device."""
@@ -1059,3 +1100,27 @@ class Engine:
             self._ctx, int(kind), _vp(params), _vp(counts), _sz(n), _sz(counts.stride(0)), _vp(rate_class), _vp(post_rate),
             _vp(norm), _vp(null_stat), _vp(null_nmin), _sz(nnull), int(nclasses), ctypes.byref(f), _sz(row_begin),
             _sz(row_end), _vp(rows), _sz(cap), _vp(count), self._stream()))
+
+    def window_null_dev(self, null_stat, null_nmin, window=0.2):
+        """build the window index of a null (float64 CUDA tensors [nnull], or None for an empty null) on the current stream;
+        the context keeps it until the next build"""
+        nnull = 0 if null_stat is None else null_stat.shape[0]
+        self._check(self._lib.cmx_window_null_dev(self._ctx, _vp(null_stat), _vp(null_nmin), _sz(nnull), ctypes.c_double(window),
+                                                  self._stream()))
+
+    def window_test_dev(self, stat, nmin, pvalue=None, count=None, nobs=None, conserved_nmin=0.01, min_nobs=1, lower=False):
+        """queries (float64 CUDA tensors [nq]) against the index: pvalue float64, count / nobs int32 or uint32 tensors (any may be
+        None); serves pairs, groups of one size, inter-gene rows and Mica's tables alike"""
+        prm = WindowParams(1.0, conserved_nmin, min_nobs, lower)
+        self._check(self._lib.cmx_window_test_dev(self._ctx, _vp(stat), _vp(nmin), _sz(stat.shape[0]), ctypes.byref(prm), _vp(pvalue),
+                                                  _vp(count), _vp(nobs), self._stream()))
+
+    def intra_window_range_dev(self, kind, counts, norm, out, lower=False, row_begin=0, row_end=None, threshold=0.99, mean_vectors=None):
+        """the UNFILTERED pair loop for rows [row_begin, row_end) against the window index as PAIR_WINDOW records (16 B per pair,
+        (i, j) order) in the CUDA uint8 tensor `out`; window_pvalues_from_records gives their p-values on the host"""
+        n = norm.shape[0]
+        row_end = n if row_end is None else int(row_end)
+        params = _stat_params(kind, threshold, mean_vectors)
+        self._check(self._lib.cmx_intra_window_range_dev(
+            self._ctx, int(kind), _vp(params), _vp(counts), _sz(n), _sz(counts.stride(0)), _vp(norm), ctypes.c_int(int(bool(lower))),
+            _sz(row_begin), _sz(row_end), _vp(out), _sz(out.numel() // PAIR_WINDOW.itemsize), self._stream()))

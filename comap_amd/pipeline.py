@@ -36,6 +36,7 @@ class IntraAnalysis:
         self._dense = None
         self._rows = None
         self._compact = None
+        self._window = None
         self._null = {}
         self._null_aln = None
 
@@ -138,6 +139,18 @@ class IntraAnalysis:
         self.eng.intra_compact_range_dev(self.kind, self.counts, self.norm, null_stat, null_nmin, self.nclasses, self._compact,
                                          row_begin, row_end, threshold=self.threshold)
         return self._compact, npairs
+
+    def compute_intra_window(self, null_stat, null_nmin, window=0.2, lower=False, row_begin=0, row_end=None):
+        """the unfiltered pair loop against the sliding window of R/CoMapFunctions.R `test` (index built from the null here) as
+        16-byte records (engine.PAIR_WINDOW) -> (uint8 CUDA tensor, number of pairs); a kept prefetch_intra_gram block serves"""
+        from .engine import PAIR_WINDOW
+        row_end = self.n if row_end is None else row_end
+        npairs = sum_pairs(self.n, row_begin, row_end)
+        if self._window is None or self._window.numel() < max(npairs, 1) * PAIR_WINDOW.itemsize:
+            self._window = torch.empty(max(npairs, 1) * PAIR_WINDOW.itemsize, dtype=torch.uint8, device=self.aln.device)
+        self.eng.window_null_dev(null_stat, null_nmin, window)
+        self.eng.intra_window_range_dev(self.kind, self.counts, self.norm, self._window, lower, row_begin, row_end, threshold=self.threshold)
+        return self._window, npairs
 
 
 def sum_pairs(n, row_begin, row_end):

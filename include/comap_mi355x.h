@@ -469,6 +469,53 @@ cmx_status cmx_intra_gram_prefetch_dev(cmx_ctx* ctx, int kind, const double* d_c
  * per-site arrays; nthreads <= 1: the calling thread alone.  npairs must equal the number of pairs of the row range. */
 cmx_status cmx_expand_compact_rows(size_t n, size_t row_begin, size_t row_end, const int32_t* rate_class, const double* post_rate,
                                    const double* norm, const cmx_pair_compact* compact, size_t npairs, cmx_pair_row* rows, int nthreads);
+
+/* ---- sliding-window conditional p-values: the "exact procedure" of `test` in the reference's R/CoMapFunctions.R:168-215,
+ * which R/computePValues.R runs on statistics.txt and the null (get.pred fixes grid.Rate = FALSE).  Of the null entries
+ * (stat_k, nmin_k) those with neither value NaN are kept.  ws = (max nmin - min nmin) * window / 2 over the kept entries,
+ * in fp64 in that order.  For a query (s, m):  nobs = #{k kept: nmin_k > m - ws and nmin_k < m + ws} (both strict),
+ * count = #{those k: stat_k >= s} (lower: <= s), and
+ *   p = 1 if m < conserved_nmin (whatever nobs and s are), else NaN if nobs < min_nobs or s is NaN, else (count + 1) / (nobs + 1).
+ * A NaN s gives count 0 and nobs as counted; a NaN m gives nobs = count = 0 and p NaN.  Counts are exact integers: the null
+ * is indexed as a wavelet matrix over the entries ordered by nmin and a query costs O(log nnull) whatever the
+ * window.  Groups with a Size column: one index and one cmx_window_test_dev per size, from that size's simulations. */
+typedef struct cmx_window_params {
+  double window;          /* window.Nmin: fraction of the kept entries' nmin range, in (0, +inf) */
+  double conserved_nmin;  /* 0.01 in the R code */
+  uint32_t min_nobs;
+  int32_t lower;
+} cmx_window_params;
+typedef struct cmx_pair_window {
+  double stat;
+  uint32_t count, nobs;   /* count = 0xffffffff: the statistic is NaN */
+} cmx_pair_window;
+/* Builds the index of the null on `stream` and keeps it in the context until the next build or cmx_ctx_destroy
+ * (nnull <= 2^32 - 2; nnull = 0, or nothing kept, is valid: every query then gets nobs = 0).  window outside (0, +inf) or
+ * NaN: CMX_ERR_INVALID.  Every later call in this section reads that index: its stream must be ordered behind this one, and
+ * before any build it fails with CMX_ERR_INVALID. */
+cmx_status cmx_window_null_dev(cmx_ctx* ctx, const double* d_null_stat, const double* d_null_nmin, size_t nnull, double window,
+                               void* stream);
+/* what the build found (any pointer may be NULL); waits for the device.  nkept = 0: ws = 0, the bounds are NaN */
+cmx_status cmx_window_null_info(cmx_ctx* ctx, size_t* nkept, double* ws, double* nmin_min, double* nmin_max);
+/* nq queries against the index (params->window is not read: the window belongs to the index); any output may be NULL */
+cmx_status cmx_window_test_dev(cmx_ctx* ctx, const double* d_stat, const double* d_nmin, size_t nq, const cmx_window_params* params,
+                               double* d_pvalue, uint32_t* d_count, uint32_t* d_nobs, void* stream);
+/* host pointers: builds the index from the null with params->window, queries it, and waits */
+cmx_status cmx_window_test(cmx_ctx* ctx, const double* null_stat, const double* null_nmin, size_t nnull, const double* stat,
+                           const double* nmin, size_t nq, const cmx_window_params* params, double* pvalue, uint32_t* count,
+                           uint32_t* nobs);
+/* The unfiltered pair loop against the index: cmx_intra_compact_range_dev's rows, positions, Gram blocks (a block kept by
+ * cmx_intra_gram_prefetch_dev is used the same way) and arguments, with m = min(norm_i, norm_j) and one 16-byte
+ * cmx_pair_window per pair. */
+cmx_status cmx_intra_window_range_dev(cmx_ctx* ctx, int kind, const double* params, const double* d_counts, size_t n, size_t ldc,
+                                      const double* d_norm, int lower, size_t row_begin, size_t row_end, cmx_pair_window* d_out,
+                                      size_t capacity, void* stream);
+/* host only: pvalue[k] of the records of the rows [row_begin, row_end) in (i, j) order, by the rule above from
+ * params->conserved_nmin and params->min_nobs (window and lower went into the records).  npairs must equal the number of
+ * pairs of the row range. */
+cmx_status cmx_window_pvalues_from_records(size_t n, size_t row_begin, size_t row_end, const double* norm,
+                                           const cmx_pair_window* records, size_t npairs, const cmx_window_params* params,
+                                           double* pvalue);
 /* AnalysisTools::compute{ScalarProduct,Cosinus,Correlation,Covariance}Matrix (CoMap/AnalysisTools.h:93-190,
  * AnalysisTools.cpp:102-339) for plain vectors: v1 [n1][dim], v2 [n2][dim] (NULL: the one-set form) in host memory, any
  * dimension (nothing here depends on the context's tree or model: a context created without them serves too).
