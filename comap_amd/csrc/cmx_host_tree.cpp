@@ -175,7 +175,7 @@ struct Recorder : RegisterOpsIgnored {
   struct Ld { int arr, slot; long t, src; };
   std::vector<Ld> loads;
   // what the wait plan counts (plan_waits): the pass's ops by stream index and, as -1, every workspace vector that moves
-  // through HBM -- the device's OpState bookkeeping of the run-time count (vs += kVecInstrs), nothing for LDS-slot transfers
+  // through HBM -- the counted walk's bookkeeping on the device (CountedWalk::load / store: vs += kVecInstrs), nothing for LDS-slot transfers
   std::vector<int> vm_events;
   explicit Recorder(HostModel* h) : hm(h), blk(h->block()) { store_time[0].assign(h->NIW, -1); store_time[1].assign(h->NIW, -1); }
   std::vector<int>& stream() { return CM ? hm->msched_m : (CT ? hm->msched_r : hm->msched); }
@@ -226,7 +226,7 @@ struct Recorder : RegisterOpsIgnored {
 std::atomic<int> g_wait_skew{-1};   // wait_plan_skew
 
 // The wait plan (cmx_layout.h) of the 64-site protein walk, from the events of one recorded pass.  The count is the
-// device's run-time one (cmx_map.hip: OpState::vs / cur_seq in the kernels that keep it), replayed over two site blocks of
+// device's run-time one (cmx_map.hip: CountedState::vs / cur_seq in the kernels that keep it), replayed over two site blocks of
 // all classes: a leaf op requests the next op's operator before it waits, a product after; the symbols of the next op come
 // with its operator unless it is op 0 of the next site block.  An op's instances differ only there (the last op of a pass),
 // and the smallest distance is kept: a smaller immediate only waits for more.  Op 0 of a block's first pass finds its

@@ -11,7 +11,7 @@
 //   internal edges, row gathers by observed symbol on leaf edges) is listed by the host in one op stream and staged
 //   in LDS by LDS-DMA one op ahead (an op requests the next op's operator and waits for its own; a product of the 64-site
 //   protein walk requests from the gaps between its first matrix instructions).  How long an op may leave later requests
-//   in flight when it waits -- the vmcnt immediate -- is counted at run time (OpState::vs) by every instantiation but the
+//   in flight when it waits -- the vmcnt immediate -- is counted at run time (CountedState::vs) by every instantiation but the
 //   64-site protein walk, which reads it from its stream entry: the host has counted it per entry and proved the plan on a
 //   model of the wave's memory queue (cmx_layout.h: wait plan; cmx_host_verify.cpp: WaitModel).  That walk's stream entry
 //   is one 16-byte scalar load per op from a running pointer: the operator's offset from the pass's class block, the
@@ -229,7 +229,7 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // step i of such a product: input tile i into all five output tiles of the four site groups.  The operator elements of
 // step i + 1 are read before the eight matrix instructions of step i (4 x 64 + 4 x 16 cycles) that cover the read; a
 // group's next 16x16x4 comes eight matrix instructions after its previous one, so no accumulator is waited for.
-// REQ: the request of the NEXT op's operator, issued in the product's gaps (DevWalk::ProductRequest).  Slot 4 I + g lies
+// REQ: the request of the NEXT op's operator, issued in the product's gaps (PlannedWalk::ProductRequest).  Slot 4 I + g lies
 // between the 16x16x4 of site group g in step I -- 64 cycles during which the matrix pipe takes nothing else from this
 // wave -- and the group's 4x4x4_4b; req.slot gets the accumulator the former wrote and the operand the latter reads.
 struct NoRequest {
@@ -460,30 +460,34 @@ struct ConstModel {
       : nrec((cmx_cint)m.nrec), msched((cmx_cint)(tables ? m.msched_r : m.msched)), rates((cmx_cdbl)m.rates),
         probs((cmx_cdbl)m.probs) {}
 };
-// Operator-stream bookkeeping of a wave (wave-uniform, lives across site blocks).  vs counts the VMEM instructions this
-// code issued and knows about (DMA rows, vector stores); an asynchronous transfer remembers vs right after its issue,
+// Operator-stream bookkeeping of a wave (wave-uniform, lives across site blocks): one struct per way an op learns how long
+// to wait (CountedWalk, PlannedWalk below).
+// The counted walk: vs counts the VMEM instructions this code issued and knows about (DMA rows, vector stores and
+// loads); an asynchronous transfer remembers vs right after its issue,
 // and "wait for X" is s_waitcnt vmcnt(vs - X_seq): VMEM completes in order, so the instructions issued after X may stay
 // in flight.  Instructions that are not counted only make the wait stricter.
-// The 64-site protein walk (kMfma16) counts nothing at run time: the distance vs - cur_seq of an op is a function of the tree,
+struct CountedState {   // (the members keep their order: the class-fused kernels' text depends on it)
+  int pre_mat;       // the NEXT op's operator, element offset in a class block
+  int pre_tx;        // op-stream entry of the NEXT op, loaded one op early (its latency hides behind the current op)
+  unsigned par;      // stage buffer / code slot of the current operator op
+  unsigned vs;       // counted VMEM instructions issued so far
+  unsigned cur_seq;  // vs right after the current operator op's operator (and symbols) were requested
+};
+// The planned walk (the 64-site protein walk, kMfma16) counts nothing at run time: the distance vs - cur_seq of an op is a function of the tree,
 // the LDS-slot plan and the op's place in the stream, the host records it per stream entry (cmx_layout.h: wait plan; proved
 // against a model of this queue by verify_walk before a context exists) and the entry carries the immediate.  Its stream
-// entry is a PlanEntry: pre_off / pre_tx / pre_w, and vs / cur_seq / pre_mat are dead.
-struct OpState {
-  // (the members keep their order: the class-fused kernels' text depends on it)
-  int pre_mat;       // run-time count only: the NEXT op's operator, element offset in a class block
-  int pre_tx;        // both walks: op-stream entry of the NEXT op, loaded one op early (its latency hides behind the current op)
-  unsigned par;      // both walks: stage buffer / code slot of the current operator op
-  unsigned vs;       // run-time count only: counted VMEM instructions issued so far
-  unsigned cur_seq;  // run-time count only: vs right after the current operator op's operator (and symbols) were requested
-  // planned walk only (the run-time-count members above are never written by it)
-  long long pre_off; // planned walk: byte offset of the NEXT op's operator from the pass's class block
-  int pre_w;         // planned walk: the vmcnt immediate of the CURRENT op's wait (it travels with the next op's entry)
+// entry is a PlanEntry: pre_off / pre_tx / pre_w.
+struct PlannedState {
+  int pre_tx;        // op-stream entry of the NEXT op, loaded one op early (its latency hides behind the current op)
+  unsigned par;      // stage buffer / code slot of the current operator op
+  long long pre_off; // byte offset of the NEXT op's operator from the pass's class block
+  int pre_w;         // the vmcnt immediate of the CURRENT op's wait (it travels with the next op's entry)
 };
 // an entry as the scalar load sees it: four dwords (off low, off high, tx, w), read through the constant address space
 typedef int cmx_i4 __attribute__((ext_vector_type(4)));
 typedef const cmx_i4 __attribute__((address_space(4)))* cmx_cplan;
 static_assert(offsetof(PlanEntry, off) == 0 && offsetof(PlanEntry, tx) == 8 && offsetof(PlanEntry, w) == 12, "dwords of an entry");
-__device__ __forceinline__ void plan_entry(cmx_cplan p, OpState& os) {
+__device__ __forceinline__ void plan_entry(cmx_cplan p, PlannedState& os) {
   const cmx_i4 q = *p;
   os.pre_off = (long long)(((unsigned long long)(unsigned)q[1] << 32) | (unsigned)q[0]);
   os.pre_tx = q[2];
@@ -495,9 +499,10 @@ __device__ __forceinline__ void plan_entry(cmx_cplan p, OpState& os) {
 // same walk on the host and checked numerically there -- says where the operators are.
 // RESOLVED: every symbol of the alignment is a state (the null's simulated or supplied alignments): leaf ops then stage the
 // S0 state rows of the transposed operator only, not its ambiguity rows
-// MSG: the walk gathers an inlined cherry's message from the cherry message table (cmx_walk.h: kCherryMsg)
-template <int S, int FUSE, int NG, bool RESOLVED, class POL, bool MSG = false>
-struct DevWalk {
+// WalkRegs is what both backends share: the register file and everything that does not care how an op learns how long to
+// wait.  CountedWalk and PlannedWalk add the operator ops; DevWalk names the one an instantiation runs.
+template <int S, int FUSE, int NG, bool RESOLVED, class POL>
+struct WalkRegs {
   static constexpr int VL = S / 4 * NG, kSites = 16 * NG;
   static constexpr bool DIAG = FUSE > 1 && S / FUSE == 4;
   static constexpr int kProductBytes = DIAG ? (S / 4) * 128 : MatStage<S>::BYTES;                      // diagonal tiles come first
@@ -505,36 +510,22 @@ struct DevWalk {
   static constexpr int kVecInstrs = (VL + 1) / 2;   // VMEM instructions of one workspace vector
   static constexpr bool kCherryTables = RESOLVED && DIAG;   // cmx_walk.h: cset / cdot instead of a cherry's operator ops
   static constexpr bool kCherryRows = FUSE == 1;            // cmx_walk.h: a cherry's outside visit keeps its leaf rows in registers
-  static constexpr bool kPlanned = kMfma16<S, NG, DIAG>;    // the planned stream and its waits (OpState)
-  static constexpr bool kCherryMsg = MSG;                   // cmx_walk.h: a cherry's message is a gathered table row
-  static_assert(!MSG || (kPlanned && RESOLVED && !kCherryTables && S == 20), "the message table serves the 64-site protein walk on resolved alignments");
   // cmx_walk.h: one workspace vector per wave stays in LDS where the records say so (the 64-site protein walk in all its
   // modes; the 16-site shape shares the records and ignores the bits, like every backend without a slot)
   static constexpr bool kLdsSlot = map_lds_slot(S, FUSE, NG);
-  static constexpr int kCherryBytes = 16 * leaf_row_stride(S) * 8;   // a table's 16 rows (one per symbol pair)
-  static_assert(kCherryBytes <= MatStage<S>::BYTES, "a cherry table fits a stage buffer");
   double R0[VL], R1[VL], R2[VL], R3[VL];
-  OpState& os;
   const ConstModel& cm;
   const double* pi;            // root frequencies (vector loads: lane-dependent index)
-  int nmv;
-  const double *mat_c, *mat_after;   // (run-time count only: the planned walk has op_base)
-  const uint8_t* op_base;      // planned walk: the pass's class block (wave-uniform); an operator is op_base + its entry's offset
-  cmx_cplan sp;                // planned walk: the stream entry the next op loads; set at the pass boundary, bumped per op
   double *wsM, *wsU, *pcnt;
   const uint8_t* gcodes;
   size_t gstride;
-  const uint8_t* cmsg;         // kCherryMsg: the message tables of the pass's class, table of cherry i at i * C * kCherryMsgTableBytes (wave-uniform)
-  cmx_cint cmsg_ref;           // kCherryMsg: the table's node index (cmx_layout.h)
-  size_t cmsg_stride;          // kCherryMsg: bytes from a cherry's table to the next cherry's
   uint8_t *stage, *cslot, *cslot2, *vslot;
   uint32_t lds_stage, lds_codes, lds_codes2;
-  int lane, c, c_end;
+  int lane;
   double pc;
   double Lg[FUSE];
-  int mi;                      // op of the pass (run-time count only: the planned walk has no use for it)
 
-  __device__ __forceinline__ DevWalk(OpState& os_, const ConstModel& cm_) : os(os_), cm(cm_) {}
+  __device__ __forceinline__ explicit WalkRegs(const ConstModel& cm_) : cm(cm_) {}
 
   // The lane index as an opaque value: address arithmetic built on it is redone at every use (a few VALU instructions)
   // instead of being hoisted out of the walk as a dozen loop-invariant 64-bit per-lane addresses, which the register
@@ -560,7 +551,6 @@ struct DevWalk {
     else return R3;
   }
   __device__ __forceinline__ void begin_pass() {
-    if constexpr (!kPlanned) mi = 0;
 #pragma unroll
     for (int g = 0; g < FUSE; ++g) Lg[g] = 0.0;
   }
@@ -589,288 +579,38 @@ struct DevWalk {
                         "=v"(r[9]), "=v"(r[10]), "=v"(r[11]), "=v"(r[12]), "=v"(r[13]), "=v"(r[14]), "=v"(r[15]), "=v"(r[16]),
                         "=v"(r[17]), "=v"(r[18]), "=v"(r[19]));
   }
-  // One operator op has two halves.  The request: the operator (and symbols) of the NEXT op of the stream -- entry mi + 1,
-  // or entry 0 of the next class / next site block -- into the other buffer, and the stream entry two ops ahead.  The
-  // wait: for this op's operator; it returns its buffer.  op_begin requests, then waits: a leaf op has no matrix
-  // instructions to hide the request behind, and every product but those of the 64-site protein walk keeps this order.
-  // (One function on purpose: as two, op_request and op_wait, hipcc orders a few instructions of the request otherwise in
-  // thirteen kernels that are to keep their text.)  The 64-site protein walk does not come here: its leaf ops run
-  // leaf_begin, its products wait (wait_planned_product) and then request from inside the product (ProductRequest).
-  // The request overwrites the other stage buffer and code slot, whose last readers are the LDS reads of the op before:
-  // op_begin waits for them (lgkmcnt(0)) first.
-  __device__ __forceinline__ const uint8_t* op_begin(unsigned& nseq) {
-    const bool more = (mi + 1 < nmv);
-    const int emat = os.pre_mat, etx = os.pre_tx;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS reads of the other buffer are done
-    unsigned issued;
-    {
-      const double* src = (more ? mat_c : mat_after) + emat;   // element offset, premultiplied on the host
-      const uint32_t dst = lds_stage + (os.par ^ 1u) * MatStage<S>::BYTES;
-      static_assert(!kPlanned, "the planned walk: leaf_begin");
-      if constexpr (kProductBytes == MatStage<S>::BYTES && kLeafBytes == MatStage<S>::BYTES) {
-        mat_dma_l<S>(src, dst, vlane());
-        issued = MatStage<S>::ROWS;
-      } else if (etx >= 0) {   // (wave-uniform: the next op is a leaf op -- or a cherry-table op)
-        if (kCherryTables && (etx & kCherryFlag)) {
-          mat_dma_part<kCherryBytes>(src, dst, vlane());
-          issued = MatPart<kCherryBytes>::ROWS;
-        } else {
-          mat_dma_part<kLeafBytes>(src, dst, vlane());
-          issued = MatPart<kLeafBytes>::ROWS;
-        }
-      } else {
-        mat_dma_part<kProductBytes>(src, dst, vlane());
-        issued = MatPart<kProductBytes>::ROWS;
-      }
-    }
-    if (etx >= 0 && (more || c + 1 < c_end)) {
-      if (kCherryTables && (etx & kCherryFlag)) {
-        code_dma_l(gcodes + (size_t)cherry_taxon1(etx) * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
-        code_dma_l(gcodes + (size_t)cherry_taxon2(etx) * gstride, lds_codes2 + (os.par ^ 1u) * kCodeSlotBytes);
-        issued += 2;
-      } else {
-        code_dma_l(gcodes + (size_t)etx * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
-        issued += 1;
-      }
-    }
-    {  // entry two ops ahead; the stream carries its first two entries again after the last (no wrap test)
-      const int i2 = more ? mi + 2 : 1;
-      os.pre_mat = cm.msched[2 * i2];
-      os.pre_tx = cm.msched[2 * i2 + 1];
-    }
-    wait_vm<S, VL>((int)(os.vs - os.cur_seq + issued));
-    os.vs += issued;
-    nseq = os.vs;
-    return stage + os.par * MatStage<S>::BYTES;
+  // what an operator op does once its operator has landed in buf: a product (req: what it issues in its gaps) ...
+  template <int SRC, int DST, bool TR, class REQ>
+  __device__ __forceinline__ void product(const uint8_t* buf, REQ& req) {
+    matvec_stage<S, TR, NG, DIAG>(buf, vlane(), reg<SRC>(), reg<DST>(), req); asm volatile("" :: "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
   }
-  // ---- The planned walk's halves of an op (kPlanned).  The wait is a dispatch on the entry's immediate over the values that
-  // occur at this kind of op (cmx_layout.h: planned_wait_dispatchable; the host uploads no other).  ONE asm statement with
-  // its own branches: written as nested ifs around seven asm waits, hipcc structurises the tree with an s_mov_b64 -1 /
-  // s_andn2 vcc / s_cbranch_vccnz triple per arm -- 16 instructions to reach vmcnt(4) or vmcnt(5).  Here the most frequent
-  // immediate is reached last and falls out of the statement: vmcnt(0) of a product (96 % of the benchmark tree's) in 3
-  // instructions, vmcnt(5) / vmcnt(4) of a leaf op (71 %) in 5 / 6, vmcnt(14) / vmcnt(15) (26 %) in 7 / 8, the rest one
-  // level deeper.  An arm that takes a range gives its smallest value to everything but the value it names: never a laxer wait.
-  __device__ __forceinline__ static void wait_planned_product(int w) {
-    asm volatile("s_cmp_lt_i32 %0, 10\n\ts_cbranch_scc1 8f\n\t"
-                 "s_cmp_lt_i32 %0, 20\n\ts_cbranch_scc1 7f\n\t"
-                 "s_cmp_lt_i32 %0, 30\n\ts_cbranch_scc1 6f\n\t"
-                 "s_waitcnt vmcnt(30)\n\ts_branch 9f\n"
-                 "6:\ts_waitcnt vmcnt(20)\n\ts_branch 9f\n"
-                 "7:\ts_waitcnt vmcnt(10)\n\ts_branch 9f\n"
-                 "8:\ts_waitcnt vmcnt(0)\n"
-                 "9:" ::"s"(w) : "scc", "memory");
-  }
-  __device__ __forceinline__ static void wait_planned_leaf(int w) {
-    asm volatile("s_cmp_lt_i32 %0, 14\n\ts_cbranch_scc1 7f\n\t"
-                 "s_cmp_lt_i32 %0, 24\n\ts_cbranch_scc1 5f\n\t"
-                 "s_cmp_lt_i32 %0, 30\n\ts_cbranch_scc1 3f\n\t"
-                 "s_waitcnt vmcnt(30)\n\ts_branch 9f\n"
-                 "3:\ts_cmp_eq_u32 %0, 25\n\ts_cbranch_scc1 4f\n\t"
-                 "s_waitcnt vmcnt(24)\n\ts_branch 9f\n"
-                 "4:\ts_waitcnt vmcnt(25)\n\ts_branch 9f\n"
-                 "5:\ts_cmp_eq_u32 %0, 15\n\ts_cbranch_scc1 6f\n\t"
-                 "s_waitcnt vmcnt(14)\n\ts_branch 9f\n"
-                 "6:\ts_waitcnt vmcnt(15)\n\ts_branch 9f\n"
-                 "7:\ts_cmp_eq_u32 %0, 5\n\ts_cbranch_scc1 8f\n\t"
-                 "s_waitcnt vmcnt(4)\n\ts_branch 9f\n"
-                 "8:\ts_waitcnt vmcnt(5)\n"
-                 "9:" ::"s"(w) : "scc", "memory");
-  }
-  // the entry two ops ahead: one 16-byte scalar load from the running pointer
-  __device__ __forceinline__ void next_entry() {
-    plan_entry(sp, os);
-    ++sp;
-  }
-  // a leaf op: request the next op's operator (and symbols), then wait for this op's.  The rows are addressed as
-  // (wave-uniform operator address in SGPRs) + (16 x lane), here and in ProductRequest: no 64-bit address per lane.  Three
-  // full rows and a partial one, whatever the next op is.
-  __device__ __forceinline__ const uint8_t* leaf_begin() {
-    static_assert(kPlanned && MatStage<S>::FULL == 3 && MatPart<kLeafBytes>::FULL == 3 && kProductBytes == MatStage<S>::BYTES, "rows of a request");
-    const uint8_t* src = op_base + os.pre_off;
-    const int etx = os.pre_tx, w = os.pre_w;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS reads of the other buffer are done
-    {
-      const uint32_t dst = lds_stage + (os.par ^ 1u) * MatStage<S>::BYTES;
-      const int l = vlane();
-      const int tl = etx != kPlanProduct ? MatPart<kLeafBytes>::TAIL : MatStage<S>::TAIL;
-      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
-      if (l < tl) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
-    }
-    if (etx >= 0) code_dma_l(gcodes + (size_t)etx * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
-    next_entry();
-    wait_planned_leaf(w);
-    return stage + os.par * MatStage<S>::BYTES;
-  }
-  __device__ __forceinline__ void planned_end() { os.par ^= 1u; }
-  __device__ __forceinline__ void op_end(unsigned nseq) {
-    os.par ^= 1u;
-    os.cur_seq = nseq;
-    ++mi;
-  }
-  // ---- The request of a product of the 64-site protein walk (kMfma16), cut into six pieces that mfma16_steps places in
-  // its slots: behind a 16x16x4 the matrix pipe is busy for 64 cycles and the wave has nothing else to issue.  The pieces:
-  // the operator's three full DMA rows (0 .. 2), its last row under the exec mask (3), the symbols (4), the stream entry
-  // two ops ahead (5); req_slot says where each goes.  All of them sit in step 0: there the accumulators of the site
-  // groups behind the slot are not live yet, so the pieces' temporaries -- a lane offset, the symbols' 64-bit address --
-  // take registers nobody holds; from step 1 on they would come on top of the kernel's peak (DESIGN.md 4.1 has the counts).
-  // The rows are addressed as (wave-uniform base in SGPRs) + (16 x lane): no 64-bit address per lane.
-  // What op_begin requests, transfer for transfer, in another place; why each point holds there:
-  //  * DMA overwrite.  The pieces write the other stage buffer and code slot; their last readers are LDS reads of earlier
-  //    ops, all of them in front of the wait's asm in program order (a "memory" clobber: no access moves across it), hence
-  //    issued before the product's first operand read.  Slot 0 lies behind the product's first matrix instruction, which
-  //    reads that operand: the wave has executed an lgkmcnt wait that covers it (lgkmcnt(0) if a scalar load is in
-  //    flight), and LDS reads return in order, so every earlier LDS read has returned.  No lgkmcnt(0) of our own is needed.
-  //  * Workspace loads in front of the product are counted in the plan (kPlanVec each) and stay in flight across the wait.
-  //  * Scheduling.  A slot begins with an empty asm that names the accumulator the 16x16x4 in front of it wrote ("+v": it
-  //    cannot rise above that instruction) and the operand of the 4x4x4_4b behind it, as every DMA asm does (the 4x4x4_4b
-  //    cannot rise above them); volatile asm statements keep their order, and the lane index the address arithmetic
-  //    starts from is an output of the slot's first asm.  No asm reads the two registers.  The stream entry is a pair of
-  //    compiler-visible scalar loads, which hipcc places where it likes.
-  //  * M0.  Every piece that issues a DMA writes M0 itself.  Nothing else in a product reads or writes it: matrix
-  //    instructions, ds_read_b64 and VALU arithmetic do not use M0 on gfx950.
-  static constexpr int kReqPieces = 6;
-  static constexpr int req_slot(int piece) { return piece < 2 ? 0 : (piece < 4 ? 1 : piece - 2); }
-  static_assert(req_slot(kReqPieces - 1) < 4, "step 0");
-  struct ProductRequest {
-    DevWalk& w;
-    int etx, tail;       // the next op's stream entry; lanes of its operator's last DMA row
-    const uint8_t* src;  // wave-uniform
-    uint32_t dst;
-    __device__ __forceinline__ explicit ProductRequest(DevWalk& w_) : w(w_) {
-      static_assert(kMfma16<S, NG, DIAG> && !kCherryTables && kProductBytes == MatStage<S>::BYTES, "the 64-site protein walk");
-      static_assert(MatStage<S>::FULL == 3 && MatPart<kLeafBytes>::FULL == 3 && MatStage<S>::TAIL > 0 && MatPart<kLeafBytes>::TAIL > 0,
-                    "three full rows and a partial one, whatever the next op is");
-      etx = w.os.pre_tx;
-      src = w.op_base + w.os.pre_off;
-      dst = w.lds_stage + (w.os.par ^ 1u) * MatStage<S>::BYTES;
-      tail = etx != kPlanProduct ? MatPart<kLeafBytes>::TAIL : MatStage<S>::TAIL;   // (a leaf op's operator may be shorter: kLeafBytes)
-    }
-    template <int P, int SLOT>
-    __device__ __forceinline__ void piece(int l, d4& acc, double& t) {
-      if constexpr (req_slot(P) == SLOT) {
-        if constexpr (P < 3) {
-          asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %4 offset:%5"
-                       : "+v"(acc), "+v"(t) : "s"(dst), "v"(16 * l), "s"(src), "i"(P * 1024) : "memory");
-        } else if constexpr (P == 3) {
-          if (l < tail)
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
-        } else if constexpr (P == 4) {
-          if (etx >= 0) code_dma_l(w.gcodes + (size_t)etx * w.gstride, w.lds_codes + (w.os.par ^ 1u) * kCodeSlotBytes);
-        } else {
-          w.next_entry();   // as leaf_begin
-        }
-      }
-    }
-    template <int SLOT>
-    __device__ __forceinline__ void slot(d4& acc, double& t) {
-      if constexpr (SLOT <= req_slot(kReqPieces - 1)) {
-        int l = w.lane;
-        if constexpr (SLOT <= req_slot(kReqPieces - 2)) asm volatile("" : "+v"(l), "+v"(acc), "+v"(t));   // (the stream entry alone: nothing to pin)
-        piece<0, SLOT>(l, acc, t);
-        piece<1, SLOT>(l, acc, t);
-        piece<2, SLOT>(l, acc, t);
-        piece<3, SLOT>(l, acc, t);
-        piece<4, SLOT>(l, acc, t);
-        piece<5, SLOT>(l, acc, t);
-      }
-    }
-  };
-  template <int SRC, int DST, bool TR>
-  __device__ __forceinline__ void mv(int, int) {
-    if constexpr (kMfma16<S, NG, DIAG>) {
-      wait_planned_product(os.pre_w);
-      const uint8_t* buf = stage + os.par * MatStage<S>::BYTES;
-      ProductRequest req(*this);
-      matvec_stage<S, TR, NG, DIAG>(buf, vlane(), reg<SRC>(), reg<DST>(), req); asm volatile("" :: "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
-      planned_end();
-    } else {
-      unsigned nseq;
-      const uint8_t* buf = op_begin(nseq);
-      NoRequest req;
-      matvec_stage<S, TR, NG, DIAG>(buf, vlane(), reg<SRC>(), reg<DST>(), req); asm volatile("" :: "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
-      op_end(nseq);
-    }
-  }
-  // a leaf op, or a cherry-table op (cmx_walk.h): the table is staged like a leaf operator, its row named by two symbols
+  // ... a leaf op, or a cherry-table op (cmx_walk.h): the table is staged like a leaf operator, its row named by two
+  // symbols.  par: the op's code slot
   template <bool CHERRY, int MODE, int SRC, int DST>
-  __device__ __forceinline__ double row_op() {
-    unsigned nseq = 0;
-    const uint8_t* buf;
-    if constexpr (kPlanned) buf = leaf_begin();
-    else buf = op_begin(nseq);
+  __device__ __forceinline__ double rows(const uint8_t* buf, unsigned par) {
     const int vl = vlane();
-    const uint8_t* codes = cslot + os.par * kCodeSlotBytes + 4 * (vl & 15);
+    const uint8_t* codes = cslot + par * kCodeSlotBytes + 4 * (vl & 15);
     double tot;
-    if constexpr (CHERRY) tot = cherry_apply<S, MODE, NG, DIAG>(buf, codes, cslot2 + os.par * kCodeSlotBytes + 4 * (vl & 15), vl, reg<SRC>(), reg<DST>());
+    if constexpr (CHERRY) tot = cherry_apply<S, MODE, NG, DIAG>(buf, codes, cslot2 + par * kCodeSlotBytes + 4 * (vl & 15), vl, reg<SRC>(), reg<DST>());
     else tot = leaf_apply<S, MODE, NG, DIAG>(buf, codes, vl, reg<SRC>(), reg<DST>());
     asm volatile("" :: "v"(tot), "v"(reg<DST>()[0]), "v"(reg<DST>()[VL - 1]));
-    if constexpr (kPlanned) planned_end();
-    else op_end(nseq);
     return tot;
   }
   // per-class count of row `row` of this lane's site (P; class-split mode: S)
   __device__ __forceinline__ void part_store(int row, double v) { state_store<POL::p_store>(v, pcnt + ((size_t)row * kSites + vsidx())); }
-  template <int D> __device__ __forceinline__ void lset(int, int) { (void)row_op<false, LEAF_SET, D, D>(); }
-  template <int SRC, int D> __device__ __forceinline__ void lmul(int, int) { (void)row_op<false, LEAF_MUL, SRC, D>(); }
-  template <int SRC> __device__ __forceinline__ void ldot(int, int, int row) {
-    const double tot = row_op<false, LEAF_DOT, SRC, SRC>();
-    part_store(row, pc * tot);
-  }
-  // kCherryMsg: row 20 s1 + s2 of the cherry's table straight into the destination register, which the walk has killed.  No
-  // stream entry, no request, no stage buffer: the lane loads the two symbols of its own site (plain loads: the alignments
-  // were written by earlier kernels), fetches the row indices of its four site groups from the lanes that hold those sites,
-  // and issues per group two 16-byte loads and one 8-byte load (cmx_layout.h: a row's quad slot).  All of it compiler-
-  // visible, so hipcc waits for it; none of it counted in the wait plan: the operator of the op behind was requested by the
-  // op in front and completes, in order, in front of these loads, and a planned wait that finds them in the queue only
-  // waits for more (cmx_host_verify.cpp: WaitModel models them so).
-  template <int D> __device__ __forceinline__ void cset(int node, int l1, int l2) {
-    if constexpr (MSG) {
-      const int ci = cmsg_ref[node], t1 = cmsg_ref[l1], t2 = cmsg_ref[l2];   // cherry index, alignment rows (scalar loads)
-      const int vl = vlane();
-      unsigned s1 = gcodes[(size_t)t1 * gstride], s2 = gcodes[(size_t)t2 * gstride];
-      s1 = s1 < 19u ? s1 : 19u;
-      s2 = s2 < 19u ? s2 : 19u;
-      const int row = (int)(20u * s1 + s2);
-      const uint8_t* quad = cmsg + (size_t)ci * cmsg_stride + (vl >> 4) * kCherryMsgQuadBytes;
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const uint8_t* p = quad + (size_t)__shfl(row, 16 * g + (vl & 15)) * kCherryMsgRowBytes;
-        const d2 a = *reinterpret_cast<const d2*>(p), b = *reinterpret_cast<const d2*>(p + 16);
-        const double e = *reinterpret_cast<const double*>(p + 32);
-        reg<D>()[vr(0, g)] = a[0];
-        reg<D>()[vr(1, g)] = a[1];
-        reg<D>()[vr(2, g)] = b[0];
-        reg<D>()[vr(3, g)] = b[1];
-        reg<D>()[vr(4, g)] = e;
-      }
-    } else {
-      (void)row_op<true, LEAF_SET, D, D>();
-    }
-  }
-  template <int SRC> __device__ __forceinline__ void cdot(int, int, int, int, int row) {
-    const double tot = row_op<true, LEAF_DOT, SRC, SRC>();
-    part_store(row, pc * tot);
-  }
   // workspace vector -> register: global loads (POL::v_load) straight into the destination register, which the walk has
   // declared dead (kill) long before -- in the outside pass the two sibling messages of a node are requested before the
   // first product and first read after it, so their latency hides behind ~100 MFMAs without a landing buffer.  The
-  // loads are compiler-visible (hipcc waits for them before the first use); they are counted in vs like every VMEM
-  // instruction this code issues so that the counted waits of the operator stream let them stay in flight.
+  // loads are compiler-visible (hipcc waits for them before the first use).
   template <int D>
   __device__ __forceinline__ void load(int arr, int slot) {
-    {
-      const int vl = vlane();
-      load_vec<VL, POL::v_load>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<D>(), vl);
-    }
-    if constexpr (!kPlanned) os.vs += kVecInstrs;   // (the planned walk: the host has counted it, cmx_layout.h: kPlanVec)
+    const int vl = vlane();
+    load_vec<VL, POL::v_load>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<D>(), vl);
   }
   template <int SRC>
   __device__ __forceinline__ void store(int arr, int slot) {
-    {
-      const int vl = vlane();
-      store_vec<VL, POL::v_store>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<SRC>(), vl);
-    }
-    if constexpr (!kPlanned) os.vs += kVecInstrs;
+    const int vl = vlane();
+    store_vec<VL, POL::v_store>((arr ? wsU : wsM) + (size_t)slot * VL * kWave, reg<SRC>(), vl);
   }
   // LDS slot (kLdsSlot): the vector in the workspace layout [VL/2][64 lanes][2], one 16-byte access per lane and row (no
   // bank conflict).  Plain accesses: the compiler's own lgkmcnt waits cover them, and they are not VMEM, so os.vs does
@@ -962,6 +702,352 @@ struct DevWalk {
   }
 };
 
+// The counted walk: every instantiation but the 64-site protein walk.
+template <int S, int FUSE, int NG, bool RESOLVED, class POL>
+struct CountedWalk : WalkRegs<S, FUSE, NG, RESOLVED, POL> {
+  using Regs = WalkRegs<S, FUSE, NG, RESOLVED, POL>;
+  using State = CountedState;
+  using Regs::VL, Regs::DIAG, Regs::kProductBytes, Regs::kLeafBytes, Regs::kVecInstrs, Regs::kCherryTables;
+  using Regs::cm, Regs::gcodes, Regs::gstride, Regs::stage, Regs::lds_stage, Regs::lds_codes, Regs::lds_codes2, Regs::pc, Regs::vlane, Regs::part_store;
+  static_assert(!kMfma16<S, NG, DIAG>, "the 64-site protein walk: PlannedWalk");
+  static constexpr bool kCherryMsg = false;
+  static constexpr int kCherryBytes = 16 * leaf_row_stride(S) * 8;   // a table's 16 rows (one per symbol pair)
+  static_assert(kCherryBytes <= MatStage<S>::BYTES, "a cherry table fits a stage buffer");
+  State& os;
+  int nmv, mi;                       // ops of a pass, op of the pass
+  const double *mat_c, *mat_after;   // class blocks of the pass and of the pass that follows
+  int c, c_end;
+
+  // (the launcher guarantees m.msched_r with cherry tables)
+  __device__ __forceinline__ CountedWalk(State& os_, const ConstModel& cm_, const MapArgs& a)
+      : Regs(cm_), os(os_), nmv(kCherryTables ? a.m.nmv_r : a.m.nmv) {}
+  // operators of class c and of the class of the pass that follows (its first operator is requested by our last op)
+  __device__ __forceinline__ void begin_class(const MapArgs& a, int c_, int c_end_, int c_after) {
+    const DevModel& m = a.m;
+    c = c_;
+    c_end = c_end_;
+    mat_c = m.MAT + (size_t)c * m.MC * MatStage<S>::UNIT;
+    mat_after = m.MAT + (size_t)((c + 1 < c_end) ? c + 1 : c_after) * m.MC * MatStage<S>::UNIT;
+    mi = 0;
+  }
+  // One operator op has two halves.  The request: the operator (and symbols) of the NEXT op of the stream -- entry mi + 1,
+  // or entry 0 of the next class / next site block -- into the other buffer, and the stream entry two ops ahead.  The
+  // wait: for this op's operator; it returns its buffer.  op_begin requests, then waits: a leaf op has no matrix
+  // instructions to hide the request behind, and every product but those of the 64-site protein walk keeps this order.
+  // (One function on purpose: as two, op_request and op_wait, hipcc orders a few instructions of the request otherwise in
+  // thirteen kernels that are to keep their text.)  The 64-site protein walk does not come here: its leaf ops run
+  // leaf_begin, its products wait (wait_planned_product) and then request from inside the product (ProductRequest).
+  // The request overwrites the other stage buffer and code slot, whose last readers are the LDS reads of the op before:
+  // op_begin waits for them (lgkmcnt(0)) first.
+  __device__ __forceinline__ const uint8_t* op_begin(unsigned& nseq) {
+    const bool more = (mi + 1 < nmv);
+    const int emat = os.pre_mat, etx = os.pre_tx;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS reads of the other buffer are done
+    unsigned issued;
+    {
+      const double* src = (more ? mat_c : mat_after) + emat;   // element offset, premultiplied on the host
+      const uint32_t dst = lds_stage + (os.par ^ 1u) * MatStage<S>::BYTES;
+      if constexpr (kProductBytes == MatStage<S>::BYTES && kLeafBytes == MatStage<S>::BYTES) {
+        mat_dma_l<S>(src, dst, vlane());
+        issued = MatStage<S>::ROWS;
+      } else if (etx >= 0) {   // (wave-uniform: the next op is a leaf op -- or a cherry-table op)
+        if (kCherryTables && (etx & kCherryFlag)) {
+          mat_dma_part<kCherryBytes>(src, dst, vlane());
+          issued = MatPart<kCherryBytes>::ROWS;
+        } else {
+          mat_dma_part<kLeafBytes>(src, dst, vlane());
+          issued = MatPart<kLeafBytes>::ROWS;
+        }
+      } else {
+        mat_dma_part<kProductBytes>(src, dst, vlane());
+        issued = MatPart<kProductBytes>::ROWS;
+      }
+    }
+    if (etx >= 0 && (more || c + 1 < c_end)) {
+      if (kCherryTables && (etx & kCherryFlag)) {
+        code_dma_l(gcodes + (size_t)cherry_taxon1(etx) * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
+        code_dma_l(gcodes + (size_t)cherry_taxon2(etx) * gstride, lds_codes2 + (os.par ^ 1u) * kCodeSlotBytes);
+        issued += 2;
+      } else {
+        code_dma_l(gcodes + (size_t)etx * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
+        issued += 1;
+      }
+    }
+    {  // entry two ops ahead; the stream carries its first two entries again after the last (no wrap test)
+      const int i2 = more ? mi + 2 : 1;
+      os.pre_mat = cm.msched[2 * i2];
+      os.pre_tx = cm.msched[2 * i2 + 1];
+    }
+    wait_vm<S, VL>((int)(os.vs - os.cur_seq + issued));
+    os.vs += issued;
+    nseq = os.vs;
+    return stage + os.par * MatStage<S>::BYTES;
+  }
+  __device__ __forceinline__ void op_end(unsigned nseq) {
+    os.par ^= 1u;
+    os.cur_seq = nseq;
+    ++mi;
+  }
+  template <int SRC, int DST, bool TR>
+  __device__ __forceinline__ void mv(int, int) {
+    unsigned nseq;
+    const uint8_t* buf = op_begin(nseq);
+    NoRequest req;
+    this->template product<SRC, DST, TR>(buf, req);
+    op_end(nseq);
+  }
+  template <bool CHERRY, int MODE, int SRC, int DST>
+  __device__ __forceinline__ double row_op() {
+    unsigned nseq;
+    const uint8_t* buf = op_begin(nseq);
+    const double tot = this->template rows<CHERRY, MODE, SRC, DST>(buf, os.par);
+    op_end(nseq);
+    return tot;
+  }
+  template <int D> __device__ __forceinline__ void lset(int, int) { (void)row_op<false, LEAF_SET, D, D>(); }
+  template <int SRC, int D> __device__ __forceinline__ void lmul(int, int) { (void)row_op<false, LEAF_MUL, SRC, D>(); }
+  template <int SRC> __device__ __forceinline__ void ldot(int, int, int row) {
+    const double tot = row_op<false, LEAF_DOT, SRC, SRC>();
+    part_store(row, pc * tot);
+  }
+  template <int D> __device__ __forceinline__ void cset(int, int, int) { (void)row_op<true, LEAF_SET, D, D>(); }
+  template <int SRC> __device__ __forceinline__ void cdot(int, int, int, int, int row) {
+    const double tot = row_op<true, LEAF_DOT, SRC, SRC>();
+    part_store(row, pc * tot);
+  }
+  // workspace vectors are counted in vs like every VMEM instruction this code issues, so that the counted waits of the
+  // operator stream let them stay in flight
+  template <int D>
+  __device__ __forceinline__ void load(int arr, int slot) {
+    Regs::template load<D>(arr, slot);
+    os.vs += kVecInstrs;
+  }
+  template <int SRC>
+  __device__ __forceinline__ void store(int arr, int slot) {
+    Regs::template store<SRC>(arr, slot);
+    os.vs += kVecInstrs;
+  }
+};
+
+// The planned walk: the 64-site protein walk (kMfma16).  The host has counted every VMEM instruction, workspace vectors
+// included (cmx_layout.h: kPlanVec), so load / store are WalkRegs's.
+// MSG: the walk gathers an inlined cherry's message from the cherry message table (cmx_walk.h: kCherryMsg)
+template <int S, int FUSE, int NG, bool RESOLVED, class POL, bool MSG>
+struct PlannedWalk : WalkRegs<S, FUSE, NG, RESOLVED, POL> {
+  using Regs = WalkRegs<S, FUSE, NG, RESOLVED, POL>;
+  using State = PlannedState;
+  using Regs::VL, Regs::DIAG, Regs::kProductBytes, Regs::kLeafBytes, Regs::kCherryTables, Regs::vr;
+  using Regs::gcodes, Regs::gstride, Regs::stage, Regs::lds_stage, Regs::lds_codes, Regs::pc, Regs::vlane, Regs::part_store;
+  static_assert(kMfma16<S, NG, DIAG>, "every other instantiation: CountedWalk");
+  static constexpr bool kCherryMsg = MSG;   // cmx_walk.h: a cherry's message is a gathered table row
+  static_assert(!MSG || (RESOLVED && !kCherryTables && S == 20), "the message table serves the 64-site protein walk on resolved alignments");
+  State& os;
+  const uint8_t* op_base;      // the pass's class block (wave-uniform); an operator is op_base + its entry's offset
+  cmx_cplan sp;                // the stream entry the next op loads; set at the pass boundary, bumped per op
+  const uint8_t* cmsg;         // kCherryMsg: the message tables of the pass's class, table of cherry i at i * C * kCherryMsgTableBytes (wave-uniform)
+  cmx_cint cmsg_ref;           // kCherryMsg: the table's node index (cmx_layout.h)
+  size_t cmsg_stride;          // kCherryMsg: bytes from a cherry's table to the next cherry's
+
+  __device__ __forceinline__ PlannedWalk(State& os_, const ConstModel& cm_, const MapArgs& a) : Regs(cm_), os(os_) {
+    if constexpr (MSG) {
+      cmsg_ref = (cmx_cint)reinterpret_cast<const int*>(a.cherry_msg);
+      cmsg_stride = (size_t)a.m.C * kCherryMsgTableBytes;
+    }
+  }
+  // the pass's class block, and the copy of the stream whose entries behind the last one lead to the pass that follows
+  // (cmx_layout.h: planned_stream_copy) -- the wrap is settled here, no op knows about it.  MSG: the planned walk over the
+  // resolved stream, and the class's message tables
+  __device__ __forceinline__ void begin_class(const MapArgs& a, int c, int c_end, int c_after) {
+    const DevModel& m = a.m;
+    const bool last = c + 1 >= c_end;
+    op_base = reinterpret_cast<const uint8_t*>(m.MAT + (size_t)c * m.MC * MatStage<S>::UNIT);
+    sp = (cmx_cplan)(MSG ? a.plan_r : m.plan) + ((size_t)planned_stream_copy(m.C, last, last ? c_after - c : 1) * (size_t)((MSG ? m.nmv_r : m.nmv) + 2) + 2);
+    if constexpr (MSG) cmsg = a.cherry_msg + cherry_msg_header_bytes(m.nn) + (size_t)c * kCherryMsgTableBytes;
+  }
+  // ---- The halves of an op.  The wait is a dispatch on the entry's immediate over the values that
+  // occur at this kind of op (cmx_layout.h: planned_wait_dispatchable; the host uploads no other).  ONE asm statement with
+  // its own branches: written as nested ifs around seven asm waits, hipcc structurises the tree with an s_mov_b64 -1 /
+  // s_andn2 vcc / s_cbranch_vccnz triple per arm -- 16 instructions to reach vmcnt(4) or vmcnt(5).  Here the most frequent
+  // immediate is reached last and falls out of the statement: vmcnt(0) of a product (96 % of the benchmark tree's) in 3
+  // instructions, vmcnt(5) / vmcnt(4) of a leaf op (71 %) in 5 / 6, vmcnt(14) / vmcnt(15) (26 %) in 7 / 8, the rest one
+  // level deeper.  An arm that takes a range gives its smallest value to everything but the value it names: never a laxer wait.
+  __device__ __forceinline__ static void wait_planned_product(int w) {
+    asm volatile("s_cmp_lt_i32 %0, 10\n\ts_cbranch_scc1 8f\n\t"
+                 "s_cmp_lt_i32 %0, 20\n\ts_cbranch_scc1 7f\n\t"
+                 "s_cmp_lt_i32 %0, 30\n\ts_cbranch_scc1 6f\n\t"
+                 "s_waitcnt vmcnt(30)\n\ts_branch 9f\n"
+                 "6:\ts_waitcnt vmcnt(20)\n\ts_branch 9f\n"
+                 "7:\ts_waitcnt vmcnt(10)\n\ts_branch 9f\n"
+                 "8:\ts_waitcnt vmcnt(0)\n"
+                 "9:" ::"s"(w) : "scc", "memory");
+  }
+  __device__ __forceinline__ static void wait_planned_leaf(int w) {
+    asm volatile("s_cmp_lt_i32 %0, 14\n\ts_cbranch_scc1 7f\n\t"
+                 "s_cmp_lt_i32 %0, 24\n\ts_cbranch_scc1 5f\n\t"
+                 "s_cmp_lt_i32 %0, 30\n\ts_cbranch_scc1 3f\n\t"
+                 "s_waitcnt vmcnt(30)\n\ts_branch 9f\n"
+                 "3:\ts_cmp_eq_u32 %0, 25\n\ts_cbranch_scc1 4f\n\t"
+                 "s_waitcnt vmcnt(24)\n\ts_branch 9f\n"
+                 "4:\ts_waitcnt vmcnt(25)\n\ts_branch 9f\n"
+                 "5:\ts_cmp_eq_u32 %0, 15\n\ts_cbranch_scc1 6f\n\t"
+                 "s_waitcnt vmcnt(14)\n\ts_branch 9f\n"
+                 "6:\ts_waitcnt vmcnt(15)\n\ts_branch 9f\n"
+                 "7:\ts_cmp_eq_u32 %0, 5\n\ts_cbranch_scc1 8f\n\t"
+                 "s_waitcnt vmcnt(4)\n\ts_branch 9f\n"
+                 "8:\ts_waitcnt vmcnt(5)\n"
+                 "9:" ::"s"(w) : "scc", "memory");
+  }
+  // the entry two ops ahead: one 16-byte scalar load from the running pointer
+  __device__ __forceinline__ void next_entry() {
+    plan_entry(sp, os);
+    ++sp;
+  }
+  // a leaf op: request the next op's operator (and symbols), then wait for this op's.  The rows are addressed as
+  // (wave-uniform operator address in SGPRs) + (16 x lane), here and in ProductRequest: no 64-bit address per lane.  Three
+  // full rows and a partial one, whatever the next op is.
+  __device__ __forceinline__ const uint8_t* leaf_begin() {
+    static_assert(MatStage<S>::FULL == 3 && MatPart<kLeafBytes>::FULL == 3 && kProductBytes == MatStage<S>::BYTES, "rows of a request");
+    const uint8_t* src = op_base + os.pre_off;
+    const int etx = os.pre_tx, w = os.pre_w;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS reads of the other buffer are done
+    {
+      const uint32_t dst = lds_stage + (os.par ^ 1u) * MatStage<S>::BYTES;
+      const int l = vlane();
+      const int tl = etx != kPlanProduct ? MatPart<kLeafBytes>::TAIL : MatStage<S>::TAIL;
+      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
+      if (l < tl) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
+    }
+    if (etx >= 0) code_dma_l(gcodes + (size_t)etx * gstride, lds_codes + (os.par ^ 1u) * kCodeSlotBytes);
+    next_entry();
+    wait_planned_leaf(w);
+    return stage + os.par * MatStage<S>::BYTES;
+  }
+  __device__ __forceinline__ void planned_end() { os.par ^= 1u; }
+  // ---- The request of a product, cut into six pieces that mfma16_steps places in
+  // its slots: behind a 16x16x4 the matrix pipe is busy for 64 cycles and the wave has nothing else to issue.  The pieces:
+  // the operator's three full DMA rows (0 .. 2), its last row under the exec mask (3), the symbols (4), the stream entry
+  // two ops ahead (5); req_slot says where each goes.  All of them sit in step 0: there the accumulators of the site
+  // groups behind the slot are not live yet, so the pieces' temporaries -- a lane offset, the symbols' 64-bit address --
+  // take registers nobody holds; from step 1 on they would come on top of the kernel's peak (DESIGN.md 4.1 has the counts).
+  // The rows are addressed as (wave-uniform base in SGPRs) + (16 x lane): no 64-bit address per lane.
+  // What op_begin requests, transfer for transfer, in another place; why each point holds there:
+  //  * DMA overwrite.  The pieces write the other stage buffer and code slot; their last readers are LDS reads of earlier
+  //    ops, all of them in front of the wait's asm in program order (a "memory" clobber: no access moves across it), hence
+  //    issued before the product's first operand read.  Slot 0 lies behind the product's first matrix instruction, which
+  //    reads that operand: the wave has executed an lgkmcnt wait that covers it (lgkmcnt(0) if a scalar load is in
+  //    flight), and LDS reads return in order, so every earlier LDS read has returned.  No lgkmcnt(0) of our own is needed.
+  //  * Workspace loads in front of the product are counted in the plan (kPlanVec each) and stay in flight across the wait.
+  //  * Scheduling.  A slot begins with an empty asm that names the accumulator the 16x16x4 in front of it wrote ("+v": it
+  //    cannot rise above that instruction) and the operand of the 4x4x4_4b behind it, as every DMA asm does (the 4x4x4_4b
+  //    cannot rise above them); volatile asm statements keep their order, and the lane index the address arithmetic
+  //    starts from is an output of the slot's first asm.  No asm reads the two registers.  The stream entry is a pair of
+  //    compiler-visible scalar loads, which hipcc places where it likes.
+  //  * M0.  Every piece that issues a DMA writes M0 itself.  Nothing else in a product reads or writes it: matrix
+  //    instructions, ds_read_b64 and VALU arithmetic do not use M0 on gfx950.
+  static constexpr int kReqPieces = 6;
+  static constexpr int req_slot(int piece) { return piece < 2 ? 0 : (piece < 4 ? 1 : piece - 2); }
+  static_assert(req_slot(kReqPieces - 1) < 4, "step 0");
+  struct ProductRequest {
+    PlannedWalk& w;
+    int etx, tail;       // the next op's stream entry; lanes of its operator's last DMA row
+    const uint8_t* src;  // wave-uniform
+    uint32_t dst;
+    __device__ __forceinline__ explicit ProductRequest(PlannedWalk& w_) : w(w_) {
+      static_assert(!kCherryTables && kProductBytes == MatStage<S>::BYTES, "the 64-site protein walk");
+      static_assert(MatStage<S>::FULL == 3 && MatPart<kLeafBytes>::FULL == 3 && MatStage<S>::TAIL > 0 && MatPart<kLeafBytes>::TAIL > 0,
+                    "three full rows and a partial one, whatever the next op is");
+      etx = w.os.pre_tx;
+      src = w.op_base + w.os.pre_off;
+      dst = w.lds_stage + (w.os.par ^ 1u) * MatStage<S>::BYTES;
+      tail = etx != kPlanProduct ? MatPart<kLeafBytes>::TAIL : MatStage<S>::TAIL;   // (a leaf op's operator may be shorter: kLeafBytes)
+    }
+    template <int P, int SLOT>
+    __device__ __forceinline__ void piece(int l, d4& acc, double& t) {
+      if constexpr (req_slot(P) == SLOT) {
+        if constexpr (P < 3) {
+          asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %4 offset:%5"
+                       : "+v"(acc), "+v"(t) : "s"(dst), "v"(16 * l), "s"(src), "i"(P * 1024) : "memory");
+        } else if constexpr (P == 3) {
+          if (l < tail)
+            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" ::"s"(dst), "v"(16 * l), "s"(src) : "memory");
+        } else if constexpr (P == 4) {
+          if (etx >= 0) code_dma_l(w.gcodes + (size_t)etx * w.gstride, w.lds_codes + (w.os.par ^ 1u) * kCodeSlotBytes);
+        } else {
+          w.next_entry();   // as leaf_begin
+        }
+      }
+    }
+    template <int SLOT>
+    __device__ __forceinline__ void slot(d4& acc, double& t) {
+      if constexpr (SLOT <= req_slot(kReqPieces - 1)) {
+        int l = w.lane;
+        if constexpr (SLOT <= req_slot(kReqPieces - 2)) asm volatile("" : "+v"(l), "+v"(acc), "+v"(t));   // (the stream entry alone: nothing to pin)
+        piece<0, SLOT>(l, acc, t);
+        piece<1, SLOT>(l, acc, t);
+        piece<2, SLOT>(l, acc, t);
+        piece<3, SLOT>(l, acc, t);
+        piece<4, SLOT>(l, acc, t);
+        piece<5, SLOT>(l, acc, t);
+      }
+    }
+  };
+  template <int SRC, int DST, bool TR>
+  __device__ __forceinline__ void mv(int, int) {
+    wait_planned_product(os.pre_w);
+    const uint8_t* buf = stage + os.par * MatStage<S>::BYTES;
+    ProductRequest req(*this);
+    this->template product<SRC, DST, TR>(buf, req);
+    planned_end();
+  }
+  template <int MODE, int SRC, int DST>
+  __device__ __forceinline__ double row_op() {
+    const uint8_t* buf = leaf_begin();
+    const double tot = this->template rows<false, MODE, SRC, DST>(buf, os.par);
+    planned_end();
+    return tot;
+  }
+  template <int D> __device__ __forceinline__ void lset(int, int) { (void)row_op<LEAF_SET, D, D>(); }
+  template <int SRC, int D> __device__ __forceinline__ void lmul(int, int) { (void)row_op<LEAF_MUL, SRC, D>(); }
+  template <int SRC> __device__ __forceinline__ void ldot(int, int, int row) {
+    const double tot = row_op<LEAF_DOT, SRC, SRC>();
+    part_store(row, pc * tot);
+  }
+  // kCherryMsg: row 20 s1 + s2 of the cherry's table straight into the destination register, which the walk has killed.  No
+  // stream entry, no request, no stage buffer: the lane loads the two symbols of its own site (plain loads: the alignments
+  // were written by earlier kernels), fetches the row indices of its four site groups from the lanes that hold those sites,
+  // and issues per group two 16-byte loads and one 8-byte load (cmx_layout.h: a row's quad slot).  All of it compiler-
+  // visible, so hipcc waits for it; none of it counted in the wait plan: the operator of the op behind was requested by the
+  // op in front and completes, in order, in front of these loads, and a planned wait that finds them in the queue only
+  // waits for more (cmx_host_verify.cpp: WaitModel models them so).
+  template <int D> __device__ __forceinline__ void cset(int node, int l1, int l2) {
+    static_assert(MSG, "no other walk of this backend asks for a cherry's message");
+    const int ci = cmsg_ref[node], t1 = cmsg_ref[l1], t2 = cmsg_ref[l2];   // cherry index, alignment rows (scalar loads)
+    const int vl = vlane();
+    unsigned s1 = gcodes[(size_t)t1 * gstride], s2 = gcodes[(size_t)t2 * gstride];
+    s1 = s1 < 19u ? s1 : 19u;
+    s2 = s2 < 19u ? s2 : 19u;
+    const int row = (int)(20u * s1 + s2);
+    const uint8_t* quad = cmsg + (size_t)ci * cmsg_stride + (vl >> 4) * kCherryMsgQuadBytes;
+    double(&d)[VL] = this->template reg<D>();
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const uint8_t* p = quad + (size_t)__shfl(row, 16 * g + (vl & 15)) * kCherryMsgRowBytes;
+      const d2 a = *reinterpret_cast<const d2*>(p), b = *reinterpret_cast<const d2*>(p + 16);
+      const double e = *reinterpret_cast<const double*>(p + 32);
+      d[vr(0, g)] = a[0];
+      d[vr(1, g)] = a[1];
+      d[vr(2, g)] = b[0];
+      d[vr(3, g)] = b[1];
+      d[vr(4, g)] = e;
+    }
+  }
+};
+
+// the backend of an instantiation
+template <int S, int FUSE, int NG, bool RESOLVED, class POL, bool MSG = false>
+using DevWalk = std::conditional_t<kMfma16<S, NG, (FUSE > 1 && S / FUSE == 4)>, PlannedWalk<S, FUSE, NG, RESOLVED, POL, MSG>,
+                                   CountedWalk<S, FUSE, NG, RESOLVED, POL>>;
+
 // Maps the 64 sites of this wave (symbol of taxon t at gcodes[t * gstride], per lane) for all rate classes: one walk of
 // the tree (cmx_walk.h) per class.  Classes [c_begin, c_end) are processed; c_after is the class of the first pass that
 // follows this call (its first operator is requested by the last operator op here).  With finalize, on return
@@ -972,10 +1058,12 @@ template <int S, int FUSE, int NG, bool RESOLVED, class POL, bool MSG = false>
 __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restrict__ wsM, double* __restrict__ wsU,
                                                double* __restrict__ part, double* __restrict__ cnt, int lds_off,
                                                const uint8_t* __restrict__ gcodes, size_t gstride, int lane,
-                                               OpState& os, double& L_out, double& pr_out, int& rc_out,
+                                               typename DevWalk<S, FUSE, NG, RESOLVED, POL, MSG>::State& os, double& L_out, double& pr_out, int& rc_out,
                                                double& norm_out, int c_begin, int c_end, int c_after, bool finalize) {
   const DevModel& m = a.m;
-  constexpr bool kTables = DevWalk<S, FUSE, NG, RESOLVED, POL, MSG>::kCherryTables;   // (the launcher guarantees m.msched_r then)
+  using Walk = DevWalk<S, FUSE, NG, RESOLVED, POL, MSG>;
+  static_assert(Walk::kCherryMsg == MSG, "the message table serves the planned walk");
+  constexpr bool kTables = Walk::kCherryTables;   // (the launcher guarantees m.msched_r then)
   const ConstModel cm(m, kTables || MSG);   // (MSG: the resolved stream, likewise)
   constexpr int kSites = 16 * NG;      // sites per wave (NG site groups of 16; an S-vector is S / 4 * NG doubles per lane)
   // site of this lane inside the wave's block for per-site scalars and arrays: NG = 4: the lane itself; NG = 1: lanes
@@ -984,9 +1072,8 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
   const int C = m.C, K = m.K;
   double Lsum = 0.0, prsum = 0.0, best = -1.0;
   int bestc = 0;
-  DevWalk<S, FUSE, NG, RESOLVED, POL, MSG> be(os, cm);
+  Walk be(os, cm, a);
   be.pi = m.pi;
-  be.nmv = (kTables || MSG) ? m.nmv_r : m.nmv;
   be.wsM = wsM;
   be.wsU = wsU;
   be.gcodes = gcodes;
@@ -999,11 +1086,6 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
   be.lds_codes = lds_addr(be.cslot);
   be.lds_codes2 = lds_addr(be.cslot2);
   be.lane = lane;
-  be.c_end = c_end;
-  if constexpr (MSG) {
-    be.cmsg_ref = (cmx_cint)reinterpret_cast<const int*>(a.cherry_msg);
-    be.cmsg_stride = (size_t)m.C * kCherryMsgTableBytes;
-  }
   {  // symbols of op 0 if it is a leaf op (the previous site block could not request them).  Everything this wave
      // wrote before (simulated symbols) is in L2 first; the request is not counted, so drain it here.
     const int tx0 = cm.msched[1];
@@ -1019,26 +1101,9 @@ __device__ __forceinline__ void map_sites_wave(const MapArgs& a, double* __restr
     }
   }
   for (int c = c_begin; c < c_end; ++c) {
-    // operators of this class and of the class of the pass that follows (its first operator is requested by our last op)
-    if constexpr (MSG) {
-      // the planned walk over the resolved stream, and the class's message tables
-      const bool last = c + 1 >= c_end;
-      be.op_base = reinterpret_cast<const uint8_t*>(m.MAT + (size_t)c * m.MC * MatStage<S>::UNIT);
-      be.sp = (cmx_cplan)a.plan_r + ((size_t)planned_stream_copy(C, last, last ? c_after - c : 1) * (size_t)(m.nmv_r + 2) + 2);
-      be.cmsg = a.cherry_msg + cherry_msg_header_bytes(m.nn) + (size_t)c * kCherryMsgTableBytes;
-    } else if constexpr (DevWalk<S, FUSE, NG, RESOLVED, POL>::kPlanned) {
-      // the planned walk: the pass's class block, and the copy of the stream whose entries behind the last one lead to the
-      // pass that follows (cmx_layout.h: planned_stream_copy) -- the wrap is settled here, no op knows about it
-      const bool last = c + 1 >= c_end;
-      be.op_base = reinterpret_cast<const uint8_t*>(m.MAT + (size_t)c * m.MC * MatStage<S>::UNIT);
-      be.sp = (cmx_cplan)m.plan + ((size_t)planned_stream_copy(C, last, last ? c_after - c : 1) * (size_t)(m.nmv + 2) + 2);
-    } else {
-      be.mat_c = m.MAT + (size_t)c * m.MC * MatStage<S>::UNIT;
-      be.mat_after = m.MAT + (size_t)((c + 1 < c_end) ? c + 1 : c_after) * m.MC * MatStage<S>::UNIT;
-    }
+    be.begin_class(a, c, c_end, c_after);
     const double pc = FUSE > 1 ? 1.0 : cm.probs[c];  // fused: the class probabilities are folded into the count operators
     be.pc = pc;
-    be.c = c;
     be.pcnt = part + (size_t)c * m.B * K * kSites;   // wave-uniform; the lane's site is added at each use
     be.begin_pass();
     walk_pass(be, m.NV, K);
@@ -1130,7 +1195,7 @@ static_assert(kWavesPerBlock * map_lds_fixed<20>(1, 4) <= 160 * 1024 / map_waves
 // sb + nwaves.  With one, the next block nobody has taken: the counter starts at nwaves (every wave's first block is its own
 // index, no atomic), lane 0 draws with one vector atomic and the index is made wave-uniform; a wave leaves at the first index
 // past the last block.  One wave-uniform branch between two blocks, outside the walk: the atomic is issued after the block's
-// epilogue, OpState::vs does not count it (an uncounted VMEM instruction only makes wait_vm stricter), and the wait for its
+// epilogue, CountedState::vs does not count it (an uncounted VMEM instruction only makes wait_vm stricter), and the wait for its
 // result drains it with the operator DMA the block's last op left in flight -- (class 0, entry 0), right for any next block.
 // Which wave maps a block changes no output: workspace, part and cnt0 / cnt1 are keyed by wave, tiles and per-site results by block.
 __device__ __forceinline__ size_t next_block(unsigned long long* queue, size_t sb, int nwaves, int lane) {
@@ -1150,7 +1215,8 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
   using POL = StatePolicy<S, MODE, FUSE, NG>;
   const DevModel& m = a.m;
   // the null's alignments are fully resolved: class-fused nucleotide models walk them with the cherry tables' stream
-  constexpr bool kTables = (MODE == kModeNull || MODE == kModeNullPatterns) && DevWalk<S, FUSE, NG, true, POL>::kCherryTables;
+  using Walk = DevWalk<S, FUSE, NG, true, POL, MSG>;   // (its State is the same for every alignment it walks)
+  constexpr bool kTables = (MODE == kModeNull || MODE == kModeNullPatterns) && Walk::kCherryTables;
   const ConstModel cm(m, kTables || MSG);
   const int lane = threadIdx.x & (kWave - 1);
   const int sidx = NG == 4 ? lane : (lane & 15);   // site of this lane in the wave's block
@@ -1168,18 +1234,21 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, map_waves_per_simd(S)) void
   const int lds_off = wib * a.lds_per_wave;
   const size_t nblocks = (a.nsites + kSites - 1) / kSites;
   // request the first op's operator (class 0, entry 0); every op then requests the next one
-  OpState os;
+  typename Walk::State os;
   os.par = 0;
   {
     const int c0 = (MODE == kModeObservedSplit) ? wave % m.C : 0;   // class of this wave's first pass
     mat_dma<S>(m.MAT + (size_t)c0 * m.MC * MatStage<S>::UNIT + cm.msched[0], cmx_smem + lds_off, lane);
   }
-  if constexpr (kMfma16<S, NG, (FUSE > 1 && S / FUSE == 4)>) {   // the planned walk: entry 1, the same in every copy
+  // ... and entry 1.  (Written out here, not a call on the backend: behind a function boundary hipcc promotes the stream
+  // pointer to the entry's two values and rebuilds their address in the caller without `inbounds`, and thirteen kernels
+  // that are to keep their text merge the stream's first scalar loads otherwise.)
+  if constexpr (kMfma16<S, NG, Walk::DIAG>) {   // the planned walk: the same in every copy
     plan_entry((cmx_cplan)(MSG ? a.plan_r : m.plan) + 1, os);
   } else {
     os.vs = MatStage<S>::ROWS;
     os.cur_seq = os.vs;
-    os.pre_mat = cm.msched[2];   // entry 1 (the stream is padded with copies of its first entries)
+    os.pre_mat = cm.msched[2];   // (the stream is padded with copies of its first entries)
     os.pre_tx = cm.msched[3];
   }
   if (MODE == kModeObservedSplit) {
