@@ -66,7 +66,8 @@ def _engines(tree, C, K, grid=None):
 
 
 def _same_bytes(eng_on, eng_off, kind, sup):
-    """the null over `sup` on both paths of both engines; every output the same bytes; -> the pattern path's result"""
+    """the null over `sup` on both paths of both engines; every output the same bytes, engine against engine within a path
+    and the pattern path against the per-site path (what test_gpu_null_patterns._both compares); -> the pattern path's result"""
     nrep, _, _, ram = sup.shape
     first = None
     for patterns in (True, False):
@@ -79,6 +80,9 @@ def _same_bytes(eng_on, eng_off, kind, sup):
             a, b = res[0][key], res[1][key]
             assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (key, "patterns" if patterns else "per site", int((a != b).sum()))
         first = first or res[0]
+        for key in OUT:
+            a, b = first[key], res[0][key]
+            assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (key, "patterns against per site", int((a != b).sum()))
     return first
 
 

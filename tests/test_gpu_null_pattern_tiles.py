@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from comap_amd import engine
+from large_tree_cases import with_patterns
 from test_gpu_null_patterns import KEYS, _both, _clean, _columns, _distinct, _dna, _protein, _supplied
 
 pytestmark = pytest.mark.gpu
@@ -33,19 +34,9 @@ def guard(request):
 
 
 def _with_patterns(eng, npat, nrep, ram, seed):
-    """[nrep][2][T][ram] alignments with exactly npat distinct columns: the first npat sites are the patterns in order, the
-    others repeat patterns drawn at random (so duplicates point into every tile)"""
-    rng = np.random.default_rng(seed)
-    n = nrep * 2 * ram
-    assert npat <= n
-    cols = set()
-    while len(cols) < npat:
-        cols.add(bytes(rng.integers(0, eng.S, size=eng.T, dtype=np.uint8)))
-    pats = np.frombuffer(b"".join(sorted(cols)), dtype=np.uint8).reshape(npat, eng.T)
-    pats = pats[rng.permutation(npat)]
-    which = np.concatenate([np.arange(npat), rng.integers(0, npat, size=n - npat)])
-    sites = pats[which]                                                   # [n][T], g = (rep * 2 + h) * ram + j
-    return np.ascontiguousarray(sites.reshape(nrep, 2, ram, eng.T).transpose(0, 1, 3, 2))
+    """[nrep][2][T][ram] alignments with exactly npat distinct columns (large_tree_cases.with_patterns, for this engine's
+    taxa and states)"""
+    return with_patterns(eng.T, eng.S, npat, nrep, ram, seed)
 
 
 @pytest.mark.parametrize("npat", [1, 63, 64, 65, 150])
